@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark of the DEWI hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line with the headline figures (`value`,
+`ms_per_step`).  Everything else below — the roofline leg and the per-kernel event timings, the latency legs, the CPU
+baseline, the parity gates against the NumPy oracle, the sharded-vs-single-GPU check, the C1 API leg, the opt-in shadow
+leg and C5's C-ABI comparison — runs only with --full.  --dump-outputs DIR writes what the timed path computed in its
+last step (ids and scores, or C5's columns) as DIR/<name>.npy, float32 / float64; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 Default (``--config c2``, the configuration BASELINE.json's metric is quoted on): queries/s (plus
 p50 latency) of brute-force cosine kNN + DEWI re-rank over a 1M x 768 fp32 corpus, query batch 1,
@@ -24,7 +31,7 @@ Other configurations of BASELINE.json, one JSON line each, same harness (1 GPU):
   --config c5   1M documents, d=512: robust fit + DEWI score of the 7 signals and the I_hat
                 row-cosine of the text/image embedding pair (the on-GPU part of configs[4]).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      achieved HBM GB/s of the dominant kernel = algorithmic bytes / its mean duration,
                 measured with hipEvents on the launch stream over >= 200 launches (a dedicated leg
                 right after the timed region, plus the sampled launches of the timed region itself)
@@ -82,6 +89,10 @@ def parse_args():
     ap.add_argument("--scan-blocks", type=int, default=0)
     ap.add_argument("--rows-per-iter", type=int, default=0)
     ap.add_argument("--nontemporal", type=int, default=-1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: roofline / per-kernel timings, latency, CPU baseline, parity gates")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32/float64, at most 64 MB in all)")
     a = ap.parse_args()
     defaults = {"c2": dict(steps=1000, warmup=50, dim=768, k=10, batch=1),
                 # c3: 100 + 500 batches = 0.24 s.  A 100-batch run (40 ms) ends before the chip has settled: 0.411 ms per
@@ -250,6 +261,39 @@ def oracle_imports():
     return orc, compare_query
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def host_array(t):
+    """Device tensor -> host ndarray, copied now (the buffers are overwritten by the --full legs)."""
+    return t.detach().cpu().numpy().copy()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, integers and doubles as float64, the rest as float32.  When
+    they hold more than DUMP_LIMIT_BYTES together, each array over 64 KB is cut to a fixed, seeded sample of its rows
+    (sorted; the row numbers beside it as <name>_rows.npy), sized so that all the files stay under the limit."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        wide = a.dtype == np.float64 or np.issubdtype(a.dtype, np.integer)
+        arrs[name] = np.ascontiguousarray(a, dtype=np.float64 if wide else np.float32)
+    small = 64 * 1024
+    big_total = sum(a.nbytes for a in arrs.values() if a.nbytes > small)
+    small_total = sum(a.nbytes for a in arrs.values() if a.nbytes <= small)
+    budget = DUMP_LIMIT_BYTES - small_total - 1024 * len(arrs)            # (npy headers)
+    # a sampled row costs its bytes plus an 8-byte row number, at most 3x the row for a 1-D float32 array
+    frac = 1.0 if big_total + small_total <= DUMP_LIMIT_BYTES - 1024 * len(arrs) else budget / (3.0 * big_total)
+    for name, a in arrs.items():
+        if frac < 1.0 and a.nbytes > small:
+            m = max(1, int(a.shape[0] * frac))
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], m, replace=False))
+            np.save(out / f"{name}_rows.npy", rows.astype(np.float64))
+            a = a[rows]
+        np.save(out / f"{name}.npy", a)
+
+
 # ======================================================================================================
 # c2 (default) and its multi-GPU forms
 # ======================================================================================================
@@ -263,8 +307,8 @@ def run_c2(args, torch, dist, eng, nat, rank, world, device):
         full, full_cols = make_corpus(torch, total_rows, args.dim, 42, device)
         emb_raw = full[lo:hi].clone() if world > 1 else full
         cols = {k: v[lo:hi] for k, v in full_cols.items()}
-        if world == 1 or rank != 0 or args.scaling != "strong":
-            full = None      # rank 0 of a sharded run keeps the whole corpus for the post-run check
+        if world == 1 or rank != 0 or args.scaling != "strong" or not args.full:
+            full = None      # rank 0 of a sharded run keeps the whole corpus for the post-run check (--full)
     else:
         total_rows = args.docs * world
         lo, hi = args.docs * rank, args.docs * (rank + 1)
@@ -410,7 +454,8 @@ def run_c2(args, torch, dist, eng, nat, rank, world, device):
     barrier()
     eng.timing_read()
     # hipEvents around every 8th scan kernel inside the timed region (the two event records cost ~5-10 us of
-    # stream time, so the timed region is only sampled; the roofline leg below brackets every launch)
+    # stream time, so the timed region is only sampled; the roofline leg below brackets every launch).  Sampled in a plain
+    # run too, so that the timed region — and `value` — is the same with and without --full.
     eng.timing(8)
     t0 = time.perf_counter()
     run(args.warmup, args.steps)
@@ -422,41 +467,11 @@ def run_c2(args, torch, dist, eng, nat, rank, world, device):
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # Roofline leg: the same loop body, every scan bracketed, at least MIN_ROOFLINE_LAUNCHES launches whatever
-    # --steps was (SURVEY §8(d): >= 200 event-timed launches).  Outside the timed region: does not touch `value`.
-    n_leg = max(MIN_ROOFLINE_LAUNCHES, 0)
-    n_leg += (-n_leg) % G
-    eng.timing(1)
-    run(0, n_leg)
-    barrier()
-    leg_ms, leg_launches = eng.timing_read()
-    eng.timing(False)
-    tot_launches = region_launches + leg_launches
-    scan_ms = (region_ms * region_launches + leg_ms * leg_launches) / tot_launches if tot_launches else 0.0
+    j_last = (args.warmup + args.steps - 1) % n_distinct            # the query slot the last timed step answered
+    outputs = {"ids": host_array(out_ids[j_last]), "scores": host_array(out_sc[j_last])} if args.dump_outputs else None
 
     qps = args.steps * B / elapsed
     ms_per_step = elapsed / args.steps * 1e3
-    elem = 2 if shadowed else corpus.emb.element_size()              # the dominant pass streams the bf16 shadow
-    algo_bytes = n_local * args.dim * elem + B * args.dim * (2 if shadowed else 4)           # per scan launch, this rank
-    achieved = algo_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
-    # --batch >= 5 over the fp32 corpus: the depth-split matrix-core pass is the dominant kernel (one per 32 queries);
-    # --batch > 32: the 256-query pass over the bf16 shadow (one per 256 queries)
-    # --batch 1 --shadow 1 (cut of at most 32 rows): the bf16 ROW kernel over the shadow
-    # (the library names the row kernel of this width itself: the tuned dim = 256 U kernels, the any-width ones, the generic)
-    depth_args = f"{-(-args.dim // 256)},false,false,{'true' if args.dim % 256 else 'false'}"   # chunks, SAMPLE, L2, partial last chunk
-    lib_name = corpus.scan_kernel_name(B, k)       # what the library's plan says streams the corpus for this shape
-    kernel = ((f"mfma_scan_f32<false,{depth_args}>" if lib_name.startswith("mfma_scan_f32") else lib_name) if not shadowed
-              else f"mfma_scan_bf16_s16<{args.dim // 16},false>" if (B > 32 and args.dim % 128 == 0 and args.dim <= 768)
-              else f"scan_rows_bf16<{args.dim // 256},1,0,1,true>" if (B == 1 and c <= 32 and args.dim <= 1024 and args.dim % 256 == 0)   # (no tuned bf16 row kernel at 1536 / other widths)
-              else f"mfma_scan_f32<true,{depth_args}>")
-    traffic, traffic_note = recorded_traffic(f"{n_local}x{args.dim}x{elem}xB{B}", kernel)
-    if traffic is None and shadowed and B < 32 and kernel.startswith("mfma_scan_f32"):
-        # the depth-split pass is one launch of the same grid over the same rows for 1..32 active queries: the counter record
-        # taken with 32 stands for the smaller batches (and says so)
-        traffic, traffic_note = recorded_traffic(f"{n_local}x{args.dim}x{elem}xB32", kernel)
-        if traffic is not None:
-            traffic_note += f"; recorded with 32 queries per pass (same launch, {B} active here)"
-
     result = {
         "metric": METRIC,
         "value": round(qps, 2),
@@ -479,14 +494,49 @@ def run_c2(args, torch, dist, eng, nat, rank, world, device):
                    "bf16_shadow": shadowed,
                    "queries_in_flight": 1 if (serial and not sharded) else (3 * G if sharded else 2),
                    "rows_per_gpu": n_local, "conditioning_steps_before_warmup": n_condition},
-        "roofline": {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "traffic_source": traffic_note,
-                     "algorithmic_bytes_per_launch": algo_bytes, "mean_kernel_ms": round(scan_ms, 5),
-                     "launches_timed": tot_launches,
-                     "timed_region": {"mean_kernel_ms": round(region_ms, 5), "launches": region_launches},
-                     "roofline_leg": {"mean_kernel_ms": round(leg_ms, 5), "launches": leg_launches}},
     }
+    if not args.full:
+        return result, outputs
+
+    # Roofline leg: the same loop body, every scan bracketed, at least MIN_ROOFLINE_LAUNCHES launches whatever
+    # --steps was (SURVEY §8(d): >= 200 event-timed launches).  Outside the timed region: does not touch `value`.
+    n_leg = max(MIN_ROOFLINE_LAUNCHES, 0)
+    n_leg += (-n_leg) % G
+    eng.timing(1)
+    run(0, n_leg)
+    barrier()
+    leg_ms, leg_launches = eng.timing_read()
+    eng.timing(False)
+    tot_launches = region_launches + leg_launches
+    scan_ms = (region_ms * region_launches + leg_ms * leg_launches) / tot_launches if tot_launches else 0.0
+
+    elem = 2 if shadowed else corpus.emb.element_size()              # the dominant pass streams the bf16 shadow
+    algo_bytes = n_local * args.dim * elem + B * args.dim * (2 if shadowed else 4)           # per scan launch, this rank
+    achieved = algo_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
+    # --batch >= 5 over the fp32 corpus: the depth-split matrix-core pass is the dominant kernel (one per 32 queries);
+    # --batch > 32: the 256-query pass over the bf16 shadow (one per 256 queries)
+    # --batch 1 --shadow 1 (cut of at most 32 rows): the bf16 ROW kernel over the shadow
+    # (the library names the row kernel of this width itself: the tuned dim = 256 U kernels, the any-width ones, the generic)
+    depth_args = f"{-(-args.dim // 256)},false,false,{'true' if args.dim % 256 else 'false'}"   # chunks, SAMPLE, L2, partial last chunk
+    lib_name = corpus.scan_kernel_name(B, k)       # what the library's plan says streams the corpus for this shape
+    kernel = ((f"mfma_scan_f32<false,{depth_args}>" if lib_name.startswith("mfma_scan_f32") else lib_name) if not shadowed
+              else f"mfma_scan_bf16_s16<{args.dim // 16},false>" if (B > 32 and args.dim % 128 == 0 and args.dim <= 768)
+              else f"scan_rows_bf16<{args.dim // 256},1,0,1,true>" if (B == 1 and c <= 32 and args.dim <= 1024 and args.dim % 256 == 0)   # (no tuned bf16 row kernel at 1536 / other widths)
+              else f"mfma_scan_f32<true,{depth_args}>")
+    traffic, traffic_note = recorded_traffic(f"{n_local}x{args.dim}x{elem}xB{B}", kernel)
+    if traffic is None and shadowed and B < 32 and kernel.startswith("mfma_scan_f32"):
+        # the depth-split pass is one launch of the same grid over the same rows for 1..32 active queries: the counter record
+        # taken with 32 stands for the smaller batches (and says so)
+        traffic, traffic_note = recorded_traffic(f"{n_local}x{args.dim}x{elem}xB32", kernel)
+        if traffic is not None:
+            traffic_note += f"; recorded with 32 queries per pass (same launch, {B} active here)"
+    result["roofline"] = {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                          "traffic_source": traffic_note,
+                          "algorithmic_bytes_per_launch": algo_bytes, "mean_kernel_ms": round(scan_ms, 5),
+                          "launches_timed": tot_launches,
+                          "timed_region": {"mean_kernel_ms": round(region_ms, 5), "launches": region_launches},
+                          "roofline_leg": {"mean_kernel_ms": round(leg_ms, 5), "launches": leg_launches}}
 
     if sharded:
         # Two scans are in flight at a time on this path (alternating scan streams), so a launch's duration
@@ -641,7 +691,7 @@ def run_c2(args, torch, dist, eng, nat, rank, world, device):
     if (rank == 0 and world == 1 and not sharded and B == 1 and not shadowed and args.shadow < 0 and args.dim in (256, 512, 768, 1024, 1536)
             and c <= 256 and n_local >= 64 * 1024):
         result["opt_in_bf16_shadow"] = shadow_leg(torch, corpus, Q, k, eta, min(64, n_distinct))
-    return result
+    return result, outputs
 
 
 def shadow_leg(torch, corpus, Q, k, eta, n_check):
@@ -748,21 +798,11 @@ def run_c3(args, torch, eng, nat, device):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     region_ms, region_launches = eng.timing_read()
-    eng.timing(1)
-    run(0, MIN_ROOFLINE_LAUNCHES)
-    torch.cuda.synchronize()
-    leg_ms, leg_launches = eng.timing_read()
     eng.timing(False)
-    tot = region_launches + leg_launches
-    kern_ms = (region_ms * region_launches + leg_ms * leg_launches) / tot if tot else 0.0
-    refused = int((out_ids[:, :, 0] < 0).sum().item())
+    j_last = (args.warmup + args.steps - 1) % n_batches
+    outputs = {"ids": host_array(out_ids[j_last]), "scores": host_array(out_sc[j_last])} if args.dump_outputs else None
+    refused = int((out_ids[:min(n_batches, args.warmup + args.steps), :, 0] < 0).sum().item())     # the batches written
     ms_per_step = elapsed / args.steps * 1e3
-    algo_bytes = n * dim * 2 + B * dim * 2
-    flops = 2.0 * B * n * dim
-    hbm = algo_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-    tf = flops / (kern_ms * 1e-3) / 1e12 if kern_ms > 0 else 0.0
-    kernel = "mfma_scan_bf16_s16<48,false>"
-    traffic, traffic_note = recorded_traffic(f"{n}x{dim}x2xB{B}", kernel)
     result = {
         "metric": "queries/sec, 1M×768 bf16 corpus, query batch=256, k=100, η=0.3 (BASELINE.json configs[2])",
         "value": round(args.steps * B / elapsed, 1), "unit": "queries/s", "n_gpus": 1, "steps": args.steps,
@@ -772,15 +812,31 @@ def run_c3(args, torch, eng, nat, device):
                                f"+ DEWI re-rank (BASELINE.json configs[2])",
                    "docs": n, "dim": dim, "k": k, "eta": eta, "batch": B, "candidates": min(2 * k, n),
                    "parallelism": "single GPU", "refused_queries": refused},
-        "roofline": {"bound": "hbm", "kernel": kernel, "achieved": round(hbm, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(hbm / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_note,
-                     "algorithmic_bytes_per_launch": algo_bytes, "mean_kernel_ms": round(kern_ms, 5), "launches_timed": tot,
-                     "mfma": {"achieved": round(tf, 1), "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s",
-                              "frac": round(tf / MFMA_BF16_PEAK_TF, 4), "flops_per_launch": flops},
-                     "whole_step": {"ms": round(ms_per_step, 5),
-                                    "hbm_frac": round(algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                    "mfma_frac": round(flops / (ms_per_step * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF, 4)}},
     }
+    if not args.full:
+        return result, outputs
+    eng.timing(1)
+    run(0, MIN_ROOFLINE_LAUNCHES)
+    torch.cuda.synchronize()
+    leg_ms, leg_launches = eng.timing_read()
+    eng.timing(False)
+    result["config"]["refused_queries"] = int((out_ids[:, :, 0] < 0).sum().item())    # every batch, the leg's included
+    tot = region_launches + leg_launches
+    kern_ms = (region_ms * region_launches + leg_ms * leg_launches) / tot if tot else 0.0
+    algo_bytes = n * dim * 2 + B * dim * 2
+    flops = 2.0 * B * n * dim
+    hbm = algo_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+    tf = flops / (kern_ms * 1e-3) / 1e12 if kern_ms > 0 else 0.0
+    kernel = "mfma_scan_bf16_s16<48,false>"
+    traffic, traffic_note = recorded_traffic(f"{n}x{dim}x2xB{B}", kernel)
+    result["roofline"] = {"bound": "hbm", "kernel": kernel, "achieved": round(hbm, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": round(hbm / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_note,
+                          "algorithmic_bytes_per_launch": algo_bytes, "mean_kernel_ms": round(kern_ms, 5), "launches_timed": tot,
+                          "mfma": {"achieved": round(tf, 1), "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s",
+                                   "frac": round(tf / MFMA_BF16_PEAK_TF, 4), "flops_per_launch": flops},
+                          "whole_step": {"ms": round(ms_per_step, 5),
+                                         "hbm_frac": round(algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                         "mfma_frac": round(flops / (ms_per_step * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF, 4)}}
     if args.cpu_queries > 0:
         orc, compare_query = oracle_imports()
         from threadpoolctl import threadpool_limits
@@ -818,7 +874,7 @@ def run_c3(args, torch, eng, nat, device):
         if bad:
             print(json.dumps(result))
             raise SystemExit("parity gate failed: the bench result is invalid")
-    return result
+    return result, outputs
 
 
 # ======================================================================================================
@@ -843,7 +899,6 @@ def run_c4(args, torch, eng, nat, device):
     for s in range(S):
         shards.append(eng.DeviceCorpus(big[s * n:(s + 1) * n], dewi_all[s * n:(s + 1) * n], ent_all[s * n:(s + 1) * n],
                                        "cosine", id_offset=s * n))
-    whole = eng.DeviceCorpus(big, dewi_all, ent_all, "cosine")
     qg = torch.Generator(device=device)
     qg.manual_seed(7)
     n_distinct = 256
@@ -869,24 +924,10 @@ def run_c4(args, torch, eng, nat, device):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kern_ms, launches = eng.timing_read()
-    eng.timing(1)
-    if launches < MIN_ROOFLINE_LAUNCHES:
-        run(0, (MIN_ROOFLINE_LAUNCHES - launches + S - 1) // S)
-        torch.cuda.synchronize()
-        ms2, l2 = eng.timing_read()
-        kern_ms, launches = (kern_ms * launches + ms2 * l2) / (launches + l2), launches + l2
     eng.timing(False)
-    # the emulated exchange must equal ONE 8M-row search bit for bit
-    bad = 0
-    n_chk = 16
-    for j in range(n_chk):
-        ri, rs = whole.search_device(Q[j], k, eta, 0.0)
-        bad += 0 if (torch.equal(ri, out_ids[j]) and torch.equal(rs, out_sc[j])) else 1
-    torch.cuda.synchronize()
-    algo_bytes = n * dim * 4 + B * dim * 4
-    hbm = algo_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+    j_last = (args.warmup + args.steps - 1) % n_distinct
+    outputs = {"ids": host_array(out_ids[j_last]), "scores": host_array(out_sc[j_last])} if args.dump_outputs else None
     ms_per_step = elapsed / args.steps * 1e3
-    c4_traffic, c4_note = recorded_traffic(f"{n}x{dim}x4xB{B}", "scan_rows_f32")
     result = {
         "metric": "queries/sec, 8M×768 fp32 corpus as 8 doc-id shards of 1M, k=10, η=0.3 (BASELINE.json configs[3]) "
                   "REPLAYED ON ONE GPU: every shard scanned in turn, records merged; no wire",
@@ -898,13 +939,33 @@ def run_c4(args, torch, eng, nat, device):
                    "docs": total, "dim": dim, "k": k, "eta": eta, "batch": B, "candidates": c, "shards": S,
                    "parallelism": f"{S} shards emulated on a single GPU (multi-GPU: unmeasured here)",
                    "ideal_8gpu_ms_per_step": round(ms_per_step / S, 5)},
-        "roofline": {"bound": "hbm", "kernel": "scan_rows_f32", "achieved": round(hbm, 1), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(hbm / HBM_PEAK_GBS, 4), "traffic": c4_traffic,
-                     "traffic_source": c4_note + " (the same kernel over one 1M-row shard: the C2 record)",
-                     "algorithmic_bytes_per_launch": algo_bytes, "mean_kernel_ms": round(kern_ms, 5),
-                     "launches_timed": launches},
-        "sharded_parity": {"queries_checked": n_chk, "mismatches_vs_single_8M_search": bad},
     }
+    if not args.full:
+        return result, outputs
+    eng.timing(1)
+    if launches < MIN_ROOFLINE_LAUNCHES:
+        run(0, (MIN_ROOFLINE_LAUNCHES - launches + S - 1) // S)
+        torch.cuda.synchronize()
+        ms2, l2 = eng.timing_read()
+        kern_ms, launches = (kern_ms * launches + ms2 * l2) / (launches + l2), launches + l2
+    eng.timing(False)
+    # the emulated exchange must equal ONE 8M-row search bit for bit
+    whole = eng.DeviceCorpus(big, dewi_all, ent_all, "cosine")
+    bad = 0
+    n_chk = 16
+    for j in range(n_chk):
+        ri, rs = whole.search_device(Q[j], k, eta, 0.0)
+        bad += 0 if (torch.equal(ri, out_ids[j]) and torch.equal(rs, out_sc[j])) else 1
+    torch.cuda.synchronize()
+    algo_bytes = n * dim * 4 + B * dim * 4
+    hbm = algo_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+    c4_traffic, c4_note = recorded_traffic(f"{n}x{dim}x4xB{B}", "scan_rows_f32")
+    result["roofline"] = {"bound": "hbm", "kernel": "scan_rows_f32", "achieved": round(hbm, 1), "peak": HBM_PEAK_GBS,
+                          "unit": "GB/s", "frac": round(hbm / HBM_PEAK_GBS, 4), "traffic": c4_traffic,
+                          "traffic_source": c4_note + " (the same kernel over one 1M-row shard: the C2 record)",
+                          "algorithmic_bytes_per_launch": algo_bytes, "mean_kernel_ms": round(kern_ms, 5),
+                          "launches_timed": launches}
+    result["sharded_parity"] = {"queries_checked": n_chk, "mismatches_vs_single_8M_search": bad}
     if args.cpu_queries > 0:
         orc, compare_query = oracle_imports()
         E = big.cpu().numpy()
@@ -928,7 +989,7 @@ def run_c4(args, torch, eng, nat, device):
         if msgs or bad:
             print(json.dumps(result))
             raise SystemExit("parity gate failed: the bench result is invalid")
-    return result
+    return result, outputs
 
 
 # ======================================================================================================
@@ -976,6 +1037,39 @@ def run_c5(args, torch, nat, device):
         scorer.fit_stats_columns(cols)
         api_out["f64"], api_out["dewi32"] = scorer.score_batch_device(cols)
 
+    def loop(step, count):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(count):
+            step()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    for _ in range(args.warmup):
+        api_step()
+    elapsed = loop(api_step, args.steps)                      # THE timed region: the Python API
+    outputs = None
+    if args.dump_outputs:
+        outputs = {"dewi_f64": host_array(api_out["f64"]), "dewi_f32": host_array(api_out["dewi32"]),
+                   "i_hat": host_array(ihat_row),
+                   "medians": np.array([scorer.stats.medians[key] for key in SIGNAL_FIELDS], np.float64),
+                   "mads": np.array([scorer.stats.mads[key] for key in SIGNAL_FIELDS], np.float64)}
+    ms_per_step = elapsed / args.steps * 1e3
+    result = {
+        "metric": "documents/sec through the on-GPU scorer part of BASELINE.json configs[4]: I_hat row-cosine (d=512) + "
+                  "robust fit (7 signals) + DEWI score, 1M documents",
+        "value": round(args.steps * n / elapsed, 1), "unit": "documents/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f32 (fit, cosine) / f64 (score)", "data": "synthetic",
+        "config": {"workload": f"{n} documents: row-cosine of two {n}x{dim} fp32 matrices, exact median/MAD of 7 fp32 "
+                               f"signal columns, float64 DEWI score (BASELINE.json configs[4], scorer part)",
+                   "docs": n, "dim": dim, "signals": 7,
+                   "driven_by": "dewi.signals.cross_modal_similarity + DewiScorer.fit_stats_columns + score_batch_device "
+                                "on CUDA tensors (device-resident, no synchronisation inside a step)"},
+    }
+    if not args.full:
+        return result, outputs
+
     # ---- the same kernels through bare ctypes calls
     def fit():
         nat.check(lib.dewi_robust_fit_f32(nat.ptr(S), n, n, 7, nat.ptr(med), nat.ptr(mad), nat.ptr(ws), wsb, st))
@@ -997,19 +1091,8 @@ def run_c5(args, torch, nat, device):
         fit()
         score()
 
-    def loop(step, count):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(count):
-            step()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0
-
-    for _ in range(args.warmup):
-        api_step()
     for _ in range(args.warmup):
         raw_step()
-    elapsed = loop(api_step, args.steps)                      # THE timed region: the Python API
     raw_runs = [loop(raw_step, args.steps) for _ in range(3)]
     api_runs = [elapsed] + [loop(api_step, args.steps) for _ in range(2)]
     raw_ms = float(np.median(raw_runs)) / args.steps * 1e3
@@ -1036,35 +1119,22 @@ def run_c5(args, torch, nat, device):
     cos_bytes = 2 * n * dim * 4 + n * 4
     fit_bytes = 2 * 7 * n * 4                       # one median pass + one MAD pass
     score_bytes = 7 * n * 4 + n * 4
-    ms_per_step = elapsed / args.steps * 1e3
     cos_traffic, cos_note = recorded_traffic(f"rowcos_{n}x{dim}", "row_cosine_512_kernel<2>")
     fit_t = [recorded_traffic(f"fit_{ph}_7x{n}", f"fit_fast_kernel<{'true' if ph == 'mad' else 'false'}>")[0] for ph in ("med", "mad")]
     fit_note = recorded_traffic(f"fit_med_7x{n}", "fit_fast_kernel<false>")[1]
-    result = {
-        "metric": "documents/sec through the on-GPU scorer part of BASELINE.json configs[4]: I_hat row-cosine (d=512) + "
-                  "robust fit (7 signals) + DEWI score, 1M documents",
-        "value": round(args.steps * n / elapsed, 1), "unit": "documents/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f32 (fit, cosine) / f64 (score)", "data": "synthetic",
-        "config": {"workload": f"{n} documents: row-cosine of two {n}x{dim} fp32 matrices, exact median/MAD of 7 fp32 "
-                               f"signal columns, float64 DEWI score (BASELINE.json configs[4], scorer part)",
-                   "docs": n, "dim": dim, "signals": 7,
-                   "driven_by": "dewi.signals.cross_modal_similarity + DewiScorer.fit_stats_columns + score_batch_device "
-                                "on CUDA tensors (device-resident, no synchronisation inside a step)"},
-        "python_api_vs_c_abi": {"api_ms_per_step": round(api_ms, 5), "c_abi_ms_per_step": round(raw_ms, 5),
-                                "ratio": round(api_ms / raw_ms, 4), "results_bit_equal": same and stats_same},
-        "roofline": {"bound": "hbm", "kernel": "row_cosine_512_kernel", "achieved": round(cos_bytes / (cos_ms * 1e-3) / 1e9, 1),
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(cos_bytes / (cos_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                     "traffic": cos_traffic, "traffic_source": cos_note,
-                     "algorithmic_bytes_per_launch": cos_bytes, "mean_kernel_ms": round(cos_ms, 5),
-                     "launches_timed": MIN_ROOFLINE_LAUNCHES,
-                     "robust_fit": {"ms": round(fit_ms, 5), "algorithmic_bytes": fit_bytes,
-                                    "frac": round(fit_bytes / (fit_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                    "traffic": (fit_t[0] + fit_t[1]) if None not in fit_t else None,
-                                    "traffic_source": "fit_fast_kernel<false> + <true>, " + fit_note},
-                     "score": {"ms": round(score_ms, 5), "algorithmic_bytes": score_bytes,
-                               "frac": round(score_bytes / (score_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}},
-    }
+    result["python_api_vs_c_abi"] = {"api_ms_per_step": round(api_ms, 5), "c_abi_ms_per_step": round(raw_ms, 5),
+                                     "ratio": round(api_ms / raw_ms, 4), "results_bit_equal": same and stats_same}
+    result["roofline"] = {"bound": "hbm", "kernel": "row_cosine_512_kernel", "achieved": round(cos_bytes / (cos_ms * 1e-3) / 1e9, 1),
+                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(cos_bytes / (cos_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                          "traffic": cos_traffic, "traffic_source": cos_note,
+                          "algorithmic_bytes_per_launch": cos_bytes, "mean_kernel_ms": round(cos_ms, 5),
+                          "launches_timed": MIN_ROOFLINE_LAUNCHES,
+                          "robust_fit": {"ms": round(fit_ms, 5), "algorithmic_bytes": fit_bytes,
+                                         "frac": round(fit_bytes / (fit_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                         "traffic": (fit_t[0] + fit_t[1]) if None not in fit_t else None,
+                                         "traffic_source": "fit_fast_kernel<false> + <true>, " + fit_note},
+                          "score": {"ms": round(score_ms, 5), "algorithmic_bytes": score_bytes,
+                                    "frac": round(score_bytes / (score_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
     if args.cpu_queries > 0:
         orc, _ = oracle_imports()
         cols = {key: sig[j] for j, key in enumerate(orc.SIGNAL_KEYS)}
@@ -1091,7 +1161,7 @@ def run_c5(args, torch, nat, device):
         if not ok_fit or rel > 1e-15 or cerr > 2e-6:
             print(json.dumps(result))
             raise SystemExit("parity gate failed: the bench result is invalid")
-    return result
+    return result, outputs
 
 
 def free_port() -> int:
@@ -1157,14 +1227,16 @@ def main():
     eng.tuning(args.scan_blocks, args.rows_per_iter, args.nontemporal)
 
     if args.config == "c2":
-        result = run_c2(args, torch, dist, eng, nat, rank, world, device)
+        result, outputs = run_c2(args, torch, dist, eng, nat, rank, world, device)
     elif args.config == "c3":
-        result = run_c3(args, torch, eng, nat, device)
+        result, outputs = run_c3(args, torch, eng, nat, device)
     elif args.config == "c4":
-        result = run_c4(args, torch, eng, nat, device)
+        result, outputs = run_c4(args, torch, eng, nat, device)
     else:
-        result = run_c5(args, torch, nat, device)
+        result, outputs = run_c5(args, torch, nat, device)
     result["sources_sha256"] = sources_digest()[:16]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps(result, ensure_ascii=False))
     if dist.is_initialized():

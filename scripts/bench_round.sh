@@ -9,7 +9,7 @@ set -e
 TAG=${1:-r04}
 OUT=gpurun_out/bench_$TAG
 mkdir -p $OUT
-run() { local name=$1; shift; python3 bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { tail -20 $OUT/bench_$name.err; exit 1; }; cut -c1-260 $OUT/bench_$name.json; }
+run() { local name=$1; shift; python3 bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { tail -20 $OUT/bench_$name.err; exit 1; }; cut -c1-260 $OUT/bench_$name.json; }
 run c2
 run c2_steps20 --steps 20 --warmup 5
 run c2_steps20_condition0 --steps 20 --warmup 5 --condition-ms 0
@@ -51,5 +51,5 @@ run dim1024 --dim 1024 --cpu-queries 0
 run dim1024_batch1_shadow --dim 1024 --batch 1 --shadow 1 --cpu-queries 0
 run dim1536 --dim 1536 --cpu-queries 0
 run dim1536_batch1_shadow --dim 1536 --batch 1 --shadow 1 --cpu-queries 0
-DEWI_BENCH_FORCE_DIST=1 python3 bench.py --docs 125000 --steps 400 --warmup 40 --cpu-queries 0 > $OUT/bench_rccl_world1_125k.json 2> $OUT/bench_rccl_world1_125k.err
+DEWI_BENCH_FORCE_DIST=1 python3 bench.py --full --docs 125000 --steps 400 --warmup 40 --cpu-queries 0 > $OUT/bench_rccl_world1_125k.json 2> $OUT/bench_rccl_world1_125k.err
 cut -c1-200 $OUT/bench_rccl_world1_125k.json

@@ -14,7 +14,7 @@ COMMIT=${2:-unknown}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-Q="--cpu-queries 0 --latency-queries 0"
+Q="--full --cpu-queries 0 --latency-queries 0"
 trace() {   # name, bench args...
   local name=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$name -o bench -- python3 bench.py "$@" $Q > $OUT/bench_under_trace_$name.json 2> $OUT/trace_$name.err || { tail -20 $OUT/trace_$name.err; exit 1; }

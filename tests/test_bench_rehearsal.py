@@ -34,7 +34,7 @@ def test_bench_two_ranks_on_one_gpu(scaling, launcher):
              "127.0.0.1", "--master-port", str(_free_port())] if launcher == "torchrun" else [sys.executable])
     cmd = head + [str(repo / "bench.py"), "--gpus", "2", "--steps", "24", "--warmup", "6",
            "--docs", "150001" if scaling == "strong" else "80000", "--condition-ms", "5", "--latency-queries", "12",
-           "--scaling", scaling]
+           "--scaling", scaling, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(repo))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -50,3 +50,34 @@ def test_bench_two_ranks_on_one_gpu(scaling, launcher):
     else:
         assert d["config"]["docs"] == 160000 and d["config"]["rows_per_gpu"] == 80000
     assert d["p50_latency_ms"] > 0 and "cpu_baseline" not in d
+
+
+def test_bench_plain_and_full_dump_the_same_outputs(tmp_path):
+    """A plain run times its steps and prints the headline line only; --full adds the legs beside it (roofline, latency,
+    CPU baseline and parity gate).  Both, given --dump-outputs, write the ids and scores of the last timed step: the
+    inputs are seeded, so the two runs must write the same arrays."""
+    import numpy as np
+    repo = Path(__file__).resolve().parent.parent
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    lines = {}
+    for mode in ("plain", "full"):
+        cmd = [sys.executable, str(repo / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "4", "--docs", "100000",
+               "--condition-ms", "5", "--cpu-queries", "50", "--dump-outputs", str(tmp_path / mode)]
+        r = subprocess.run(cmd + (["--full"] if mode == "full" else []), capture_output=True, text=True, timeout=600,
+                           env=env, cwd=str(repo))
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[mode] = json.loads(out[0])
+    for d in lines.values():
+        assert d["steps"] == 20 and d["warmup"] == 4 and d["value"] > 0 and d["unit"] == "queries/s"
+        assert abs(d["ms_per_step"] - 1e3 / d["value"]) < 1e-3 * d["ms_per_step"] + 1e-4
+    assert not {"roofline", "cpu_baseline", "parity", "p50_latency_ms"} & set(lines["plain"])
+    assert {"roofline", "cpu_baseline", "parity", "p50_latency_ms"} <= set(lines["full"])
+    assert lines["full"]["parity"]["mismatches"] == 0
+    for name, dtype in (("ids", np.float64), ("scores", np.float32)):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype == dtype and a.shape == (1, 10)
+        assert np.array_equal(a, b)
+    ids = np.load(tmp_path / "plain" / "ids.npy")
+    assert ids.min() >= 0 and ids.max() < 100000 and len(np.unique(ids)) == 10

@@ -262,3 +262,31 @@ def test_profiles_readme_block_matches_the_committed_files():
     for tag in ("r03", "r04"):
         rc = subprocess.run([sys.executable, str(repo / "scripts" / "profiles_table.py"), tag, "--check"], cwd=repo).returncode
         assert rc == 0, f"profiles/{tag}/README.md: run `python scripts/profiles_table.py {tag}`"
+
+
+def test_bench_dump_outputs_types_and_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: integers and doubles are written as float64, the rest as float32; outputs that together
+    exceed the cap are cut to the same seeded sample of rows on every run, and the files stay under the cap."""
+    import bench
+    ids = np.arange(40, dtype=np.int64).reshape(4, 10)
+    sc = np.linspace(0, 1, 40, dtype=np.float32).reshape(4, 10)
+    bench.dump_outputs(tmp_path / "small", {"ids": ids, "scores": sc})
+    assert np.load(tmp_path / "small" / "ids.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "small" / "ids.npy"), ids)
+    assert np.array_equal(np.load(tmp_path / "small" / "scores.npy"), sc)
+    assert sorted(p.name for p in (tmp_path / "small").iterdir()) == ["ids.npy", "scores.npy"]
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    rs = np.random.RandomState(3)
+    big = {"col64": rs.rand(300_000), "col32": rs.rand(300_000).astype(np.float32), "stats": rs.rand(7)}
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, big)
+    total = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    assert total <= 1 << 20, total
+    for name in ("col64", "col32"):
+        rows = np.load(tmp_path / "a" / f"{name}_rows.npy")
+        assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0)
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert np.array_equal(got, big[name][rows.astype(np.int64)])
+        assert np.array_equal(rows, np.load(tmp_path / "b" / f"{name}_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "stats.npy"), big["stats"])
