@@ -158,8 +158,9 @@ dewi::RerankParams make_rerank(double eta, double pref, int transform = DEWI_SIM
 }
 
 // Steps 1-3 for every query: fills the keys region of the workspace.
+// d_filter (fp32 corpus only): scan the rows of that prepared filter instead (L planned on the filter's length).
 int run_scan(const KnnLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_Q,
-             int n_queries, int n_candidates, int space, char* ws, hipStream_t stream) {
+             int n_queries, int n_candidates, int space, char* ws, hipStream_t stream, const uint32_t* d_filter = nullptr) {
   uint64_t* keys = reinterpret_cast<uint64_t*>(ws + L.keys_off);
   float* qn = reinterpret_cast<float*>(ws + L.qn_off);
   hipError_t e;
@@ -174,7 +175,10 @@ int run_scan(const KnnLayout& L, const void* d_E, int elem_type, int64_t n_rows,
     static const bool nq8_enabled = [] { const char* e = getenv("DEWI_SCAN_NQ8"); return e == nullptr || atoi(e) != 0; }();
     const bool can8 = !elem_type && L.plan.fast && L.plan.slots == 1 && nq8_enabled;
     const int nq = (can8 && n_queries - q >= 8) ? 8 : ((L.plan.nq_max > 1 && n_queries - q >= L.plan.nq_max) ? L.plan.nq_max : 1);
-    if (elem_type)
+    if (d_filter)
+      e = dewi::launch_scan_f32_filtered(L.plan, static_cast<const float*>(d_E), dim, d_Q, L.plan.raw_queries ? nullptr : qn, q, nq,
+                                         n_candidates, space, keys, d_filter, stream);
+    else if (elem_type)
       e = dewi::launch_scan_bf16(L.plan, static_cast<const uint16_t*>(d_E), n_rows, dim, d_Q, L.plan.raw_queries ? nullptr : qn,
                                  q, nq, n_candidates, space, keys, stream);
     else
@@ -753,6 +757,107 @@ int dewi_knn_candidates(const void* d_E, int elem_type, int64_t n_rows, int dim,
   if (rc) return rc;
   return batch_select(P, d_workspace, workspace_bytes, n_queries, n_candidates, 0, make_rerank(0.0, 0.0), d_dewi32, d_ent32,
                       id_offset, nullptr, nullptr, d_out, stream, d_E, elem_type, n_rows, dim, space, d_Q);
+}
+
+// ---- filtered search (ABI 6) ----------------------------------------------------------------------------------------
+// buckets of a prepared filter: the residue period of rows that are not whole 16-byte units where the row kernels take their
+// PH form (scan_any.hpp), else 1
+static int filter_buckets(int dim, int elem_type) {
+  const int elem_bytes = elem_type ? 2 : 4;
+  const dewi::ScanPlan p = dewi::plan_scan(1, dim, elem_bytes, 1, 1, dewi::Tuning{0, 0, -1, 1});
+  if (!p.odd_rows) return 1;
+  const int row_bytes = dim * elem_bytes;
+  int tz = 0;   // G = 16 / gcd(16, row bytes), as the kernels' row_step
+  while (tz < 4 && (row_bytes >> tz) % 2 == 0) ++tz;
+  return 16 >> tz;
+}
+
+size_t dewi_filter_bytes(int64_t n_rows, int dim, int elem_type) {
+  if (n_rows <= 0 || n_rows > 0xFFFFFFFFll || dim <= 0 || (elem_type != 0 && elem_type != 1)) return 0;
+  const int g = filter_buckets(dim, elem_type);
+  return 4 * (static_cast<size_t>(dewi::kFilterHeaderWords) + static_cast<size_t>(n_rows) + dewi::filter_scratch_words(n_rows, g));
+}
+
+int dewi_filter_prepare(int elem_type, int64_t n_rows, int dim, const uint8_t* d_mask, void* d_filter, size_t filter_bytes,
+                        int64_t* out_n_allowed, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!d_mask || !d_filter || !out_n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (elem_type != 0 && elem_type != 1) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+  if (n_rows <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
+  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  const size_t need = dewi_filter_bytes(n_rows, dim, elem_type);
+  if (filter_bytes < need) return fail(DEWI_ERR_WORKSPACE, "filter buffer %zu B < required %zu B", filter_bytes, need);
+  uint32_t* filt = static_cast<uint32_t*>(d_filter);
+  const int g = filter_buckets(dim, elem_type);
+  hipError_t e = dewi::launch_filter_prepare(d_mask, n_rows, g, filt, filt + dewi::kFilterHeaderWords + n_rows, stream);
+  if (e != hipSuccess) return hip_fail(e, "filter_prepare launch");
+  uint32_t count = 0;
+  e = hipMemcpyAsync(&count, filt + dewi::kFilterMaxBuckets, sizeof(count), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hip_fail(e, "filter count read-back");
+  *out_n_allowed = static_cast<int64_t>(count);
+  return DEWI_OK;
+}
+
+size_t dewi_knn_filtered_workspace_bytes(int64_t n_allowed, int dim, int n_queries, int n_candidates) {
+  DeviceInfo dev;
+  if (ensure_device(dev)) return 0;
+  if (n_allowed <= 0 || dim <= 0 || n_queries <= 0 || n_candidates <= 0) return 0;
+  const int c = n_candidates < n_allowed ? n_candidates : static_cast<int>(n_allowed);
+  return layout_knn(n_allowed, dim, 4, n_queries, c, dev.cus).total;
+}
+
+int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_allowed,
+                             const float* d_Q, int n_queries, const float* d_dewi32, const float* d_ent32, int k, int n_candidates,
+                             int sim_transform, double eta, double entropy_pref, int space, int64_t* d_out_ids,
+                             float* d_out_scores, void* d_workspace, size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  int rc = check_common(d_E, n_rows, dim, d_Q, n_queries, space);
+  if (rc) return rc;
+  if (elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "filtered search serves fp32 corpora (bf16: not in this build)");
+  if (elem_type != 0) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+  if (!d_filter) return fail(DEWI_ERR_INVALID_ARG, "null filter pointer");
+  if (n_allowed < 0 || n_allowed > n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+  if (sim_transform != DEWI_SIM_RAW && sim_transform != DEWI_SIM_ONE_MINUS_DIST && sim_transform != DEWI_SIM_INV_ONE_PLUS_DIST)
+    return fail(DEWI_ERR_INVALID_ARG, "unknown sim_transform %d", sim_transform);
+  if (sim_transform != DEWI_SIM_RAW && n_candidates <= 0)
+    return fail(DEWI_ERR_INVALID_ARG, "similarity transforms belong to the ANN re-rank rule: pass n_candidates as well");
+  // the reference's rule on a score vector of length |A| (backends.py:439-441, 468): no candidates -> nothing; k > |A| -> error
+  if (k <= 0 || n_allowed == 0) return DEWI_OK;
+  if (k > n_allowed)
+    return fail(DEWI_ERR_K_OUT_OF_BOUNDS, "kth(=%lld) out of bounds (%lld)", static_cast<long long>(n_allowed - k),
+                static_cast<long long>(n_allowed));
+  if (!d_dewi32 || !d_ent32 || !d_out_ids || !d_out_scores) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
+  int64_t c64 = (2ll * k < n_allowed) ? 2ll * k : n_allowed;
+  if (n_candidates > 0) {
+    if (n_candidates < k) return fail(DEWI_ERR_INVALID_ARG, "n_candidates %d must be at least k = %d", n_candidates, k);
+    c64 = n_candidates < n_allowed ? n_candidates : n_allowed;
+  }
+  if (c64 > (1ll << 30)) return fail(DEWI_ERR_UNSUPPORTED, "candidate count %lld exceeds 2^30", static_cast<long long>(c64));
+  const int c = static_cast<int>(c64);
+  DeviceInfo dev;
+  rc = ensure_device(dev);
+  if (rc) return rc;
+  // the row kernels of this dim, planned on |A| rows (grid, lists or dense keys, keys per query); no matrix-core pass
+  const KnnLayout L = layout_knn(n_allowed, dim, 4, n_queries, c, dev.cus);
+  if (!d_workspace || workspace_bytes < L.total)
+    return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, L.total);
+  char* ws = static_cast<char*>(d_workspace);
+  rc = run_scan(L, d_E, 0, n_allowed, dim, d_Q, n_queries, c, space, ws, stream, static_cast<const uint32_t*>(d_filter));
+  if (rc) return rc;
+  const dewi::RerankParams rp = make_rerank(eta, entropy_pref, sim_transform, space);
+  const uint64_t* keys = reinterpret_cast<const uint64_t*>(ws + L.keys_off);
+  hipError_t e;
+  if (c > dewi::kMaxSortCandidates) {
+    uint64_t* g1 = reinterpret_cast<uint64_t*>(ws + L.big_off);
+    e = dewi::launch_select_rerank_large(keys, L.plan.keys_per_query, n_queries, c, L.p2, k, rp, d_dewi32, d_ent32, 0, g1,
+                                         g1 + static_cast<size_t>(n_queries) * L.p2, d_out_ids, d_out_scores, nullptr, c, stream);
+  } else {
+    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, L.plan.slots == 1 ? L.plan.n_lists : 0, n_queries, c, k, rp,
+                                   d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr, nullptr, dewi::SegmentLayout{}, stream);
+  }
+  return e == hipSuccess ? DEWI_OK : hip_fail(e, "select launch (filtered)");
 }
 
 size_t dewi_merge_workspace_bytes(int n_lists, int n_queries, int list_len, int n_candidates) {

@@ -26,11 +26,13 @@ namespace dewi {
 // ---------------------------------------------------------------------------------------------
 // S = key slots per lane: 1 (c <= 64, block-merged sorted output, one list per workgroup),
 // 4 (c <= 256, one unsorted list per wave) or 0 (dense: one key per row).
-template <int U, int R, int NQ, int SPACE, int S, bool NT>
+// LIST (filtered scan): the rows are the list of a prepared filter `filt` (scan_common.hpp, one bucket) instead of
+// 0 .. n_rows; `n_rows` is then unused and a dense key goes to the list position.
+template <int U, int R, int NQ, int SPACE, int S, bool NT, bool LIST = false>
 __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, int64_t n_rows,
                                                    const float* __restrict__ Q, int n_candidates,
                                                    uint64_t* __restrict__ keys, int64_t keys_per_query,
-                                                   MergeShared& merge_buf) {
+                                                   MergeShared& merge_buf, const uint32_t* __restrict__ filt = nullptr) {
   constexpr int D4 = 64 * U;  // float4 units per row
   constexpr bool DENSE = S == 0;
   const int lane = lane_id();
@@ -72,7 +74,14 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
   }
 
   const f32x4* Ev = reinterpret_cast<const f32x4*>(E);
-  auto consume = [&](const f32x4(&v)[U], int64_t row) {
+  [[maybe_unused]] const uint32_t* __restrict__ list = filt + kFilterHeaderWords;
+  if constexpr (LIST) n_rows = filt[kFilterMaxBuckets];   // (one bucket; the prepare step fills the unused offsets with the count)
+  auto row_of = [&](int64_t i) -> int64_t {   // list position -> row (wave-uniform)
+    if constexpr (LIST) return list_row(list, i);
+    else return i;
+  };
+  // slot: where a dense key goes (the row; LIST: the list position)
+  auto consume = [&](const f32x4(&v)[U], int64_t row, int64_t slot) {
 #pragma unroll
     for (int qi = 0; qi < NQ; ++qi) {
       float acc = 0.f;
@@ -81,7 +90,7 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
       float s = wave_sum_f32(acc);
       if constexpr (SPACE == DEWI_SPACE_L2) s = -s;
       if constexpr (DENSE) {
-        if (lane == 0) keys[qi * keys_per_query + row] = make_key(s, static_cast<uint32_t>(row));
+        if (lane == 0) keys[qi * keys_per_query + slot] = make_key(s, static_cast<uint32_t>(row));
       } else {
         lst[qi].offer(s, static_cast<uint32_t>(row), lane);
       }
@@ -94,25 +103,52 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
   // apart, so that the chip still sweeps one window: 0.437 vs 0.429) — more outstanding requests lower
   // the achieved HBM rate instead of raising it.
   const int64_t n_groups = n_rows / R;
+  if constexpr (LIST) {
+    // The list entries of this wave's next 64 groups arrive in one vector load (lane l: group g + l * n_waves) and are read
+    // out with readlane: a row's address never waits for a load of its own list entry.
+    uint32_t ahead[R];
+    int slot = 0;
+    for (int64_t g = gwave; g < n_groups; g += n_waves) {
+      if (slot == 0) {
+        const int64_t gl = g + static_cast<int64_t>(lane) * n_waves;
+#pragma unroll
+        for (int r = 0; r < R; ++r) ahead[r] = gl < n_groups ? list[gl * R + r] : 0u;
+      }
+      const int64_t row0 = g * R;
+      int64_t rows[R];
+      f32x4 v[R][U];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        rows[r] = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(ahead[r]), slot));
+        const f32x4* p = Ev + rows[r] * D4 + lane;
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[r][u] = load_x4<NT>(p + u * 64);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) consume(v[r], rows[r], row0 + r);
+      slot = (slot + 1) & (kWave - 1);
+    }
+  } else {
   for (int64_t g = gwave; g < n_groups; g += n_waves) {
     const int64_t row0 = g * R;
     f32x4 v[R][U];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const f32x4* p = Ev + (row0 + r) * D4 + lane;
+      const f32x4* p = Ev + row_of(row0 + r) * D4 + lane;
 #pragma unroll
       for (int u = 0; u < U; ++u) v[r][u] = load_x4<NT>(p + u * 64);
     }
 #pragma unroll
-    for (int r = 0; r < R; ++r) consume(v[r], row0 + r);
+    for (int r = 0; r < R; ++r) consume(v[r], row_of(row0 + r), row0 + r);
+  }
   }
   // Remainder rows (fewer than R), one per wave.
   for (int64_t row = n_groups * R + gwave; row < n_rows; row += n_waves) {
     f32x4 v[U];
-    const f32x4* p = Ev + row * D4 + lane;
+    const f32x4* p = Ev + row_of(row) * D4 + lane;
 #pragma unroll
     for (int u = 0; u < U; ++u) v[u] = load_x4<NT>(p + u * 64);
-    consume(v, row);
+    consume(v, row_of(row), row);
   }
 
   if constexpr (S == 1) {
@@ -134,6 +170,15 @@ __global__ __launch_bounds__(kScanThreads) void scan_rows_f32(const float* __res
                                                               int64_t keys_per_query) {
   __shared__ MergeShared merge_buf;
   scan_rows_f32_body<U, R, NQ, SPACE, S, NT>(E, n_rows, Q, n_candidates, keys, keys_per_query, merge_buf);
+}
+
+// filtered scan: the rows of a prepared filter; keys_per_query comes from the plan on the list's length
+template <int U, int R, int NQ, int SPACE, int S, bool NT>
+__global__ __launch_bounds__(kScanThreads) void scan_rows_f32_list(const float* __restrict__ E, const uint32_t* __restrict__ filt,
+                                                                   const float* __restrict__ Q, int n_candidates,
+                                                                   uint64_t* __restrict__ keys, int64_t keys_per_query) {
+  __shared__ MergeShared merge_buf;
+  scan_rows_f32_body<U, R, NQ, SPACE, S, NT, true>(E, 0, Q, n_candidates, keys, keys_per_query, merge_buf, filt);
 }
 
 // REPAIR form (abi.cpp batch_repair): one launch answers every query of a batch whose flag is set — the queries a
@@ -227,6 +272,92 @@ __global__ __launch_bounds__(kScanThreads) void scan_generic_f32(const float* __
           if (lane == 0) keys[qi * keys_per_query + rr] = make_key(s, static_cast<uint32_t>(rr));
         } else {
           lst[qi].offer(s, static_cast<uint32_t>(rr), lane);
+        }
+      }
+    }
+  }
+  if constexpr (S == 1) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi)
+      block_merge_store(lst[qi], merge_buf, keys + qi * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates,
+                        n_candidates, lane, wave_in_block);
+  } else if constexpr (!DENSE) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi)
+      lst[qi].store(keys + qi * keys_per_query + gwave * n_candidates, n_candidates, lane);
+  }
+}
+
+// Filtered scan: the same kernel over the list positions of a prepared filter (scan_common.hpp); the row comes from the
+// list, a dense key goes to the list position.
+template <int VEC, int NQ, int SPACE, int S>
+__global__ __launch_bounds__(kScanThreads) void scan_generic_f32_list(const float* __restrict__ E, const uint32_t* __restrict__ filt, int dim,
+                                                                      const float* __restrict__ Qn, int group,
+                                                                      int n_candidates, uint64_t* __restrict__ keys,
+                                                                      int64_t keys_per_query) {
+  using V = typename VecT<VEC>::type;
+  constexpr bool DENSE = S == 0;
+  __shared__ MergeShared merge_buf;
+  const int lane = lane_id();
+  const int wave_in_block = static_cast<int>(threadIdx.x) >> 6;
+  const int64_t gwave = static_cast<int64_t>(blockIdx.x) * (kScanThreads / kWave) + wave_in_block;
+  const int64_t n_waves = static_cast<int64_t>(gridDim.x) * (kScanThreads / kWave);
+  const int rows_per_step = kWave / group;
+  const int sub = lane / group;  // which row of the step
+  const int lg = lane % group;   // position inside the row group
+  const int units = dim / VEC;
+  const uint32_t* __restrict__ list = filt + kFilterHeaderWords;
+  const int64_t n_rows = filt[kFilterMaxBuckets];   // list positions (every bucket in order); the prepare step fills the
+                                                    // offsets past the last bucket with the count
+
+  WaveList<DENSE ? 1 : S> lst[DENSE ? 1 : NQ];
+  if constexpr (!DENSE) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) lst[qi].init(n_candidates, lane);
+  }
+
+  const int64_t n_steps = (n_rows + rows_per_step - 1) / rows_per_step;
+  for (int64_t st = gwave; st < n_steps; st += n_waves) {
+    const int64_t row = st * rows_per_step + sub;
+    float acc[NQ];
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) acc[qi] = 0.f;
+    if (row < n_rows) {
+      const V* ep = reinterpret_cast<const V*>(E + static_cast<int64_t>(list[row]) * dim);
+      for (int u = lg; u < units; u += group) {
+        const V e = ep[u];
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi) {
+          const V q = reinterpret_cast<const V*>(Qn + static_cast<int64_t>(qi) * dim)[u];
+          if constexpr (VEC == 4) {
+            acc[qi] = accum4<SPACE>(e, q, acc[qi]);
+          } else {
+            if constexpr (SPACE == DEWI_SPACE_COSINE) {
+              acc[qi] = __builtin_fmaf(e, q, acc[qi]);
+            } else {
+              const float d = e - q;
+              acc[qi] = __builtin_fmaf(d, d, acc[qi]);
+            }
+          }
+        }
+      }
+    }
+    // butterfly inside each group of `group` lanes
+    for (int off = group >> 1; off > 0; off >>= 1) {
+#pragma unroll
+      for (int qi = 0; qi < NQ; ++qi) acc[qi] += __shfl_xor(acc[qi], off, kWave);
+    }
+    for (int r = 0; r < rows_per_step; ++r) {
+      const int64_t rr = st * rows_per_step + r;
+      if (rr >= n_rows) break;
+#pragma unroll
+      for (int qi = 0; qi < NQ; ++qi) {
+        float s = __shfl(acc[qi], r * group, kWave);
+        if constexpr (SPACE == DEWI_SPACE_L2) s = -s;
+        if constexpr (DENSE) {
+          if (lane == 0) keys[qi * keys_per_query + rr] = make_key(s, list[rr]);
+        } else {
+          lst[qi].offer(s, list[rr], lane);
         }
       }
     }
@@ -466,9 +597,19 @@ ScanPlan plan_scan(int64_t n_rows, int dim, int elem_bytes, int n_candidates, in
   return p;
 }
 
-template <int U, int R, int NQ, int SPACE, int S>
+// LIST: the filtered scan over the prepared filter `filt` (n_rows unused)
+template <int U, int R, int NQ, int SPACE, int S, bool LIST>
 static void launch_fast_nt(const ScanPlan& plan, const float* E, int64_t n_rows, const float* Q, int c,
-                           uint64_t* keys, hipStream_t stream) {
+                           uint64_t* keys, hipStream_t stream, const uint32_t* filt) {
+  if constexpr (LIST) {
+    if (plan.nontemporal)
+      hipLaunchKernelGGL((scan_rows_f32_list<U, R, NQ, SPACE, S, true>), dim3(plan.blocks), dim3(kScanThreads), 0,
+                         stream, E, filt, Q, c, keys, plan.keys_per_query);
+    else
+      hipLaunchKernelGGL((scan_rows_f32_list<U, R, NQ, SPACE, S, false>), dim3(plan.blocks), dim3(kScanThreads), 0,
+                         stream, E, filt, Q, c, keys, plan.keys_per_query);
+    return;
+  }
   if (plan.nontemporal)
     hipLaunchKernelGGL((scan_rows_f32<U, R, NQ, SPACE, S, true>), dim3(plan.blocks), dim3(kScanThreads), 0,
                        stream, E, n_rows, Q, c, keys, plan.keys_per_query);
@@ -477,50 +618,59 @@ static void launch_fast_nt(const ScanPlan& plan, const float* E, int64_t n_rows,
                        stream, E, n_rows, Q, c, keys, plan.keys_per_query);
 }
 
-template <int U, int NQ, int SPACE, int S>
+template <int U, int NQ, int SPACE, int S, bool LIST>
 static bool launch_fast_r(const ScanPlan& plan, const float* E, int64_t n_rows, const float* Q, int c,
-                          uint64_t* keys, hipStream_t stream) {
+                          uint64_t* keys, hipStream_t stream, const uint32_t* filt) {
   // R only changes how rows are grouped per wave; results do not depend on it.  Combinations that
   // are not instantiated (register budget, build time) step down to the next smaller R.
   const int r = NQ >= 4 ? plan.rows_per_iter_batch : plan.rows_per_iter;
   if (r >= 8) {
     if constexpr (U <= 3 && NQ == 1 && S == 1) {
-      launch_fast_nt<U, 8, NQ, SPACE, S>(plan, E, n_rows, Q, c, keys, stream);
+      launch_fast_nt<U, 8, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
       return true;
     }
   }
   if (r >= 4) {
     if constexpr (U <= 3 && NQ == 1) {
-      launch_fast_nt<U, 4, NQ, SPACE, S>(plan, E, n_rows, Q, c, keys, stream);
+      launch_fast_nt<U, 4, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
       return true;
     }
   }
   if (r >= 2) {
     if constexpr (U <= 3) {
-      launch_fast_nt<U, 2, NQ, SPACE, S>(plan, E, n_rows, Q, c, keys, stream);
+      launch_fast_nt<U, 2, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
       return true;
     }
   }
-  launch_fast_nt<U, 1, NQ, SPACE, S>(plan, E, n_rows, Q, c, keys, stream);
+  launch_fast_nt<U, 1, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
   return true;
 }
 
-template <int NQ, int SPACE, int S>
+template <int NQ, int SPACE, int S, bool LIST>
 static bool launch_fast_u(const ScanPlan& plan, int dim, const float* E, int64_t n_rows, const float* Q, int c,
-                          uint64_t* keys, hipStream_t stream) {
+                          uint64_t* keys, hipStream_t stream, const uint32_t* filt) {
   switch (dim / 256) {
-    case 1: return launch_fast_r<1, NQ, SPACE, S>(plan, E, n_rows, Q, c, keys, stream);
-    case 2: return launch_fast_r<2, NQ, SPACE, S>(plan, E, n_rows, Q, c, keys, stream);
-    case 3: return launch_fast_r<3, NQ, SPACE, S>(plan, E, n_rows, Q, c, keys, stream);
-    case 4: return launch_fast_r<4, NQ, SPACE, S>(plan, E, n_rows, Q, c, keys, stream);
-    case 6: return launch_fast_r<6, NQ, SPACE, S>(plan, E, n_rows, Q, c, keys, stream);
+    case 1: return launch_fast_r<1, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
+    case 2: return launch_fast_r<2, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
+    case 3: return launch_fast_r<3, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
+    case 4: return launch_fast_r<4, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
+    case 6: return launch_fast_r<6, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
     default: return false;
   }
 }
 
-template <int NQ, int SPACE, int S>
+template <int NQ, int SPACE, int S, bool LIST>
 static void launch_generic(const ScanPlan& plan, int dim, const float* E, int64_t n_rows, const float* Qn, int c,
-                           uint64_t* keys, hipStream_t stream) {
+                           uint64_t* keys, hipStream_t stream, const uint32_t* filt) {
+  if constexpr (LIST) {
+    if (plan.vec == 4)
+      hipLaunchKernelGGL((scan_generic_f32_list<4, NQ, SPACE, S>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E,
+                         filt, dim, Qn, plan.group, c, keys, plan.keys_per_query);
+    else
+      hipLaunchKernelGGL((scan_generic_f32_list<1, NQ, SPACE, S>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E,
+                         filt, dim, Qn, plan.group, c, keys, plan.keys_per_query);
+    return;
+  }
   if (plan.vec == 4)
     hipLaunchKernelGGL((scan_generic_f32<4, NQ, SPACE, S>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E,
                        n_rows, dim, Qn, plan.group, c, keys, plan.keys_per_query);
@@ -529,13 +679,13 @@ static void launch_generic(const ScanPlan& plan, int dim, const float* E, int64_
                        n_rows, dim, Qn, plan.group, c, keys, plan.keys_per_query);
 }
 
-template <int NQ, int SPACE, int S>
+template <int NQ, int SPACE, int S, bool LIST = false>
 static hipError_t launch_scan_impl(const ScanPlan& plan, const float* E, int64_t n_rows, int dim, const float* Qraw,
-                                   const float* Qn, int c, uint64_t* keys, hipStream_t stream) {
+                                   const float* Qn, int c, uint64_t* keys, hipStream_t stream, const uint32_t* filt = nullptr) {
   if (plan.fast) {
-    if (!launch_fast_u<NQ, SPACE, S>(plan, dim, E, n_rows, Qraw, c, keys, stream)) return hipErrorInvalidValue;
+    if (!launch_fast_u<NQ, SPACE, S, LIST>(plan, dim, E, n_rows, Qraw, c, keys, stream, filt)) return hipErrorInvalidValue;
   } else {
-    launch_generic<NQ, SPACE, S>(plan, dim, E, n_rows, Qn, c, keys, stream);
+    launch_generic<NQ, SPACE, S, LIST>(plan, dim, E, n_rows, Qn, c, keys, stream, filt);
   }
   return hipGetLastError();
 }
@@ -593,20 +743,25 @@ hipError_t launch_scan_flagged_f32(const ScanPlan& plan, const float* d_E, int64
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_scan_f32(const ScanPlan& plan, const float* d_E, int64_t n_rows, int dim, const float* d_q_raw,
-                           const float* d_q_norm, int q0, int nq, int n_candidates, int space, uint64_t* d_keys,
-                           hipStream_t stream) {
-  if (plan.odd_rows) return launch_scan_odd_f32(plan, d_E, n_rows, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, stream);
+// LIST: the filtered scan over the prepared filter `filt` (n_rows unused)
+template <bool LIST>
+static hipError_t scan_f32_dispatch(const ScanPlan& plan, const float* d_E, int64_t n_rows, int dim, const float* d_q_raw,
+                                    const float* d_q_norm, int q0, int nq, int n_candidates, int space, uint64_t* d_keys,
+                                    hipStream_t stream, const uint32_t* filt) {
+  if (plan.odd_rows)
+    return LIST ? launch_scan_odd_f32_list(plan, d_E, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, filt, stream)
+                : launch_scan_odd_f32(plan, d_E, n_rows, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, stream);
   if (plan.kind == kScanAnyLong || plan.kind == kScanAnyShort)
-    return launch_scan_any_f32(plan, d_E, n_rows, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, stream);
+    return LIST ? launch_scan_any_f32_list(plan, d_E, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, filt, stream)
+                : launch_scan_any_f32(plan, d_E, n_rows, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, stream);
   const float* qr = d_q_raw + static_cast<int64_t>(q0) * dim;
   const float* qn = d_q_norm ? d_q_norm + static_cast<int64_t>(q0) * dim : nullptr;
   uint64_t* keys = d_keys + static_cast<int64_t>(q0) * plan.keys_per_query;
 #define DEWI_DISPATCH_S(NQ, SPACE)                                                                              \
   switch (plan.slots) {                                                                                          \
-    case 0: return launch_scan_impl<NQ, SPACE, 0>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream);   \
-    case 1: return launch_scan_impl<NQ, SPACE, 1>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream);   \
-    default: return launch_scan_impl<NQ, SPACE, kMaxSlots>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream); \
+    case 0: return launch_scan_impl<NQ, SPACE, 0, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt);   \
+    case 1: return launch_scan_impl<NQ, SPACE, 1, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt);   \
+    default: return launch_scan_impl<NQ, SPACE, kMaxSlots, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt); \
   }
 #define DEWI_DISPATCH(NQ)                                  \
   if (space == DEWI_SPACE_COSINE) {                        \
@@ -620,12 +775,24 @@ hipError_t launch_scan_f32(const ScanPlan& plan, const float* d_E, int64_t n_row
     DEWI_DISPATCH(4)
   } else if (nq == 8 && plan.fast && plan.slots == 1) {   // eight queries per corpus pass: row-per-wave kernel, c <= 64 only
     if (space == DEWI_SPACE_COSINE)
-      return launch_scan_impl<8, DEWI_SPACE_COSINE, 1>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream);
-    return launch_scan_impl<8, DEWI_SPACE_L2, 1>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream);
+      return launch_scan_impl<8, DEWI_SPACE_COSINE, 1, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt);
+    return launch_scan_impl<8, DEWI_SPACE_L2, 1, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt);
   }
 #undef DEWI_DISPATCH
 #undef DEWI_DISPATCH_S
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_scan_f32(const ScanPlan& plan, const float* d_E, int64_t n_rows, int dim, const float* d_q_raw,
+                           const float* d_q_norm, int q0, int nq, int n_candidates, int space, uint64_t* d_keys,
+                           hipStream_t stream) {
+  return scan_f32_dispatch<false>(plan, d_E, n_rows, dim, d_q_raw, d_q_norm, q0, nq, n_candidates, space, d_keys, stream, nullptr);
+}
+
+hipError_t launch_scan_f32_filtered(const ScanPlan& plan, const float* d_E, int dim, const float* d_q_raw, const float* d_q_norm,
+                                    int q0, int nq, int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter,
+                                    hipStream_t stream) {
+  return scan_f32_dispatch<true>(plan, d_E, 0, dim, d_q_raw, d_q_norm, q0, nq, n_candidates, space, d_keys, stream, d_filter);
 }
 
 }  // namespace dewi

@@ -107,6 +107,27 @@ hipError_t launch_scan_f32(const ScanPlan& plan, const float* d_E, int64_t n_row
                            const float* d_q_norm, int q0, int nq, int n_candidates, int space, uint64_t* d_keys,
                            hipStream_t stream);
 
+// Filtered scan (fp32 corpus): the same pass over the rows of a prepared filter (d_filter: dewi_filter_prepare's buffer, see
+// scan_common.hpp kFilterHeaderWords) — plan made on the list's length, keys_per_query keys per query, dense keys at list
+// positions; the kernel family is the one launch_scan_f32 takes for this dim (never scan_rows_odd_contig).
+hipError_t launch_scan_f32_filtered(const ScanPlan& plan, const float* d_E, int dim, const float* d_q_raw, const float* d_q_norm,
+                                    int q0, int nq, int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter,
+                                    hipStream_t stream);
+hipError_t launch_scan_any_f32_list(const ScanPlan& plan, const float* d_E, int dim, const float* d_q_raw, int q0, int nq,
+                                    int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter, hipStream_t stream);
+hipError_t launch_scan_odd_f32_list(const ScanPlan& plan, const float* d_E, int dim, const float* d_q_raw, int q0, int nq,
+                                    int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter, hipStream_t stream);
+// Layout of a prepared filter (u32 words): bucket offsets [0 .. kFilterMaxBuckets] (past the last bucket: the count), the
+// number of buckets at [kFilterMaxBuckets + 1], the allowed rows from kFilterHeaderWords on (filter.hip).
+constexpr int kFilterHeaderWords = 16;
+constexpr int kFilterMaxBuckets = 8;
+// Filter preparation (filter.hip): byte mask [n_rows] -> bucketed sorted row list, n_buckets = the residue period of the
+// rows (1 for whole 16-byte units); d_scratch: filter_scratch_words(n_rows, n_buckets) u32; d_count: the list's length.
+int64_t filter_blocks(int64_t n_rows);
+size_t filter_scratch_words(int64_t n_rows, int n_buckets);
+hipError_t launch_filter_prepare(const uint8_t* d_mask, int64_t n_rows, int n_buckets, uint32_t* d_filter, uint32_t* d_scratch,
+                                 hipStream_t stream);
+
 // ---- knn_scan_any_f32.hip / knn_scan_any_bf16.hip: plan.kind == kScanAnyLong / kScanAnyShort (raw queries)
 hipError_t launch_scan_any_f32(const ScanPlan& plan, const float* d_E, int64_t n_rows, int dim, const float* d_q_raw, int q0,
                                int nq, int n_candidates, int space, uint64_t* d_keys, hipStream_t stream);

@@ -176,10 +176,13 @@ constexpr int kAnyShortRows = DEWI_ANY_RSHORT;   // loads (of 64 / P rows each) 
 // 33 .. 64 U units per row
 // ---------------------------------------------------------------------------------------------
 // `units`: 16-byte units per row; PH (rows that are not whole units): COLUMNS per row instead.
-template <int ELEM, int U, int R, int NQ, int SPACE, int S, bool PH = false>
+// LIST (filtered scan): the rows are the list of a prepared filter `filt` (scan_common.hpp) instead of 0 .. n_rows; `n_rows` is
+// then unused.  A wave takes list entries of one bucket (PH: one residue, as above); dense keys go to the list position.
+template <int ELEM, int U, int R, int NQ, int SPACE, int S, bool PH = false, bool LIST = false>
 __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, int64_t n_rows, int units,
                                                    const float* __restrict__ Q, int n_candidates,
-                                                   uint64_t* __restrict__ keys, int64_t keys_per_query, MergeShared& merge_buf) {
+                                                   uint64_t* __restrict__ keys, int64_t keys_per_query, MergeShared& merge_buf,
+                                                   const uint32_t* __restrict__ filt = nullptr) {
   constexpr int kCols = ELEM ? 8 : 4;
   constexpr int kElemBytes = ELEM ? 2 : 4;
   constexpr bool DENSE = S == 0;
@@ -193,15 +196,30 @@ __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, 
   // PH: this wave takes the rows ph, ph + G, ph + 2 G, ... — all of them start head_el columns into their first unit
   int row_step = 1, ph = 0, off0 = 0, head_el = 0, row_bytes = 0;
   int64_t wave_pos = gwave, wave_cnt = n_waves;      // this wave's place among the waves that share its rows
+  [[maybe_unused]] int64_t list_base = 0, list_count = 0;
+  if constexpr (LIST && !PH) {
+    const ListPart part = list_part(filt, 1, gwave, n_waves);
+    list_base = part.base;
+    list_count = part.count;
+  }
   if constexpr (PH) {
     off0 = static_cast<int>(reinterpret_cast<uintptr_t>(E) & 15u);
     E = reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(E) - off0);   // (pointer arithmetic: stays a global pointer)
     row_bytes = dim * kElemBytes;
     const int tz = __builtin_ctz(static_cast<unsigned>(row_bytes) | 16u);   // row_step = 16 / gcd(16, row bytes)
     row_step = 16 >> tz;
-    ph = static_cast<int>(gwave & (row_step - 1));
-    wave_pos = gwave >> (4 - tz);
-    wave_cnt = (n_waves - ph + row_step - 1) >> (4 - tz);                   // (n_waves >= 8 >= row_step: never 0)
+    if constexpr (LIST) {
+      const ListPart part = list_part(filt, row_step, gwave, n_waves);
+      ph = part.bucket;
+      wave_pos = part.wave_pos;
+      wave_cnt = part.wave_cnt;
+      list_base = part.base;
+      list_count = part.count;
+    } else {
+      ph = static_cast<int>(gwave & (row_step - 1));
+      wave_pos = gwave >> (4 - tz);
+      wave_cnt = (n_waves - ph + row_step - 1) >> (4 - tz);                 // (n_waves >= 8 >= row_step: never 0)
+    }
     const int head = (off0 + ph * row_bytes) & 15;
     head_el = head / kElemBytes;
     units = (head + row_bytes + 15) >> 4;                                   // units THIS wave's rows touch
@@ -253,9 +271,18 @@ __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, 
   }
 
   // i: index among this wave's rows (not PH: the row itself).  Consecutive rows of a wave are a whole number of units apart.
+  // LIST: i is a position inside the wave's bucket, the row comes from the list (rows of a group are then anywhere).
   const int64_t row_units = PH ? (static_cast<int64_t>(row_step) * row_bytes) >> 4 : units;
-  auto row_of = [&](int64_t i) { return PH ? ph + row_step * i : i; };
-  auto first_unit = [&](int64_t i) { return PH ? (off0 + row_of(i) * row_bytes) >> 4 : i * units; };
+  const uint32_t* __restrict__ list = filt + kFilterHeaderWords + list_base;
+  auto row_of = [&](int64_t i) -> int64_t {
+    if constexpr (LIST) return list_row(list, i);
+    else return PH ? ph + row_step * i : i;
+  };
+  auto first_unit = [&](int64_t i) { return PH ? (off0 + row_of(i) * row_bytes) >> 4 : row_of(i) * units; };
+  auto slot_of = [&](int64_t i) -> int64_t {   // where a dense key goes: the row (LIST: the list position)
+    if constexpr (LIST) return list_base + i;
+    else return row_of(i);
+  };
   auto fetch = [&](u32x4(&v)[U], const u32x4* p) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -263,7 +290,7 @@ __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, 
       if (act[u]) v[u] = load_u4<true>(p + 64 * u);
     }
   };
-  auto consume = [&](u32x4(&v)[U], int64_t row) {
+  auto consume = [&](u32x4(&v)[U], int64_t row, int64_t slot) {
     if constexpr (PH) {
       v[0] = and_u4(v[0], keep_first);
 #pragma unroll
@@ -278,28 +305,33 @@ __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, 
       float s = wave_sum_f32(acc);
       if constexpr (SPACE == DEWI_SPACE_L2) s = -s;
       if constexpr (DENSE) {
-        if (lane == 0) keys[qi * keys_per_query + row] = make_key(s, static_cast<uint32_t>(row));
+        if (lane == 0) keys[qi * keys_per_query + slot] = make_key(s, static_cast<uint32_t>(row));
       } else {
         lst[qi].offer(s, static_cast<uint32_t>(row), lane);
       }
     }
   };
 
-  // rows of this wave's residue: ph + row_step * i, i in [0, n_mine)   (not PH: every row, i = the row)
-  const int64_t n_mine = PH ? (n_rows > ph ? (n_rows - ph + row_step - 1) / row_step : 0) : n_rows;
+  // rows of this wave's residue: ph + row_step * i, i in [0, n_mine)   (not PH: every row, i = the row; LIST: the bucket)
+  const int64_t n_mine = LIST ? list_count : (PH ? (n_rows > ph ? (n_rows - ph + row_step - 1) / row_step : 0) : n_rows);
   const int64_t n_groups = n_mine / R;
   for (int64_t g = wave_pos; g < n_groups; g += wave_cnt) {
     u32x4 v[R][U];
-    const u32x4* p = E + first_unit(g * R) + lane;
+    if constexpr (LIST) {
 #pragma unroll
-    for (int r = 0; r < R; ++r) fetch(v[r], p + r * row_units);
+      for (int r = 0; r < R; ++r) fetch(v[r], E + first_unit(g * R + r) + lane);
+    } else {
+      const u32x4* p = E + first_unit(g * R) + lane;
 #pragma unroll
-    for (int r = 0; r < R; ++r) consume(v[r], row_of(g * R + r));
+      for (int r = 0; r < R; ++r) fetch(v[r], p + r * row_units);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) consume(v[r], row_of(g * R + r), slot_of(g * R + r));
   }
   for (int64_t i = n_groups * R + wave_pos; i < n_mine; i += wave_cnt) {   // fewer than R rows left
     u32x4 v[U];
     fetch(v, E + first_unit(i) + lane);
-    consume(v, row_of(i));
+    consume(v, row_of(i), slot_of(i));
   }
 
   if constexpr (S == 1) {
@@ -320,6 +352,15 @@ __global__ __launch_bounds__(kScanThreads) void scan_rows_any(const u32x4* __res
                                                               uint64_t* __restrict__ keys, int64_t keys_per_query) {
   __shared__ MergeShared merge_buf;
   scan_rows_any_body<ELEM, U, R, NQ, SPACE, S, PH>(E, n_rows, units, Q, n_candidates, keys, keys_per_query, merge_buf);
+}
+
+// filtered scan: the rows of a prepared filter (scan_common.hpp); keys_per_query comes from the plan on the list's length
+template <int ELEM, int U, int R, int NQ, int SPACE, int S, bool PH = false>
+__global__ __launch_bounds__(kScanThreads) void scan_rows_any_list(const u32x4* __restrict__ E, const uint32_t* __restrict__ filt,
+                                                                   int units, const float* __restrict__ Q, int n_candidates,
+                                                                   uint64_t* __restrict__ keys, int64_t keys_per_query) {
+  __shared__ MergeShared merge_buf;
+  scan_rows_any_body<ELEM, U, R, NQ, SPACE, S, PH, true>(E, 0, units, Q, n_candidates, keys, keys_per_query, merge_buf, filt);
 }
 
 // Rows that are not whole units, ONE query, up to two units per lane: a wave on CONSECUTIVE rows (scan_rows_odd_contig).
@@ -466,11 +507,13 @@ __device__ __forceinline__ float group_sum_f32(float v, int log2p) {
 
 // `units`: 16-byte units per row; PH (rows that are not whole units): COLUMNS per row instead, and the planner has made sure that
 // the rows of one load are a multiple of the period G of the rows' offsets — a lane's rows all have the residue sub mod G.
-template <int ELEM, int R, int NQ, int SPACE, int S, bool PH = false>
+// LIST (filtered scan): a wave takes list entries of one bucket of the prepared filter `filt` — PH: every lane group then
+// has the bucket's residue — and a lane group's rows come from the list; `n_rows` is unused, dense keys go to list positions.
+template <int ELEM, int R, int NQ, int SPACE, int S, bool PH = false, bool LIST = false>
 __device__ __forceinline__ void scan_short_rows_any_body(const u32x4* __restrict__ E, int64_t n_rows, int units, int log2p,
                                                          const float* __restrict__ Q, int n_candidates,
                                                          uint64_t* __restrict__ keys, int64_t keys_per_query,
-                                                         MergeShared& merge_buf) {
+                                                         MergeShared& merge_buf, const uint32_t* __restrict__ filt = nullptr) {
   constexpr int kCols = ELEM ? 8 : 4;
   constexpr int kElemBytes = ELEM ? 2 : 4;
   constexpr bool DENSE = S == 0;
@@ -485,12 +528,17 @@ __device__ __forceinline__ void scan_short_rows_any_body(const u32x4* __restrict
   const int pos = lane & (group - 1);     // which unit of the row
   int off0 = 0, row_bytes = 0, head_el = 0;
   [[maybe_unused]] u32x4 keep;            // PH: the row's own columns in this lane's unit
+  [[maybe_unused]] ListPart part{0, gwave, n_waves, 0, 0};
+  if constexpr (LIST) {
+    const int n_buckets = PH ? 16 >> __builtin_ctz(static_cast<unsigned>(dim * kElemBytes) | 16u) : 1;
+    part = list_part(filt, n_buckets, gwave, n_waves);
+  }
   if constexpr (PH) {
     off0 = static_cast<int>(reinterpret_cast<uintptr_t>(E) & 15u);
     E = reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(E) - off0);
     row_bytes = dim * kElemBytes;
     const int row_step = 16 >> __builtin_ctz(static_cast<unsigned>(row_bytes) | 16u);
-    const int head = (off0 + (sub & (row_step - 1)) * row_bytes) & 15;
+    const int head = (off0 + (LIST ? part.bucket : (sub & (row_step - 1))) * row_bytes) & 15;
     head_el = head / kElemBytes;
     units = (head + row_bytes + 15) >> 4;                  // units THIS lane's rows touch
     keep = unit_keep_mask<ELEM>(pos * kCols - head_el, dim);
@@ -519,6 +567,50 @@ __device__ __forceinline__ void scan_short_rows_any_body(const u32x4* __restrict
   }
 
   const int64_t rows_per_step = static_cast<int64_t>(rows_per_load) * R;
+  if constexpr (LIST) {
+    // bucket position j: lane group sub, load r of step st holds j = st * rows_per_step + r * rows_per_load + sub (rows of one
+    // load are no longer consecutive: one address per lane group)
+    const uint32_t* __restrict__ list = filt + kFilterHeaderWords + part.base;
+    const int64_t n_steps = (part.count + rows_per_step - 1) / rows_per_step;
+    for (int64_t st = part.wave_pos; st < n_steps; st += part.wave_cnt) {
+      u32x4 v[R];
+      int64_t row[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int64_t j = st * rows_per_step + static_cast<int64_t>(r) * rows_per_load + sub;
+        row[r] = j < part.count ? static_cast<int64_t>(list[j]) : -1;
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        v[r] = u32x4{0u, 0u, 0u, 0u};
+        if (act && row[r] >= 0) v[r] = load_u4<true>(E + (PH ? (off0 + row[r] * row_bytes) >> 4 : row[r] * units) + pos);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const bool mine = holder && row[r] >= 0;
+        if constexpr (PH) v[r] = and_u4(v[r], keep);
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi) {
+          float s = group_sum_f32(qf[qi].dot(v[r], 0.f), log2p);
+          if constexpr (SPACE == DEWI_SPACE_L2) s = -s;
+          if constexpr (DENSE) {
+            if (mine)
+              keys[qi * keys_per_query + part.base + st * rows_per_step + static_cast<int64_t>(r) * rows_per_load + sub] =
+                  make_key(s, static_cast<uint32_t>(row[r]));
+          } else {
+            unsigned long long m = __ballot(mine && !(s < lst[qi].thr_s));
+            while (m != 0ull) {
+              const int src = __ffsll(m) - 1;
+              m &= m - 1ull;
+              const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), src));
+              const uint32_t rw = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(row[r])), src));
+              lst[qi].offer(sc, rw, lane);
+            }
+          }
+        }
+      }
+    }
+  } else {
   const int64_t n_steps = (n_rows + rows_per_step - 1) / rows_per_step;
   const int64_t load_units = PH ? (static_cast<int64_t>(rows_per_load) * row_bytes) >> 4 : static_cast<int64_t>(rows_per_load) * units;
   for (int64_t st = gwave; st < n_steps; st += n_waves) {
@@ -557,6 +649,7 @@ __device__ __forceinline__ void scan_short_rows_any_body(const u32x4* __restrict
       }
     }
   }
+  }
 
   if constexpr (S == 1) {
 #pragma unroll
@@ -578,6 +671,16 @@ __global__ __launch_bounds__(kScanThreads) void scan_short_rows_any(const u32x4*
   scan_short_rows_any_body<ELEM, R, NQ, SPACE, S, PH>(E, n_rows, units, log2p, Q, n_candidates, keys, keys_per_query, merge_buf);
 }
 
+// filtered scan (scan_rows_any_list)
+template <int ELEM, int R, int NQ, int SPACE, int S, bool PH = false>
+__global__ __launch_bounds__(kScanThreads) void scan_short_rows_any_list(const u32x4* __restrict__ E, const uint32_t* __restrict__ filt,
+                                                                         int units, int log2p, const float* __restrict__ Q,
+                                                                         int n_candidates, uint64_t* __restrict__ keys,
+                                                                         int64_t keys_per_query) {
+  __shared__ MergeShared merge_buf;
+  scan_short_rows_any_body<ELEM, R, NQ, SPACE, S, PH, true>(E, 0, units, log2p, Q, n_candidates, keys, keys_per_query, merge_buf, filt);
+}
+
 template <int ELEM, int R, int SPACE, int S>
 __global__ __launch_bounds__(kScanThreads) void scan_short_rows_any_flagged(const u32x4* __restrict__ E, int64_t n_rows, int units,
                                                                             int log2p, const float* __restrict__ Q,
@@ -595,13 +698,18 @@ __global__ __launch_bounds__(kScanThreads) void scan_short_rows_any_flagged(cons
 // ---------------------------------------------------------------------------------------------
 // dispatch (one translation unit per element type instantiates it: knn_scan_any_f32.hip, knn_scan_any_bf16.hip)
 // ---------------------------------------------------------------------------------------------
-template <int ELEM, int NQ, int SPACE, int S, bool PH>
+// LIST: the filtered scan over the prepared filter `filt` (n_rows unused)
+template <int ELEM, int NQ, int SPACE, int S, bool PH, bool LIST = false>
 static hipError_t launch_any_long(const ScanPlan& plan, const u32x4* E, int64_t n_rows, const float* Q, int c, uint64_t* keys,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, const uint32_t* filt = nullptr) {
   const int width = PH ? plan.row_cols : plan.units;
 #define DEWI_ANY_LAUNCH(UU, RR)                                                                                          \
-  hipLaunchKernelGGL((scan_rows_any<ELEM, UU, RR, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E, n_rows, \
-                     width, Q, c, keys, plan.keys_per_query);                                                           \
+  if constexpr (LIST)                                                                                                    \
+    hipLaunchKernelGGL((scan_rows_any_list<ELEM, UU, RR, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E, \
+                       filt, width, Q, c, keys, plan.keys_per_query);                                                   \
+  else                                                                                                                   \
+    hipLaunchKernelGGL((scan_rows_any<ELEM, UU, RR, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E, n_rows, \
+                       width, Q, c, keys, plan.keys_per_query);                                                         \
   return hipGetLastError();
 #define DEWI_ANY_CASE(UU)                                                                                       \
   case UU:                                                                                                      \
@@ -648,33 +756,40 @@ static hipError_t launch_any_long(const ScanPlan& plan, const u32x4* E, int64_t 
   return hipErrorInvalidValue;
 }
 
-template <int ELEM, int NQ, int SPACE, int S, bool PH>
+template <int ELEM, int NQ, int SPACE, int S, bool PH, bool LIST = false>
 static hipError_t launch_any_kind(const ScanPlan& plan, const u32x4* E, int64_t n_rows, const float* Q, int c, uint64_t* keys,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, const uint32_t* filt = nullptr) {
   if (plan.kind == kScanAnyShort) {
     if constexpr (NQ == 2) {
       return hipErrorInvalidValue;
+    } else if constexpr (LIST) {
+      hipLaunchKernelGGL((scan_short_rows_any_list<ELEM, kAnyShortRows, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0,
+                         stream, E, filt, PH ? plan.row_cols : plan.units, plan.log2p, Q, c, keys, plan.keys_per_query);
+      return hipGetLastError();
     } else {
       hipLaunchKernelGGL((scan_short_rows_any<ELEM, kAnyShortRows, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0, stream,
                          E, n_rows, PH ? plan.row_cols : plan.units, plan.log2p, Q, c, keys, plan.keys_per_query);
       return hipGetLastError();
     }
   }
-  return launch_any_long<ELEM, NQ, SPACE, S, PH>(plan, E, n_rows, Q, c, keys, stream);
+  return launch_any_long<ELEM, NQ, SPACE, S, PH, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
 }
 
 // PH = false: rows of whole units (knn_scan_any_*.hip); PH = true: the others (knn_scan_odd_*.hip)
-template <int ELEM, bool PH = false>
+// LIST: the filtered scan over the prepared filter `filt` (plan made on the list's length; never scan_rows_odd_contig, whose
+// results the per-residue form repeats bit for bit)
+template <int ELEM, bool PH = false, bool LIST = false>
 static hipError_t launch_scan_any_impl(const ScanPlan& plan, const void* d_E, int64_t n_rows, int dim, const float* d_q_raw, int q0,
-                                       int nq, int n_candidates, int space, uint64_t* d_keys, hipStream_t stream) {
+                                       int nq, int n_candidates, int space, uint64_t* d_keys, hipStream_t stream,
+                                       const uint32_t* filt = nullptr) {
   const u32x4* E = static_cast<const u32x4*>(d_E);
   const float* Q = d_q_raw + static_cast<int64_t>(q0) * dim;
   uint64_t* keys = d_keys + static_cast<int64_t>(q0) * plan.keys_per_query;
 #define DEWI_ANY_S(NQ, SPACE)                                                                                        \
   switch (plan.slots) {                                                                                              \
-    case 0: return launch_any_kind<ELEM, NQ, SPACE, 0, PH>(plan, E, n_rows, Q, n_candidates, keys, stream);          \
-    case 1: return launch_any_kind<ELEM, NQ, SPACE, 1, PH>(plan, E, n_rows, Q, n_candidates, keys, stream);          \
-    default: return launch_any_kind<ELEM, NQ, SPACE, kMaxSlots, PH>(plan, E, n_rows, Q, n_candidates, keys, stream); \
+    case 0: return launch_any_kind<ELEM, NQ, SPACE, 0, PH, LIST>(plan, E, n_rows, Q, n_candidates, keys, stream, filt);          \
+    case 1: return launch_any_kind<ELEM, NQ, SPACE, 1, PH, LIST>(plan, E, n_rows, Q, n_candidates, keys, stream, filt);          \
+    default: return launch_any_kind<ELEM, NQ, SPACE, kMaxSlots, PH, LIST>(plan, E, n_rows, Q, n_candidates, keys, stream, filt); \
   }
 #define DEWI_ANY_Q(NQ)                 \
   if (space == DEWI_SPACE_COSINE) {    \
@@ -682,7 +797,7 @@ static hipError_t launch_scan_any_impl(const ScanPlan& plan, const void* d_E, in
   } else {                             \
     DEWI_ANY_S(NQ, DEWI_SPACE_L2)      \
   }
-  if constexpr (PH) {
+  if constexpr (PH && !LIST) {
     if (nq == 1 && plan.odd_contig) {   // narrow rows, one query: a wave on consecutive rows (scan_rows_odd_contig)
 #define DEWI_ODD_CONTIG(UU, RR, SPACE)                                                                                              \
   switch (plan.slots) {                                                                                                             \
@@ -717,7 +832,8 @@ static hipError_t launch_scan_any_impl(const ScanPlan& plan, const void* d_E, in
       // bf16 l2 keeps 8 fp32 registers per query and unit next to the masks: four queries spill — one pass per query there
       if (space != DEWI_SPACE_COSINE) {
         for (int i = 0; i < 4; ++i) {
-          const hipError_t e = launch_scan_any_impl<ELEM, PH>(plan, d_E, n_rows, dim, d_q_raw, q0 + i, 1, n_candidates, space, d_keys, stream);
+          const hipError_t e = launch_scan_any_impl<ELEM, PH, LIST>(plan, d_E, n_rows, dim, d_q_raw, q0 + i, 1, n_candidates, space, d_keys,
+                                                                    stream, filt);
           if (e != hipSuccess) return e;
         }
         return hipSuccess;

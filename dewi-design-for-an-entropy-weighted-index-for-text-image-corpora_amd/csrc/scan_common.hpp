@@ -188,4 +188,37 @@ __device__ __forceinline__ void for_each_flagged(const uint32_t* __restrict__ fl
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Filtered scans (LIST = true forms of the row kernels; abi.cpp dewi_filter_prepare builds the list).
+// A prepared filter (launch.hpp) is kFilterHeaderWords u32 of bucket offsets — bucket b holds list positions [filt[b], filt[b + 1]) —
+// followed by the allowed rows, ascending inside each bucket.  Bucket b holds the rows r with r mod G == b, G the period of
+// a row's offset inside its first 16-byte unit (rows that are not whole units: G = 16 / gcd(16, row bytes); else G = 1).
+// ---------------------------------------------------------------------------------------------
+struct ListPart {
+  int bucket;
+  int64_t wave_pos, wave_cnt;   // this wave's place among the waves of its bucket
+  int64_t base, count;          // the bucket's list positions
+};
+// Waves are split across the buckets in proportion to their sizes, one wave at least per bucket: bucket b starts at wave
+// filt[b] * (W - G) / n + b.  `gwave` must be wave-uniform (everything here then lives in scalar registers).
+__device__ __forceinline__ ListPart list_part(const uint32_t* __restrict__ filt, int n_buckets, int64_t gwave, int64_t n_waves) {
+  const int64_t n = filt[n_buckets];
+  const int64_t spare = n_waves - n_buckets;
+  auto start = [&](int b) { return n > 0 ? static_cast<int64_t>(filt[b]) * spare / n + b : static_cast<int64_t>(b); };
+  int b = 0;
+  for (int j = 1; j < n_buckets; ++j)
+    if (gwave >= start(j)) b = j;
+  ListPart p;
+  p.bucket = b;
+  p.wave_pos = gwave - start(b);
+  p.wave_cnt = (b + 1 < n_buckets ? start(b + 1) : n_waves) - start(b);
+  p.base = filt[b];
+  p.count = static_cast<int64_t>(filt[b + 1]) - p.base;
+  return p;
+}
+// list entry i as a wave-uniform row number (scalar registers: see scan_rows_any_body)
+__device__ __forceinline__ int64_t list_row(const uint32_t* __restrict__ rows, int64_t i) {
+  return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(rows[i])));
+}
+
 }  // namespace dewi

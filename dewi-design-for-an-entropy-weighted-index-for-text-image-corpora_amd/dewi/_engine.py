@@ -9,6 +9,7 @@ host<->device copies.
 from __future__ import annotations
 
 import ctypes
+import itertools
 import threading
 from typing import Dict, List, Optional, Tuple, Union
 
@@ -22,6 +23,30 @@ ArrayLike = Union[np.ndarray, "torch.Tensor"]  # noqa: F821
 def _torch():
     import torch
     return torch
+
+
+_corpus_ids = itertools.count(1)
+
+
+class DeviceFilter:
+    """A prepared allow-list of corpus rows (``DeviceCorpus.make_filter``): the device buffer the filtered row kernels walk
+    (``dewi_filter_prepare``: the allowed rows, sorted, grouped by the residue of their offset inside a 16-byte unit), the
+    number of allowed rows and the identity of the corpus it was prepared for.  Prepare once, search many times; a filter
+    used with another corpus — an index rebuilt since — raises ``ValueError`` instead of answering from stale rows."""
+
+    __slots__ = ("buf", "n_allowed", "corpus_id", "n_rows")
+
+    def __init__(self, buf, n_allowed: int, corpus_id: int, n_rows: int):
+        self.buf = buf
+        self.n_allowed = int(n_allowed)
+        self.corpus_id = int(corpus_id)
+        self.n_rows = int(n_rows)
+
+    def __len__(self) -> int:
+        return self.n_allowed
+
+    def __repr__(self) -> str:
+        return f"DeviceFilter({self.n_allowed} of {self.n_rows} rows)"
 
 
 class DeviceCorpus:
@@ -41,6 +66,7 @@ class DeviceCorpus:
         self.space = space
         self.id_offset = int(id_offset)
         self.device = emb.device
+        self.corpus_id = next(_corpus_ids)      # what a DeviceFilter is checked against
         self._lib = nat.load_library()
         self._ws: Dict[Tuple[int, int], "torch.Tensor"] = {}
         self._ws_need: Dict[Tuple[int, int, int], Tuple[int, int]] = {}     # (batch, cut, thread) -> (tuning epoch, bytes)
@@ -192,9 +218,83 @@ class DeviceCorpus:
         self._q_dev.copy_(self._q_pinned, non_blocking=True)
         return self._q_dev
 
+    # ------------------------------------------------------------------ filters
+    def make_filter(self, mask) -> DeviceFilter:
+        """Prepare an allow-list from a bool mask of length N (numpy or torch, host or device).  Synchronises the current
+        stream once (the count of allowed rows comes back to the host)."""
+        torch = _torch()
+        if isinstance(mask, torch.Tensor):
+            m = mask
+        else:
+            m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask)))
+        if m.dim() != 1 or int(m.shape[0]) != self.n_rows:
+            raise ValueError(f"filter mask must have shape ({self.n_rows},), got {tuple(m.shape)}")
+        if m.dtype != torch.bool:
+            raise ValueError(f"filter mask must be boolean, got {m.dtype}")
+        elem = 1 if self.is_bf16 else 0
+        need = int(self._lib.dewi_filter_bytes(self.n_rows, self.dim, elem))
+        if need == 0:
+            raise nat.NativeLibraryError("dewi_filter_bytes returned 0: " + nat.last_error())
+        with torch.cuda.device(self.device):
+            m8 = m.to(device=self.device).view(torch.uint8).contiguous()
+            buf = torch.empty(need, dtype=torch.uint8, device=self.device)
+            n_allowed = ctypes.c_int64(0)
+            nat.check(self._lib.dewi_filter_prepare(elem, self.n_rows, self.dim, nat.ptr(m8), nat.ptr(buf), need,
+                                                    ctypes.byref(n_allowed), nat.stream_ptr()))
+        return DeviceFilter(buf, n_allowed.value, self.corpus_id, self.n_rows)
+
+    def check_filter(self, filter: DeviceFilter) -> None:
+        if not isinstance(filter, DeviceFilter):
+            raise TypeError(f"expected a DeviceFilter (make_filter), got {type(filter).__name__}")
+        if filter.corpus_id != self.corpus_id:
+            raise ValueError("this filter was prepared for another corpus (the index was rebuilt or reloaded since): "
+                             "prepare it again with make_filter")
+
+    def _search_filtered(self, q_dev, k: int, eta: float, entropy_pref: float, out_ids, out_scores,
+                         candidates: Optional[int], similarity: str, filter: DeviceFilter):
+        """``search_device`` over the rows of a prepared filter (``dewi_knn_rerank_filtered``): the row kernels of this
+        dim over the list, then the same select / blend / top-k.  k <= 0 or an empty filter: empty results."""
+        torch = _torch()
+        self.check_filter(filter)
+        b = int(q_dev.shape[0])
+        if q_dev.shape[1] != self.dim:
+            raise ValueError(f"Expected query shape ({self.dim},), got {tuple(q_dev.shape[1:])}")
+        if similarity not in nat.SIM_CODES:
+            raise ValueError(f"unknown similarity {similarity!r}")
+        if candidates is None and similarity != "ip":
+            raise ValueError("similarity transforms belong to the ANN re-rank rule: pass candidates=k as well")
+        k = int(k)
+        n_a = filter.n_allowed
+        if k <= 0 or n_a == 0:
+            return (torch.empty((b, 0), dtype=torch.int64, device=self.device),
+                    torch.empty((b, 0), dtype=torch.float32, device=self.device))
+        if out_ids is None:
+            out_ids = torch.empty((b, k), dtype=torch.int64, device=self.device)
+        if out_scores is None:
+            out_scores = torch.empty((b, k), dtype=torch.float32, device=self.device)
+        c = min(2 * k, n_a) if candidates is None else min(max(int(candidates), 1), n_a)
+        key = ("filtered", b, n_a, c)
+        ws = self._ws.get(key)
+        if ws is None:
+            need = int(self._lib.dewi_knn_filtered_workspace_bytes(n_a, self.dim, b, c))
+            if need == 0:
+                raise nat.NativeLibraryError("dewi_knn_filtered_workspace_bytes returned 0: " + nat.last_error())
+            if len(self._ws) > 8:
+                self._ws.clear()
+            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._last_call = (b, k, c, False, ws)
+        rc = self._lib.dewi_knn_rerank_filtered(
+            nat.ptr(self.emb), 1 if self.is_bf16 else 0, self.n_rows, self.dim, nat.ptr(filter.buf), n_a, nat.ptr(q_dev), b,
+            nat.ptr(self.dewi32), nat.ptr(self.ent32), k, 0 if candidates is None else int(candidates), nat.SIM_CODES[similarity],
+            float(eta), float(entropy_pref), nat.SPACE_CODES[self.space], nat.ptr(out_ids), nat.ptr(out_scores), nat.ptr(ws),
+            ws.numel(), nat.stream_ptr())
+        nat.check(rc)
+        return out_ids, out_scores
+
     # ------------------------------------------------------------------ hot path
     def search_device(self, q_dev, k: int, eta: float, entropy_pref: float, out_ids=None, out_scores=None,
-                      candidates: Optional[int] = None, similarity: str = "ip", use_shadow: bool = True):
+                      candidates: Optional[int] = None, similarity: str = "ip", use_shadow: bool = True,
+                      filter: Optional[DeviceFilter] = None):
         """Enqueue one search on the current stream; returns device tensors, no sync.
 
         q_dev: fp32 [B, d] on this device (raw queries; cosine normalisation happens in-kernel).
@@ -207,7 +307,13 @@ class DeviceCorpus:
         NOT thread-safe on one instance (shared workspaces).  Always answered: a query that a matrix-core pass of
         the batch refuses (adversarial corpora) is repaired inside the library call, on the same stream (ABI 5) — no
         id -1 ever reaches the outputs, so there is nothing for the caller to check after synchronising.
+
+        ``filter`` (a ``DeviceFilter`` of this corpus): search only its rows (ABI 6) — the fp32 row kernels over the
+        list, whatever the batch size; ids stay rows of the whole corpus.  Results are [B, 0] when k <= 0 or the filter
+        is empty.
         """
+        if filter is not None:
+            return self._search_filtered(q_dev, k, eta, entropy_pref, out_ids, out_scores, candidates, similarity, filter)
         torch = _torch()
         b = int(q_dev.shape[0])
         if q_dev.shape[1] != self.dim:
@@ -271,10 +377,16 @@ class DeviceCorpus:
         return buf.value.decode()
 
     def search(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
-               candidates: Optional[int] = None, similarity: str = "ip") -> Tuple[np.ndarray, np.ndarray]:
+               candidates: Optional[int] = None, similarity: str = "ip",
+               filter: Optional[DeviceFilter] = None) -> Tuple[np.ndarray, np.ndarray]:
         """Blocking convenience: (ids int64 [B,k] including id_offset, scores fp32 [B,k]) on the host.
-        Safe to call from several threads on one instance (serialised by a per-corpus lock)."""
+        Safe to call from several threads on one instance (serialised by a per-corpus lock).
+        ``filter``: see ``search_device`` (an empty filter gives [B, 0])."""
         torch = _torch()
+        if filter is not None:
+            self.check_filter(filter)
+            if filter.n_allowed == 0:
+                k = 0
         with self._lock, torch.cuda.device(self.device):
             q = self.stage_queries(queries)
             # Small result sets (one query, a handful: what the reference's search returns) are written by the select kernel
@@ -297,7 +409,8 @@ class DeviceCorpus:
                       dbuf, hbuf)
                 self._io[(b, kk)] = io
             if kk > 0:
-                self.search_device(q, k, eta, entropy_pref, io[0], io[1], candidates=candidates, similarity=similarity)
+                self.search_device(q, k, eta, entropy_pref, io[0], io[1], candidates=candidates, similarity=similarity,
+                                   filter=filter)
                 if io[4] is not None:
                     io[5].copy_(io[4], non_blocking=True)
                 torch.cuda.current_stream().synchronize()

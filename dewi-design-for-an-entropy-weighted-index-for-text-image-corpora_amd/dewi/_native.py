@@ -31,7 +31,7 @@ MODE_CODES = {"standard": 0, "conditional": 1}
 #: similarity the ANN-semantics re-rank blends (include/dewi_hip.h DEWI_SIM_*; reference backends.py:229-231, 335-338)
 SIM_CODES = {"ip": 0, "one_minus_dist": 1, "inv_one_plus_dist": 2}
 NUM_SIGNALS = 7
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 #: every symbol include/dewi_hip.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "dewi_knn_rerank_bf16", "dewi_knn_rerank_candidates", "dewi_prepare_queries_bf16", "dewi_knn_scan", "dewi_knn_finish", "dewi_knn_candidates", "dewi_merge_workspace_bytes", "dewi_merge_rerank", "dewi_robust_fit_workspace_bytes",
     "dewi_robust_fit_f32", "dewi_robust_fit_begin", "dewi_robust_fit_hist_f32", "dewi_robust_fit_region",
     "dewi_robust_fit_pick", "dewi_robust_fit_finish", "dewi_score_f64", "dewi_score_f64_dev", "dewi_timing_enable", "dewi_timing_read", "dewi_tuning_set",
+    "dewi_filter_bytes", "dewi_filter_prepare", "dewi_knn_filtered_workspace_bytes", "dewi_knn_rerank_filtered",
 )
 
 
@@ -124,6 +125,15 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_timing_read.argtypes = [c.POINTER(f64), c.POINTER(i32)]
     lib.dewi_tuning_set.restype = i32
     lib.dewi_tuning_set.argtypes = [i32, i32, i32, i32]
+    lib.dewi_filter_bytes.restype = sz
+    lib.dewi_filter_bytes.argtypes = [i64, i32, i32]
+    lib.dewi_filter_prepare.restype = i32
+    lib.dewi_filter_prepare.argtypes = [i32, i64, i32, vp, vp, sz, c.POINTER(i64), vp]
+    lib.dewi_knn_filtered_workspace_bytes.restype = sz
+    lib.dewi_knn_filtered_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_knn_rerank_filtered.restype = i32
+    lib.dewi_knn_rerank_filtered.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, vp, vp, i32, i32, i32, f64, f64, i32, vp, vp,
+                                             vp, sz, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

@@ -98,6 +98,22 @@ class BaseIndex:
         return inst
 
 
+def filter_kwargs(filter) -> Dict[str, Any]:
+    """What an unprepared ``filter=`` argument is, as ``make_filter`` keywords: a bool array is a mask, strings are doc
+    ids, integers are row positions."""
+    if isinstance(filter, str):
+        return {"doc_ids": [filter]}
+    if hasattr(filter, "dtype"):
+        return {"mask": filter} if "bool" in str(filter.dtype) else {"rows": filter}
+    items = list(filter)
+    if items and all(isinstance(x, str) for x in items):
+        return {"doc_ids": items}
+    arr = np.asarray(items)
+    if arr.dtype == np.bool_:
+        return {"mask": arr}
+    return {"rows": arr.astype(np.int64) if arr.size else np.zeros(0, np.int64)}
+
+
 class HNSWIndex(BaseIndex):
     """hnswlib graph index — not part of this build (reference backends.py:166-241)."""
 
@@ -416,8 +432,64 @@ class ExactIndex(BaseIndex):
         if self._corpus is None or self._pending or not self._is_trained:
             self.build()
 
+    # ---------------------------------------------------------------- filters (additive)
+    def filter_mask(self, mask=None, *, doc_ids: Optional[Sequence[str]] = None, rows=None):
+        """The bool row mask of exactly one of: ``mask`` (bool array of length N, numpy or torch, host or device: returned
+        as it is after the checks), ``doc_ids`` (through this index's ids; an unknown id raises ``KeyError``) or ``rows``
+        (integer row positions, 0 <= row < N).  Host logic only: no device work."""
+        given = [x is not None for x in (mask, doc_ids, rows)]
+        if sum(given) != 1:
+            raise ValueError("pass exactly one of mask, doc_ids, rows")
+        n = len(self._doc_ids)
+        if mask is not None:
+            shape = tuple(mask.shape) if hasattr(mask, "shape") else (len(mask),)
+            if shape != (n,):
+                raise ValueError(f"filter mask must have shape ({n},), got {shape}")
+            if hasattr(mask, "is_cuda"):
+                import torch
+                if mask.dtype != torch.bool:
+                    raise ValueError(f"filter mask must be boolean, got {mask.dtype}")
+                return mask
+            m = np.asarray(mask)
+            if m.dtype != np.bool_:
+                raise ValueError(f"filter mask must be boolean, got {m.dtype}")
+            return m
+        if doc_ids is not None:
+            if isinstance(doc_ids, str):
+                doc_ids = [doc_ids]
+            wanted = set(doc_ids)
+            hit = np.fromiter((d in wanted for d in self._doc_ids), dtype=bool, count=n)
+            missing = wanted.difference(np.asarray(self._doc_ids, dtype=object)[hit].tolist()) if wanted else set()
+            if missing:
+                raise KeyError(f"unknown doc ids: {sorted(missing, key=str)[:5]}")
+            return hit
+        r = rows.detach().cpu().numpy() if hasattr(rows, "is_cuda") else np.asarray(rows)
+        r = r.reshape(-1)
+        if r.size and not np.issubdtype(r.dtype, np.integer):
+            raise ValueError(f"filter rows must be integers, got {r.dtype}")
+        if r.size and (int(r.min()) < 0 or int(r.max()) >= n):
+            raise ValueError(f"filter rows must lie in [0, {n})")
+        out = np.zeros(n, dtype=bool)
+        out[r.astype(np.int64)] = True
+        return out
+
+    def make_filter(self, mask=None, *, doc_ids: Optional[Sequence[str]] = None, rows=None):
+        """Prepare an allow-list for ``search`` / ``search_batch(filter=...)`` (additive): one of a bool ``mask`` of
+        length N, ``doc_ids`` or row positions ``rows`` (see ``filter_mask``).  The result is a ``DeviceFilter`` bound
+        to the index as it is built now: after ``add`` + ``build`` (or on another index, ``load`` included) it raises
+        ``ValueError`` instead of answering from stale rows."""
+        self._ensure_built()
+        return self._corpus.make_filter(self.filter_mask(mask, doc_ids=doc_ids, rows=rows))
+
+    def _prepared(self, filter):
+        """A ``DeviceFilter``, or anything ``make_filter`` takes (bool mask, doc ids, integer rows) prepared on the fly."""
+        from ._engine import DeviceFilter
+        if filter is None or isinstance(filter, DeviceFilter):
+            return filter
+        return self.make_filter(**filter_kwargs(filter))
+
     def search(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
-               candidates: Optional[int] = None, similarity: str = "ip") -> SearchResult:
+               candidates: Optional[int] = None, similarity: str = "ip", filter=None) -> SearchResult:
         """Reference ``ExactIndex.search`` (backends.py:414-481) for one query.
 
         ``candidates`` (additive): how many nearest rows are re-ranked.  Default ``min(2k, N)``, the
@@ -427,20 +499,28 @@ class ExactIndex(BaseIndex):
         "one_minus_dist" (hnswlib ``1 - dist``, :229-231) or "inv_one_plus_dist" (faiss L2
         ``1/(1+dist)``, :337-338).  hnswlib / faiss are not installed here: that rule is restated by
         reading and its parity is unpinned.
+
+        ``filter`` (additive): restrict the search to an allow-list — a prepared filter (``make_filter``) or anything
+        ``make_filter`` takes.  The result is the reference's search applied to the allowed rows only: c = min(2k, |A|),
+        ``[]`` for an empty filter, ``ValueError`` for k > |A|.
         """
         q = np.asarray(query, dtype=np.float32)
         if q.ndim == 1:
             q = q.reshape(1, -1)
-        rows, scores = self.search_batch(q, k, eta, entropy_pref, candidates, similarity)
+        rows, scores = self.search_batch(q, k, eta, entropy_pref, candidates, similarity, filter=filter)
         return self.results_for(rows[:1], scores[:1])[0]
 
     def search_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
-                     candidates: Optional[int] = None, similarity: str = "ip") -> Tuple[np.ndarray, np.ndarray]:
-        """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k])."""
+                     candidates: Optional[int] = None, similarity: str = "ip", filter=None) -> Tuple[np.ndarray, np.ndarray]:
+        """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k]).  ``filter``: see ``search``
+        (one allow-list for every query of the batch; [B, 0] results when it is empty or k <= 0)."""
         self._ensure_built()
         q = np.asarray(queries, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        if filter is not None:
+            return self._corpus.search(q, int(k), float(eta), float(entropy_pref), candidates=candidates,
+                                       similarity=similarity, filter=self._prepared(filter))
         return self._corpus.search(q, int(k), float(eta), float(entropy_pref), candidates=candidates,
                                    similarity=similarity)
 

@@ -70,26 +70,39 @@ class DewiIndex(BaseIndex):
     def _defaults(self, eta: Optional[float], entropy_pref: Optional[float]) -> Tuple[float, float]:
         return (self.rerank_eta if eta is None else eta, self.entropy_pref if entropy_pref is None else entropy_pref)
 
+    def make_filter(self, mask=None, *, doc_ids: Optional[Sequence[str]] = None, rows=None):
+        """Prepare an allow-list for ``search`` / ``search_batch(filter=...)`` (``ExactIndex.make_filter``)."""
+        if not self._built:
+            self.build()
+        return self._backend.make_filter(mask, doc_ids=doc_ids, rows=rows)
+
     def search(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
-               entropy_pref: Optional[float] = None) -> List[Tuple[str, float, Payload]]:
+               entropy_pref: Optional[float] = None, filter=None) -> List[Tuple[str, float, Payload]]:
+        """``filter`` (additive): search only an allow-list — a prepared filter (``make_filter``), a bool mask, doc ids
+        or row positions."""
         if not self._built:
             self.build()
         eta, entropy_pref = self._defaults(eta, entropy_pref)
         q = np.asarray(query, dtype=np.float32)
         if q.shape != (self.dim,):
             raise ValueError(f"Expected query shape ({self.dim},), got {q.shape}")
+        if filter is not None:
+            return self._backend.search(q, k, eta, entropy_pref, filter=filter)
         return self._backend.search(q, k, eta, entropy_pref)
 
     def search_batch(self, queries: np.ndarray, k: int = 10, eta: Optional[float] = None,
-                     entropy_pref: Optional[float] = None) -> List[List[Tuple[str, float, Payload]]]:
-        """One call for B queries ([B, dim]); each result list equals ``search`` of that row."""
+                     entropy_pref: Optional[float] = None, filter=None) -> List[List[Tuple[str, float, Payload]]]:
+        """One call for B queries ([B, dim]); each result list equals ``search`` of that row (``filter``: see ``search``)."""
         if not self._built:
             self.build()
         eta, entropy_pref = self._defaults(eta, entropy_pref)
         q = np.asarray(queries, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
-        rows, scores = self._backend.search_batch(q, k, eta, entropy_pref)
+        if filter is not None:
+            rows, scores = self._backend.search_batch(q, k, eta, entropy_pref, filter=filter)
+        else:
+            rows, scores = self._backend.search_batch(q, k, eta, entropy_pref)
         return self._backend.results_for(rows, scores)
 
     # ------------------------------------------------------------------ accessors (index.py:95-119)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DEWI_ABI_VERSION 5
+#define DEWI_ABI_VERSION 6
 
 /* status codes */
 #define DEWI_OK 0
@@ -173,6 +173,35 @@ int dewi_knn_rerank_candidates(const void* d_E, int elem_type, int64_t n_rows, i
                                const float* d_dewi32, const float* d_ent32, int k, int n_candidates, double eta,
                                double entropy_pref, int space, int sim_transform, int64_t* d_out_ids,
                                float* d_out_scores, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Filtered search (ABI 6): the same search restricted to an allow-list A of rows — reference ExactIndex.search
+ * (backends.py:414-481) applied to the rows of A only.  Every row of A is scored with exactly the arithmetic the
+ * unfiltered one-query search uses for it (same row kernel, lanes and summation order), the cut is c = min(2k, |A|)
+ * (or n_candidates, as dewi_knn_rerank_candidates) with ties to the lower row, then the same blend and top-k.
+ *
+ * dewi_filter_bytes: size of the device buffer that holds one prepared filter for a corpus of this shape (0 for a bad
+ * shape).  dewi_filter_prepare turns d_mask (DEVICE, one byte per row, nonzero = allowed) into that buffer — the allowed
+ * rows as a sorted u32 list, grouped by the residue of the row's offset inside its 16-byte unit (rows that are not whole
+ * units) — and returns |A| in *out_n_allowed.  It SYNCHRONISES `stream` (|A| comes back to the host once per filter: the cut
+ * and the k-bound checks need it).  A prepared filter serves every search of a corpus with the same n_rows / dim /
+ * elem_type, whatever its base address; the caller keeps it valid (a rebuilt corpus needs a new filter).
+ * dewi_knn_filtered_workspace_bytes: workspace of dewi_knn_rerank_filtered for |A| = n_allowed (0 if n_allowed <= 0:
+ * nothing is launched then).
+ * dewi_knn_rerank_filtered: ids [n_queries][k] are GLOBAL rows of the corpus.  k <= 0 or |A| = 0: returns DEWI_OK and
+ * writes nothing (every query's answer is empty); k > |A|: DEWI_ERR_K_OUT_OF_BOUNDS.  n_candidates <= 0: min(2k, |A|);
+ * sim_transform as dewi_knn_rerank_candidates (DEWI_SIM_RAW unless n_candidates > 0).  Batches run the row kernels'
+ * 4- and 8-query passes over the list — never a matrix-core pass, so nothing is refused.  elem_type 0 (fp32) only:
+ * a bf16 corpus returns DEWI_ERR_UNSUPPORTED.  Asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------------ */
+size_t dewi_filter_bytes(int64_t n_rows, int dim, int elem_type);
+int dewi_filter_prepare(int elem_type, int64_t n_rows, int dim, const uint8_t* d_mask, void* d_filter, size_t filter_bytes,
+                        int64_t* out_n_allowed, void* stream);
+size_t dewi_knn_filtered_workspace_bytes(int64_t n_allowed, int dim, int n_queries, int n_candidates);
+int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_allowed,
+                             const float* d_Q, int n_queries, const float* d_dewi32, const float* d_ent32, int k, int n_candidates,
+                             int sim_transform, double eta, double entropy_pref, int space, int64_t* d_out_ids,
+                             float* d_out_scores, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Step 1 of the bf16 search alone (backends.py:420-424 followed by the bf16 rounding of config C3): q / ||q||
  * in fp32 unless the norm is 0 (cosine), then round-to-nearest-even to bf16.  This is the kernel the batched
