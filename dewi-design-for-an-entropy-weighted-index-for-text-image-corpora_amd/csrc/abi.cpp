@@ -159,8 +159,11 @@ dewi::RerankParams make_rerank(double eta, double pref, int transform = DEWI_SIM
 
 // Steps 1-3 for every query: fills the keys region of the workspace.
 // d_filter (fp32 corpus only): scan the rows of that prepared filter instead (L planned on the filter's length).
+// d_qwords (with d_filter: the union of per-query lists): the query-word planes [ceil(n_queries / 32)][n_union] of a prepared
+// query-filter buffer — every pass takes its queries' bits (QMASK kernels).
 int run_scan(const KnnLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_Q,
-             int n_queries, int n_candidates, int space, char* ws, hipStream_t stream, const uint32_t* d_filter = nullptr) {
+             int n_queries, int n_candidates, int space, char* ws, hipStream_t stream, const uint32_t* d_filter = nullptr,
+             const uint32_t* d_qwords = nullptr, int64_t n_union = 0) {
   uint64_t* keys = reinterpret_cast<uint64_t*>(ws + L.keys_off);
   float* qn = reinterpret_cast<float*>(ws + L.qn_off);
   hipError_t e;
@@ -175,9 +178,15 @@ int run_scan(const KnnLayout& L, const void* d_E, int elem_type, int64_t n_rows,
     static const bool nq8_enabled = [] { const char* e = getenv("DEWI_SCAN_NQ8"); return e == nullptr || atoi(e) != 0; }();
     const bool can8 = !elem_type && L.plan.fast && L.plan.slots == 1 && nq8_enabled;
     const int nq = (can8 && n_queries - q >= 8) ? 8 : ((L.plan.nq_max > 1 && n_queries - q >= L.plan.nq_max) ? L.plan.nq_max : 1);
-    if (d_filter)
+    if (d_filter) {
+      dewi::QWords qw;
+      if (d_qwords) {
+        qw.words = d_qwords + static_cast<int64_t>(q / 32) * n_union;
+        qw.shift = q % 32;
+      }
       e = dewi::launch_scan_f32_filtered(L.plan, static_cast<const float*>(d_E), dim, d_Q, L.plan.raw_queries ? nullptr : qn, q, nq,
-                                         n_candidates, space, keys, d_filter, stream);
+                                         n_candidates, space, keys, d_filter, stream, qw);
+    }
     else if (elem_type)
       e = dewi::launch_scan_bf16(L.plan, static_cast<const uint16_t*>(d_E), n_rows, dim, d_Q, L.plan.raw_queries ? nullptr : qn,
                                  q, nq, n_candidates, space, keys, stream);
@@ -858,6 +867,125 @@ int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int
                                    d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr, nullptr, dewi::SegmentLayout{}, stream);
   }
   return e == hipSuccess ? DEWI_OK : hip_fail(e, "select launch (filtered)");
+}
+
+// ---- per-query filters (additive to ABI 6) ----------------------------------------------------------------------------
+// Prepared query-filter buffer (u32 words): the prepared filter of the union U (dewi_filter_prepare's layout: header, then the
+// union list, capacity n_rows), the query-word planes [ceil(B / 32)][|U|] (capacity [ceil(B / 32)][n_rows]), |F_j| for every j,
+// the union byte mask and the preparation scratch.
+struct QueryFilterLayout {
+  size_t words_off, counts_off, union_off, scratch_off, total;   // u32 offsets; total in bytes
+};
+static QueryFilterLayout query_filter_layout(int64_t n_rows, int n_buckets, int n_queries) {
+  QueryFilterLayout L;
+  const size_t n = static_cast<size_t>(n_rows);
+  L.words_off = dewi::kFilterHeaderWords + n;
+  L.counts_off = L.words_off + static_cast<size_t>((n_queries + 31) / 32) * n;
+  L.union_off = L.counts_off + static_cast<size_t>(n_queries);
+  L.scratch_off = L.union_off + (n + 3) / 4;
+  L.total = 4 * (L.scratch_off + dewi::filter_scratch_words(n_rows, n_buckets));
+  return L;
+}
+
+size_t dewi_query_filter_bytes(int64_t n_rows, int dim, int elem_type, int n_queries) {
+  if (n_rows <= 0 || n_rows > 0xFFFFFFFFll || dim <= 0 || (elem_type != 0 && elem_type != 1)) return 0;
+  if (n_queries <= 0 || n_queries > 65535) return 0;
+  return query_filter_layout(n_rows, filter_buckets(dim, elem_type), n_queries).total;
+}
+
+int dewi_query_filter_prepare(int elem_type, int64_t n_rows, int dim, int n_queries, const uint8_t* d_masks, void* d_filter,
+                              size_t filter_bytes, int64_t* out_n_union, int64_t* out_n_allowed, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!d_masks || !d_filter || !out_n_union || !out_n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (elem_type != 0 && elem_type != 1) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+  if (n_rows <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
+  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (n_queries <= 0 || n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
+  const size_t need = dewi_query_filter_bytes(n_rows, dim, elem_type, n_queries);
+  if (filter_bytes < need) return fail(DEWI_ERR_WORKSPACE, "query filter buffer %zu B < required %zu B", filter_bytes, need);
+  const int g = filter_buckets(dim, elem_type);
+  const QueryFilterLayout L = query_filter_layout(n_rows, g, n_queries);
+  uint32_t* buf = static_cast<uint32_t*>(d_filter);
+  hipError_t e = dewi::launch_query_filter_prepare(d_masks, n_rows, n_queries, g, reinterpret_cast<uint8_t*>(buf + L.union_off),
+                                                   buf + L.counts_off, buf, buf + L.scratch_off, buf + L.words_off, stream);
+  if (e != hipSuccess) return hip_fail(e, "query_filter_prepare launch");
+  std::vector<uint32_t> counts(static_cast<size_t>(n_queries) + 1);
+  e = hipMemcpyAsync(counts.data(), buf + dewi::kFilterMaxBuckets, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(counts.data() + 1, buf + L.counts_off, sizeof(uint32_t) * static_cast<size_t>(n_queries),
+                       hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hip_fail(e, "query filter count read-back");
+  *out_n_union = static_cast<int64_t>(counts[0]);
+  for (int j = 0; j < n_queries; ++j) out_n_allowed[j] = static_cast<int64_t>(counts[j + 1]);
+  return DEWI_OK;
+}
+
+size_t dewi_knn_query_filtered_workspace_bytes(int64_t n_union, int dim, int n_queries, int n_candidates) {
+  return dewi_knn_filtered_workspace_bytes(n_union, dim, n_queries, n_candidates);
+}
+
+int dewi_knn_rerank_query_filtered(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_union,
+                                   const int64_t* n_allowed, const float* d_Q, int n_queries, const float* d_dewi32,
+                                   const float* d_ent32, int k, int n_candidates, int sim_transform, double eta,
+                                   double entropy_pref, int space, int64_t* d_out_ids, float* d_out_scores, void* d_workspace,
+                                   size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  int rc = check_common(d_E, n_rows, dim, d_Q, n_queries, space);
+  if (rc) return rc;
+  if (elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "filtered search serves fp32 corpora (bf16: not in this build)");
+  if (elem_type != 0) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+  if (!d_filter || !n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null filter or count pointer");
+  if (n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
+  if (n_union < 0 || n_union > n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_union %lld outside [0, %lld]", static_cast<long long>(n_union), static_cast<long long>(n_rows));
+  if (sim_transform != DEWI_SIM_RAW && sim_transform != DEWI_SIM_ONE_MINUS_DIST && sim_transform != DEWI_SIM_INV_ONE_PLUS_DIST)
+    return fail(DEWI_ERR_INVALID_ARG, "unknown sim_transform %d", sim_transform);
+  if (sim_transform != DEWI_SIM_RAW && n_candidates <= 0)
+    return fail(DEWI_ERR_INVALID_ARG, "similarity transforms belong to the ANN re-rank rule: pass n_candidates as well");
+  if (k <= 0) return DEWI_OK;
+  if (n_candidates > 0 && n_candidates < k) return fail(DEWI_ERR_INVALID_ARG, "n_candidates %d must be at least k = %d", n_candidates, k);
+  // one cut for the batch: c = 2k (or n_candidates), and every list at least that long — shorter lists are searched one by one
+  // with dewi_knn_rerank_filtered (their c is |F_j|)
+  const int64_t c64 = n_candidates > 0 ? n_candidates : 2ll * k;
+  for (int j = 0; j < n_queries; ++j) {
+    if (n_allowed[j] < 0 || n_allowed[j] > n_union)
+      return fail(DEWI_ERR_INVALID_ARG, "query %d: n_allowed %lld outside [0, %lld]", j, static_cast<long long>(n_allowed[j]),
+                  static_cast<long long>(n_union));
+    if (k > n_allowed[j])
+      return fail(DEWI_ERR_K_OUT_OF_BOUNDS, "query %d: kth(=%lld) out of bounds (%lld)", j, static_cast<long long>(n_allowed[j] - k),
+                  static_cast<long long>(n_allowed[j]));
+    if (n_allowed[j] < c64)
+      return fail(DEWI_ERR_INVALID_ARG, "query %d: %lld allowed rows < the batch's cut %lld (search it on its own filter)", j,
+                  static_cast<long long>(n_allowed[j]), static_cast<long long>(c64));
+  }
+  if (!d_dewi32 || !d_ent32 || !d_out_ids || !d_out_scores) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
+  if (c64 > (1ll << 30)) return fail(DEWI_ERR_UNSUPPORTED, "candidate count %lld exceeds 2^30", static_cast<long long>(c64));
+  const int c = static_cast<int>(c64);
+  DeviceInfo dev;
+  rc = ensure_device(dev);
+  if (rc) return rc;
+  // the row kernels of this dim, planned on |U| rows; no matrix-core pass
+  const KnnLayout L = layout_knn(n_union, dim, 4, n_queries, c, dev.cus);
+  if (!d_workspace || workspace_bytes < L.total)
+    return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, L.total);
+  char* ws = static_cast<char*>(d_workspace);
+  const uint32_t* filt = static_cast<const uint32_t*>(d_filter);
+  rc = run_scan(L, d_E, 0, n_union, dim, d_Q, n_queries, c, space, ws, stream, filt, filt + dewi::kFilterHeaderWords + n_rows,
+                n_union);
+  if (rc) return rc;
+  const dewi::RerankParams rp = make_rerank(eta, entropy_pref, sim_transform, space);
+  const uint64_t* keys = reinterpret_cast<const uint64_t*>(ws + L.keys_off);
+  hipError_t e;
+  if (c > dewi::kMaxSortCandidates) {
+    uint64_t* g1 = reinterpret_cast<uint64_t*>(ws + L.big_off);
+    e = dewi::launch_select_rerank_large(keys, L.plan.keys_per_query, n_queries, c, L.p2, k, rp, d_dewi32, d_ent32, 0, g1,
+                                         g1 + static_cast<size_t>(n_queries) * L.p2, d_out_ids, d_out_scores, nullptr, c, stream);
+  } else {
+    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, L.plan.slots == 1 ? L.plan.n_lists : 0, n_queries, c, k, rp,
+                                   d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr, nullptr, dewi::SegmentLayout{}, stream);
+  }
+  return e == hipSuccess ? DEWI_OK : hip_fail(e, "select launch (query-filtered)");
 }
 
 size_t dewi_merge_workspace_bytes(int n_lists, int n_queries, int list_len, int n_candidates) {

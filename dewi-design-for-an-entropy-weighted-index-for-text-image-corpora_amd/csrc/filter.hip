@@ -143,4 +143,76 @@ hipError_t launch_filter_prepare(const uint8_t* d_mask, int64_t n_rows, int n_bu
   return hipGetLastError();
 }
 
+// ---- per-query filters (dewi_query_filter_prepare): B byte masks -> the prepared filter of their union U (the kernels above)
+// plus, per list position of U, one u32 of query bits per 32 queries, planar [ceil(B / 32)][|U|] — lane l of a wave that reads
+// the words of 64 consecutive positions gets position l: one coalesced load.  Roofline: B * n_rows mask bytes read twice (the
+// OR and the counts) + the B bytes of each union row gathered once; prepared once per batch of lists.
+
+// union[row] = OR over the queries of masks[q][row]
+__global__ __launch_bounds__(kFilterThreads) void qfilter_union(const uint8_t* __restrict__ masks, int64_t n_rows, int n_queries,
+                                                                uint8_t* __restrict__ uni) {
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * kFilterThreads + threadIdx.x;
+  if (row >= n_rows) return;
+  uint8_t any = 0;
+  for (int q = 0; q < n_queries && any == 0; ++q) any = masks[static_cast<int64_t>(q) * n_rows + row] != 0 ? 1 : 0;
+  uni[row] = any;
+}
+
+// counts[q] += allowed rows of query blockIdx.y inside block blockIdx.x of kFilterChunk rows (counts zeroed by the caller)
+__global__ __launch_bounds__(kFilterThreads) void qfilter_count(const uint8_t* __restrict__ masks, int64_t n_rows,
+                                                                uint32_t* __restrict__ counts) {
+  __shared__ uint32_t tot;
+  if (threadIdx.x == 0) tot = 0;
+  __syncthreads();
+  const uint8_t* __restrict__ m = masks + static_cast<int64_t>(blockIdx.y) * n_rows;
+  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kFilterChunk;
+  uint32_t mine = 0;
+  for (int i = threadIdx.x; i < kFilterChunk; i += kFilterThreads) {
+    const int64_t row = row0 + i;
+    if (row < n_rows && m[row] != 0) ++mine;
+  }
+  for (int off = kWave / 2; off > 0; off >>= 1) mine += __shfl_xor(mine, off, kWave);
+  if ((threadIdx.x & (kWave - 1)) == 0 && mine != 0u) atomicAdd(&tot, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && tot != 0u) atomicAdd(&counts[blockIdx.y], tot);
+}
+
+// words[w][p] (stride |U|, read from the prepared filter): bit i <=> masks[32 w + i][row at list position p]
+__global__ __launch_bounds__(kFilterThreads) void qfilter_bits(const uint8_t* __restrict__ masks, int64_t n_rows, int n_queries,
+                                                               const uint32_t* __restrict__ filt, uint32_t* __restrict__ words) {
+  const int64_t n_union = filt[kFilterMaxBuckets];
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * kFilterThreads + threadIdx.x;
+  if (p >= n_union) return;
+  const int64_t row = filt[kFilterHeaderWords + p];
+  const int q0 = static_cast<int>(blockIdx.y) * 32;
+  const int nq = n_queries - q0 < 32 ? n_queries - q0 : 32;
+  uint32_t bits = 0;
+  for (int i = 0; i < nq; ++i) bits |= (masks[static_cast<int64_t>(q0 + i) * n_rows + row] != 0 ? 1u : 0u) << i;
+  words[static_cast<int64_t>(blockIdx.y) * n_union + p] = bits;
+}
+
+hipError_t launch_query_filter_prepare(const uint8_t* d_masks, int64_t n_rows, int n_queries, int n_buckets, uint8_t* d_union,
+                                       uint32_t* d_counts, uint32_t* d_filter, uint32_t* d_scratch, uint32_t* d_words,
+                                       hipStream_t stream) {
+  const int64_t nblk = filter_blocks(n_rows);
+  const int64_t row_blocks = (n_rows + kFilterThreads - 1) / kFilterThreads;
+  const int n_words = (n_queries + 31) / 32;
+  if (n_queries <= 0 || n_queries > 65535 || row_blocks > 0x7FFFFFFF) return hipErrorInvalidValue;   // (grid limits)
+  hipLaunchKernelGGL(qfilter_union, dim3(static_cast<unsigned>(row_blocks)), dim3(kFilterThreads), 0, stream, d_masks, n_rows,
+                     n_queries, d_union);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * static_cast<size_t>(n_queries), stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(qfilter_count, dim3(static_cast<unsigned>(nblk), static_cast<unsigned>(n_queries)), dim3(kFilterThreads), 0,
+                     stream, d_masks, n_rows, d_counts);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = launch_filter_prepare(d_union, n_rows, n_buckets, d_filter, d_scratch, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(qfilter_bits, dim3(static_cast<unsigned>(row_blocks), static_cast<unsigned>(n_words)), dim3(kFilterThreads), 0,
+                     stream, d_masks, n_rows, n_queries, d_filter, d_words);
+  return hipGetLastError();
+}
+
 }  // namespace dewi

@@ -28,11 +28,15 @@ namespace dewi {
 // 4 (c <= 256, one unsorted list per wave) or 0 (dense: one key per row).
 // LIST (filtered scan): the rows are the list of a prepared filter `filt` (scan_common.hpp, one bucket) instead of
 // 0 .. n_rows; `n_rows` is then unused and a dense key goes to the list position.
-template <int U, int R, int NQ, int SPACE, int S, bool NT, bool LIST = false>
+// QMASK (per-query filters, LIST only): `filt` is the union of the batch's lists and qword[p] holds the query bits of list
+// position p — query qi of the pass takes the row only if bit qshift + qi is set (a scalar branch: the word is wave-uniform);
+// a dense key of a pair it does not take is kKeyEmpty.
+template <int U, int R, int NQ, int SPACE, int S, bool NT, bool LIST = false, bool QMASK = false>
 __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, int64_t n_rows,
                                                    const float* __restrict__ Q, int n_candidates,
                                                    uint64_t* __restrict__ keys, int64_t keys_per_query,
-                                                   MergeShared& merge_buf, const uint32_t* __restrict__ filt = nullptr) {
+                                                   MergeShared& merge_buf, const uint32_t* __restrict__ filt = nullptr,
+                                                   const uint32_t* __restrict__ qword = nullptr, int qshift = 0) {
   constexpr int D4 = 64 * U;  // float4 units per row
   constexpr bool DENSE = S == 0;
   const int lane = lane_id();
@@ -96,6 +100,26 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
       }
     }
   };
+  // QMASK: the same for the queries whose bit of qb (the row's query word: wave-uniform, a scalar branch) is set
+  [[maybe_unused]] auto consume_q = [&](const f32x4(&v)[U], int64_t row, int64_t slot, uint32_t qb) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) {
+      if (((qb >> (qshift + qi)) & 1u) != 0u) {
+        float acc = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc = accum4<SPACE>(v[u], qf[qi][u], acc);
+        float s = wave_sum_f32(acc);
+        if constexpr (SPACE == DEWI_SPACE_L2) s = -s;
+        if constexpr (DENSE) {
+          if (lane == 0) keys[qi * keys_per_query + slot] = make_key(s, static_cast<uint32_t>(row));
+        } else {
+          lst[qi].offer(s, static_cast<uint32_t>(row), lane);
+        }
+      } else if constexpr (DENSE) {
+        if (lane == 0) keys[qi * keys_per_query + slot] = kKeyEmpty;
+      }
+    }
+  };
 
   // Full R-row groups.  Deliberately NOT software-pipelined and with a small R: on MI355X the scan
   // is fastest with only ~24 KiB of loads in flight per CU (8 waves x one 3 KiB row; 1M x 768:
@@ -103,7 +127,36 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
   // apart, so that the chip still sweeps one window: 0.437 vs 0.429) — more outstanding requests lower
   // the achieved HBM rate instead of raising it.
   const int64_t n_groups = n_rows / R;
-  if constexpr (LIST) {
+  if constexpr (LIST && QMASK) {
+    // as below, with the query words of the same 64 groups loaded beside the list entries and read out the same way
+    uint32_t ahead[R], qahead[R];
+    int slot = 0;
+    for (int64_t g = gwave; g < n_groups; g += n_waves) {
+      if (slot == 0) {
+        const int64_t gl = g + static_cast<int64_t>(lane) * n_waves;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          ahead[r] = gl < n_groups ? list[gl * R + r] : 0u;
+          qahead[r] = gl < n_groups ? qword[gl * R + r] : 0u;
+        }
+      }
+      const int64_t row0 = g * R;
+      int64_t rows[R];
+      uint32_t qbits[R];
+      f32x4 v[R][U];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        rows[r] = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(ahead[r]), slot));
+        qbits[r] = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(qahead[r]), slot));
+        const f32x4* p = Ev + rows[r] * D4 + lane;
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[r][u] = load_x4<NT>(p + u * 64);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) consume_q(v[r], rows[r], row0 + r, qbits[r]);
+      slot = (slot + 1) & (kWave - 1);
+    }
+  } else if constexpr (LIST) {
     // The list entries of this wave's next 64 groups arrive in one vector load (lane l: group g + l * n_waves) and are read
     // out with readlane: a row's address never waits for a load of its own list entry.
     uint32_t ahead[R];
@@ -148,7 +201,8 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
     const f32x4* p = Ev + row_of(row) * D4 + lane;
 #pragma unroll
     for (int u = 0; u < U; ++u) v[u] = load_x4<NT>(p + u * 64);
-    consume(v, row_of(row), row);
+    if constexpr (QMASK) consume_q(v, row_of(row), row, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(qword[row]))));
+    else consume(v, row_of(row), row);
   }
 
   if constexpr (S == 1) {
@@ -179,6 +233,17 @@ __global__ __launch_bounds__(kScanThreads) void scan_rows_f32_list(const float* 
                                                                    uint64_t* __restrict__ keys, int64_t keys_per_query) {
   __shared__ MergeShared merge_buf;
   scan_rows_f32_body<U, R, NQ, SPACE, S, NT, true>(E, 0, Q, n_candidates, keys, keys_per_query, merge_buf, filt);
+}
+
+// per-query filtered scan (QMASK): the union list `filt`, query words `qword` (this pass's word plane), bits from `qshift` on
+template <int U, int R, int NQ, int SPACE, int S, bool NT>
+__global__ __launch_bounds__(kScanThreads) void scan_rows_f32_qmask(const float* __restrict__ E, const uint32_t* __restrict__ filt,
+                                                                    const uint32_t* __restrict__ qword, int qshift,
+                                                                    const float* __restrict__ Q, int n_candidates,
+                                                                    uint64_t* __restrict__ keys, int64_t keys_per_query) {
+  __shared__ MergeShared merge_buf;
+  scan_rows_f32_body<U, R, NQ, SPACE, S, NT, true, true>(E, 0, Q, n_candidates, keys, keys_per_query, merge_buf, filt, qword,
+                                                          qshift);
 }
 
 // REPAIR form (abi.cpp batch_repair): one launch answers every query of a batch whose flag is set — the queries a
@@ -352,6 +417,100 @@ __global__ __launch_bounds__(kScanThreads) void scan_generic_f32_list(const floa
       if (rr >= n_rows) break;
 #pragma unroll
       for (int qi = 0; qi < NQ; ++qi) {
+        float s = __shfl(acc[qi], r * group, kWave);
+        if constexpr (SPACE == DEWI_SPACE_L2) s = -s;
+        if constexpr (DENSE) {
+          if (lane == 0) keys[qi * keys_per_query + rr] = make_key(s, list[rr]);
+        } else {
+          lst[qi].offer(s, list[rr], lane);
+        }
+      }
+    }
+  }
+  if constexpr (S == 1) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi)
+      block_merge_store(lst[qi], merge_buf, keys + qi * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates,
+                        n_candidates, lane, wave_in_block);
+  } else if constexpr (!DENSE) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi)
+      lst[qi].store(keys + qi * keys_per_query + gwave * n_candidates, n_candidates, lane);
+  }
+}
+
+// Per-query filtered scan (QMASK): the same over the union list `filt`; qword[p] holds list position p's query bits from bit
+// qshift on — a query takes a row only if its bit is set (else its dense key is kKeyEmpty).
+template <int VEC, int NQ, int SPACE, int S>
+__global__ __launch_bounds__(kScanThreads) void scan_generic_f32_qmask(const float* __restrict__ E, const uint32_t* __restrict__ filt,
+                                                                       const uint32_t* __restrict__ qword, int qshift, int dim,
+                                                                       const float* __restrict__ Qn, int group,
+                                                                      int n_candidates, uint64_t* __restrict__ keys,
+                                                                      int64_t keys_per_query) {
+  using V = typename VecT<VEC>::type;
+  constexpr bool DENSE = S == 0;
+  __shared__ MergeShared merge_buf;
+  const int lane = lane_id();
+  const int wave_in_block = static_cast<int>(threadIdx.x) >> 6;
+  const int64_t gwave = static_cast<int64_t>(blockIdx.x) * (kScanThreads / kWave) + wave_in_block;
+  const int64_t n_waves = static_cast<int64_t>(gridDim.x) * (kScanThreads / kWave);
+  const int rows_per_step = kWave / group;
+  const int sub = lane / group;  // which row of the step
+  const int lg = lane % group;   // position inside the row group
+  const int units = dim / VEC;
+  const uint32_t* __restrict__ list = filt + kFilterHeaderWords;
+  const int64_t n_rows = filt[kFilterMaxBuckets];   // list positions (every bucket in order); the prepare step fills the
+                                                    // offsets past the last bucket with the count
+
+  WaveList<DENSE ? 1 : S> lst[DENSE ? 1 : NQ];
+  if constexpr (!DENSE) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) lst[qi].init(n_candidates, lane);
+  }
+
+  const int64_t n_steps = (n_rows + rows_per_step - 1) / rows_per_step;
+  for (int64_t st = gwave; st < n_steps; st += n_waves) {
+    const int64_t row = st * rows_per_step + sub;
+    float acc[NQ];
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) acc[qi] = 0.f;
+    if (row < n_rows) {
+      const V* ep = reinterpret_cast<const V*>(E + static_cast<int64_t>(list[row]) * dim);
+      for (int u = lg; u < units; u += group) {
+        const V e = ep[u];
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi) {
+          const V q = reinterpret_cast<const V*>(Qn + static_cast<int64_t>(qi) * dim)[u];
+          if constexpr (VEC == 4) {
+            acc[qi] = accum4<SPACE>(e, q, acc[qi]);
+          } else {
+            if constexpr (SPACE == DEWI_SPACE_COSINE) {
+              acc[qi] = __builtin_fmaf(e, q, acc[qi]);
+            } else {
+              const float d = e - q;
+              acc[qi] = __builtin_fmaf(d, d, acc[qi]);
+            }
+          }
+        }
+      }
+    }
+    // butterfly inside each group of `group` lanes
+    for (int off = group >> 1; off > 0; off >>= 1) {
+#pragma unroll
+      for (int qi = 0; qi < NQ; ++qi) acc[qi] += __shfl_xor(acc[qi], off, kWave);
+    }
+    for (int r = 0; r < rows_per_step; ++r) {
+      const int64_t rr = st * rows_per_step + r;
+      if (rr >= n_rows) break;
+      const uint32_t qb = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(qword[rr])));
+#pragma unroll
+      for (int qi = 0; qi < NQ; ++qi) {
+        if (((qb >> (qshift + qi)) & 1u) == 0u) {   // (wave-uniform) query qi does not take this row
+          if constexpr (DENSE) {
+            if (lane == 0) keys[qi * keys_per_query + rr] = kKeyEmpty;
+          }
+          continue;
+        }
         float s = __shfl(acc[qi], r * group, kWave);
         if constexpr (SPACE == DEWI_SPACE_L2) s = -s;
         if constexpr (DENSE) {
@@ -597,11 +756,20 @@ ScanPlan plan_scan(int64_t n_rows, int dim, int elem_bytes, int n_candidates, in
   return p;
 }
 
-// LIST: the filtered scan over the prepared filter `filt` (n_rows unused)
+// LIST: the filtered scan over the prepared filter `filt` (n_rows unused); qw.words set: the per-query (QMASK) form
 template <int U, int R, int NQ, int SPACE, int S, bool LIST>
 static void launch_fast_nt(const ScanPlan& plan, const float* E, int64_t n_rows, const float* Q, int c,
-                           uint64_t* keys, hipStream_t stream, const uint32_t* filt) {
+                           uint64_t* keys, hipStream_t stream, const uint32_t* filt, QWords qw) {
   if constexpr (LIST) {
+    if (qw.words) {
+      if (plan.nontemporal)
+        hipLaunchKernelGGL((scan_rows_f32_qmask<U, R, NQ, SPACE, S, true>), dim3(plan.blocks), dim3(kScanThreads), 0,
+                           stream, E, filt, qw.words, qw.shift, Q, c, keys, plan.keys_per_query);
+      else
+        hipLaunchKernelGGL((scan_rows_f32_qmask<U, R, NQ, SPACE, S, false>), dim3(plan.blocks), dim3(kScanThreads), 0,
+                           stream, E, filt, qw.words, qw.shift, Q, c, keys, plan.keys_per_query);
+      return;
+    }
     if (plan.nontemporal)
       hipLaunchKernelGGL((scan_rows_f32_list<U, R, NQ, SPACE, S, true>), dim3(plan.blocks), dim3(kScanThreads), 0,
                          stream, E, filt, Q, c, keys, plan.keys_per_query);
@@ -620,49 +788,58 @@ static void launch_fast_nt(const ScanPlan& plan, const float* E, int64_t n_rows,
 
 template <int U, int NQ, int SPACE, int S, bool LIST>
 static bool launch_fast_r(const ScanPlan& plan, const float* E, int64_t n_rows, const float* Q, int c,
-                          uint64_t* keys, hipStream_t stream, const uint32_t* filt) {
+                          uint64_t* keys, hipStream_t stream, const uint32_t* filt, QWords qw) {
   // R only changes how rows are grouped per wave; results do not depend on it.  Combinations that
   // are not instantiated (register budget, build time) step down to the next smaller R.
   const int r = NQ >= 4 ? plan.rows_per_iter_batch : plan.rows_per_iter;
   if (r >= 8) {
     if constexpr (U <= 3 && NQ == 1 && S == 1) {
-      launch_fast_nt<U, 8, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
+      launch_fast_nt<U, 8, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt, qw);
       return true;
     }
   }
   if (r >= 4) {
     if constexpr (U <= 3 && NQ == 1) {
-      launch_fast_nt<U, 4, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
+      launch_fast_nt<U, 4, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt, qw);
       return true;
     }
   }
   if (r >= 2) {
     if constexpr (U <= 3) {
-      launch_fast_nt<U, 2, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
+      launch_fast_nt<U, 2, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt, qw);
       return true;
     }
   }
-  launch_fast_nt<U, 1, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
+  launch_fast_nt<U, 1, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt, qw);
   return true;
 }
 
 template <int NQ, int SPACE, int S, bool LIST>
 static bool launch_fast_u(const ScanPlan& plan, int dim, const float* E, int64_t n_rows, const float* Q, int c,
-                          uint64_t* keys, hipStream_t stream, const uint32_t* filt) {
+                          uint64_t* keys, hipStream_t stream, const uint32_t* filt, QWords qw) {
   switch (dim / 256) {
-    case 1: return launch_fast_r<1, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
-    case 2: return launch_fast_r<2, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
-    case 3: return launch_fast_r<3, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
-    case 4: return launch_fast_r<4, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
-    case 6: return launch_fast_r<6, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
+    case 1: return launch_fast_r<1, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt, qw);
+    case 2: return launch_fast_r<2, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt, qw);
+    case 3: return launch_fast_r<3, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt, qw);
+    case 4: return launch_fast_r<4, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt, qw);
+    case 6: return launch_fast_r<6, NQ, SPACE, S, LIST>(plan, E, n_rows, Q, c, keys, stream, filt, qw);
     default: return false;
   }
 }
 
 template <int NQ, int SPACE, int S, bool LIST>
 static void launch_generic(const ScanPlan& plan, int dim, const float* E, int64_t n_rows, const float* Qn, int c,
-                           uint64_t* keys, hipStream_t stream, const uint32_t* filt) {
+                           uint64_t* keys, hipStream_t stream, const uint32_t* filt, QWords qw) {
   if constexpr (LIST) {
+    if (qw.words) {
+      if (plan.vec == 4)
+        hipLaunchKernelGGL((scan_generic_f32_qmask<4, NQ, SPACE, S>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E,
+                           filt, qw.words, qw.shift, dim, Qn, plan.group, c, keys, plan.keys_per_query);
+      else
+        hipLaunchKernelGGL((scan_generic_f32_qmask<1, NQ, SPACE, S>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E,
+                           filt, qw.words, qw.shift, dim, Qn, plan.group, c, keys, plan.keys_per_query);
+      return;
+    }
     if (plan.vec == 4)
       hipLaunchKernelGGL((scan_generic_f32_list<4, NQ, SPACE, S>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E,
                          filt, dim, Qn, plan.group, c, keys, plan.keys_per_query);
@@ -681,11 +858,12 @@ static void launch_generic(const ScanPlan& plan, int dim, const float* E, int64_
 
 template <int NQ, int SPACE, int S, bool LIST = false>
 static hipError_t launch_scan_impl(const ScanPlan& plan, const float* E, int64_t n_rows, int dim, const float* Qraw,
-                                   const float* Qn, int c, uint64_t* keys, hipStream_t stream, const uint32_t* filt = nullptr) {
+                                   const float* Qn, int c, uint64_t* keys, hipStream_t stream, const uint32_t* filt = nullptr,
+                                   QWords qw = {}) {
   if (plan.fast) {
-    if (!launch_fast_u<NQ, SPACE, S, LIST>(plan, dim, E, n_rows, Qraw, c, keys, stream, filt)) return hipErrorInvalidValue;
+    if (!launch_fast_u<NQ, SPACE, S, LIST>(plan, dim, E, n_rows, Qraw, c, keys, stream, filt, qw)) return hipErrorInvalidValue;
   } else {
-    launch_generic<NQ, SPACE, S, LIST>(plan, dim, E, n_rows, Qn, c, keys, stream, filt);
+    launch_generic<NQ, SPACE, S, LIST>(plan, dim, E, n_rows, Qn, c, keys, stream, filt, qw);
   }
   return hipGetLastError();
 }
@@ -747,21 +925,21 @@ hipError_t launch_scan_flagged_f32(const ScanPlan& plan, const float* d_E, int64
 template <bool LIST>
 static hipError_t scan_f32_dispatch(const ScanPlan& plan, const float* d_E, int64_t n_rows, int dim, const float* d_q_raw,
                                     const float* d_q_norm, int q0, int nq, int n_candidates, int space, uint64_t* d_keys,
-                                    hipStream_t stream, const uint32_t* filt) {
+                                    hipStream_t stream, const uint32_t* filt, QWords qw) {
   if (plan.odd_rows)
-    return LIST ? launch_scan_odd_f32_list(plan, d_E, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, filt, stream)
+    return LIST ? launch_scan_odd_f32_list(plan, d_E, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, filt, stream, qw)
                 : launch_scan_odd_f32(plan, d_E, n_rows, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, stream);
   if (plan.kind == kScanAnyLong || plan.kind == kScanAnyShort)
-    return LIST ? launch_scan_any_f32_list(plan, d_E, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, filt, stream)
+    return LIST ? launch_scan_any_f32_list(plan, d_E, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, filt, stream, qw)
                 : launch_scan_any_f32(plan, d_E, n_rows, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, stream);
   const float* qr = d_q_raw + static_cast<int64_t>(q0) * dim;
   const float* qn = d_q_norm ? d_q_norm + static_cast<int64_t>(q0) * dim : nullptr;
   uint64_t* keys = d_keys + static_cast<int64_t>(q0) * plan.keys_per_query;
 #define DEWI_DISPATCH_S(NQ, SPACE)                                                                              \
   switch (plan.slots) {                                                                                          \
-    case 0: return launch_scan_impl<NQ, SPACE, 0, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt);   \
-    case 1: return launch_scan_impl<NQ, SPACE, 1, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt);   \
-    default: return launch_scan_impl<NQ, SPACE, kMaxSlots, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt); \
+    case 0: return launch_scan_impl<NQ, SPACE, 0, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt, qw);   \
+    case 1: return launch_scan_impl<NQ, SPACE, 1, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt, qw);   \
+    default: return launch_scan_impl<NQ, SPACE, kMaxSlots, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt, qw); \
   }
 #define DEWI_DISPATCH(NQ)                                  \
   if (space == DEWI_SPACE_COSINE) {                        \
@@ -775,8 +953,8 @@ static hipError_t scan_f32_dispatch(const ScanPlan& plan, const float* d_E, int6
     DEWI_DISPATCH(4)
   } else if (nq == 8 && plan.fast && plan.slots == 1) {   // eight queries per corpus pass: row-per-wave kernel, c <= 64 only
     if (space == DEWI_SPACE_COSINE)
-      return launch_scan_impl<8, DEWI_SPACE_COSINE, 1, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt);
-    return launch_scan_impl<8, DEWI_SPACE_L2, 1, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt);
+      return launch_scan_impl<8, DEWI_SPACE_COSINE, 1, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt, qw);
+    return launch_scan_impl<8, DEWI_SPACE_L2, 1, LIST>(plan, d_E, n_rows, dim, qr, qn, n_candidates, keys, stream, filt, qw);
   }
 #undef DEWI_DISPATCH
 #undef DEWI_DISPATCH_S
@@ -786,13 +964,16 @@ static hipError_t scan_f32_dispatch(const ScanPlan& plan, const float* d_E, int6
 hipError_t launch_scan_f32(const ScanPlan& plan, const float* d_E, int64_t n_rows, int dim, const float* d_q_raw,
                            const float* d_q_norm, int q0, int nq, int n_candidates, int space, uint64_t* d_keys,
                            hipStream_t stream) {
-  return scan_f32_dispatch<false>(plan, d_E, n_rows, dim, d_q_raw, d_q_norm, q0, nq, n_candidates, space, d_keys, stream, nullptr);
+  return scan_f32_dispatch<false>(plan, d_E, n_rows, dim, d_q_raw, d_q_norm, q0, nq, n_candidates, space, d_keys, stream, nullptr,
+                                  QWords{});
 }
 
 hipError_t launch_scan_f32_filtered(const ScanPlan& plan, const float* d_E, int dim, const float* d_q_raw, const float* d_q_norm,
                                     int q0, int nq, int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter,
-                                    hipStream_t stream) {
-  return scan_f32_dispatch<true>(plan, d_E, 0, dim, d_q_raw, d_q_norm, q0, nq, n_candidates, space, d_keys, stream, d_filter);
+                                    hipStream_t stream, QWords qw) {
+  // a pass's query bits never straddle two words (passes of 8, 4, 2, 1 queries start at multiples of their size)
+  if (qw.words && (qw.shift < 0 || qw.shift + nq > 32)) return hipErrorInvalidValue;
+  return scan_f32_dispatch<true>(plan, d_E, 0, dim, d_q_raw, d_q_norm, q0, nq, n_candidates, space, d_keys, stream, d_filter, qw);
 }
 
 }  // namespace dewi

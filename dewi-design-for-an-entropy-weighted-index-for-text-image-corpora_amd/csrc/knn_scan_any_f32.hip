@@ -9,8 +9,9 @@ hipError_t launch_scan_any_f32(const ScanPlan& plan, const float* d_E, int64_t n
 }
 
 hipError_t launch_scan_any_f32_list(const ScanPlan& plan, const float* d_E, int dim, const float* d_q_raw, int q0, int nq,
-                                    int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter, hipStream_t stream) {
-  return launch_scan_any_impl<0, false, true>(plan, d_E, 0, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, stream, d_filter);
+                                    int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter, hipStream_t stream,
+                                    QWords qw) {
+  return launch_scan_any_impl<0, false, true>(plan, d_E, 0, dim, d_q_raw, q0, nq, n_candidates, space, d_keys, stream, d_filter, qw);
 }
 
 hipError_t launch_scan_any_flagged_f32(const ScanPlan& plan, const float* d_E, int64_t n_rows, int dim, const float* d_q_raw,

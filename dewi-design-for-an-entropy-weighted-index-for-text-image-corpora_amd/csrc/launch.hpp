@@ -107,16 +107,26 @@ hipError_t launch_scan_f32(const ScanPlan& plan, const float* d_E, int64_t n_row
                            const float* d_q_norm, int q0, int nq, int n_candidates, int space, uint64_t* d_keys,
                            hipStream_t stream);
 
+// Per-query filters (QMASK forms of the filtered scan): `words` is the pass's plane of query words of a prepared query-filter
+// buffer (filter.hip) — words[p] bit shift + qi set: query q0 + qi of the pass may take list position p of the union.
+// words == nullptr: one list for every query.
+struct QWords {
+  const uint32_t* words = nullptr;
+  int shift = 0;
+};
+
 // Filtered scan (fp32 corpus): the same pass over the rows of a prepared filter (d_filter: dewi_filter_prepare's buffer, see
 // scan_common.hpp kFilterHeaderWords) — plan made on the list's length, keys_per_query keys per query, dense keys at list
 // positions; the kernel family is the one launch_scan_f32 takes for this dim (never scan_rows_odd_contig).
 hipError_t launch_scan_f32_filtered(const ScanPlan& plan, const float* d_E, int dim, const float* d_q_raw, const float* d_q_norm,
                                     int q0, int nq, int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter,
-                                    hipStream_t stream);
+                                    hipStream_t stream, QWords qw = {});
 hipError_t launch_scan_any_f32_list(const ScanPlan& plan, const float* d_E, int dim, const float* d_q_raw, int q0, int nq,
-                                    int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter, hipStream_t stream);
+                                    int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter, hipStream_t stream,
+                                    QWords qw = {});
 hipError_t launch_scan_odd_f32_list(const ScanPlan& plan, const float* d_E, int dim, const float* d_q_raw, int q0, int nq,
-                                    int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter, hipStream_t stream);
+                                    int n_candidates, int space, uint64_t* d_keys, const uint32_t* d_filter, hipStream_t stream,
+                                    QWords qw = {});
 // Layout of a prepared filter (u32 words): bucket offsets [0 .. kFilterMaxBuckets] (past the last bucket: the count), the
 // number of buckets at [kFilterMaxBuckets + 1], the allowed rows from kFilterHeaderWords on (filter.hip).
 constexpr int kFilterHeaderWords = 16;
@@ -127,6 +137,13 @@ int64_t filter_blocks(int64_t n_rows);
 size_t filter_scratch_words(int64_t n_rows, int n_buckets);
 hipError_t launch_filter_prepare(const uint8_t* d_mask, int64_t n_rows, int n_buckets, uint32_t* d_filter, uint32_t* d_scratch,
                                  hipStream_t stream);
+// Query-filter preparation (filter.hip): byte masks [n_queries][n_rows] -> d_union (n_rows bytes: the OR of the masks),
+// d_counts[n_queries] (allowed rows per query), the prepared filter of the union in d_filter (launch_filter_prepare, d_scratch as
+// there) and the query words [ceil(n_queries / 32)][|U|] at d_words — word w of list position p: bit i set <=> mask 32 w + i
+// allows the row at p.
+hipError_t launch_query_filter_prepare(const uint8_t* d_masks, int64_t n_rows, int n_queries, int n_buckets, uint8_t* d_union,
+                                       uint32_t* d_counts, uint32_t* d_filter, uint32_t* d_scratch, uint32_t* d_words,
+                                       hipStream_t stream);
 
 // ---- knn_scan_any_f32.hip / knn_scan_any_bf16.hip: plan.kind == kScanAnyLong / kScanAnyShort (raw queries)
 hipError_t launch_scan_any_f32(const ScanPlan& plan, const float* d_E, int64_t n_rows, int dim, const float* d_q_raw, int q0,

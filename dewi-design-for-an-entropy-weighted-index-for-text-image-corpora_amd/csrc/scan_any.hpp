@@ -178,11 +178,15 @@ constexpr int kAnyShortRows = DEWI_ANY_RSHORT;   // loads (of 64 / P rows each) 
 // `units`: 16-byte units per row; PH (rows that are not whole units): COLUMNS per row instead.
 // LIST (filtered scan): the rows are the list of a prepared filter `filt` (scan_common.hpp) instead of 0 .. n_rows; `n_rows` is
 // then unused.  A wave takes list entries of one bucket (PH: one residue, as above); dense keys go to the list position.
-template <int ELEM, int U, int R, int NQ, int SPACE, int S, bool PH = false, bool LIST = false>
+// QMASK (per-query filters, LIST only): `filt` is the union of the batch's lists and qword[p] the query bits of list position p;
+// query qi of the pass takes a row only if bit qshift + qi is set (a wave-uniform word: a scalar branch), else its dense key is
+// kKeyEmpty.
+template <int ELEM, int U, int R, int NQ, int SPACE, int S, bool PH = false, bool LIST = false, bool QMASK = false>
 __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, int64_t n_rows, int units,
                                                    const float* __restrict__ Q, int n_candidates,
                                                    uint64_t* __restrict__ keys, int64_t keys_per_query, MergeShared& merge_buf,
-                                                   const uint32_t* __restrict__ filt = nullptr) {
+                                                   const uint32_t* __restrict__ filt = nullptr,
+                                                   const uint32_t* __restrict__ qword = nullptr, int qshift = 0) {
   constexpr int kCols = ELEM ? 8 : 4;
   constexpr int kElemBytes = ELEM ? 2 : 4;
   constexpr bool DENSE = S == 0;
@@ -290,7 +294,11 @@ __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, 
       if (act[u]) v[u] = load_u4<true>(p + 64 * u);
     }
   };
-  auto consume = [&](u32x4(&v)[U], int64_t row, int64_t slot) {
+  auto qbits_of = [&](int64_t i) -> uint32_t {   // QMASK: the query bits of the wave's i-th row (wave-uniform)
+    if constexpr (QMASK) return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(qword[list_base + i])));
+    else return 0u;
+  };
+  auto consume = [&](u32x4(&v)[U], int64_t row, int64_t slot, [[maybe_unused]] uint32_t qb) {
     if constexpr (PH) {
       v[0] = and_u4(v[0], keep_first);
 #pragma unroll
@@ -299,6 +307,14 @@ __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, 
     }
 #pragma unroll
     for (int qi = 0; qi < NQ; ++qi) {
+      if constexpr (QMASK) {
+        if (((qb >> (qshift + qi)) & 1u) == 0u) {
+          if constexpr (DENSE) {
+            if (lane == 0) keys[qi * keys_per_query + slot] = kKeyEmpty;
+          }
+          continue;
+        }
+      }
       float acc = 0.f;
 #pragma unroll
       for (int u = 0; u < U; ++u) acc = qf[qi][u].dot(v[u], acc);
@@ -326,12 +342,12 @@ __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, 
       for (int r = 0; r < R; ++r) fetch(v[r], p + r * row_units);
     }
 #pragma unroll
-    for (int r = 0; r < R; ++r) consume(v[r], row_of(g * R + r), slot_of(g * R + r));
+    for (int r = 0; r < R; ++r) consume(v[r], row_of(g * R + r), slot_of(g * R + r), qbits_of(g * R + r));
   }
   for (int64_t i = n_groups * R + wave_pos; i < n_mine; i += wave_cnt) {   // fewer than R rows left
     u32x4 v[U];
     fetch(v, E + first_unit(i) + lane);
-    consume(v, row_of(i), slot_of(i));
+    consume(v, row_of(i), slot_of(i), qbits_of(i));
   }
 
   if constexpr (S == 1) {
@@ -361,6 +377,17 @@ __global__ __launch_bounds__(kScanThreads) void scan_rows_any_list(const u32x4* 
                                                                    uint64_t* __restrict__ keys, int64_t keys_per_query) {
   __shared__ MergeShared merge_buf;
   scan_rows_any_body<ELEM, U, R, NQ, SPACE, S, PH, true>(E, 0, units, Q, n_candidates, keys, keys_per_query, merge_buf, filt);
+}
+
+// per-query filtered scan (QMASK): the union list `filt`, this pass's query words `qword`, bits from `qshift` on
+template <int ELEM, int U, int R, int NQ, int SPACE, int S, bool PH = false>
+__global__ __launch_bounds__(kScanThreads) void scan_rows_any_qmask(const u32x4* __restrict__ E, const uint32_t* __restrict__ filt,
+                                                                    const uint32_t* __restrict__ qword, int qshift, int units,
+                                                                    const float* __restrict__ Q, int n_candidates,
+                                                                    uint64_t* __restrict__ keys, int64_t keys_per_query) {
+  __shared__ MergeShared merge_buf;
+  scan_rows_any_body<ELEM, U, R, NQ, SPACE, S, PH, true, true>(E, 0, units, Q, n_candidates, keys, keys_per_query, merge_buf, filt,
+                                                               qword, qshift);
 }
 
 // Rows that are not whole units, ONE query, up to two units per lane: a wave on CONSECUTIVE rows (scan_rows_odd_contig).
@@ -509,11 +536,14 @@ __device__ __forceinline__ float group_sum_f32(float v, int log2p) {
 // the rows of one load are a multiple of the period G of the rows' offsets — a lane's rows all have the residue sub mod G.
 // LIST (filtered scan): a wave takes list entries of one bucket of the prepared filter `filt` — PH: every lane group then
 // has the bucket's residue — and a lane group's rows come from the list; `n_rows` is unused, dense keys go to list positions.
-template <int ELEM, int R, int NQ, int SPACE, int S, bool PH = false, bool LIST = false>
+// QMASK (per-query filters, LIST only): qword[j] holds the query bits of list position j — here one word per lane group, so
+// a query's bit joins the lane predicate instead of a branch.
+template <int ELEM, int R, int NQ, int SPACE, int S, bool PH = false, bool LIST = false, bool QMASK = false>
 __device__ __forceinline__ void scan_short_rows_any_body(const u32x4* __restrict__ E, int64_t n_rows, int units, int log2p,
                                                          const float* __restrict__ Q, int n_candidates,
                                                          uint64_t* __restrict__ keys, int64_t keys_per_query,
-                                                         MergeShared& merge_buf, const uint32_t* __restrict__ filt = nullptr) {
+                                                         MergeShared& merge_buf, const uint32_t* __restrict__ filt = nullptr,
+                                                         const uint32_t* __restrict__ qword = nullptr, int qshift = 0) {
   constexpr int kCols = ELEM ? 8 : 4;
   constexpr int kElemBytes = ELEM ? 2 : 4;
   constexpr bool DENSE = S == 0;
@@ -575,10 +605,12 @@ __device__ __forceinline__ void scan_short_rows_any_body(const u32x4* __restrict
     for (int64_t st = part.wave_pos; st < n_steps; st += part.wave_cnt) {
       u32x4 v[R];
       int64_t row[R];
+      [[maybe_unused]] uint32_t qb[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const int64_t j = st * rows_per_step + static_cast<int64_t>(r) * rows_per_load + sub;
         row[r] = j < part.count ? static_cast<int64_t>(list[j]) : -1;
+        if constexpr (QMASK) qb[r] = j < part.count ? qword[part.base + j] >> qshift : 0u;
       }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
@@ -593,12 +625,14 @@ __device__ __forceinline__ void scan_short_rows_any_body(const u32x4* __restrict
         for (int qi = 0; qi < NQ; ++qi) {
           float s = group_sum_f32(qf[qi].dot(v[r], 0.f), log2p);
           if constexpr (SPACE == DEWI_SPACE_L2) s = -s;
+          bool take = true;   // QMASK: query qi may take this lane group's row
+          if constexpr (QMASK) take = ((qb[r] >> qi) & 1u) != 0u;
           if constexpr (DENSE) {
             if (mine)
               keys[qi * keys_per_query + part.base + st * rows_per_step + static_cast<int64_t>(r) * rows_per_load + sub] =
-                  make_key(s, static_cast<uint32_t>(row[r]));
+                  take ? make_key(s, static_cast<uint32_t>(row[r])) : kKeyEmpty;
           } else {
-            unsigned long long m = __ballot(mine && !(s < lst[qi].thr_s));
+            unsigned long long m = __ballot(mine && take && !(s < lst[qi].thr_s));
             while (m != 0ull) {
               const int src = __ffsll(m) - 1;
               m &= m - 1ull;
@@ -681,6 +715,17 @@ __global__ __launch_bounds__(kScanThreads) void scan_short_rows_any_list(const u
   scan_short_rows_any_body<ELEM, R, NQ, SPACE, S, PH, true>(E, 0, units, log2p, Q, n_candidates, keys, keys_per_query, merge_buf, filt);
 }
 
+// per-query filtered scan (QMASK, scan_rows_any_qmask)
+template <int ELEM, int R, int NQ, int SPACE, int S, bool PH = false>
+__global__ __launch_bounds__(kScanThreads) void scan_short_rows_any_qmask(const u32x4* __restrict__ E, const uint32_t* __restrict__ filt,
+                                                                          const uint32_t* __restrict__ qword, int qshift, int units,
+                                                                          int log2p, const float* __restrict__ Q, int n_candidates,
+                                                                          uint64_t* __restrict__ keys, int64_t keys_per_query) {
+  __shared__ MergeShared merge_buf;
+  scan_short_rows_any_body<ELEM, R, NQ, SPACE, S, PH, true, true>(E, 0, units, log2p, Q, n_candidates, keys, keys_per_query, merge_buf,
+                                                                  filt, qword, qshift);
+}
+
 template <int ELEM, int R, int SPACE, int S>
 __global__ __launch_bounds__(kScanThreads) void scan_short_rows_any_flagged(const u32x4* __restrict__ E, int64_t n_rows, int units,
                                                                             int log2p, const float* __restrict__ Q,
@@ -699,17 +744,23 @@ __global__ __launch_bounds__(kScanThreads) void scan_short_rows_any_flagged(cons
 // dispatch (one translation unit per element type instantiates it: knn_scan_any_f32.hip, knn_scan_any_bf16.hip)
 // ---------------------------------------------------------------------------------------------
 // LIST: the filtered scan over the prepared filter `filt` (n_rows unused)
+// qw.words set (LIST only): the per-query (QMASK) form
 template <int ELEM, int NQ, int SPACE, int S, bool PH, bool LIST = false>
 static hipError_t launch_any_long(const ScanPlan& plan, const u32x4* E, int64_t n_rows, const float* Q, int c, uint64_t* keys,
-                                  hipStream_t stream, const uint32_t* filt = nullptr) {
+                                  hipStream_t stream, const uint32_t* filt = nullptr, QWords qw = {}) {
   const int width = PH ? plan.row_cols : plan.units;
 #define DEWI_ANY_LAUNCH(UU, RR)                                                                                          \
-  if constexpr (LIST)                                                                                                    \
-    hipLaunchKernelGGL((scan_rows_any_list<ELEM, UU, RR, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E, \
-                       filt, width, Q, c, keys, plan.keys_per_query);                                                   \
-  else                                                                                                                   \
-    hipLaunchKernelGGL((scan_rows_any<ELEM, UU, RR, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E, n_rows, \
-                       width, Q, c, keys, plan.keys_per_query);                                                         \
+  if constexpr (LIST) {                                                                                                  \
+    if (qw.words)                                                                                                        \
+      hipLaunchKernelGGL((scan_rows_any_qmask<ELEM, UU, RR, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0, stream,\
+                         E, filt, qw.words, qw.shift, width, Q, c, keys, plan.keys_per_query);                           \
+    else                                                                                                                 \
+      hipLaunchKernelGGL((scan_rows_any_list<ELEM, UU, RR, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0, stream,\
+                         E, filt, width, Q, c, keys, plan.keys_per_query);                                               \
+  } else {                                                                                                               \
+    hipLaunchKernelGGL((scan_rows_any<ELEM, UU, RR, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, E,\
+                       n_rows, width, Q, c, keys, plan.keys_per_query);                                                  \
+  }                                                                                                                      \
   return hipGetLastError();
 #define DEWI_ANY_CASE(UU)                                                                                       \
   case UU:                                                                                                      \
@@ -758,11 +809,17 @@ static hipError_t launch_any_long(const ScanPlan& plan, const u32x4* E, int64_t 
 
 template <int ELEM, int NQ, int SPACE, int S, bool PH, bool LIST = false>
 static hipError_t launch_any_kind(const ScanPlan& plan, const u32x4* E, int64_t n_rows, const float* Q, int c, uint64_t* keys,
-                                  hipStream_t stream, const uint32_t* filt = nullptr) {
+                                  hipStream_t stream, const uint32_t* filt = nullptr, QWords qw = {}) {
   if (plan.kind == kScanAnyShort) {
     if constexpr (NQ == 2) {
       return hipErrorInvalidValue;
     } else if constexpr (LIST) {
+      if (qw.words) {
+        hipLaunchKernelGGL((scan_short_rows_any_qmask<ELEM, kAnyShortRows, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads),
+                           0, stream, E, filt, qw.words, qw.shift, PH ? plan.row_cols : plan.units, plan.log2p, Q, c, keys,
+                           plan.keys_per_query);
+        return hipGetLastError();
+      }
       hipLaunchKernelGGL((scan_short_rows_any_list<ELEM, kAnyShortRows, NQ, SPACE, S, PH>), dim3(plan.blocks), dim3(kScanThreads), 0,
                          stream, E, filt, PH ? plan.row_cols : plan.units, plan.log2p, Q, c, keys, plan.keys_per_query);
       return hipGetLastError();
@@ -772,7 +829,7 @@ static hipError_t launch_any_kind(const ScanPlan& plan, const u32x4* E, int64_t 
       return hipGetLastError();
     }
   }
-  return launch_any_long<ELEM, NQ, SPACE, S, PH, LIST>(plan, E, n_rows, Q, c, keys, stream, filt);
+  return launch_any_long<ELEM, NQ, SPACE, S, PH, LIST>(plan, E, n_rows, Q, c, keys, stream, filt, qw);
 }
 
 // PH = false: rows of whole units (knn_scan_any_*.hip); PH = true: the others (knn_scan_odd_*.hip)
@@ -781,15 +838,15 @@ static hipError_t launch_any_kind(const ScanPlan& plan, const u32x4* E, int64_t 
 template <int ELEM, bool PH = false, bool LIST = false>
 static hipError_t launch_scan_any_impl(const ScanPlan& plan, const void* d_E, int64_t n_rows, int dim, const float* d_q_raw, int q0,
                                        int nq, int n_candidates, int space, uint64_t* d_keys, hipStream_t stream,
-                                       const uint32_t* filt = nullptr) {
+                                       const uint32_t* filt = nullptr, QWords qw = {}) {
   const u32x4* E = static_cast<const u32x4*>(d_E);
   const float* Q = d_q_raw + static_cast<int64_t>(q0) * dim;
   uint64_t* keys = d_keys + static_cast<int64_t>(q0) * plan.keys_per_query;
 #define DEWI_ANY_S(NQ, SPACE)                                                                                        \
   switch (plan.slots) {                                                                                              \
-    case 0: return launch_any_kind<ELEM, NQ, SPACE, 0, PH, LIST>(plan, E, n_rows, Q, n_candidates, keys, stream, filt);          \
-    case 1: return launch_any_kind<ELEM, NQ, SPACE, 1, PH, LIST>(plan, E, n_rows, Q, n_candidates, keys, stream, filt);          \
-    default: return launch_any_kind<ELEM, NQ, SPACE, kMaxSlots, PH, LIST>(plan, E, n_rows, Q, n_candidates, keys, stream, filt); \
+    case 0: return launch_any_kind<ELEM, NQ, SPACE, 0, PH, LIST>(plan, E, n_rows, Q, n_candidates, keys, stream, filt, qw);          \
+    case 1: return launch_any_kind<ELEM, NQ, SPACE, 1, PH, LIST>(plan, E, n_rows, Q, n_candidates, keys, stream, filt, qw);          \
+    default: return launch_any_kind<ELEM, NQ, SPACE, kMaxSlots, PH, LIST>(plan, E, n_rows, Q, n_candidates, keys, stream, filt, qw); \
   }
 #define DEWI_ANY_Q(NQ)                 \
   if (space == DEWI_SPACE_COSINE) {    \
@@ -833,7 +890,7 @@ static hipError_t launch_scan_any_impl(const ScanPlan& plan, const void* d_E, in
       if (space != DEWI_SPACE_COSINE) {
         for (int i = 0; i < 4; ++i) {
           const hipError_t e = launch_scan_any_impl<ELEM, PH, LIST>(plan, d_E, n_rows, dim, d_q_raw, q0 + i, 1, n_candidates, space, d_keys,
-                                                                    stream, filt);
+                                                                    stream, filt, qw);
           if (e != hipSuccess) return e;
         }
         return hipSuccess;

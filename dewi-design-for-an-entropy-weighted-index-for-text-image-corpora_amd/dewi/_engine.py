@@ -49,6 +49,37 @@ class DeviceFilter:
         return f"DeviceFilter({self.n_allowed} of {self.n_rows} rows)"
 
 
+class DeviceQueryFilters:
+    """Prepared per-query allow-lists (``DeviceCorpus.make_query_filters``): query j of a batch of ``n_queries`` searches
+    only the rows of its own list F_j.  Holds the device buffer ``dewi_query_filter_prepare`` made (the union U of the lists,
+    prepared like one filter, plus one word of query bits per 32 queries for every row of U), the device masks, |U|
+    (``n_union``) and |F_j| (``n_allowed``, int64 [n_queries]).  Stale-checked like ``DeviceFilter``: a set used with
+    another corpus raises ``ValueError``."""
+
+    __slots__ = ("buf", "masks", "n_allowed", "n_union", "corpus_id", "n_rows", "_singles", "_subsets")
+
+    def __init__(self, buf, masks, n_allowed, n_union: int, corpus_id: int, n_rows: int):
+        self.buf = buf
+        self.masks = masks                      # device uint8 [n_queries, n_rows]: lists of queries searched on their own
+        self.n_allowed = np.asarray(n_allowed, dtype=np.int64)
+        self.n_union = int(n_union)
+        self.corpus_id = int(corpus_id)
+        self.n_rows = int(n_rows)
+        self._singles: Dict[int, DeviceFilter] = {}
+        self._subsets: Dict[Tuple[int, ...], "DeviceQueryFilters"] = {}
+
+    @property
+    def n_queries(self) -> int:
+        return int(self.n_allowed.shape[0])
+
+    def __len__(self) -> int:
+        return self.n_queries
+
+    def __repr__(self) -> str:
+        return (f"DeviceQueryFilters({self.n_queries} queries, {int(self.n_allowed.min())}-{int(self.n_allowed.max())} "
+                f"of {self.n_rows} rows each, union {self.n_union})")
+
+
 class DeviceCorpus:
     """Embedding block + payload columns of one doc-id shard, resident on one GPU."""
 
@@ -250,6 +281,122 @@ class DeviceCorpus:
             raise ValueError("this filter was prepared for another corpus (the index was rebuilt or reloaded since): "
                              "prepare it again with make_filter")
 
+    def make_query_filters(self, masks) -> DeviceQueryFilters:
+        """Prepare per-query allow-lists from a bool mask of shape [B, N] (numpy or torch, host or device): row j is the
+        list of query j of the batches this set serves.  Synchronises the current stream once (|U| and every |F_j| come
+        back to the host)."""
+        torch = _torch()
+        if isinstance(masks, torch.Tensor):
+            m = masks
+        else:
+            m = torch.from_numpy(np.ascontiguousarray(np.asarray(masks)))
+        if m.dim() != 2 or int(m.shape[1]) != self.n_rows or int(m.shape[0]) < 1:
+            raise ValueError(f"query filter masks must have shape (B, {self.n_rows}) with B >= 1, got {tuple(m.shape)}")
+        if m.dtype != torch.bool:
+            raise ValueError(f"query filter masks must be boolean, got {m.dtype}")
+        b = int(m.shape[0])
+        elem = 1 if self.is_bf16 else 0
+        need = int(self._lib.dewi_query_filter_bytes(self.n_rows, self.dim, elem, b))
+        if need == 0:
+            raise nat.NativeLibraryError("dewi_query_filter_bytes returned 0: " + nat.last_error())
+        with torch.cuda.device(self.device):
+            m8 = m.to(device=self.device).view(torch.uint8).contiguous()
+            buf = torch.empty(need, dtype=torch.uint8, device=self.device)
+            n_union = ctypes.c_int64(0)
+            counts = (ctypes.c_int64 * b)()
+            nat.check(self._lib.dewi_query_filter_prepare(elem, self.n_rows, self.dim, b, nat.ptr(m8), nat.ptr(buf), need,
+                                                          ctypes.byref(n_union), counts, nat.stream_ptr()))
+        return DeviceQueryFilters(buf, m8, np.frombuffer(counts, dtype=np.int64).copy(), n_union.value, self.corpus_id,
+                                  self.n_rows)
+
+    def check_query_filters(self, qf: DeviceQueryFilters, n_queries: Optional[int] = None) -> None:
+        if not isinstance(qf, DeviceQueryFilters):
+            raise TypeError(f"expected DeviceQueryFilters (make_query_filters), got {type(qf).__name__}")
+        if qf.corpus_id != self.corpus_id:
+            raise ValueError("these query filters were prepared for another corpus (the index was rebuilt or reloaded "
+                             "since): prepare them again with make_query_filters")
+        if n_queries is not None and qf.n_queries != n_queries:
+            raise ValueError(f"query filters hold {qf.n_queries} lists for a batch of {n_queries} queries")
+
+    def _search_query_filtered(self, q_dev, k: int, eta: float, entropy_pref: float, out_ids, out_scores,
+                               candidates: Optional[int], similarity: str, qf: DeviceQueryFilters):
+        """``search_device`` where query j searches only its own list F_j.  Queries with |F_j| >= c (c = 2k, or
+        ``candidates``) share one pass of the QMASK row kernels over the union (``dewi_knn_rerank_query_filtered``); a
+        query with 0 < |F_j| < c runs the one-list search on a filter of its own list (its cut is |F_j|); an empty list
+        gives id -1 / score NaN in that query's row.  Every query's result is bit-equal to its one-list search."""
+        torch = _torch()
+        b = int(q_dev.shape[0])
+        self.check_query_filters(qf, b)
+        if q_dev.shape[1] != self.dim:
+            raise ValueError(f"Expected query shape ({self.dim},), got {tuple(q_dev.shape[1:])}")
+        if similarity not in nat.SIM_CODES:
+            raise ValueError(f"unknown similarity {similarity!r}")
+        if candidates is None and similarity != "ip":
+            raise ValueError("similarity transforms belong to the ANN re-rank rule: pass candidates=k as well")
+        if self.is_bf16:
+            raise NotImplementedError("filtered search serves fp32 corpora (bf16: not in this build)")
+        k = int(k)
+        if k <= 0:
+            return (torch.empty((b, 0), dtype=torch.int64, device=self.device),
+                    torch.empty((b, 0), dtype=torch.float32, device=self.device))
+        counts = qf.n_allowed
+        for j in range(b):
+            if 0 < counts[j] < k:
+                raise ValueError(f"query {j}: kth(={int(counts[j]) - k}) out of bounds ({int(counts[j])}): k = {k} exceeds "
+                                 f"the {int(counts[j])} rows its filter allows")
+        if out_ids is None:
+            out_ids = torch.empty((b, k), dtype=torch.int64, device=self.device)
+        if out_scores is None:
+            out_scores = torch.empty((b, k), dtype=torch.float32, device=self.device)
+        c = 2 * k if candidates is None else max(int(candidates), 1)
+        shared = [j for j in range(b) if counts[j] >= c]
+        if len(shared) < b:
+            out_ids.fill_(-1)
+            out_scores.fill_(float("nan"))
+        if shared:
+            if len(shared) == b:
+                sub, q_sub, o_ids, o_sc = qf, q_dev, out_ids, out_scores
+            else:
+                key = tuple(shared)
+                sub = qf._subsets.get(key)
+                if sub is None:
+                    if len(qf._subsets) > 8:
+                        qf._subsets.clear()
+                    sub = qf._subsets[key] = self.make_query_filters(qf.masks[list(shared)].view(torch.bool))
+                q_sub = q_dev[shared].contiguous()
+                o_ids = torch.empty((len(shared), k), dtype=torch.int64, device=self.device)
+                o_sc = torch.empty((len(shared), k), dtype=torch.float32, device=self.device)
+            nb = len(shared)
+            wkey = ("qfiltered", nb, sub.n_union, c)
+            ws = self._ws.get(wkey)
+            if ws is None:
+                need = int(self._lib.dewi_knn_query_filtered_workspace_bytes(sub.n_union, self.dim, nb, c))
+                if need == 0:
+                    raise nat.NativeLibraryError("dewi_knn_query_filtered_workspace_bytes returned 0: " + nat.last_error())
+                if len(self._ws) > 8:
+                    self._ws.clear()
+                ws = self._ws[wkey] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._last_call = (nb, k, c, False, ws)
+            n_a = (ctypes.c_int64 * nb)(*[int(x) for x in sub.n_allowed])
+            rc = self._lib.dewi_knn_rerank_query_filtered(
+                nat.ptr(self.emb), 0, self.n_rows, self.dim, nat.ptr(sub.buf), sub.n_union, n_a, nat.ptr(q_sub), nb,
+                nat.ptr(self.dewi32), nat.ptr(self.ent32), k, 0 if candidates is None else int(candidates),
+                nat.SIM_CODES[similarity], float(eta), float(entropy_pref), nat.SPACE_CODES[self.space], nat.ptr(o_ids),
+                nat.ptr(o_sc), nat.ptr(ws), ws.numel(), nat.stream_ptr())
+            nat.check(rc)
+            if o_ids is not out_ids:
+                idx = torch.tensor(shared, dtype=torch.int64, device=self.device)
+                out_ids.index_copy_(0, idx, o_ids)
+                out_scores.index_copy_(0, idx, o_sc)
+        for j in range(b):
+            if 0 < counts[j] < c:          # a short list: the one-list search on its own filter (cut |F_j|)
+                f = qf._singles.get(j)
+                if f is None:
+                    f = qf._singles[j] = self.make_filter(qf.masks[j].view(torch.bool))
+                self._search_filtered(q_dev[j:j + 1], k, eta, entropy_pref, out_ids[j:j + 1], out_scores[j:j + 1],
+                                      candidates, similarity, f)
+        return out_ids, out_scores
+
     def _search_filtered(self, q_dev, k: int, eta: float, entropy_pref: float, out_ids, out_scores,
                          candidates: Optional[int], similarity: str, filter: DeviceFilter):
         """``search_device`` over the rows of a prepared filter (``dewi_knn_rerank_filtered``): the row kernels of this
@@ -310,8 +457,12 @@ class DeviceCorpus:
 
         ``filter`` (a ``DeviceFilter`` of this corpus): search only its rows (ABI 6) — the fp32 row kernels over the
         list, whatever the batch size; ids stay rows of the whole corpus.  Results are [B, 0] when k <= 0 or the filter
-        is empty.
+        is empty.  A ``DeviceQueryFilters`` of B lists: query j searches only its own list (``_search_query_filtered``);
+        the results keep their [B, k] shape and the row of a query whose list is empty holds id -1 and score NaN.
         """
+        if isinstance(filter, DeviceQueryFilters):
+            return self._search_query_filtered(q_dev, k, eta, entropy_pref, out_ids, out_scores, candidates, similarity,
+                                               filter)
         if filter is not None:
             return self._search_filtered(q_dev, k, eta, entropy_pref, out_ids, out_scores, candidates, similarity, filter)
         torch = _torch()
@@ -381,8 +532,18 @@ class DeviceCorpus:
                filter: Optional[DeviceFilter] = None) -> Tuple[np.ndarray, np.ndarray]:
         """Blocking convenience: (ids int64 [B,k] including id_offset, scores fp32 [B,k]) on the host.
         Safe to call from several threads on one instance (serialised by a per-corpus lock).
-        ``filter``: see ``search_device`` (an empty filter gives [B, 0])."""
+        ``filter``: see ``search_device`` (an empty filter gives [B, 0]; per-query filters pad the row of a query with an
+        empty list with id -1 and score NaN)."""
         torch = _torch()
+        if isinstance(filter, DeviceQueryFilters):
+            with self._lock, torch.cuda.device(self.device):
+                q = self.stage_queries(queries)
+                ids_d, sc_d = self.search_device(q, k, eta, entropy_pref, candidates=candidates, similarity=similarity,
+                                                 filter=filter)
+                ids_h, scores_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
+            if self.id_offset:
+                ids_h = np.where(ids_h >= 0, ids_h + self.id_offset, ids_h)
+            return ids_h, scores_h
         if filter is not None:
             self.check_filter(filter)
             if filter.n_allowed == 0:

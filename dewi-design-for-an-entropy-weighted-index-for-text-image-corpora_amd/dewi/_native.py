@@ -41,6 +41,8 @@ EXPORTED_SYMBOLS = (
     "dewi_robust_fit_f32", "dewi_robust_fit_begin", "dewi_robust_fit_hist_f32", "dewi_robust_fit_region",
     "dewi_robust_fit_pick", "dewi_robust_fit_finish", "dewi_score_f64", "dewi_score_f64_dev", "dewi_timing_enable", "dewi_timing_read", "dewi_tuning_set",
     "dewi_filter_bytes", "dewi_filter_prepare", "dewi_knn_filtered_workspace_bytes", "dewi_knn_rerank_filtered",
+    "dewi_query_filter_bytes", "dewi_query_filter_prepare", "dewi_knn_query_filtered_workspace_bytes",
+    "dewi_knn_rerank_query_filtered",
 )
 
 
@@ -134,6 +136,15 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_knn_rerank_filtered.restype = i32
     lib.dewi_knn_rerank_filtered.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, vp, vp, i32, i32, i32, f64, f64, i32, vp, vp,
                                              vp, sz, vp]
+    lib.dewi_query_filter_bytes.restype = sz
+    lib.dewi_query_filter_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_query_filter_prepare.restype = i32
+    lib.dewi_query_filter_prepare.argtypes = [i32, i64, i32, i32, vp, vp, sz, c.POINTER(i64), c.POINTER(i64), vp]
+    lib.dewi_knn_query_filtered_workspace_bytes.restype = sz
+    lib.dewi_knn_query_filtered_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_knn_rerank_query_filtered.restype = i32
+    lib.dewi_knn_rerank_query_filtered.argtypes = [vp, i32, i64, i32, vp, i64, c.POINTER(i64), vp, i32, vp, vp, i32, i32, i32, f64,
+                                                   f64, i32, vp, vp, vp, sz, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

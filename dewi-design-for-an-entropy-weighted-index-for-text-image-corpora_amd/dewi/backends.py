@@ -481,11 +481,46 @@ class ExactIndex(BaseIndex):
         self._ensure_built()
         return self._corpus.make_filter(self.filter_mask(mask, doc_ids=doc_ids, rows=rows))
 
+    def query_filter_masks(self, masks=None, *, doc_ids=None, rows=None):
+        """The bool [B, N] masks of exactly one of: ``masks`` (bool array of shape [B, N], numpy or torch, host or device:
+        returned as it is after the checks), ``doc_ids`` (B sequences of doc ids) or ``rows`` (B integer row arrays).
+        Every row goes through the checks of ``filter_mask``.  Host logic only: no device work."""
+        given = [x is not None for x in (masks, doc_ids, rows)]
+        if sum(given) != 1:
+            raise ValueError("pass exactly one of masks, doc_ids, rows")
+        n = len(self._doc_ids)
+        if masks is not None:
+            shape = tuple(masks.shape) if hasattr(masks, "shape") else tuple(np.shape(masks))
+            if len(shape) != 2 or shape[0] < 1:
+                raise ValueError(f"query filter masks must have shape (B, {n}) with B >= 1, got {shape}")
+            if hasattr(masks, "is_cuda"):
+                for j in range(shape[0]):
+                    self.filter_mask(masks[j])
+                return masks
+            return np.stack([self.filter_mask(np.asarray(masks[j])) for j in range(shape[0])])
+        lists = list(doc_ids if doc_ids is not None else rows)
+        if not lists:
+            raise ValueError("query filters need at least one list")
+        if doc_ids is not None:
+            return np.stack([self.filter_mask(doc_ids=[d] if isinstance(d, str) else list(d)) for d in lists])
+        return np.stack([self.filter_mask(rows=r) for r in lists])
+
+    def make_query_filters(self, masks=None, *, doc_ids=None, rows=None):
+        """Prepare one allow-list per query for ``search_batch(filter=...)`` (additive): exactly one of a bool ``masks``
+        array of shape [B, N], ``doc_ids`` (B sequences of doc ids) or ``rows`` (B integer row arrays), see
+        ``query_filter_masks``.  Query j of a batch of B then searches only its own list.  The result is a
+        ``DeviceQueryFilters`` bound to the index as it is built now (stale-checked like ``make_filter``)."""
+        self._ensure_built()
+        return self._corpus.make_query_filters(self.query_filter_masks(masks, doc_ids=doc_ids, rows=rows))
+
     def _prepared(self, filter):
-        """A ``DeviceFilter``, or anything ``make_filter`` takes (bool mask, doc ids, integer rows) prepared on the fly."""
-        from ._engine import DeviceFilter
-        if filter is None or isinstance(filter, DeviceFilter):
+        """A ``DeviceFilter`` / ``DeviceQueryFilters``, anything ``make_filter`` takes (bool mask, doc ids, integer rows)
+        or a bool [B, N] mask (``make_query_filters``), prepared on the fly."""
+        from ._engine import DeviceFilter, DeviceQueryFilters
+        if filter is None or isinstance(filter, (DeviceFilter, DeviceQueryFilters)):
             return filter
+        if len(getattr(filter, "shape", ())) == 2:
+            return self.make_query_filters(filter)
         return self.make_filter(**filter_kwargs(filter))
 
     def search(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
@@ -502,18 +537,23 @@ class ExactIndex(BaseIndex):
 
         ``filter`` (additive): restrict the search to an allow-list — a prepared filter (``make_filter``) or anything
         ``make_filter`` takes.  The result is the reference's search applied to the allowed rows only: c = min(2k, |A|),
-        ``[]`` for an empty filter, ``ValueError`` for k > |A|.
+        ``[]`` for an empty filter, ``ValueError`` for k > |A|.  Per-query filters (``make_query_filters``) of one query
+        are accepted as well.
         """
         q = np.asarray(query, dtype=np.float32)
         if q.ndim == 1:
             q = q.reshape(1, -1)
         rows, scores = self.search_batch(q, k, eta, entropy_pref, candidates, similarity, filter=filter)
-        return self.results_for(rows[:1], scores[:1])[0]
+        keep = rows[:1] >= 0            # (per-query filters: an empty list pads its row with id -1)
+        return self.results_for(rows[:1][:, keep[0]], scores[:1][:, keep[0]])[0]
 
     def search_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
                      candidates: Optional[int] = None, similarity: str = "ip", filter=None) -> Tuple[np.ndarray, np.ndarray]:
         """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k]).  ``filter``: see ``search``
-        (one allow-list for every query of the batch; [B, 0] results when it is empty or k <= 0)."""
+        (one allow-list for every query of the batch; [B, 0] results when it is empty or k <= 0).  Per-query filters —
+        a ``DeviceQueryFilters`` of B lists (``make_query_filters``) or a bool [B, N] mask — restrict query j to its own
+        list F_j, with the rules of one list per query (c = min(2k, |F_j|), ``ValueError`` naming the query for
+        k > |F_j| > 0); the row of a query whose list is empty is padded with id -1 and score NaN."""
         self._ensure_built()
         q = np.asarray(queries, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.dim:

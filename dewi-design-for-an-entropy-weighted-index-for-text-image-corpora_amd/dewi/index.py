@@ -76,6 +76,12 @@ class DewiIndex(BaseIndex):
             self.build()
         return self._backend.make_filter(mask, doc_ids=doc_ids, rows=rows)
 
+    def make_query_filters(self, masks=None, *, doc_ids=None, rows=None):
+        """Prepare one allow-list per query for ``search_batch(filter=...)`` (``ExactIndex.make_query_filters``)."""
+        if not self._built:
+            self.build()
+        return self._backend.make_query_filters(masks, doc_ids=doc_ids, rows=rows)
+
     def search(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
                entropy_pref: Optional[float] = None, filter=None) -> List[Tuple[str, float, Payload]]:
         """``filter`` (additive): search only an allow-list — a prepared filter (``make_filter``), a bool mask, doc ids
@@ -92,7 +98,8 @@ class DewiIndex(BaseIndex):
 
     def search_batch(self, queries: np.ndarray, k: int = 10, eta: Optional[float] = None,
                      entropy_pref: Optional[float] = None, filter=None) -> List[List[Tuple[str, float, Payload]]]:
-        """One call for B queries ([B, dim]); each result list equals ``search`` of that row (``filter``: see ``search``)."""
+        """One call for B queries ([B, dim]); each result list equals ``search`` of that row (``filter``: see ``search``;
+        per-query filters — ``make_query_filters`` or a bool [B, N] mask — give ``[]`` for a query whose list is empty)."""
         if not self._built:
             self.build()
         eta, entropy_pref = self._defaults(eta, entropy_pref)
@@ -101,6 +108,10 @@ class DewiIndex(BaseIndex):
             raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
         if filter is not None:
             rows, scores = self._backend.search_batch(q, k, eta, entropy_pref, filter=filter)
+            if rows.size and (rows < 0).any():     # per-query filters: an empty list pads its row with id -1
+                n_real = (rows >= 0).sum(axis=1)
+                res = self._backend.results_for(np.where(rows < 0, 0, rows), scores)
+                return [r[:int(m)] for r, m in zip(res, n_real)]
         else:
             rows, scores = self._backend.search_batch(q, k, eta, entropy_pref)
         return self._backend.results_for(rows, scores)

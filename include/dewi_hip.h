@@ -203,6 +203,34 @@ int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int
                              int sim_transform, double eta, double entropy_pref, int space, int64_t* d_out_ids,
                              float* d_out_scores, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-query filters (additive to ABI 6): one batch in which query j has its own allow-list F_j.  Query j's ids and scores
+ * are bit-equal to dewi_knn_rerank_filtered of that query alone on a filter prepared from F_j.
+ *
+ * dewi_query_filter_bytes: size of the device buffer that holds the prepared lists of n_queries queries (0 for a bad shape;
+ * needs no device).  dewi_query_filter_prepare turns d_masks (DEVICE, [n_queries][n_rows] bytes, nonzero = allowed) into
+ * that buffer — the union U of the lists, prepared as dewi_filter_prepare prepares one list, and per position of U one u32
+ * of query bits for every 32 queries — and returns |U| in *out_n_union and |F_j| in out_n_allowed[j] (HOST, n_queries
+ * entries).  It SYNCHRONISES `stream`.  A prepared buffer serves every search of a corpus with the same n_rows / dim /
+ * elem_type, as a prepared filter does.
+ * dewi_knn_query_filtered_workspace_bytes: workspace of dewi_knn_rerank_query_filtered (0 if n_union <= 0).
+ * dewi_knn_rerank_query_filtered: one pass of the row kernels over U per 8 / 4 / 1 queries, where a query only takes the
+ * rows of its own list, then the same select / blend / top-k with one cut c = 2k (or n_candidates) for the batch.
+ * n_allowed: the HOST counts the prepare step returned.  k <= 0: DEWI_OK, nothing written.  Any j with k > |F_j|:
+ * DEWI_ERR_K_OUT_OF_BOUNDS; any j with |F_j| < c: DEWI_ERR_INVALID_ARG (such a query, an empty list included, is searched on
+ * its own filter — the caller's split).  ids are GLOBAL rows.  fp32 corpora only (bf16: DEWI_ERR_UNSUPPORTED).
+ * Asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------------ */
+size_t dewi_query_filter_bytes(int64_t n_rows, int dim, int elem_type, int n_queries);
+int dewi_query_filter_prepare(int elem_type, int64_t n_rows, int dim, int n_queries, const uint8_t* d_masks, void* d_filter,
+                              size_t filter_bytes, int64_t* out_n_union, int64_t* out_n_allowed, void* stream);
+size_t dewi_knn_query_filtered_workspace_bytes(int64_t n_union, int dim, int n_queries, int n_candidates);
+int dewi_knn_rerank_query_filtered(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_union,
+                                   const int64_t* n_allowed, const float* d_Q, int n_queries, const float* d_dewi32,
+                                   const float* d_ent32, int k, int n_candidates, int sim_transform, double eta,
+                                   double entropy_pref, int space, int64_t* d_out_ids, float* d_out_scores, void* d_workspace,
+                                   size_t workspace_bytes, void* stream);
+
 /* Step 1 of the bf16 search alone (backends.py:420-424 followed by the bf16 rounding of config C3): q / ||q||
  * in fp32 unless the norm is 0 (cosine), then round-to-nearest-even to bf16.  This is the kernel the batched
  * matrix-core path runs on its queries; exposed so that parity tests can check the normalisation on its own
