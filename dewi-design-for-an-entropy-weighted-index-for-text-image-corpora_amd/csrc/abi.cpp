@@ -988,6 +988,99 @@ int dewi_knn_rerank_query_filtered(const void* d_E, int elem_type, int64_t n_row
   return e == hipSuccess ? DEWI_OK : hip_fail(e, "select launch (query-filtered)");
 }
 
+// ---- IVF: cell lists and probe expansion (additive to ABI 6) -----------------------------------------------------------
+static bool ivf_shape_ok(int64_t n_rows, int dim, int elem_type) {
+  return n_rows > 0 && n_rows <= 0xFFFFFFFFll && dim > 0 && (elem_type == 0 || elem_type == 1);
+}
+
+int dewi_ivf_buckets(int dim, int elem_type) {
+  if (dim <= 0 || (elem_type != 0 && elem_type != 1)) return 0;
+  return filter_buckets(dim, elem_type);
+}
+
+size_t dewi_ivf_lists_bytes(int64_t n_rows, int dim, int elem_type, int n_cells) {
+  if (!ivf_shape_ok(n_rows, dim, elem_type) || n_cells <= 0 || n_cells > dewi::kIvfMaxCells || n_cells > n_rows) return 0;
+  return 4 * dewi::ivf_lists_layout(n_rows, n_cells, filter_buckets(dim, elem_type)).total_words;
+}
+
+int dewi_ivf_lists_build(int elem_type, int64_t n_rows, int dim, int n_cells, const int32_t* d_assign, void* d_lists,
+                         size_t lists_bytes, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!d_assign || !d_lists) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "IVF serves fp32 corpora (bf16: not in this build)");
+  if (elem_type != 0) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+  if (n_rows <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
+  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (n_cells <= 0 || n_cells > dewi::kIvfMaxCells || n_cells > n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_cells %d outside [1, min(%d, n_rows)]", n_cells, dewi::kIvfMaxCells);
+  const size_t need = dewi_ivf_lists_bytes(n_rows, dim, elem_type, n_cells);
+  if (lists_bytes < need) return fail(DEWI_ERR_WORKSPACE, "cell-list buffer %zu B < required %zu B", lists_bytes, need);
+  hipError_t e = dewi::launch_ivf_lists_build(d_assign, n_rows, n_cells, filter_buckets(dim, elem_type),
+                                              static_cast<uint32_t*>(d_lists), stream);
+  return e == hipSuccess ? DEWI_OK : hip_fail(e, "ivf_lists_build launch");
+}
+
+static size_t ivf_group_words(int64_t n_rows, int n_buckets, int group) {
+  size_t words = query_filter_layout(n_rows, n_buckets, group).total / 4;   // what the QMASK passes may rely on
+  const size_t mine = static_cast<size_t>(dewi::kFilterHeaderWords) + 2 * static_cast<size_t>(n_rows);
+  if (words < mine) words = mine;
+  return (words + 63) / 64 * 64;
+}
+
+// n_cells is not known when the buffer is sized: the cell words and segment tables take room for min(kIvfMaxCells, n_rows) cells
+static dewi::IvfProbeLayout ivf_probe_layout(int64_t n_rows, int n_buckets, int n_queries, int group) {
+  dewi::IvfProbeLayout L;
+  const size_t cap = static_cast<size_t>(n_rows < dewi::kIvfMaxCells ? n_rows : dewi::kIvfMaxCells);
+  L.n_groups = (n_queries + group - 1) / group;
+  L.group_words = ivf_group_words(n_rows, n_buckets, group);
+  L.counts_off = L.group_words * static_cast<size_t>(L.n_groups);
+  L.bits_off = L.counts_off + (static_cast<size_t>(L.n_groups) + static_cast<size_t>(n_queries) + 63) / 64 * 64;
+  L.seg_off = L.bits_off + cap * static_cast<size_t>(L.n_groups);
+  L.total_words = L.seg_off + (cap * static_cast<size_t>(n_buckets) + 1) * static_cast<size_t>(L.n_groups);
+  return L;
+}
+
+size_t dewi_ivf_probe_group_bytes(int64_t n_rows, int dim, int elem_type, int group) {
+  if (!ivf_shape_ok(n_rows, dim, elem_type) || group <= 0 || group > 32) return 0;
+  return 4 * ivf_group_words(n_rows, filter_buckets(dim, elem_type), group);
+}
+
+size_t dewi_ivf_probe_bytes(int64_t n_rows, int dim, int elem_type, int n_queries, int group) {
+  if (!ivf_shape_ok(n_rows, dim, elem_type) || group <= 0 || group > 32 || n_queries <= 0 || n_queries > 65535) return 0;
+  return 4 * ivf_probe_layout(n_rows, filter_buckets(dim, elem_type), n_queries, group).total_words;
+}
+
+int dewi_ivf_probe_prepare(int elem_type, int64_t n_rows, int dim, const void* d_lists, int n_cells, const int64_t* d_probe_ids,
+                           int n_queries, int nprobe, int group, void* d_out, size_t out_bytes, int64_t* out_n_union,
+                           int64_t* out_n_allowed, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!d_lists || !d_probe_ids || !d_out || !out_n_union || !out_n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "IVF serves fp32 corpora (bf16: not in this build)");
+  if (elem_type != 0) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+  if (n_rows <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
+  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (n_cells <= 0 || n_cells > dewi::kIvfMaxCells || n_cells > n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_cells %d outside [1, min(%d, n_rows)]", n_cells, dewi::kIvfMaxCells);
+  if (n_queries <= 0 || n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
+  if (nprobe <= 0 || nprobe > n_cells) return fail(DEWI_ERR_INVALID_ARG, "nprobe %d outside [1, n_cells = %d]", nprobe, n_cells);
+  if (group <= 0 || group > 32) return fail(DEWI_ERR_INVALID_ARG, "group %d outside [1, 32]", group);
+  const size_t need = dewi_ivf_probe_bytes(n_rows, dim, elem_type, n_queries, group);
+  if (out_bytes < need) return fail(DEWI_ERR_WORKSPACE, "probe buffer %zu B < required %zu B", out_bytes, need);
+  const int g = filter_buckets(dim, elem_type);
+  const dewi::IvfProbeLayout L = ivf_probe_layout(n_rows, g, n_queries, group);
+  uint32_t* out = static_cast<uint32_t*>(d_out);
+  hipError_t e = dewi::launch_ivf_probe_prepare(static_cast<const uint32_t*>(d_lists), n_rows, n_cells, g, d_probe_ids, n_queries,
+                                                nprobe, group, out, L, stream);
+  if (e != hipSuccess) return hip_fail(e, "ivf_probe_prepare launch");
+  std::vector<uint32_t> counts(static_cast<size_t>(L.n_groups) + static_cast<size_t>(n_queries));
+  e = hipMemcpyAsync(counts.data(), out + L.counts_off, sizeof(uint32_t) * counts.size(), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hip_fail(e, "probe count read-back");
+  for (int i = 0; i < L.n_groups; ++i) out_n_union[i] = static_cast<int64_t>(counts[i]);
+  for (int j = 0; j < n_queries; ++j) out_n_allowed[j] = static_cast<int64_t>(counts[L.n_groups + j]);
+  return DEWI_OK;
+}
+
 size_t dewi_merge_workspace_bytes(int n_lists, int n_queries, int list_len, int n_candidates) {
   if (n_lists <= 0 || n_queries <= 0 || list_len <= 0 || n_candidates <= 0) return 0;
   if (static_cast<int64_t>(n_lists) * list_len <= dewi::kMaxSortCandidates) return 0;   // sorted in LDS

@@ -145,6 +145,40 @@ hipError_t launch_query_filter_prepare(const uint8_t* d_masks, int64_t n_rows, i
                                        uint32_t* d_counts, uint32_t* d_filter, uint32_t* d_scratch, uint32_t* d_words,
                                        hipStream_t stream);
 
+// ---- ivf.hip: k-means cells as row lists, and the probed cells of a query group as a prepared (query-)filter
+constexpr int kIvfMaxCells = 65536;
+// Cell lists (u32 words): offsets [bins + 1] (bins = n_cells * n_buckets, cell-major), the n_rows row numbers, one error word,
+// scratch (one count per bin and block of `chunk` rows; chunk >= bins keeps it below n_rows + bins words).
+struct IvfListsLayout {
+  int64_t bins, chunk, blocks;
+  size_t rows_off, err_off, scratch_off, total_words;
+};
+inline IvfListsLayout ivf_lists_layout(int64_t n_rows, int n_cells, int n_buckets) {
+  IvfListsLayout L;
+  L.bins = static_cast<int64_t>(n_cells) * n_buckets;
+  L.chunk = L.bins > 4096 ? (L.bins + 63) / 64 * 64 : 4096;
+  L.blocks = (n_rows + L.chunk - 1) / L.chunk;
+  L.rows_off = static_cast<size_t>(L.bins) + 1;
+  L.err_off = L.rows_off + static_cast<size_t>(n_rows);
+  L.scratch_off = L.err_off + 1;
+  L.total_words = L.scratch_off + static_cast<size_t>(L.bins) * static_cast<size_t>(L.blocks);
+  return L;
+}
+// d_assign int32 [n_rows] -> d_lists (ivf_lists_layout(...).total_words u32).  Rows assigned outside [0, n_cells) are dropped
+// and counted in the error word.
+hipError_t launch_ivf_lists_build(const int32_t* d_assign, int64_t n_rows, int n_cells, int n_buckets, uint32_t* d_lists,
+                                  hipStream_t stream);
+// Probe buffer (u32 words): n_groups prepared query-filter buffers of group_words each (header, list, one plane of query
+// words at kFilterHeaderWords + n_rows), then the counts ([n_groups] |U|, [n_queries] |F_j|), the cell words
+// [n_groups][n_cells] and the scanned segment sizes [n_groups][n_cells * n_buckets + 1] (abi.cpp ivf_probe_layout).
+struct IvfProbeLayout {
+  int n_groups;
+  size_t group_words, counts_off, bits_off, seg_off, total_words;
+};
+hipError_t launch_ivf_probe_prepare(const uint32_t* d_lists, int64_t n_rows, int n_cells, int n_buckets, const int64_t* d_probe_ids,
+                                    int n_queries, int nprobe, int group, uint32_t* d_out, const IvfProbeLayout& L,
+                                    hipStream_t stream);
+
 // ---- knn_scan_any_f32.hip / knn_scan_any_bf16.hip: plan.kind == kScanAnyLong / kScanAnyShort (raw queries)
 hipError_t launch_scan_any_f32(const ScanPlan& plan, const float* d_E, int64_t n_rows, int dim, const float* d_q_raw, int q0,
                                int nq, int n_candidates, int space, uint64_t* d_keys, hipStream_t stream);

@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = (
     "dewi_filter_bytes", "dewi_filter_prepare", "dewi_knn_filtered_workspace_bytes", "dewi_knn_rerank_filtered",
     "dewi_query_filter_bytes", "dewi_query_filter_prepare", "dewi_knn_query_filtered_workspace_bytes",
     "dewi_knn_rerank_query_filtered",
+    "dewi_ivf_buckets", "dewi_ivf_lists_bytes", "dewi_ivf_lists_build", "dewi_ivf_probe_group_bytes", "dewi_ivf_probe_bytes",
+    "dewi_ivf_probe_prepare",
 )
 
 
@@ -145,6 +147,18 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_knn_rerank_query_filtered.restype = i32
     lib.dewi_knn_rerank_query_filtered.argtypes = [vp, i32, i64, i32, vp, i64, c.POINTER(i64), vp, i32, vp, vp, i32, i32, i32, f64,
                                                    f64, i32, vp, vp, vp, sz, vp]
+    lib.dewi_ivf_buckets.restype = i32
+    lib.dewi_ivf_buckets.argtypes = [i32, i32]
+    lib.dewi_ivf_lists_bytes.restype = sz
+    lib.dewi_ivf_lists_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_ivf_lists_build.restype = i32
+    lib.dewi_ivf_lists_build.argtypes = [i32, i64, i32, i32, vp, vp, sz, vp]
+    lib.dewi_ivf_probe_group_bytes.restype = sz
+    lib.dewi_ivf_probe_group_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_ivf_probe_bytes.restype = sz
+    lib.dewi_ivf_probe_bytes.argtypes = [i64, i32, i32, i32, i32]
+    lib.dewi_ivf_probe_prepare.restype = i32
+    lib.dewi_ivf_probe_prepare.argtypes = [i32, i64, i32, vp, i32, vp, i32, i32, i32, vp, sz, c.POINTER(i64), c.POINTER(i64), vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

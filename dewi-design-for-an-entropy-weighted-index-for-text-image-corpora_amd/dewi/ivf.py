@@ -1,0 +1,402 @@
+"""``IVFIndex``: approximate search that scans only the rows of the k-means cells nearest to the query (IVF-Flat).
+
+The corpus stays exactly what ``ExactIndex`` keeps (same row order, ids, payload columns, files).  On top of it ``build``
+trains ``nlist`` centroids (Lloyd's k-means on the device, in torch: plumbing, once per build), assigns every row to its
+nearest centroid and sorts the rows into per-cell lists (``dewi_ivf_lists_build``).  A search is three steps on one stream:
+
+1. coarse: the ``nprobe`` nearest centroids of every query — the exact search over the centroid matrix, ids left on the device;
+2. ``dewi_ivf_probe_prepare``: the rows of those cells as a prepared filter, one per group of 8 queries (so that a pass
+   streams the union of 8 queries' cells, not of the whole batch), with one word of query bits per row;
+3. the filtered search entry points on that buffer (``dewi_knn_rerank_filtered`` for one query,
+   ``dewi_knn_rerank_query_filtered`` for a group).
+
+So query j's answer is, bit for bit, ``ExactIndex.search(q_j, k, ..., filter=<rows of its probed cells>)``: the reference's
+search on those rows only.  ``nprobe >= nlist`` probes every row and returns the exact result.
+"""
+from __future__ import annotations
+
+import ctypes
+import json
+import math
+from pathlib import Path
+from typing import Any, Optional, Tuple, Union
+
+import numpy as np
+
+from .backends import ExactIndex, SearchResult
+
+IVF_FORMAT_VERSION = 1
+MAX_CELLS = 65536          # dewi_hip.h: 1 <= n_cells <= min(65536, n_rows)
+PROBE_GROUP = 8            # queries that share one pass over the union of their cells (what the QMASK passes take)
+
+
+def default_nlist(n_rows: int) -> int:
+    return min(4096, max(1, int(round(math.sqrt(n_rows)))))
+
+
+def default_nprobe(nlist: int) -> int:
+    return max(1, nlist // 64)
+
+
+class _IvfState:
+    """What a built IVF index keeps on the device: centroids (as a small exact corpus), the cell of every row, the lists."""
+
+    __slots__ = ("nlist", "buckets", "centroids", "coarse", "assign", "lists", "corpus_id")
+
+
+class IVFIndex(ExactIndex):
+    """IVF-Flat over an ``ExactIndex`` corpus (fp32 only).
+
+    ``nlist=None``: ``min(4096, max(1, round(sqrt(N))))`` at build; ``nprobe=None``: ``max(1, nlist // 64)``.  Training:
+    ``train_iters`` rounds of k-means from ``nlist`` distinct rows drawn with ``np.random.RandomState(train_seed)``, at most
+    ``max_train_rows`` (default ``256 * nlist``) sampled rows per round, every row in the final assignment; spherical
+    (centroids re-normalised every round) for ``space="cosine"``, plain means for ``"l2"``; an empty cell keeps its previous
+    centroid.  The same corpus and seed give the same cells on the same machine.  ``add`` + ``build`` after a build retrains.
+    """
+
+    def __init__(self, dim: int, space: str = "cosine", nlist: Optional[int] = None, nprobe: Optional[int] = None,
+                 train_iters: int = 10, train_seed: int = 0, max_train_rows: Optional[int] = None, **kwargs: Any):
+        if nlist is not None and not (1 <= int(nlist) <= MAX_CELLS):
+            raise ValueError(f"nlist must lie in [1, {MAX_CELLS}], got {nlist}")
+        if nprobe is not None and int(nprobe) < 1:
+            raise ValueError(f"nprobe must be at least 1, got {nprobe}")
+        if int(train_iters) < 0:
+            raise ValueError(f"train_iters must not be negative, got {train_iters}")
+        if max_train_rows is not None and int(max_train_rows) < 1:
+            raise ValueError(f"max_train_rows must be at least 1, got {max_train_rows}")
+        super().__init__(dim, space, **kwargs)
+        self.nlist = None if nlist is None else int(nlist)
+        self.nprobe = None if nprobe is None else int(nprobe)
+        self.train_iters = int(train_iters)
+        self.train_seed = int(train_seed)
+        self.max_train_rows = None if max_train_rows is None else int(max_train_rows)
+        self._ivf: Optional[_IvfState] = None
+        self._ivf_loaded = None                   # (centroids, assign) read by load(): taken instead of training
+        self._probe_buf = None                    # one probe buffer and one search workspace, both only ever grow
+        self._ivf_ws = None
+
+    # ---------------------------------------------------------------- build
+    def build(self, **kwargs: Any) -> None:
+        """``ExactIndex.build`` (the corpus in its row order), then the centroids, the assignment and the cell lists."""
+        super().build(**kwargs)
+        self._build_ivf()
+
+    def _ensure_built(self) -> None:
+        super()._ensure_built()
+        if self._ivf is None or self._ivf.corpus_id != self._corpus.corpus_id:
+            self._build_ivf()
+
+    def _build_ivf(self) -> None:
+        import torch
+        from . import _native as nat
+        from ._engine import DeviceCorpus
+        corpus = self._corpus
+        if corpus.is_bf16:
+            raise NotImplementedError("IVFIndex serves fp32 corpora (bf16: not in this build)")
+        lib = nat.load_library()
+        n, dev = corpus.n_rows, corpus.device
+        loaded, self._ivf_loaded = self._ivf_loaded, None
+        with torch.cuda.device(dev):
+            if loaded is not None and loaded[1].shape[0] == n and loaded[0].shape[1] == self.dim:
+                centroids = torch.from_numpy(np.ascontiguousarray(loaded[0], dtype=np.float32)).to(dev)
+                assign = torch.from_numpy(np.ascontiguousarray(loaded[1], dtype=np.int32)).to(dev)
+                nlist = int(centroids.shape[0])
+            else:
+                nlist = default_nlist(n) if self.nlist is None else self.nlist
+                if nlist > n:
+                    raise ValueError(f"nlist = {nlist} exceeds the {n} rows of the corpus")
+                centroids, assign = self._train(corpus.emb, nlist)
+            st = _IvfState()
+            st.nlist = nlist
+            st.buckets = int(lib.dewi_ivf_buckets(self.dim, 0))
+            need = int(lib.dewi_ivf_lists_bytes(n, self.dim, 0, nlist))
+            if need == 0 or st.buckets == 0:
+                raise nat.NativeLibraryError(f"dewi_ivf_lists_bytes returned 0 for {n} x {self.dim}, {nlist} cells")
+            st.lists = torch.empty(need, dtype=torch.uint8, device=dev)
+            nat.check(lib.dewi_ivf_lists_build(0, n, self.dim, nlist, nat.ptr(assign), nat.ptr(st.lists), need, nat.stream_ptr()))
+            words = st.lists.view(torch.int32)
+            dropped = int(words[nlist * st.buckets + 1 + n].item())           # the error word (synchronises)
+            if dropped:
+                raise ValueError(f"{dropped} rows are assigned to cells outside [0, {nlist})")
+            zeros = torch.zeros(nlist, dtype=torch.float32, device=dev)
+            st.centroids, st.assign = centroids, assign
+            st.coarse = DeviceCorpus(centroids, zeros, zeros.clone(), self.space)
+            st.corpus_id = corpus.corpus_id
+        self._ivf = st
+
+    def _assign(self, X, C):
+        """Nearest centroid of every row of X (int64): largest inner product (cosine) / smallest distance (l2)."""
+        import torch
+        out = torch.empty(X.shape[0], dtype=torch.int64, device=X.device)
+        bias = None if self.space != "l2" else (C * C).sum(dim=1)
+        ct = C.t().contiguous()
+        step = max(1024, (1 << 26) // max(int(C.shape[0]), 1))               # <= 256 MiB of scores at a time
+        for s in range(0, int(X.shape[0]), step):
+            sc = torch.mm(X[s:s + step], ct)
+            if bias is not None:
+                sc = 2.0 * sc - bias
+            out[s:s + step] = torch.argmax(torch.nan_to_num(sc, nan=-float("inf")), dim=1)
+        return out
+
+    def _train(self, X, nlist: int):
+        import torch
+        n = int(X.shape[0])
+        rs = np.random.RandomState(self.train_seed)
+        init = np.sort(rs.choice(n, nlist, replace=False))
+        C = torch.nan_to_num(X[torch.from_numpy(init).to(X.device)].clone())
+        cap = 256 * nlist if self.max_train_rows is None else self.max_train_rows
+        for _ in range(self.train_iters):
+            if n > cap:
+                pick = torch.from_numpy(np.sort(rs.choice(n, cap, replace=False))).to(X.device)
+                Xs = X[pick]
+            else:
+                Xs = X
+            a = self._assign(Xs, C)
+            # sorted form of the update (no floating-point atomics: the same cells on every run)
+            order = torch.argsort(a, stable=True)
+            counts = torch.bincount(a, minlength=nlist)
+            sums = torch.segment_reduce(torch.nan_to_num(Xs[order]), "sum", lengths=counts, axis=0)
+            means = sums / counts.clamp(min=1).to(sums.dtype).unsqueeze(1)
+            keep = counts > 0
+            if self.space == "cosine":
+                norm = torch.linalg.vector_norm(means, dim=1, keepdim=True)
+                keep = keep & (norm.squeeze(1) > 0)
+                means = means / norm.clamp(min=1e-30)
+            C = torch.where(keep.unsqueeze(1), means, C)                        # an empty cell keeps its previous centroid
+        return C.contiguous(), self._assign(X, C).to(torch.int32).contiguous()
+
+    def _invalidate(self) -> None:
+        super()._invalidate()
+        self._ivf_loaded = None
+
+    # ---------------------------------------------------------------- introspection
+    @property
+    def centroids(self) -> np.ndarray:
+        self._ensure_built()
+        return self._ivf.centroids.cpu().numpy()
+
+    @property
+    def cell_of_row(self) -> np.ndarray:
+        self._ensure_built()
+        return self._ivf.assign.cpu().numpy()
+
+    @property
+    def cell_sizes(self) -> np.ndarray:
+        return np.bincount(self.cell_of_row, minlength=self._ivf.nlist).astype(np.int64)
+
+    def cell_lists(self) -> Tuple[np.ndarray, np.ndarray, int]:
+        """(offsets uint32 [nlist * G + 1], rows uint32 [N], G): the device's cell lists as ``dewi_ivf_lists_build`` wrote
+        them — segment (cell, b) holds the cell's rows with row mod G == b, ascending."""
+        self._ensure_built()
+        import torch
+        st = self._ivf
+        words = st.lists.view(torch.int32).cpu().numpy().view(np.uint32)
+        bins = st.nlist * st.buckets
+        return words[: bins + 1].copy(), words[bins + 1: bins + 1 + self._corpus.n_rows].copy(), st.buckets
+
+    def _resolve_nprobe(self, nprobe: Optional[int], nlist: int) -> int:
+        if nprobe is None:
+            nprobe = self.nprobe
+        if nprobe is None:
+            nprobe = default_nprobe(nlist)
+        if int(nprobe) < 1:
+            raise ValueError(f"nprobe must be at least 1, got {nprobe}")
+        return min(int(nprobe), nlist)
+
+    def probe(self, queries: np.ndarray, nprobe: Optional[int] = None) -> np.ndarray:
+        """The cells each query probes: int64 [B, nprobe], nearest first (the coarse step on its own)."""
+        if nprobe is not None and int(nprobe) < 1:
+            raise ValueError(f"nprobe must be at least 1, got {nprobe}")
+        self._ensure_built()
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        npb = self._resolve_nprobe(nprobe, self._ivf.nlist)
+        ids, _ = self._ivf.coarse.search(q, npb, 0.0, 0.0, candidates=npb)
+        return ids
+
+    # ---------------------------------------------------------------- search
+    def _prepare_probe(self, probe_ids, b: int, nprobe: int):
+        """``dewi_ivf_probe_prepare`` into the index's probe buffer -> (|U| per group, |F_j| per query, bytes per group)."""
+        import torch
+        from . import _native as nat
+        lib, st, corpus = nat.load_library(), self._ivf, self._corpus
+        need = int(lib.dewi_ivf_probe_bytes(corpus.n_rows, self.dim, 0, b, PROBE_GROUP))
+        stride = int(lib.dewi_ivf_probe_group_bytes(corpus.n_rows, self.dim, 0, PROBE_GROUP))
+        if need == 0 or stride == 0:
+            raise nat.NativeLibraryError(f"dewi_ivf_probe_bytes returned 0 for {b} queries")
+        if self._probe_buf is None or self._probe_buf.numel() < need or self._probe_buf.device != corpus.device:
+            self._probe_buf = torch.empty(need, dtype=torch.uint8, device=corpus.device)
+        n_groups = (b + PROBE_GROUP - 1) // PROBE_GROUP
+        n_union = (ctypes.c_int64 * n_groups)()
+        n_allowed = (ctypes.c_int64 * b)()
+        nat.check(lib.dewi_ivf_probe_prepare(0, corpus.n_rows, self.dim, nat.ptr(st.lists), st.nlist, nat.ptr(probe_ids), b,
+                                             nprobe, PROBE_GROUP, nat.ptr(self._probe_buf), self._probe_buf.numel(), n_union,
+                                             n_allowed, nat.stream_ptr()))
+        return list(n_union), list(n_allowed), stride
+
+    def _workspace_for(self, n_union: int, nq: int, c: int):
+        import torch
+        from . import _native as nat
+        need = int(self._corpus._lib.dewi_knn_filtered_workspace_bytes(n_union, self.dim, nq, c))
+        if need == 0:
+            raise nat.NativeLibraryError("dewi_knn_filtered_workspace_bytes returned 0: " + nat.last_error())
+        if self._ivf_ws is None or self._ivf_ws.numel() < need or self._ivf_ws.device != self._corpus.device:
+            self._ivf_ws = torch.empty(need, dtype=torch.uint8, device=self._corpus.device)
+        return self._ivf_ws
+
+    def _search_groups(self, q_dev, n_union, n_allowed, stride: int, k: int, c: int, candidates: Optional[int], sim: int,
+                       eta: float, pref: float, out_ids, out_scores) -> None:
+        """Step 3 on a prepared probe buffer whose every query holds at least c rows (one query: at least k)."""
+        from . import _native as nat
+        corpus, lib = self._corpus, self._corpus._lib
+        b = int(q_dev.shape[0])
+        space = nat.SPACE_CODES[self.space]
+        n_cand = 0 if candidates is None else int(candidates)
+        for g, q0 in enumerate(range(0, b, PROBE_GROUP)):
+            nq = min(PROBE_GROUP, b - q0)
+            buf = self._probe_buf[g * stride:]
+            ws = self._workspace_for(n_union[g], nq, c)
+            if nq == 1:
+                rc = lib.dewi_knn_rerank_filtered(
+                    nat.ptr(corpus.emb), 0, corpus.n_rows, self.dim, nat.ptr(buf), n_union[g], nat.ptr(q_dev[q0:q0 + 1]), 1,
+                    nat.ptr(corpus.dewi32), nat.ptr(corpus.ent32), k, n_cand, sim, eta, pref, space,
+                    nat.ptr(out_ids[q0:q0 + 1]), nat.ptr(out_scores[q0:q0 + 1]), nat.ptr(ws), ws.numel(), nat.stream_ptr())
+            else:
+                counts = (ctypes.c_int64 * nq)(*n_allowed[q0:q0 + nq])
+                rc = lib.dewi_knn_rerank_query_filtered(
+                    nat.ptr(corpus.emb), 0, corpus.n_rows, self.dim, nat.ptr(buf), n_union[g], counts, nat.ptr(q_dev[q0:q0 + nq]),
+                    nq, nat.ptr(corpus.dewi32), nat.ptr(corpus.ent32), k, n_cand, sim, eta, pref, space,
+                    nat.ptr(out_ids[q0:q0 + nq]), nat.ptr(out_scores[q0:q0 + nq]), nat.ptr(ws), ws.numel(), nat.stream_ptr())
+            nat.check(rc)
+
+    def search_device(self, q_dev, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, candidates: Optional[int] = None,
+                      similarity: str = "ip", nprobe: Optional[int] = None):
+        """The three steps for fp32 queries [B, dim] on the corpus's device -> (ids int64 [B, k], scores fp32 [B, k]) device
+        tensors.  Synchronises the current stream once (the probe's row counts come back to the host to plan the scan); the
+        search itself is left enqueued.  A query whose cells hold fewer than k rows fills the rest of its row with id -1 /
+        score NaN.  One caller at a time (shared buffers)."""
+        import torch
+        from . import _native as nat
+        self._ensure_built()
+        corpus, st = self._corpus, self._ivf
+        if corpus.is_bf16:
+            raise NotImplementedError("IVFIndex serves fp32 corpora (bf16: not in this build)")
+        npb = self._resolve_nprobe(nprobe, st.nlist)
+        if similarity not in nat.SIM_CODES:
+            raise ValueError(f"unknown similarity {similarity!r}")
+        if candidates is None and similarity != "ip":
+            raise ValueError("similarity transforms belong to the ANN re-rank rule: pass candidates=k as well")
+        b, k = int(q_dev.shape[0]), int(k)
+        if q_dev.shape[1] != self.dim:
+            raise ValueError(f"Expected query shape ({self.dim},), got {tuple(q_dev.shape[1:])}")
+        if k <= 0:
+            return (torch.empty((b, 0), dtype=torch.int64, device=corpus.device),
+                    torch.empty((b, 0), dtype=torch.float32, device=corpus.device))
+        if candidates is not None and int(candidates) < k:
+            raise ValueError(f"candidates = {candidates} must be at least k = {k}")
+        c = 2 * k if candidates is None else int(candidates)
+        sim, eta, pref = nat.SIM_CODES[similarity], float(eta), float(entropy_pref)
+        out_ids = torch.empty((b, k), dtype=torch.int64, device=corpus.device)
+        out_scores = torch.empty((b, k), dtype=torch.float32, device=corpus.device)
+        probe_ids, _ = st.coarse.search_device(q_dev, npb, 0.0, 0.0, candidates=npb)
+        n_union, n_allowed, stride = self._prepare_probe(probe_ids, b, npb)
+        short = [j for j in range(b) if n_allowed[j] < c]
+        if not short:
+            self._search_groups(q_dev, n_union, n_allowed, stride, k, c, candidates, sim, eta, pref, out_ids, out_scores)
+            return out_ids, out_scores
+        # queries whose cells hold fewer rows than the cut leave the shared passes: one list each, cut |F_j|, at most |F_j| results
+        out_ids.fill_(-1)
+        out_scores.fill_(float("nan"))
+        shared = [j for j in range(b) if n_allowed[j] >= c]
+        if shared:
+            idx = torch.tensor(shared, dtype=torch.int64, device=corpus.device)
+            pid_s, q_s = probe_ids[idx].contiguous(), q_dev[idx].contiguous()
+            o_ids = torch.empty((len(shared), k), dtype=torch.int64, device=corpus.device)
+            o_sc = torch.empty((len(shared), k), dtype=torch.float32, device=corpus.device)
+            u_s, a_s, stride = self._prepare_probe(pid_s, len(shared), npb)
+            self._search_groups(q_s, u_s, a_s, stride, k, c, candidates, sim, eta, pref, o_ids, o_sc)
+            out_ids.index_copy_(0, idx, o_ids)
+            out_scores.index_copy_(0, idx, o_sc)
+        for j in short:
+            if n_allowed[j] == 0:
+                continue
+            kk = min(k, n_allowed[j])
+            u_1, a_1, stride = self._prepare_probe(probe_ids[j:j + 1], 1, npb)
+            o_ids = torch.empty((1, kk), dtype=torch.int64, device=corpus.device)
+            o_sc = torch.empty((1, kk), dtype=torch.float32, device=corpus.device)
+            self._search_groups(q_dev[j:j + 1], u_1, a_1, stride, kk, c, candidates, sim, eta, pref, o_ids, o_sc)
+            out_ids[j, :kk] = o_ids[0]
+            out_scores[j, :kk] = o_sc[0]
+        return out_ids, out_scores
+
+    def search_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                     candidates: Optional[int] = None, similarity: str = "ip", filter=None, *,
+                     nprobe: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k]); query j searches the rows F_j of its
+        ``nprobe`` nearest cells with the rules of ``ExactIndex.search`` on those rows (cut ``min(2k, |F_j|)`` or
+        ``candidates``, blend, top-k).  An approximate index does not raise when the probe is short: with ``|F_j| < k`` the
+        row holds ``|F_j|`` results and is padded with id -1 / score NaN.
+
+        ``filter=`` together with IVF is not supported: passing one runs the parent's EXACT filtered search over the whole
+        allow-list (``nprobe`` is then ignored)."""
+        if nprobe is not None and int(nprobe) < 1:
+            raise ValueError(f"nprobe must be at least 1, got {nprobe}")
+        if filter is not None:
+            return super().search_batch(queries, k, eta, entropy_pref, candidates, similarity, filter=filter)
+        self._ensure_built()
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        import torch
+        corpus = self._corpus
+        with corpus._lock, torch.cuda.device(corpus.device):
+            q_dev = corpus.stage_queries(q)
+            ids, scores = self.search_device(q_dev, k, eta, entropy_pref, candidates, similarity, nprobe)
+            return ids.cpu().numpy(), scores.cpu().numpy()
+
+    def search(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+               candidates: Optional[int] = None, similarity: str = "ip", filter=None, *,
+               nprobe: Optional[int] = None) -> SearchResult:
+        """``ExactIndex.search`` over the rows of the query's ``nprobe`` nearest cells (see ``search_batch``); fewer than k
+        results when those cells hold fewer than k rows."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        rows, scores = self.search_batch(q, k, eta, entropy_pref, candidates, similarity, filter=filter, nprobe=nprobe)
+        keep = rows[0] >= 0
+        return self.results_for(rows[:1][:, keep], scores[:1][:, keep])[0]
+
+    # ---------------------------------------------------------------- persistence
+    def save(self, path: Union[str, Path]) -> None:
+        """The ``ExactIndex`` files unchanged (the directory still loads as an ``ExactIndex``) plus ``ivf.json``,
+        ``ivf_centroids.npy`` and ``ivf_assign.npy``."""
+        self._ensure_built()
+        super().save(path)
+        root = Path(path)
+        st = self._ivf
+        with open(root / "ivf.json", "w") as fh:
+            json.dump({"format_version": IVF_FORMAT_VERSION, "nlist": st.nlist, "nprobe": self.nprobe,
+                       "train_seed": self.train_seed, "train_iters": self.train_iters, "max_train_rows": self.max_train_rows,
+                       "num_rows": int(self._corpus.n_rows)}, fh)
+        np.save(str(root / "ivf_centroids.npy"), st.centroids.cpu().numpy())
+        np.save(str(root / "ivf_assign.npy"), st.assign.cpu().numpy())
+
+    @classmethod
+    def load(cls, path: Union[str, Path], **kwargs: Any) -> "IVFIndex":
+        """Load without retraining: the saved centroids and assignment are taken as they are (a directory without the IVF
+        files — one an ``ExactIndex`` saved — loads too and is trained at the first build)."""
+        root = Path(path)
+        meta = None
+        if (root / "ivf.json").exists():
+            with open(root / "ivf.json") as fh:
+                meta = json.load(fh)
+            if meta.get("format_version") != IVF_FORMAT_VERSION:
+                raise ValueError(f"unknown ivf.json format version {meta.get('format_version')}")
+            for key in ("nlist", "nprobe", "train_seed", "train_iters", "max_train_rows"):
+                kwargs.setdefault(key, meta[key])
+        inst = super().load(path, **kwargs)
+        if meta is not None:
+            inst._ivf_loaded = (np.load(str(root / "ivf_centroids.npy"), allow_pickle=False),
+                                np.load(str(root / "ivf_assign.npy"), allow_pickle=False))
+        return inst

@@ -231,6 +231,41 @@ int dewi_knn_rerank_query_filtered(const void* d_E, int elem_type, int64_t n_row
                                    double entropy_pref, int space, int64_t* d_out_ids, float* d_out_scores, void* d_workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * IVF-Flat support (additive to ABI 6): the k-means cells of a corpus as row lists, and the cells a query probes as
+ * a prepared filter, so that an approximate search is dewi_knn_rerank_filtered / dewi_knn_rerank_query_filtered over the
+ * probed rows only.  fp32 corpora (elem_type 0); a bf16 corpus returns DEWI_ERR_UNSUPPORTED.  1 <= n_cells <= min(65536, n_rows).
+ *
+ * dewi_ivf_buckets: G, the number of buckets a prepared filter of this row shape has (1 for rows of whole 16-byte units,
+ * else 2, 4 or 8; 0 for a bad shape; needs no device).
+ * dewi_ivf_lists_bytes: size of the cell-list buffer (0 for a bad shape; needs no device).
+ * dewi_ivf_lists_build: d_assign (DEVICE, int32 [n_rows]: the cell of every row) -> d_lists, u32 words: n_cells * G + 1 offsets
+ * (segment (cell, b) = rows of the cell with row mod G == b, cell-major), then the n_rows row numbers, ascending inside every
+ * segment (deterministic), then ONE ERROR WORD: the number of rows whose assignment lay outside [0, n_cells) — such a row is
+ * dropped, nothing is written out of bounds, and the caller checks the word once after the build.  Asynchronous on `stream`.
+ *
+ * dewi_ivf_probe_bytes: size of the probe buffer for n_queries queries in groups of `group` (1..32) consecutive queries (0 for
+ * a bad shape; needs no device); dewi_ivf_probe_group_bytes: the distance between the buffers of consecutive groups inside it
+ * (at least dewi_query_filter_bytes of `group` queries).
+ * dewi_ivf_probe_prepare: d_probe_ids (DEVICE, int64 [n_queries][nprobe]: the cells each query probes, e.g. the ids a search
+ * over the centroids wrote) -> for group i, at d_out + i * dewi_ivf_probe_group_bytes(...), a buffer in exactly the layout
+ * dewi_knn_rerank_query_filtered reads, holding the rows of the group's distinct cells (per bucket the cells' segments in
+ * ascending cell order; ascending rows inside a segment, not across a bucket) and per list position the group's query bits.
+ * A group of one query is a prepared filter for dewi_knn_rerank_filtered.  Returns |U_i| in out_n_union[i] (HOST, one per
+ * group) and |F_j| in out_n_allowed[j] (HOST, n_queries).  It SYNCHRONISES `stream` once.  A probe id outside [0, n_cells) is
+ * IGNORED, and so is the repetition of an id inside one query (neither is knowable on the host without a read-back).
+ * Work: O(n_cells * G) per group + O(rows probed).
+ * ------------------------------------------------------------------------------------------ */
+int dewi_ivf_buckets(int dim, int elem_type);
+size_t dewi_ivf_lists_bytes(int64_t n_rows, int dim, int elem_type, int n_cells);
+int dewi_ivf_lists_build(int elem_type, int64_t n_rows, int dim, int n_cells, const int32_t* d_assign, void* d_lists,
+                         size_t lists_bytes, void* stream);
+size_t dewi_ivf_probe_group_bytes(int64_t n_rows, int dim, int elem_type, int group);
+size_t dewi_ivf_probe_bytes(int64_t n_rows, int dim, int elem_type, int n_queries, int group);
+int dewi_ivf_probe_prepare(int elem_type, int64_t n_rows, int dim, const void* d_lists, int n_cells, const int64_t* d_probe_ids,
+                           int n_queries, int nprobe, int group, void* d_out, size_t out_bytes, int64_t* out_n_union,
+                           int64_t* out_n_allowed, void* stream);
+
 /* Step 1 of the bf16 search alone (backends.py:420-424 followed by the bf16 rounding of config C3): q / ||q||
  * in fp32 unless the norm is 0 (cosine), then round-to-nearest-even to bf16.  This is the kernel the batched
  * matrix-core path runs on its queries; exposed so that parity tests can check the normalisation on its own
