@@ -1081,6 +1081,92 @@ int dewi_ivf_probe_prepare(int elem_type, int64_t n_rows, int dim, const void* d
   return DEWI_OK;
 }
 
+// ---- range search (additive to ABI 6) ---------------------------------------------------------------------------------
+// Workspace: the dense keys [n_queries][n_scan] from offset 0 (where run_scan puts them), the selection's chunk counts
+// [n_queries][range_chunks(n_scan)], then the prepared queries of the generic row kernel.  The first two depend on n_scan and
+// n_queries alone, so dewi_knn_range_collect finds them without the corpus shape; nothing depends on the device.
+struct RangeLayout {
+  size_t keys_bytes, chunks_off, chunks_bytes, qn_off, total;
+};
+static RangeLayout range_layout(int64_t n_scan, int dim, int n_queries) {
+  RangeLayout R;
+  R.keys_bytes = align_up(static_cast<size_t>(n_queries) * static_cast<size_t>(n_scan) * 8, 256);
+  R.chunks_off = R.keys_bytes;
+  R.chunks_bytes = align_up(static_cast<size_t>(n_queries) * static_cast<size_t>(dewi::range_chunks(n_scan)) * 4, 256);
+  R.qn_off = R.chunks_off + R.chunks_bytes;
+  R.total = R.qn_off + align_up(static_cast<size_t>(n_queries) * dim * 4, 256);
+  return R;
+}
+// a candidate count that makes plan_scan choose the dense form of the row kernels (they ignore its value there)
+constexpr int kRangeDenseCandidates = dewi::kMaxListCandidates + 1;
+
+size_t dewi_knn_range_workspace_bytes(int64_t n_scan, int dim, int elem_type, int n_queries) {
+  if (n_scan <= 0 || n_scan > 0xFFFFFFFFll || dim <= 0 || (elem_type != 0 && elem_type != 1)) return 0;
+  if (n_queries <= 0 || n_queries > DEWI_RANGE_MAX_QUERIES) return 0;
+  return range_layout(n_scan, dim, n_queries).total;
+}
+
+int dewi_knn_range_count(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_allowed,
+                         const float* d_Q, int n_queries, const float* d_thresholds, int space, int64_t* d_counts,
+                         void* d_workspace, size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  int rc = check_common(d_E, n_rows, dim, d_Q, n_queries, space);
+  if (rc) return rc;
+  if (elem_type != 0 && elem_type != 1) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+  if (n_queries > DEWI_RANGE_MAX_QUERIES)
+    return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, %d]: split the batch", n_queries, DEWI_RANGE_MAX_QUERIES);
+  if (!d_thresholds || !d_counts) return fail(DEWI_ERR_INVALID_ARG, "null threshold or count pointer");
+  if (d_filter && elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "filtered search serves fp32 corpora (bf16: not in this build)");
+  if (d_filter && (n_allowed < 0 || n_allowed > n_rows))
+    return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+  const int64_t n_scan = d_filter ? n_allowed : n_rows;
+  if (n_scan == 0) {   // an empty allow-list: every query's answer is empty
+    const hipError_t e = hipMemsetAsync(d_counts, 0, sizeof(int64_t) * static_cast<size_t>(n_queries), stream);
+    return e == hipSuccess ? DEWI_OK : hip_fail(e, "hipMemsetAsync (range counts)");
+  }
+  const RangeLayout R = range_layout(n_scan, dim, n_queries);
+  if (!d_workspace || workspace_bytes < R.total) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, R.total);
+  if (reinterpret_cast<uintptr_t>(d_workspace) % 16 != 0) return fail(DEWI_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+  DeviceInfo dev;
+  rc = ensure_device(dev);
+  if (rc) return rc;
+  // the row kernels of this shape in their dense form, planned on the rows a query scans: the one-query search's arithmetic
+  KnnLayout L = layout_knn(n_scan, dim, elem_type ? 2 : 4, n_queries, kRangeDenseCandidates, dev.cus);
+  if (!L.plan.dense || L.plan.keys_per_query != n_scan || L.keys_off != 0)
+    return fail(DEWI_ERR_UNSUPPORTED, "no dense row scan for this shape");
+  L.qn_off = R.qn_off;   // (the chunk counts sit between the keys and the prepared queries)
+  char* ws = static_cast<char*>(d_workspace);
+  rc = run_scan(L, d_E, elem_type, n_scan, dim, d_Q, n_queries, kRangeDenseCandidates, space, ws, stream,
+                static_cast<const uint32_t*>(d_filter));
+  if (rc) return rc;
+  const hipError_t e = dewi::launch_range_count(reinterpret_cast<const uint64_t*>(ws), n_scan, n_queries, d_thresholds,
+                                                reinterpret_cast<uint32_t*>(ws + R.chunks_off), d_counts, stream);
+  return e == hipSuccess ? DEWI_OK : hip_fail(e, "range count launch");
+}
+
+int dewi_knn_range_collect(const void* d_workspace, size_t workspace_bytes, int64_t n_scan, int n_queries,
+                           const float* d_thresholds, const int64_t* d_lims, int64_t capacity, const float* d_dewi32,
+                           const float* d_ent32, double eta, double entropy_pref, int64_t* d_out_rows, float* d_out_sims,
+                           float* d_out_scores, void* stream_) {
+  if (n_scan < 0 || n_scan > 0xFFFFFFFFll) return fail(DEWI_ERR_INVALID_ARG, "n_scan %lld outside [0, 2^32)", static_cast<long long>(n_scan));
+  if (n_queries <= 0 || n_queries > DEWI_RANGE_MAX_QUERIES)
+    return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, %d]", n_queries, DEWI_RANGE_MAX_QUERIES);
+  if (capacity < 0) return fail(DEWI_ERR_INVALID_ARG, "negative capacity");
+  if (n_scan == 0 || capacity == 0) return DEWI_OK;
+  if (!d_thresholds || !d_lims || !d_dewi32 || !d_ent32 || !d_out_rows || !d_out_sims || !d_out_scores)
+    return fail(DEWI_ERR_INVALID_ARG, "null threshold, lims, payload or output pointer");
+  const RangeLayout R = range_layout(n_scan, 1, n_queries);
+  const size_t need = R.chunks_off + R.chunks_bytes;
+  if (!d_workspace || workspace_bytes < need) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
+  if (reinterpret_cast<uintptr_t>(d_workspace) % 16 != 0) return fail(DEWI_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+  const char* ws = static_cast<const char*>(d_workspace);
+  const hipError_t e = dewi::launch_range_collect(reinterpret_cast<const uint64_t*>(ws), n_scan, n_queries, d_thresholds,
+                                                  reinterpret_cast<const uint32_t*>(ws + R.chunks_off), d_lims, capacity,
+                                                  make_rerank(eta, entropy_pref), d_dewi32, d_ent32, d_out_rows, d_out_sims,
+                                                  d_out_scores, static_cast<hipStream_t>(stream_));
+  return e == hipSuccess ? DEWI_OK : hip_fail(e, "range collect launch");
+}
+
 size_t dewi_merge_workspace_bytes(int n_lists, int n_queries, int list_len, int n_candidates) {
   if (n_lists <= 0 || n_queries <= 0 || list_len <= 0 || n_candidates <= 0) return 0;
   if (static_cast<int64_t>(n_lists) * list_len <= dewi::kMaxSortCandidates) return 0;   // sorted in LDS

@@ -348,6 +348,21 @@ hipError_t launch_merge_rerank(const dewi_candidate* d_lists, int n_lists, int n
                                int n_candidates, int k, const RerankParams& rp, int64_t* d_out_ids,
                                float* d_out_scores, hipStream_t stream);
 
+// ---- range.hip: every scanned row at or above a per-query threshold, from the dense keys of the row kernels
+// range_chunks: chunk counts the selection keeps per query (one u32 per chunk of keys) between its two calls.
+int64_t range_chunks(int64_t n_scan);
+// d_keys [n_queries][n_scan] dense keys (16-byte aligned, readable up to the next multiple of 16 bytes) -> d_chunk_counts
+// [n_queries][range_chunks(n_scan)] as exclusive per-query offsets, d_counts[q] = the query's number of rows with
+// key_score(key) >= d_thresholds[q] (NaN and empty keys never pass).
+hipError_t launch_range_count(const uint64_t* d_keys, int64_t n_scan, int n_queries, const float* d_thresholds,
+                              uint32_t* d_chunk_counts, int64_t* d_counts, hipStream_t stream);
+// Survivor i of query q (key-array order) -> position d_lims[q] + i of the three outputs (global row, similarity, blend);
+// nothing is written at or beyond d_lims[q + 1] or `capacity`.
+hipError_t launch_range_collect(const uint64_t* d_keys, int64_t n_scan, int n_queries, const float* d_thresholds,
+                                const uint32_t* d_chunk_offsets, const int64_t* d_lims, int64_t capacity, const RerankParams& rp,
+                                const float* d_dewi32, const float* d_ent32, int64_t* d_out_rows, float* d_out_sims,
+                                float* d_out_scores, hipStream_t stream);
+
 // ---- ingest.hip ---------------------------------------------------------------------------
 hipError_t launch_normalize_rows(const float* d_src, float* d_dst, int64_t n_rows, int dim, hipStream_t stream);
 hipError_t launch_row_cosine(const float* d_a, const float* d_b, float* d_out, int64_t n_rows, int dim, float eps,

@@ -28,6 +28,24 @@ def _torch():
 _corpus_ids = itertools.count(1)
 
 
+def check_thresholds(thresholds, n_queries: int) -> np.ndarray:
+    """A scalar or [B] thresholds -> fp32 [B] host array (``ValueError`` for any other shape).  Host logic only."""
+    t = np.asarray(thresholds, dtype=np.float32)
+    if t.ndim == 0 or t.shape == (1,):
+        return np.full(n_queries, t.reshape(-1)[0], dtype=np.float32)
+    if t.shape != (n_queries,):
+        raise ValueError(f"thresholds must be a scalar or have shape ({n_queries},), got {t.shape}")
+    return np.ascontiguousarray(t)
+
+
+def _order_key(x):
+    """fp32 tensor -> int64 keys in the order of the kernels' ``ord_f32``: larger float, larger key; -0 == +0; NaN on top."""
+    torch = _torch()
+    u = (x + 0.0).view(torch.int32).to(torch.int64)
+    k = torch.where(u >= 0, u, -(u & 0x7FFFFFFF))
+    return torch.where(torch.isnan(x), torch.full_like(k, 1 << 31), k)
+
+
 class DeviceFilter:
     """A prepared allow-list of corpus rows (``DeviceCorpus.make_filter``): the device buffer the filtered row kernels walk
     (``dewi_filter_prepare``: the allowed rows, sorted, grouped by the residue of their offset inside a 16-byte unit), the
@@ -502,6 +520,121 @@ class DeviceCorpus:
                 nat.SIM_CODES[similarity], nat.ptr(out_ids), nat.ptr(out_scores), nat.ptr(ws), ws.numel(), nat.stream_ptr())
         nat.check(rc)
         return out_ids, out_scores
+
+    # ------------------------------------------------------------------ range search
+    def stage_thresholds(self, thresholds, n_queries: int):
+        """A scalar or [B] thresholds (numbers, numpy or torch) -> fp32 [B] tensor on this device.  The length is checked
+        before anything touches the device."""
+        torch = _torch()
+        if isinstance(thresholds, torch.Tensor):
+            t = thresholds.reshape(-1) if thresholds.dim() == 0 else thresholds
+            if t.dim() != 1 or int(t.shape[0]) not in (1, n_queries):
+                raise ValueError(f"thresholds must be a scalar or have shape ({n_queries},), got {tuple(thresholds.shape)}")
+            t = t.to(device=self.device, dtype=torch.float32)
+            return (t.expand(n_queries) if int(t.shape[0]) != n_queries else t).contiguous()
+        return torch.from_numpy(check_thresholds(thresholds, n_queries)).to(self.device)
+
+    def range_search_device(self, q_dev, thresholds, eta: float, entropy_pref: float, filter: Optional[DeviceFilter] = None,
+                            max_results: Optional[int] = None, sort: bool = True):
+        """Every row at least as similar to the query as its threshold, however many that is: device tensors
+        ``(lims int64 [B + 1], rows int64 [T], sims fp32 [T], scores fp32 [T])`` — query j's rows are
+        ``rows[lims[j]:lims[j + 1]]`` (``id_offset`` added), ``sims`` their similarities, ``scores`` the adjusted scores.
+
+        The rule is steps 1-2 of the search (``dewi_hip.h``), the test ``sim >= threshold`` instead of a cut, then the
+        blend: a row's ``sims`` / ``scores`` are bit for bit what the one-query search gives it, and a NaN similarity
+        never passes.  ``space="l2"``: the similarity is ``-||e - q||^2``, so a radius r is ``threshold = -r * r``.
+        ``thresholds``: one number, or one per query.  ``sort=True`` orders every query's segment as the search orders its
+        answers (adjusted score descending, ties to the higher similarity, then to the lower row); ``sort=False`` leaves
+        ascending rows.  ``filter``: a ``DeviceFilter`` of this corpus (fp32 corpora): only its rows are scanned.
+        ``max_results``: raise ``ValueError`` — before the rows of the offending chunk are collected — once the batch has
+        more rows than that.
+
+        The batch runs in chunks of up to 32 queries: ``dewi_knn_range_count`` (dense row scan + count), ONE host
+        synchronisation to read the chunk's counts and size its outputs, ``dewi_knn_range_collect``.  The workspace
+        belongs to the chunk between its two calls: NOT thread-safe on one instance."""
+        torch = _torch()
+        if isinstance(filter, DeviceQueryFilters):
+            raise NotImplementedError("range search takes one allow-list for the batch (per-query filters: not in this build)")
+        if filter is not None:
+            self.check_filter(filter)
+        b = int(q_dev.shape[0])
+        if q_dev.dim() != 2 or q_dev.shape[1] != self.dim:
+            raise ValueError(f"Expected query shape ({self.dim},), got {tuple(q_dev.shape[1:])}")
+        thr = self.stage_thresholds(thresholds, b)
+        if filter is not None and self.is_bf16:
+            raise NotImplementedError("filtered search serves fp32 corpora (bf16: not in this build)")
+        n_scan = self.n_rows if filter is None else filter.n_allowed
+        dev = self.device
+        parts = []
+        counts_h = np.zeros(b, dtype=np.int64)
+        elem = 1 if self.is_bf16 else 0
+        total = 0
+        for q0 in range(0, b if n_scan > 0 else 0, nat.RANGE_MAX_QUERIES):
+            nb = min(nat.RANGE_MAX_QUERIES, b - q0)
+            wkey = ("range", nb, n_scan)
+            ws = self._ws.get(wkey)
+            if ws is None:
+                need = int(self._lib.dewi_knn_range_workspace_bytes(n_scan, self.dim, elem, nb))
+                if need == 0:
+                    raise nat.NativeLibraryError(f"dewi_knn_range_workspace_bytes returned 0 for {n_scan} x {self.dim}")
+                if len(self._ws) > 8:
+                    self._ws.clear()
+                ws = self._ws[wkey] = torch.empty(need, dtype=torch.uint8, device=dev)
+            q_c, thr_c = q_dev[q0:q0 + nb], thr[q0:q0 + nb]
+            counts_d = torch.empty(nb, dtype=torch.int64, device=dev)
+            nat.check(self._lib.dewi_knn_range_count(
+                nat.ptr(self.emb), elem, self.n_rows, self.dim, nat.ptr(filter.buf) if filter is not None else None,
+                n_scan if filter is not None else 0, nat.ptr(q_c), nb, nat.ptr(thr_c), nat.SPACE_CODES[self.space],
+                nat.ptr(counts_d), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+            c_h = counts_d.cpu().numpy()                   # the chunk's one synchronisation
+            counts_h[q0:q0 + nb] = c_h
+            t_c = int(c_h.sum())
+            total += t_c
+            if max_results is not None and total > int(max_results):
+                raise ValueError(f"range search found more than max_results = {int(max_results)} rows "
+                                 f"({total} after {q0 + nb} of {b} queries): raise the threshold or max_results")
+            if t_c == 0:
+                continue
+            lims_c = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(counts_d, 0, out=lims_c[1:])
+            rows = torch.empty(t_c, dtype=torch.int64, device=dev)
+            sims = torch.empty(t_c, dtype=torch.float32, device=dev)
+            scores = torch.empty(t_c, dtype=torch.float32, device=dev)
+            nat.check(self._lib.dewi_knn_range_collect(
+                nat.ptr(ws), ws.numel(), n_scan, nb, nat.ptr(thr_c), nat.ptr(lims_c), t_c, nat.ptr(self.dewi32),
+                nat.ptr(self.ent32), float(eta), float(entropy_pref), nat.ptr(rows), nat.ptr(sims), nat.ptr(scores),
+                nat.stream_ptr()))
+            parts.append((rows, sims, scores))
+        if b <= nat.RANGE_MAX_QUERIES and parts:
+            lims = lims_c                      # one chunk: its running sum is the batch's
+        else:
+            lims_h = np.zeros(b + 1, dtype=np.int64)
+            np.cumsum(counts_h, out=lims_h[1:])
+            lims = torch.from_numpy(lims_h).to(dev)
+        if not parts:
+            return (lims, torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
+                    torch.empty(0, dtype=torch.float32, device=dev))
+        rows, sims, scores = parts[0] if len(parts) == 1 else tuple(torch.cat(x) for x in zip(*parts))
+        # plumbing from here on (torch): the order inside a query's segment
+        bucketed = filter is not None and self.dim % 4 != 0
+        seg = None
+        if b > 1 and (sort or bucketed):       # the query of every result, as the high bits of a sort key
+            seg = torch.bucketize(torch.arange(rows.shape[0], dtype=torch.int64, device=dev), lims[1:], right=True)
+        if bucketed:
+            # a filter over rows that are not whole 16-byte units is scanned bucket by bucket: ascending rows first
+            order = torch.argsort(rows if seg is None else seg * (1 << 32) + rows, stable=True)
+            rows, sims, scores = rows[order], sims[order], scores[order]
+        if sort:
+            # two stable sorts over ascending rows: by similarity, then by (query, adjusted score) — ties on the adjusted
+            # score keep the higher similarity first, ties on both the lower row
+            o1 = torch.sort(-_order_key(sims), stable=True).indices
+            key = (1 << 32) - _order_key(scores[o1])
+            o2 = torch.sort(key if seg is None else seg[o1] * (1 << 34) + key, stable=True).indices
+            order = o1[o2]
+            rows, sims, scores = rows[order], sims[order], scores[order]
+        if self.id_offset:
+            rows = rows + self.id_offset
+        return lims, rows, sims, scores
 
     def refused_by_last_call(self) -> np.ndarray:
         """Monitoring / tests: bool [B] — which queries of the LAST ``search_device`` call a matrix-core pass refused (and the

@@ -32,6 +32,8 @@ MODE_CODES = {"standard": 0, "conditional": 1}
 SIM_CODES = {"ip": 0, "one_minus_dist": 1, "inv_one_plus_dist": 2}
 NUM_SIGNALS = 7
 ABI_VERSION = 6
+#: most queries one dewi_knn_range_count call takes (include/dewi_hip.h DEWI_RANGE_MAX_QUERIES)
+RANGE_MAX_QUERIES = 32
 
 #: every symbol include/dewi_hip.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -45,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "dewi_knn_rerank_query_filtered",
     "dewi_ivf_buckets", "dewi_ivf_lists_bytes", "dewi_ivf_lists_build", "dewi_ivf_probe_group_bytes", "dewi_ivf_probe_bytes",
     "dewi_ivf_probe_prepare",
+    "dewi_knn_range_workspace_bytes", "dewi_knn_range_count", "dewi_knn_range_collect",
 )
 
 
@@ -159,6 +162,12 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_ivf_probe_bytes.argtypes = [i64, i32, i32, i32, i32]
     lib.dewi_ivf_probe_prepare.restype = i32
     lib.dewi_ivf_probe_prepare.argtypes = [i32, i64, i32, vp, i32, vp, i32, i32, i32, vp, sz, c.POINTER(i64), c.POINTER(i64), vp]
+    lib.dewi_knn_range_workspace_bytes.restype = sz
+    lib.dewi_knn_range_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_knn_range_count.restype = i32
+    lib.dewi_knn_range_count.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, vp, i32, vp, vp, sz, vp]
+    lib.dewi_knn_range_collect.restype = i32
+    lib.dewi_knn_range_collect.argtypes = [vp, sz, i64, i32, vp, vp, i64, vp, vp, f64, f64, vp, vp, vp, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

@@ -564,6 +564,50 @@ class ExactIndex(BaseIndex):
         return self._corpus.search(q, int(k), float(eta), float(entropy_pref), candidates=candidates,
                                    similarity=similarity)
 
+    # ---------------------------------------------------------------- range search (additive)
+    def range_search(self, query: np.ndarray, threshold: float, eta: float = 0.5, entropy_pref: float = 0.0, filter=None,
+                     max_results: Optional[int] = None) -> SearchResult:
+        """Every document at least as similar to ``query`` as ``threshold`` (additive; the reference has no such method):
+        ``(doc_id, adjusted score, Payload)`` tuples in the order ``search`` gives its answers.
+
+        The similarity is the one ``search`` computes (steps 1-2 of reference backends.py:414-436) and the test is
+        ``sim >= threshold``; there is no cut and no k, so the result has as many rows as pass — ``[]`` when none does or the
+        index is empty.  A document's adjusted score is what ``search`` would give it (the blend with ``eta`` /
+        ``entropy_pref``).  ``space="l2"``: the similarity is ``-||e - q||^2``, so a radius r is ``threshold = -r * r``.
+        ``filter``: one allow-list, as ``search`` takes it (a prepared filter, a bool mask, doc ids or rows).
+        ``max_results``: ``ValueError`` instead of a larger result."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        lims, rows, scores, _ = self.range_search_batch(q[:1], threshold, eta, entropy_pref, filter=filter, max_results=max_results)
+        m = int(lims[1])
+        return self.results_for(rows[None, :m], scores[None, :m])[0]
+
+    def range_search_batch(self, queries: np.ndarray, threshold, eta: float = 0.5, entropy_pref: float = 0.0, filter=None,
+                           max_results: Optional[int] = None, sort: bool = True):
+        """[B, dim] queries -> ``(lims int64 [B + 1], rows int64 [T], scores fp32 [T], sims fp32 [T])``: query j's rows are
+        ``rows[lims[j]:lims[j + 1]]`` with their adjusted scores and similarities.  ``threshold``: one number or one per
+        query.  ``sort=False`` leaves every query's rows ascending instead of in ``search`` order.  Per-query filters are not
+        served (``NotImplementedError``).  See ``range_search``."""
+        from ._engine import DeviceQueryFilters, check_thresholds
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        b = int(q.shape[0])
+        thr = check_thresholds(threshold, b)
+        if isinstance(filter, DeviceQueryFilters) or (filter is not None and len(getattr(filter, "shape", ())) == 2):
+            raise NotImplementedError("range search takes one allow-list for the batch (per-query filters: not in this build)")
+        if not self._doc_ids or b == 0:         # an empty index has no rows to return (and nothing to build)
+            return (np.zeros(b + 1, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32), np.zeros(0, np.float32))
+        self._ensure_built()
+        import torch
+        corpus = self._corpus
+        with corpus._lock, torch.cuda.device(corpus.device):
+            lims, rows, sims, scores = corpus.range_search_device(
+                corpus.stage_queries(q), thr, float(eta), float(entropy_pref), filter=self._prepared(filter),
+                max_results=max_results, sort=sort)
+            return lims.cpu().numpy(), rows.cpu().numpy(), scores.cpu().numpy(), sims.cpu().numpy()
+
     def results_for(self, rows: np.ndarray, scores: np.ndarray) -> List[SearchResult]:
         """Row indices/scores of ``search_batch`` -> the reference's (doc_id, score, Payload) tuples."""
         ids, at_row = self._doc_ids, self._payloads.at_row

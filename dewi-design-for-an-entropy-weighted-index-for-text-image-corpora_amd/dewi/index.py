@@ -4,7 +4,7 @@ Same constructor, defaults and methods as the reference (index.py:22-166): it va
 the query, fills in the default ``eta`` / ``entropy_pref`` and delegates to a backend.  In
 this build every backend choice resolves to the HIP ``ExactIndex`` (ANN graph libraries
 are out of scope), with the reference's own warning when an ANN backend was asked for.
-Additions: ``add_batch`` and ``search_batch``.
+Additions: ``add_batch``, ``search_batch``, ``range_search`` and ``range_search_batch``.
 """
 from __future__ import annotations
 
@@ -115,6 +115,34 @@ class DewiIndex(BaseIndex):
         else:
             rows, scores = self._backend.search_batch(q, k, eta, entropy_pref)
         return self._backend.results_for(rows, scores)
+
+    def range_search(self, query: np.ndarray, threshold: float, eta: Optional[float] = None,
+                     entropy_pref: Optional[float] = None, filter=None,
+                     max_results: Optional[int] = None) -> List[Tuple[str, float, Payload]]:
+        """Every document at least as similar to ``query`` as ``threshold`` (additive; ``ExactIndex.range_search``), in
+        ``search`` order; ``[]`` when nothing reaches the threshold or the index is empty."""
+        eta, entropy_pref = self._defaults(eta, entropy_pref)
+        q = np.asarray(query, dtype=np.float32)
+        if q.shape != (self.dim,):
+            raise ValueError(f"Expected query shape ({self.dim},), got {q.shape}")
+        return self.range_search_batch(q.reshape(1, -1), threshold, eta, entropy_pref, filter=filter, max_results=max_results)[0]
+
+    def range_search_batch(self, queries: np.ndarray, threshold, eta: Optional[float] = None,
+                           entropy_pref: Optional[float] = None, filter=None,
+                           max_results: Optional[int] = None) -> List[List[Tuple[str, float, Payload]]]:
+        """One call for B queries ([B, dim]; ``threshold``: one number or one per query); each result list equals
+        ``range_search`` of that row."""
+        eta, entropy_pref = self._defaults(eta, entropy_pref)
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        # (the backend checks the arguments, then builds itself on first use; an empty index answers with empty results)
+        lims, rows, scores, _ = self._backend.range_search_batch(q, threshold, eta, entropy_pref, filter=filter,
+                                                                 max_results=max_results)
+        if len(self) > 0 and q.shape[0] > 0:
+            self._built = True
+        return [self._backend.results_for(rows[None, lims[j]:lims[j + 1]], scores[None, lims[j]:lims[j + 1]])[0]
+                for j in range(q.shape[0])]
 
     # ------------------------------------------------------------------ accessors (index.py:95-119)
     def __len__(self) -> int:

@@ -52,6 +52,10 @@ class IVFIndex(ExactIndex):
     ``max_train_rows`` (default ``256 * nlist``) sampled rows per round, every row in the final assignment; spherical
     (centroids re-normalised every round) for ``space="cosine"``, plain means for ``"l2"``; an empty cell keeps its previous
     centroid.  The same corpus and seed give the same cells on the same machine.  ``add`` + ``build`` after a build retrains.
+
+    ``range_search`` / ``range_search_batch`` are ``ExactIndex``'s, unchanged: they scan EVERY row (or every row of
+    ``filter``) and are exact — the cells are not consulted and there is no ``nprobe`` argument.  A range search over the
+    probed cells only is not part of this build.
     """
 
     def __init__(self, dim: int, space: str = "cosine", nlist: Optional[int] = None, nprobe: Optional[int] = None,

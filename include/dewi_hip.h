@@ -266,6 +266,48 @@ int dewi_ivf_probe_prepare(int elem_type, int64_t n_rows, int dim, const void* d
                            int n_queries, int nprobe, int group, void* d_out, size_t out_bytes, int64_t* out_n_union,
                            int64_t* out_n_allowed, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Range search (additive to ABI 6): every row at least as similar to the query as a threshold, however many that is — steps
+ * 1-2 of the search above (query preparation, sim[i] for every scanned row, with exactly the arithmetic the one-query search
+ * of this shape uses for the row), then the test  sim[i] >= threshold  in fp32 instead of the cut of step 3: NO cut, no k.
+ * A NaN similarity (a zero-norm row of a cosine corpus) never passes; a row whose similarity EQUALS the threshold does.
+ * Every row that passes gets the blend of step 4 (adj = fp32(1-eta)*sim + fp32(eta)*dewi32[i], + fp32(pref)*ent32[i] if
+ * pref != 0; DEWI_SIM_RAW).  space = DEWI_SPACE_L2: the score is -||e - q||^2, so a radius r is threshold = -r^2.
+ *
+ * Two calls around ONE host synchronisation, because only the caller can size the output:
+ *   dewi_knn_range_count    scans and counts: d_counts[j] (DEVICE int64 [n_queries]) = rows of query j that pass
+ *   <the caller reads the counts, allocates T = sum of them and uploads lims[j] = counts[0] + .. + counts[j - 1]>
+ *   dewi_knn_range_collect  writes query j's rows to positions lims[j] .. lims[j + 1] of the three outputs
+ * Between the two nothing else may touch the workspace (the scores live there: 8 * n_queries * n_scan bytes, hence at most
+ * DEWI_RANGE_MAX_QUERIES queries per call; larger batches are the caller's loop).
+ *
+ * dewi_knn_range_workspace_bytes: n_scan = the rows a query scans: n_rows, or |A| under a filter.  0 for a bad shape
+ * (n_scan <= 0 or > 2^32 - 1, dim <= 0, unknown elem_type, n_queries outside [1, DEWI_RANGE_MAX_QUERIES]); needs no device.
+ * dewi_knn_range_count: d_E / elem_type (0 fp32, 1 bf16) / d_Q (raw fp32 queries) as the search.  d_filter: NULL, or a
+ * prepared filter of this corpus (dewi_filter_prepare; one list for every query) with n_allowed = |A| (ignored without a
+ * filter): fp32 corpora only, a bf16 corpus with a filter returns DEWI_ERR_UNSUPPORTED as the filtered search does;
+ * |A| = 0: DEWI_OK, all counts 0, nothing scanned.  d_thresholds: DEVICE fp32 [n_queries].  The row kernels run in their
+ * dense form (one key per scanned row), one or several queries per corpus pass as the search's small batches — never a matrix-core
+ * pass, so nothing is refused.  d_workspace: 16-byte aligned.  Bad arguments and a short workspace are reported before any
+ * device work.  Asynchronous on `stream`.
+ * dewi_knn_range_collect: the workspace dewi_knn_range_count left, with the same n_scan / n_queries / d_thresholds.  d_lims:
+ * DEVICE int64 [n_queries + 1]; capacity: elements each output holds.  Per row: d_out_rows (GLOBAL row, int64), d_out_sims
+ * (fp32) and d_out_scores (the blend).  Order inside a query: the order the rows were scanned in — ascending rows, except
+ * under a filter over rows that are not whole 16-byte units (fp32 dim % 4 != 0), where it is ascending inside each of the
+ * filter's residue buckets, bucket after bucket.  Deterministic: the same inputs give the same bytes.  Nothing is written at or
+ * beyond `capacity` or beyond lims[j + 1], whatever lims holds.  n_scan = 0 or capacity = 0: DEWI_OK, nothing written.
+ * Asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_RANGE_MAX_QUERIES 32
+size_t dewi_knn_range_workspace_bytes(int64_t n_scan, int dim, int elem_type, int n_queries);
+int dewi_knn_range_count(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_allowed,
+                         const float* d_Q, int n_queries, const float* d_thresholds, int space, int64_t* d_counts,
+                         void* d_workspace, size_t workspace_bytes, void* stream);
+int dewi_knn_range_collect(const void* d_workspace, size_t workspace_bytes, int64_t n_scan, int n_queries,
+                           const float* d_thresholds, const int64_t* d_lims, int64_t capacity, const float* d_dewi32,
+                           const float* d_ent32, double eta, double entropy_pref, int64_t* d_out_rows, float* d_out_sims,
+                           float* d_out_scores, void* stream);
+
 /* Step 1 of the bf16 search alone (backends.py:420-424 followed by the bf16 rounding of config C3): q / ||q||
  * in fp32 unless the norm is 0 (cosine), then round-to-nearest-even to bf16.  This is the kernel the batched
  * matrix-core path runs on its queries; exposed so that parity tests can check the normalisation on its own
