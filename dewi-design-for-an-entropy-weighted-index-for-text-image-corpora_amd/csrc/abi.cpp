@@ -1167,6 +1167,82 @@ int dewi_knn_range_collect(const void* d_workspace, size_t workspace_bytes, int6
   return e == hipSuccess ? DEWI_OK : hip_fail(e, "range collect launch");
 }
 
+// ---- range search through the bf16 shadow (additive to ABI 6) ---------------------------------------------------------
+// The layout (range_shadow.hip plan_range_shadow) depends on the shapes, seg_cap and the device's compute units; both calls
+// plan it again from the same arguments.
+// a seg_cap no device can take (one workgroup: 4 segments x 256 queries x 8 bytes x seg_cap >= 2^32): refused without a device
+constexpr int kRangeShadowNeverFits = 1 << 19;
+static bool range_shadow_shape_ok(int64_t n_rows, int dim, int space) {
+  return g_tuning.mfma != 0 && dewi::range_shadow_supported(n_rows, dim, space);
+}
+
+int dewi_knn_range_shadow_supported(int64_t n_rows, int dim, int space) { return range_shadow_shape_ok(n_rows, dim, space) ? 1 : 0; }
+
+size_t dewi_knn_range_shadow_workspace_bytes(int64_t n_rows, int dim, int space, int n_queries, int seg_cap) {
+  if (!range_shadow_shape_ok(n_rows, dim, space)) return 0;
+  if (n_queries <= 0 || n_queries > DEWI_RANGE_SHADOW_MAX_QUERIES || seg_cap <= 0) return 0;
+  if (seg_cap >= kRangeShadowNeverFits) return 0;
+  DeviceInfo dev;
+  if (ensure_device(dev)) return 0;
+  const dewi::RangeShadowLayout L = dewi::plan_range_shadow(n_rows, dim, n_queries, seg_cap, dev.cus);
+  return L.fits ? L.total : 0;
+}
+
+// the argument checks both calls share; *L is planned only when everything before the device is in order
+static int range_shadow_check(int64_t n_rows, int dim, int64_t first_row, int n_queries, int seg_cap, const void* d_workspace,
+                              size_t workspace_bytes, dewi::RangeShadowLayout* L) {
+  if (n_rows <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
+  if (!range_shadow_shape_ok(n_rows, dim, DEWI_SPACE_COSINE))
+    return fail(DEWI_ERR_UNSUPPORTED, "no shadow route for %lld x %d (cosine, dim %% 128 == 0 from 256 to 768, >= 32 rows)",
+                static_cast<long long>(n_rows), dim);
+  if (first_row < 0 || first_row >= n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "first_row %lld outside [0, %lld)", static_cast<long long>(first_row), static_cast<long long>(n_rows));
+  if (n_queries <= 0 || n_queries > DEWI_RANGE_SHADOW_MAX_QUERIES)
+    return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, %d]: split the batch", n_queries, DEWI_RANGE_SHADOW_MAX_QUERIES);
+  if (seg_cap <= 0 || seg_cap >= kRangeShadowNeverFits)
+    return fail(DEWI_ERR_INVALID_ARG, "seg_cap %d: a group's records must stay below 2^32 bytes", seg_cap);
+  if (!d_workspace) return fail(DEWI_ERR_WORKSPACE, "null workspace");
+  if (reinterpret_cast<uintptr_t>(d_workspace) % 16 != 0) return fail(DEWI_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+  if (workspace_bytes < 4096) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B is too small", workspace_bytes);
+  DeviceInfo dev;
+  const int rc = ensure_device(dev);
+  if (rc) return rc;
+  *L = dewi::plan_range_shadow(n_rows, dim, n_queries, seg_cap, dev.cus);
+  if (!L->fits) return fail(DEWI_ERR_INVALID_ARG, "seg_cap %d: a group's records must stay below 2^32 bytes", seg_cap);
+  if (workspace_bytes < L->total) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, L->total);
+  return DEWI_OK;
+}
+
+int dewi_knn_range_shadow_count(const float* d_E, const uint16_t* d_E_bf16, int64_t n_rows, int dim, int64_t first_row,
+                                const float* d_Q, int n_queries, const float* d_thresholds, int seg_cap, int64_t* d_counts,
+                                void* d_workspace, size_t workspace_bytes, void* stream_) {
+  if (!d_E || !d_E_bf16 || !d_Q || !d_thresholds || !d_counts)
+    return fail(DEWI_ERR_INVALID_ARG, "null matrix, shadow, query, threshold or count pointer");
+  dewi::RangeShadowLayout L;
+  const int rc = range_shadow_check(n_rows, dim, first_row, n_queries, seg_cap, d_workspace, workspace_bytes, &L);
+  if (rc) return rc;
+  const hipError_t e = dewi::launch_range_shadow_count(L, d_E, d_E_bf16, n_rows, dim, first_row, d_Q, n_queries, d_thresholds,
+                                                       d_counts, static_cast<char*>(d_workspace), static_cast<hipStream_t>(stream_));
+  return e == hipSuccess ? DEWI_OK : hip_fail(e, "range shadow count launch");
+}
+
+int dewi_knn_range_shadow_collect(const void* d_workspace, size_t workspace_bytes, int64_t n_rows, int dim, int64_t first_row,
+                                  int n_queries, int seg_cap, const int64_t* d_lims, int64_t capacity, const float* d_dewi32,
+                                  const float* d_ent32, double eta, double entropy_pref, int64_t* d_out_rows, float* d_out_sims,
+                                  float* d_out_scores, void* stream_) {
+  if (capacity < 0) return fail(DEWI_ERR_INVALID_ARG, "negative capacity");
+  if (!d_lims || !d_dewi32 || !d_ent32 || !d_out_rows || !d_out_sims || !d_out_scores)
+    return fail(DEWI_ERR_INVALID_ARG, "null lims, payload or output pointer");
+  dewi::RangeShadowLayout L;
+  const int rc = range_shadow_check(n_rows, dim, first_row, n_queries, seg_cap, d_workspace, workspace_bytes, &L);
+  if (rc) return rc;
+  if (capacity == 0) return DEWI_OK;
+  const hipError_t e = dewi::launch_range_shadow_collect(L, n_rows, first_row, n_queries, static_cast<const char*>(d_workspace), d_lims,
+                                                         capacity, make_rerank(eta, entropy_pref), d_dewi32, d_ent32, d_out_rows,
+                                                         d_out_sims, d_out_scores, static_cast<hipStream_t>(stream_));
+  return e == hipSuccess ? DEWI_OK : hip_fail(e, "range shadow collect launch");
+}
+
 size_t dewi_merge_workspace_bytes(int n_lists, int n_queries, int list_len, int n_candidates) {
   if (n_lists <= 0 || n_queries <= 0 || list_len <= 0 || n_candidates <= 0) return 0;
   if (static_cast<int64_t>(n_lists) * list_len <= dewi::kMaxSortCandidates) return 0;   // sorted in LDS

@@ -791,4 +791,50 @@ hipError_t launch_mfma_bf16(const MfmaLayout& m, const uint16_t* d_E, int64_t n_
   }
 }
 
+// The filter pass ALONE for one group of up to 256 queries whose thresholds the caller supplies (range search through the
+// shadow, range_shadow.hip): no sample, no threshold launch.  d_qb: the group's fragment-order image; d_thr[q] is read for
+// q < n_active; records [4 n_blocks][256][seg_cap], counts [256][4 n_blocks].
+template <int KS>
+static hipError_t run_filter_dim(const uint16_t* E, int64_t n_rows, const uint16_t* qb, const float* thr, int n_active,
+                                 float thr_bias, uint64_t* out, int seg_cap, uint32_t* cnt, int n_blocks, hipStream_t stream) {
+  constexpr int DIM = KS * 16;
+  const int lds_bytes = kTileBufs * kTileRows * DIM * 2;
+  static PerDeviceOnce attr_once;   // one per KS instantiation
+  const hipError_t ea = attr_once.run([] {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<KS, false>()),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  });
+  if (ea != hipSuccess) return ea;
+  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
+  const ScanKernel k_filter = scan_kernel<KS, false>();
+  timing_begin(stream);
+  hipLaunchKernelGGL(k_filter, dim3(n_blocks), dim3(kMfmaThreads), lds_bytes, stream, E, n_rows, qb, n_tiles,
+                     static_cast<int64_t>(1), thr, out, static_cast<int64_t>(seg_cap), cnt, n_active, thr_bias);
+  timing_end(stream);
+  return hipGetLastError();
+}
+
+hipError_t launch_mfma_bf16_filter(const uint16_t* d_E, int64_t n_rows, int dim, const uint16_t* d_qb, const float* d_thr,
+                                   int n_active, float thr_bias, uint64_t* d_out, int seg_cap, uint32_t* d_cnt, int n_blocks,
+                                   hipStream_t stream) {
+  if (n_rows <= 0 || n_blocks <= 0 || n_active <= 0 || n_active > kQueriesPerPass || seg_cap <= 0) return hipErrorInvalidValue;
+  switch (dim % 128 == 0 ? dim / 16 : 0) {
+    case 8: return run_filter_dim<8>(d_E, n_rows, d_qb, d_thr, n_active, thr_bias, d_out, seg_cap, d_cnt, n_blocks, stream);
+    case 16: return run_filter_dim<16>(d_E, n_rows, d_qb, d_thr, n_active, thr_bias, d_out, seg_cap, d_cnt, n_blocks, stream);
+    case 24: return run_filter_dim<24>(d_E, n_rows, d_qb, d_thr, n_active, thr_bias, d_out, seg_cap, d_cnt, n_blocks, stream);
+    case 32: return run_filter_dim<32>(d_E, n_rows, d_qb, d_thr, n_active, thr_bias, d_out, seg_cap, d_cnt, n_blocks, stream);
+    case 40: return run_filter_dim<40>(d_E, n_rows, d_qb, d_thr, n_active, thr_bias, d_out, seg_cap, d_cnt, n_blocks, stream);
+    case 48: return run_filter_dim<48>(d_E, n_rows, d_qb, d_thr, n_active, thr_bias, d_out, seg_cap, d_cnt, n_blocks, stream);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The fragment-order image of n_rows_out (a multiple of 256) cosine queries, as launch_mfma_bf16 prepares it.
+hipError_t launch_prepare_queries_bf16_frag(const float* d_Q, uint16_t* d_out, int n_queries, int n_rows_out, int dim,
+                                            hipStream_t stream) {
+  hipLaunchKernelGGL(prepare_queries_bf16, dim3(n_rows_out), dim3(kWave), 0, stream, d_Q, d_out, n_queries, dim,
+                     static_cast<int>(DEWI_SPACE_COSINE), static_cast<float*>(nullptr), 1);
+  return hipGetLastError();
+}
+
 }  // namespace dewi

@@ -240,6 +240,12 @@ hipError_t launch_mfma_bf16(const MfmaLayout& m, const uint16_t* d_E, int64_t n_
                             int n_queries, int n_candidates, int space, char* ws, int compute_units,
                             hipStream_t stream, float thr_bias = 0.f);
 float shadow_margin(int dim);
+// The filter pass alone, thresholds supplied by the caller (range_shadow.hip): one group of up to 256 queries.
+hipError_t launch_mfma_bf16_filter(const uint16_t* d_E, int64_t n_rows, int dim, const uint16_t* d_qb, const float* d_thr,
+                                   int n_active, float thr_bias, uint64_t* d_out, int seg_cap, uint32_t* d_cnt, int n_blocks,
+                                   hipStream_t stream);
+hipError_t launch_prepare_queries_bf16_frag(const float* d_Q, uint16_t* d_out, int n_queries, int n_rows_out, int dim,
+                                            hipStream_t stream);
 
 // ---- knn_mfma_f32.hip: batched (32 queries per corpus pass) fp32 path on the matrix cores
 constexpr int kMfmaF32MinQueries = 5;  // fp32 corpus: batches of at least this many queries take the matrix-core path
@@ -362,6 +368,28 @@ hipError_t launch_range_collect(const uint64_t* d_keys, int64_t n_scan, int n_qu
                                 const uint32_t* d_chunk_offsets, const int64_t* d_lims, int64_t capacity, const RerankParams& rp,
                                 const float* d_dewi32, const float* d_ent32, int64_t* d_out_rows, float* d_out_sims,
                                 float* d_out_scores, hipStream_t stream);
+
+// ---- range_shadow.hip: range search over an fp32 corpus through its bf16 shadow (256 queries per corpus pass)
+struct RangeShadowLayout {
+  int groups;     // passes of up to 256 queries
+  int q_pad;      // groups * 256
+  int n_blocks;   // workgroups of the pass over the WHOLE corpus (a call with first_row > 0 may launch fewer)
+  int n_seg;      // 4 * n_blocks survivor segments per query
+  int seg_cap;    // records per segment
+  bool fits;      // the group's record region stays inside the pass's 32-bit byte offsets
+  size_t qb_off, cnt_off, offs_off, pass_off, flags_off, cand_off, total;
+};
+bool range_shadow_supported(int64_t n_rows, int dim, int space);
+RangeShadowLayout plan_range_shadow(int64_t n_rows, int dim, int n_queries, int seg_cap, int compute_units);
+// d_counts[q] = rows of [first_row, n_rows) with similarity >= d_thresholds[q], or -1: a survivor segment of the query
+// overflowed (answer it on the dense route).  The workspace then holds what launch_range_shadow_collect reads.
+hipError_t launch_range_shadow_count(const RangeShadowLayout& L, const float* d_E, const uint16_t* d_E_bf16, int64_t n_rows, int dim,
+                                     int64_t first_row, const float* d_Q, int n_queries, const float* d_thresholds,
+                                     int64_t* d_counts, char* ws, hipStream_t stream);
+hipError_t launch_range_shadow_collect(const RangeShadowLayout& L, int64_t n_rows, int64_t first_row, int n_queries, const char* ws,
+                                       const int64_t* d_lims, int64_t capacity, const RerankParams& rp, const float* d_dewi32,
+                                       const float* d_ent32, int64_t* d_out_rows, float* d_out_sims, float* d_out_scores,
+                                       hipStream_t stream);
 
 // ---- ingest.hip ---------------------------------------------------------------------------
 hipError_t launch_normalize_rows(const float* d_src, float* d_dst, int64_t n_rows, int dim, hipStream_t stream);

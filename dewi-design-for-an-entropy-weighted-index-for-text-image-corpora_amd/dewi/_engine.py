@@ -98,6 +98,29 @@ class DeviceQueryFilters:
                 f"of {self.n_rows} rows each, union {self.n_union})")
 
 
+#: smallest range batch that goes through the bf16 shadow (DeviceCorpus.range_shadow_min_batch): the smallest MEASURED batch at
+#: which the shadow route wins at 1 M x 768 — 8 queries 0.40 ms against 1.27 ms dense (profiles/r08/range_shadow/); smaller
+#: batches have not been measured
+RANGE_SHADOW_MIN_BATCH = 8
+
+
+class _RangeBudget:
+    """``max_results`` of one range call across its chunks and routes: the rows so far, and the queries they belong to."""
+
+    def __init__(self, max_results, n_queries: int):
+        self.max_results = None if max_results is None else int(max_results)
+        self.n_queries = int(n_queries)
+        self.total = 0
+        self.done = 0
+
+    def add(self, rows: int, queries: int) -> None:
+        self.total += int(rows)
+        self.done += int(queries)
+        if self.max_results is not None and self.total > self.max_results:
+            raise ValueError(f"range search found more than max_results = {self.max_results} rows "
+                             f"({self.total} after {self.done} of {self.n_queries} queries): raise the threshold or max_results")
+
+
 class DeviceCorpus:
     """Embedding block + payload columns of one doc-id shard, resident on one GPU."""
 
@@ -123,6 +146,8 @@ class DeviceCorpus:
         self._q_dev = None
         self.shadow = None            # bf16 copy of an fp32 matrix (enable_bf16_shadow): pre-selection over half the bytes
         self.shadow_min_batch = 2     # smallest batch that goes through the shadow (enable_bf16_shadow(single_query=True): 1)
+        self.range_shadow_min_batch = RANGE_SHADOW_MIN_BATCH   # smallest range batch that goes through the shadow
+        self.range_shadow_seg_cap = 32                         # records per survivor segment of its pass (dewi_hip.h seg_cap)
         self._io: Dict[Tuple[int, int], tuple] = {}      # (batch, k) -> device + pinned result buffers of search()
         self._last_call = None        # (batch, k, cut, through the shadow, workspace) of the last search_device
         # The blocking search() stages queries and results through per-instance buffers (pinned query, device
@@ -536,6 +561,12 @@ class DeviceCorpus:
 
     def range_search_device(self, q_dev, thresholds, eta: float, entropy_pref: float, filter: Optional[DeviceFilter] = None,
                             max_results: Optional[int] = None, sort: bool = True):
+        """``range_search_routed`` with ``use_shadow=True``: the shadow route wherever it applies, the dense route elsewhere —
+        the same answer, bit for bit, either way."""
+        return self.range_search_routed(q_dev, thresholds, eta, entropy_pref, filter=filter, max_results=max_results, sort=sort)
+
+    def range_search_routed(self, q_dev, thresholds, eta: float, entropy_pref: float, filter: Optional[DeviceFilter] = None,
+                            max_results: Optional[int] = None, sort: bool = True, use_shadow: bool = True):
         """Every row at least as similar to the query as its threshold, however many that is: device tensors
         ``(lims int64 [B + 1], rows int64 [T], sims fp32 [T], scores fp32 [T])`` — query j's rows are
         ``rows[lims[j]:lims[j + 1]]`` (``id_offset`` added), ``sims`` their similarities, ``scores`` the adjusted scores.
@@ -549,9 +580,45 @@ class DeviceCorpus:
         ``max_results``: raise ``ValueError`` — before the rows of the offending chunk are collected — once the batch has
         more rows than that.
 
-        The batch runs in chunks of up to 32 queries: ``dewi_knn_range_count`` (dense row scan + count), ONE host
-        synchronisation to read the chunk's counts and size its outputs, ``dewi_knn_range_collect``.  The workspace
-        belongs to the chunk between its two calls: NOT thread-safe on one instance."""
+        Two routes with the same answer, bit for bit.  DENSE: chunks of up to 32 queries: ``dewi_knn_range_count`` (dense row
+        scan + count), ONE host synchronisation to read the chunk's counts and size its outputs, ``dewi_knn_range_collect``.
+        SHADOW (``use_shadow``, an fp32 corpus with ``enable_bf16_shadow``, no filter, a shape
+        ``dewi_knn_range_shadow_supported`` takes, at least ``range_shadow_min_batch`` queries): chunks of up to 2048 queries,
+        one pass over the bf16 copy per 256 of them, the same one synchronisation per chunk; a query whose survivor segment
+        overflowed is answered by the dense route and spliced back.  The workspace belongs to the chunk between its two
+        calls: NOT thread-safe on one instance."""
+        lims, rows, sims, scores, ascending = self._range_rows(q_dev, thresholds, eta, entropy_pref, filter, max_results, use_shadow)
+        torch = _torch()
+        dev = self.device
+        b = int(q_dev.shape[0])
+        if rows.shape[0] == 0:
+            return lims, rows, sims, scores
+        # plumbing from here on (torch): the order inside a query's segment
+        seg = None
+        if b > 1 and (sort or not ascending):  # the query of every result, as the high bits of a sort key
+            seg = torch.bucketize(torch.arange(rows.shape[0], dtype=torch.int64, device=dev), lims[1:], right=True)
+        if not ascending:
+            # a filter over rows that are not whole 16-byte units is scanned bucket by bucket, and the shadow route leaves
+            # the order of its survivor segments: ascending rows first
+            order = torch.argsort(rows if seg is None else seg * (1 << 32) + rows, stable=True)
+            rows, sims, scores = rows[order], sims[order], scores[order]
+        if sort:
+            # two stable sorts over ascending rows: by similarity, then by (query, adjusted score) — ties on the adjusted
+            # score keep the higher similarity first, ties on both the lower row
+            o1 = torch.sort(-_order_key(sims), stable=True).indices
+            key = (1 << 32) - _order_key(scores[o1])
+            o2 = torch.sort(key if seg is None else seg[o1] * (1 << 34) + key, stable=True).indices
+            order = o1[o2]
+            rows, sims, scores = rows[order], sims[order], scores[order]
+        if self.id_offset:
+            rows = rows + self.id_offset
+        return lims, rows, sims, scores
+
+    def _range_rows(self, q_dev, thresholds, eta: float, entropy_pref: float, filter, max_results, use_shadow: bool,
+                    first_row: int = 0):
+        """The two routes of ``range_search_device``: ``(lims, LOCAL rows, sims, scores, ascending)`` in query order;
+        ``ascending``: every query's rows already ascend.  ``first_row`` (the self-join): rows below it are not wanted — the
+        shadow route does not scan them, the dense route returns them all the same."""
         torch = _torch()
         if isinstance(filter, DeviceQueryFilters):
             raise NotImplementedError("range search takes one allow-list for the batch (per-query filters: not in this build)")
@@ -563,12 +630,40 @@ class DeviceCorpus:
         thr = self.stage_thresholds(thresholds, b)
         if filter is not None and self.is_bf16:
             raise NotImplementedError("filtered search serves fp32 corpora (bf16: not in this build)")
+        dev = self.device
+        through_shadow = (use_shadow and self.shadow is not None and filter is None and not self.is_bf16
+                          and b >= max(1, int(self.range_shadow_min_batch))
+                          and bool(self._lib.dewi_knn_range_shadow_supported(self.n_rows, self.dim, nat.SPACE_CODES[self.space])))
+        budget = _RangeBudget(max_results, b)
+        if through_shadow:
+            counts_h, parts = self._range_shadow(q_dev, thr, eta, entropy_pref, budget, int(first_row))
+            lims_c = None
+        else:
+            counts_h, parts, lims_c = self._range_dense(q_dev, thr, eta, entropy_pref, filter, budget)
+        if lims_c is not None and b <= nat.RANGE_MAX_QUERIES and parts:
+            lims = lims_c                      # one chunk: its running sum is the batch's
+        else:
+            lims_h = np.zeros(b + 1, dtype=np.int64)
+            np.cumsum(counts_h, out=lims_h[1:])
+            lims = torch.from_numpy(lims_h).to(dev)
+        if not parts:
+            return (lims, torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
+                    torch.empty(0, dtype=torch.float32, device=dev), True)
+        rows, sims, scores = parts[0] if len(parts) == 1 else tuple(torch.cat(x) for x in zip(*parts))
+        ascending = not through_shadow and not (filter is not None and self.dim % 4 != 0)
+        return lims, rows, sims, scores, ascending
+
+    def _range_dense(self, q_dev, thr, eta: float, entropy_pref: float, filter, budget: "_RangeBudget"):
+        """The dense route over all of ``q_dev``: ``(counts int64 [B] on the host, [(rows, sims, scores)] per chunk with
+        rows, the last chunk's device lims)``."""
+        torch = _torch()
+        b = int(q_dev.shape[0])
         n_scan = self.n_rows if filter is None else filter.n_allowed
         dev = self.device
         parts = []
         counts_h = np.zeros(b, dtype=np.int64)
         elem = 1 if self.is_bf16 else 0
-        total = 0
+        lims_c = None
         for q0 in range(0, b if n_scan > 0 else 0, nat.RANGE_MAX_QUERIES):
             nb = min(nat.RANGE_MAX_QUERIES, b - q0)
             wkey = ("range", nb, n_scan)
@@ -589,10 +684,7 @@ class DeviceCorpus:
             c_h = counts_d.cpu().numpy()                   # the chunk's one synchronisation
             counts_h[q0:q0 + nb] = c_h
             t_c = int(c_h.sum())
-            total += t_c
-            if max_results is not None and total > int(max_results):
-                raise ValueError(f"range search found more than max_results = {int(max_results)} rows "
-                                 f"({total} after {q0 + nb} of {b} queries): raise the threshold or max_results")
+            budget.add(t_c, nb)
             if t_c == 0:
                 continue
             lims_c = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
@@ -605,36 +697,129 @@ class DeviceCorpus:
                 nat.ptr(self.ent32), float(eta), float(entropy_pref), nat.ptr(rows), nat.ptr(sims), nat.ptr(scores),
                 nat.stream_ptr()))
             parts.append((rows, sims, scores))
-        if b <= nat.RANGE_MAX_QUERIES and parts:
-            lims = lims_c                      # one chunk: its running sum is the batch's
-        else:
-            lims_h = np.zeros(b + 1, dtype=np.int64)
-            np.cumsum(counts_h, out=lims_h[1:])
-            lims = torch.from_numpy(lims_h).to(dev)
-        if not parts:
-            return (lims, torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
+        return counts_h, parts, lims_c
+
+    def _range_shadow(self, q_dev, thr, eta: float, entropy_pref: float, budget: "_RangeBudget", first_row: int):
+        """The shadow route over all of ``q_dev`` (rows from ``first_row`` on): ``(counts int64 [B] on the host, [(rows, sims,
+        scores)] per chunk)``, every query's rows in the order of its survivor segments (a repaired query's: ascending)."""
+        torch = _torch()
+        b = int(q_dev.shape[0])
+        dev = self.device
+        seg_cap = int(self.range_shadow_seg_cap)
+        parts = []
+        counts_h = np.zeros(b, dtype=np.int64)
+        for q0 in range(0, b, nat.RANGE_SHADOW_MAX_QUERIES):
+            nb = min(nat.RANGE_SHADOW_MAX_QUERIES, b - q0)
+            wkey = ("range_shadow", nb, seg_cap)
+            ws = self._ws.get(wkey)
+            if ws is None:
+                need = int(self._lib.dewi_knn_range_shadow_workspace_bytes(self.n_rows, self.dim, nat.SPACE_CODES[self.space], nb,
+                                                                           seg_cap))
+                if need == 0:
+                    raise nat.NativeLibraryError(f"dewi_knn_range_shadow_workspace_bytes returned 0 for {self.n_rows} x "
+                                                 f"{self.dim}, seg_cap {seg_cap}")
+                if len(self._ws) > 8:
+                    self._ws.clear()
+                ws = self._ws[wkey] = torch.empty(need, dtype=torch.uint8, device=dev)
+            q_c, thr_c = q_dev[q0:q0 + nb], thr[q0:q0 + nb]
+            counts_d = torch.empty(nb, dtype=torch.int64, device=dev)
+            nat.check(self._lib.dewi_knn_range_shadow_count(
+                nat.ptr(self.emb), nat.ptr(self.shadow), self.n_rows, self.dim, first_row, nat.ptr(q_c), nb, nat.ptr(thr_c),
+                seg_cap, nat.ptr(counts_d), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+            c_h = counts_d.cpu().numpy()                   # the chunk's one synchronisation
+            flagged = np.flatnonzero(c_h < 0)
+            c_ok = np.where(c_h < 0, 0, c_h)
+            t_c = int(c_ok.sum())
+            budget.add(t_c, nb - int(flagged.size))     # (the flagged queries are counted by their dense repair)
+            lims_ok = np.zeros(nb + 1, dtype=np.int64)
+            np.cumsum(c_ok, out=lims_ok[1:])
+            rows = torch.empty(t_c, dtype=torch.int64, device=dev)
+            sims = torch.empty(t_c, dtype=torch.float32, device=dev)
+            scores = torch.empty(t_c, dtype=torch.float32, device=dev)
+            if t_c:
+                lims_c = torch.from_numpy(lims_ok).to(dev)
+                nat.check(self._lib.dewi_knn_range_shadow_collect(
+                    nat.ptr(ws), ws.numel(), self.n_rows, self.dim, first_row, nb, seg_cap, nat.ptr(lims_c), t_c,
+                    nat.ptr(self.dewi32), nat.ptr(self.ent32), float(eta), float(entropy_pref), nat.ptr(rows), nat.ptr(sims),
+                    nat.ptr(scores), nat.stream_ptr()))
+            if flagged.size:
+                # overflowed queries: the dense route, gathered into dense chunks of <= 32, spliced back into their places
+                idx = torch.from_numpy(flagged).to(dev)
+                d_counts, d_parts, _ = self._range_dense(q_c[idx].contiguous(), thr_c[idx].contiguous(), eta, entropy_pref, None,
+                                                         budget)
+                d_lims = np.zeros(flagged.size + 1, dtype=np.int64)
+                np.cumsum(d_counts, out=d_lims[1:])
+                c_fin = c_ok.copy()
+                c_fin[flagged] = d_counts
+                starts = lims_ok[:-1].copy()               # where each query's rows start in [shadow rows | dense rows]
+                starts[flagged] = t_c + d_lims[:-1]
+                out_lims = np.zeros(nb + 1, dtype=np.int64)
+                np.cumsum(c_fin, out=out_lims[1:])
+                gather = np.repeat(starts - out_lims[:-1], c_fin) + np.arange(int(out_lims[-1]), dtype=np.int64)
+                g = torch.from_numpy(gather).to(dev)
+                both = [torch.cat([x] + [p[i] for p in d_parts]) for i, x in enumerate((rows, sims, scores))]
+                rows, sims, scores = both[0][g], both[1][g], both[2][g]
+                c_ok = c_fin
+            counts_h[q0:q0 + nb] = c_ok
+            if rows.shape[0]:
+                parts.append((rows, sims, scores))
+        return counts_h, parts
+
+    # ------------------------------------------------------------------ near-duplicate self-join
+    def near_duplicates_device(self, threshold: float, chunk: int = 2048, max_pairs: Optional[int] = None,
+                               use_shadow: bool = True):
+        """Every pair of stored rows at least ``threshold`` similar: device tensors ``(a int64 [P], b int64 [P], sims fp32
+        [P])`` with ``a < b``, ordered by ``(a, b)`` (``id_offset`` added to both).
+
+        DEFINITION: the pair ``(a, b)``, ``a < b``, is reported iff row ``b`` is in ``range_search(E[a], threshold)`` — the
+        stored row ``a`` as the query — and ``sims`` is that directed similarity.  (Similarities are not bit-symmetric: the
+        query side is normalised once more, so the direction is part of the contract.)
+
+        The queries are slices of the stored matrix (no host copy), ``chunk`` rows (at most 2048) at a time; chunk ``[s, e)``
+        scans only the rows from ``s`` on, which makes the join the upper triangle.  With a bf16 shadow every chunk is one
+        ``range_search_routed`` batch on the shadow route; anything else (``use_shadow=False``, l2, bf16 corpora, other
+        widths) runs the same definition on the dense route, slowly.  ``max_pairs``: ``ValueError`` once there are more pairs
+        — before a chunk is collected when its counts alone prove it (they include each query's rows up to itself, at most
+        ``chunk * (chunk + 1) / 2`` per chunk), otherwise right after it."""
+        torch = _torch()
+        dev = self.device
+        n = self.n_rows
+        chunk = max(1, min(int(chunk), nat.RANGE_SHADOW_MAX_QUERIES))
+        thr = float(threshold)
+        out = []
+        pairs = 0
+        for s in range(0, n - 1, chunk):
+            e = min(n, s + chunk)
+            nb = e - s
+            q = self.emb[s:e] if not self.is_bf16 else self.emb[s:e].float()
+            room = None if max_pairs is None else int(max_pairs) - pairs + nb * (nb + 1) // 2
+            try:
+                lims, rows, sims, _, ascending = self._range_rows(q, thr, 0.0, 0.0, None, room, use_shadow, first_row=s)
+            except ValueError as err:
+                if max_pairs is not None and "max_results" in str(err):
+                    raise ValueError(f"near_duplicates found more than max_pairs = {int(max_pairs)} pairs (rows {s} to {e} of "
+                                     f"{n}): raise the threshold or max_pairs") from None
+                raise
+            if rows.shape[0] == 0:
+                continue
+            a = torch.bucketize(torch.arange(rows.shape[0], dtype=torch.int64, device=dev), lims[1:], right=True) + s
+            keep = rows > a
+            a, rows, sims = a[keep], rows[keep], sims[keep]
+            if not ascending:
+                order = torch.argsort(a * (1 << 32) + rows, stable=True)
+                a, rows, sims = a[order], rows[order], sims[order]
+            pairs += int(a.shape[0])
+            if max_pairs is not None and pairs > int(max_pairs):
+                raise ValueError(f"near_duplicates found more than max_pairs = {int(max_pairs)} pairs (rows {s} to {e} of {n}): "
+                                 f"raise the threshold or max_pairs")
+            out.append((a, rows, sims))
+        if not out:
+            return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
                     torch.empty(0, dtype=torch.float32, device=dev))
-        rows, sims, scores = parts[0] if len(parts) == 1 else tuple(torch.cat(x) for x in zip(*parts))
-        # plumbing from here on (torch): the order inside a query's segment
-        bucketed = filter is not None and self.dim % 4 != 0
-        seg = None
-        if b > 1 and (sort or bucketed):       # the query of every result, as the high bits of a sort key
-            seg = torch.bucketize(torch.arange(rows.shape[0], dtype=torch.int64, device=dev), lims[1:], right=True)
-        if bucketed:
-            # a filter over rows that are not whole 16-byte units is scanned bucket by bucket: ascending rows first
-            order = torch.argsort(rows if seg is None else seg * (1 << 32) + rows, stable=True)
-            rows, sims, scores = rows[order], sims[order], scores[order]
-        if sort:
-            # two stable sorts over ascending rows: by similarity, then by (query, adjusted score) — ties on the adjusted
-            # score keep the higher similarity first, ties on both the lower row
-            o1 = torch.sort(-_order_key(sims), stable=True).indices
-            key = (1 << 32) - _order_key(scores[o1])
-            o2 = torch.sort(key if seg is None else seg[o1] * (1 << 34) + key, stable=True).indices
-            order = o1[o2]
-            rows, sims, scores = rows[order], sims[order], scores[order]
+        a, rows, sims = out[0] if len(out) == 1 else tuple(torch.cat(x) for x in zip(*out))
         if self.id_offset:
-            rows = rows + self.id_offset
-        return lims, rows, sims, scores
+            a, rows = a + self.id_offset, rows + self.id_offset
+        return a, rows, sims
 
     def refused_by_last_call(self) -> np.ndarray:
         """Monitoring / tests: bool [B] — which queries of the LAST ``search_device`` call a matrix-core pass refused (and the

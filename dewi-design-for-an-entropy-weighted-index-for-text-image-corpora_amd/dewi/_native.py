@@ -34,6 +34,8 @@ NUM_SIGNALS = 7
 ABI_VERSION = 6
 #: most queries one dewi_knn_range_count call takes (include/dewi_hip.h DEWI_RANGE_MAX_QUERIES)
 RANGE_MAX_QUERIES = 32
+#: most queries one dewi_knn_range_shadow_count call takes (DEWI_RANGE_SHADOW_MAX_QUERIES: 8 groups of 256)
+RANGE_SHADOW_MAX_QUERIES = 2048
 
 #: every symbol include/dewi_hip.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -48,6 +50,8 @@ EXPORTED_SYMBOLS = (
     "dewi_ivf_buckets", "dewi_ivf_lists_bytes", "dewi_ivf_lists_build", "dewi_ivf_probe_group_bytes", "dewi_ivf_probe_bytes",
     "dewi_ivf_probe_prepare",
     "dewi_knn_range_workspace_bytes", "dewi_knn_range_count", "dewi_knn_range_collect",
+    "dewi_knn_range_shadow_supported", "dewi_knn_range_shadow_workspace_bytes", "dewi_knn_range_shadow_count",
+    "dewi_knn_range_shadow_collect",
 )
 
 
@@ -168,6 +172,14 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_knn_range_count.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, vp, i32, vp, vp, sz, vp]
     lib.dewi_knn_range_collect.restype = i32
     lib.dewi_knn_range_collect.argtypes = [vp, sz, i64, i32, vp, vp, i64, vp, vp, f64, f64, vp, vp, vp, vp]
+    lib.dewi_knn_range_shadow_supported.restype = i32
+    lib.dewi_knn_range_shadow_supported.argtypes = [i64, i32, i32]
+    lib.dewi_knn_range_shadow_workspace_bytes.restype = sz
+    lib.dewi_knn_range_shadow_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
+    lib.dewi_knn_range_shadow_count.restype = i32
+    lib.dewi_knn_range_shadow_count.argtypes = [vp, vp, i64, i32, i64, vp, i32, vp, i32, vp, vp, sz, vp]
+    lib.dewi_knn_range_shadow_collect.restype = i32
+    lib.dewi_knn_range_shadow_collect.argtypes = [vp, sz, i64, i32, i64, i32, i32, vp, i64, vp, vp, f64, f64, vp, vp, vp, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

@@ -608,6 +608,30 @@ class ExactIndex(BaseIndex):
                 max_results=max_results, sort=sort)
             return lims.cpu().numpy(), rows.cpu().numpy(), scores.cpu().numpy(), sims.cpu().numpy()
 
+    # ---------------------------------------------------------------- near-duplicate self-join (additive)
+    def near_duplicates(self, threshold: float, max_pairs: Optional[int] = None, doc_ids: bool = False):
+        """Every pair of documents at least ``threshold`` similar (additive; the reference has no such method): numpy
+        ``(a int64 [P], b int64 [P], sims fp32 [P])`` — rows ``a < b``, ordered by ``(a, b)`` — or, with ``doc_ids=True``,
+        ``(ids_a, ids_b, sims)`` with two lists of doc ids.
+
+        The pair ``(a, b)`` is reported iff document ``b`` is in ``range_search`` of document ``a``'s stored embedding at
+        this threshold, and ``sims`` is that similarity (``DeviceCorpus.near_duplicates_device``).  With ``batch_shadow`` the
+        join runs 2048 rows per call on the matrix cores; without it, it is one dense corpus pass per 4-8 rows.  An empty
+        index, or one document, has no pairs.  ``max_pairs``: ``ValueError`` instead of a larger result."""
+        if len(self._doc_ids) < 2:
+            a = b = np.zeros(0, np.int64)
+            sims = np.zeros(0, np.float32)
+        else:
+            self._ensure_built()
+            import torch
+            corpus = self._corpus
+            with corpus._lock, torch.cuda.device(corpus.device):
+                a, b, sims = (t.cpu().numpy() for t in corpus.near_duplicates_device(float(threshold), max_pairs=max_pairs))
+        if doc_ids:
+            ids = self._doc_ids
+            return [ids[i] for i in a.tolist()], [ids[i] for i in b.tolist()], sims
+        return a, b, sims
+
     def results_for(self, rows: np.ndarray, scores: np.ndarray) -> List[SearchResult]:
         """Row indices/scores of ``search_batch`` -> the reference's (doc_id, score, Payload) tuples."""
         ids, at_row = self._doc_ids, self._payloads.at_row

@@ -4,7 +4,7 @@ Same constructor, defaults and methods as the reference (index.py:22-166): it va
 the query, fills in the default ``eta`` / ``entropy_pref`` and delegates to a backend.  In
 this build every backend choice resolves to the HIP ``ExactIndex`` (ANN graph libraries
 are out of scope), with the reference's own warning when an ANN backend was asked for.
-Additions: ``add_batch``, ``search_batch``, ``range_search`` and ``range_search_batch``.
+Additions: ``add_batch``, ``search_batch``, ``range_search``, ``range_search_batch`` and ``near_duplicates``.
 """
 from __future__ import annotations
 
@@ -143,6 +143,14 @@ class DewiIndex(BaseIndex):
             self._built = True
         return [self._backend.results_for(rows[None, lims[j]:lims[j + 1]], scores[None, lims[j]:lims[j + 1]])[0]
                 for j in range(q.shape[0])]
+
+    def near_duplicates(self, threshold: float, max_pairs: Optional[int] = None, doc_ids: bool = False):
+        """Every pair of documents at least ``threshold`` similar (additive; ``ExactIndex.near_duplicates``): rows
+        ``(a, b, sims)`` with ``a < b``, or doc-id pairs.  Exact, whatever the backend probes for ``search``."""
+        out = self._backend.near_duplicates(threshold, max_pairs=max_pairs, doc_ids=doc_ids)
+        if len(self) > 1:
+            self._built = True
+        return out
 
     # ------------------------------------------------------------------ accessors (index.py:95-119)
     def __len__(self) -> int:

@@ -145,7 +145,7 @@ int dewi_knn_rerank_f32(const float* d_E, int64_t n_rows, int dim, const float* 
  * proven bound of the fp32 ones (bf16 rounding of unit vectors: 2^-8 plus accumulation), the candidate cut is widened by
  * that bound — and the candidates are re-scored from the fp32 rows with the row kernels' arithmetic, so ids and scores
  * equal dewi_knn_rerank_f32's one-query results bit for bit.  The bound assumes STORED rows of norm <= 1.0001 (what
- * dewi_normalize_rows_f32 leaves; the host layer checks it once).  Cosine, every dim % 32 == 0 from 160 to 1536 columns (ABI 5; ABI 4: 256 / 512 / 768 / 1024 / 1536), corpus >= 64 K rows;
+ * dewi_normalize_rows_f32 leaves; the host layer checks it once).  Cosine, every dim % 8 == 0 from 136 to 1536 columns (ABI 5; ABI 4: 256 / 512 / 768 / 1024 / 1536), corpus >= 64 K rows;
  * any other call (and d_E_bf16 == NULL) behaves exactly as dewi_knn_rerank_f32.  A query with more candidates inside
  * the error band than the sort holds is answered by the repair launches on the plain fp32 scan (ABI 5; ABI 4 returned
  * it refused, id -1).  (ABI 4.) */
@@ -307,6 +307,44 @@ int dewi_knn_range_collect(const void* d_workspace, size_t workspace_bytes, int6
                            const float* d_thresholds, const int64_t* d_lims, int64_t capacity, const float* d_dewi32,
                            const float* d_ent32, double eta, double entropy_pref, int64_t* d_out_rows, float* d_out_sims,
                            float* d_out_scores, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Range search through the bf16 SHADOW of an fp32 corpus (additive to ABI 6): the same answer as dewi_knn_range_count /
+ * dewi_knn_range_collect give without a filter — the same rows, and similarities and blends equal bit for bit — at one pass
+ * over the shadow (half the bytes) per 256 queries instead of one pass over the fp32 rows per 4-8.  The 256-query
+ * matrix-core pass of dewi_knn_rerank_f32_shadow filters against the CALLER's thresholds lowered by one error bound of its
+ * scores (the bound assumes stored rows of norm <= 1.0001, as there); every record it leaves is re-scored from its fp32 row
+ * with the one-query row kernel's arithmetic and tested again, sim >= threshold in fp32: NaN never passes, equality does.
+ *
+ * Shapes: cosine, dim % 128 == 0 from 256 to 768 columns, at least 32 rows and fewer than 2^31 (no other floor: nothing is
+ * sampled), matrix-core passes not switched off by dewi_tuning_set.  dewi_knn_range_shadow_supported: 1 / 0; needs no device.
+ * seg_cap: records the pass may leave per (workgroup, lane quarter, query) segment — 4 x workgroups segments per query, one
+ * workgroup per compute unit.  The pass addresses a group's records with 32-bit byte offsets: 4 * workgroups * 256 * seg_cap
+ * * 8 (plus the little a lane counts past a full segment) must stay below 2^32, or the entry points return
+ * DEWI_ERR_INVALID_ARG and the workspace function 0.
+ * dewi_knn_range_shadow_workspace_bytes: 0 for an unsupported shape or space, n_queries outside
+ * [1, DEWI_RANGE_SHADOW_MAX_QUERIES], seg_cap <= 0 or too large — all of that without a device; otherwise the size for the
+ * calling thread's device.
+ * dewi_knn_range_shadow_count: d_E fp32 [n_rows][dim], d_E_bf16 its shadow, d_Q raw fp32 queries, d_thresholds DEVICE fp32
+ * [n_queries].  first_row: only rows [first_row, n_rows) are scanned (the shadow pointer is advanced; rows below are not
+ * read).  d_counts[j] (DEVICE int64): the rows of query j that pass, or -1: one of the query's segments OVERFLOWED — the
+ * caller answers that query with dewi_knn_range_count.  Bad arguments and a short workspace are reported before any device work.
+ * dewi_knn_range_shadow_collect: the workspace the count call left, with the same n_rows / dim / first_row / n_queries /
+ * seg_cap.  d_lims DEVICE int64 [n_queries + 1] (a query counted -1 gets an empty segment and nothing is written for it);
+ * outputs as dewi_knn_range_collect: GLOBAL rows.  Order inside a query: segment order (NOT ascending rows).  No atomics:
+ * the same inputs give the same bytes.  Nothing is written at or beyond `capacity` or lims[j + 1].  capacity = 0: DEWI_OK.
+ * Both calls are asynchronous on `stream`; between them nothing else may touch the workspace.
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_RANGE_SHADOW_MAX_QUERIES 2048        /* 8 groups of 256 */
+int dewi_knn_range_shadow_supported(int64_t n_rows, int dim, int space);
+size_t dewi_knn_range_shadow_workspace_bytes(int64_t n_rows, int dim, int space, int n_queries, int seg_cap);
+int dewi_knn_range_shadow_count(const float* d_E, const uint16_t* d_E_bf16, int64_t n_rows, int dim, int64_t first_row,
+                                const float* d_Q, int n_queries, const float* d_thresholds, int seg_cap, int64_t* d_counts,
+                                void* d_workspace, size_t workspace_bytes, void* stream);
+int dewi_knn_range_shadow_collect(const void* d_workspace, size_t workspace_bytes, int64_t n_rows, int dim, int64_t first_row,
+                                  int n_queries, int seg_cap, const int64_t* d_lims, int64_t capacity, const float* d_dewi32,
+                                  const float* d_ent32, double eta, double entropy_pref, int64_t* d_out_rows, float* d_out_sims,
+                                  float* d_out_scores, void* stream);
 
 /* Step 1 of the bf16 search alone (backends.py:420-424 followed by the bf16 rounding of config C3): q / ||q||
  * in fp32 unless the norm is 0 (cosine), then round-to-nearest-even to bf16.  This is the kernel the batched
