@@ -123,3 +123,19 @@ for dim,n,b,k in [(768, 70_001, 256, 100), (768, 66_000, 40, 10), (512, 80_000, 
     Eb = orc.bf16_round(raw); d,e=soa(cols)
     Q = orc.synth_queries(b, dim, seed=b)[:32]; Qp = np.stack([orc.bf16_round(orc.prepare_query(q)) for q in Q])
     print(dim,n,b,k, parity.count_decisive(Eb,Qp,d,e,k,0.3,0.1,"cosine",gap=G,prepared=True,exact_gaps=False), "/", len(Q))
+print("== dense neighbourhoods (tests/corpora.py): fp32 / bf16 decisive among the queries the oracle checks; the GPU tests' floor is 0.75")
+import corpora  # noqa: E402
+def both(X, Q, seed, k, eta=0.3, pref=0.1):
+    d, e = soa(orc.synth_payload_columns(X.shape[0], seed=seed))
+    Eb = orc.bf16_round(X); Qp = np.stack([orc.bf16_round(orc.prepare_query(q)) for q in Q])
+    return (parity.count_decisive(X, Q, d, e, k, eta, pref, "cosine", exact_gaps=False),
+            parity.count_decisive(Eb, Qp, d, e, k, eta, pref, "cosine", gap=G, prepared=True, exact_gaps=False))
+for name, (n, dim, b, k, d_max) in corpora.PLANTED_CASES.items():
+    X, Q, D, rows = corpora.planted_runs(n, dim, b, seed=dim + b, d_max=d_max)
+    sel = corpora.oracle_queries(b)
+    print("planted", name, "k", k, both(X, Q[sel], dim + b, k), "/", sel.size)
+n, dim, nq, seed = corpora.EMBEDDING_CASE
+X, Q, _, _ = corpora.embedding_like(n, dim, seed, n_queries=nq)
+sel = corpora.oracle_queries(nq)
+for k, eta, pref in ((10, 0.3, 0.1), (10, 0.0, 0.0), (100, 0.3, 0.1), (100, 0.0, 0.0)):
+    print("embedding-like k", k, "eta", eta, "pref", pref, both(X, Q[sel], seed, k, eta, pref), "/", sel.size)
