@@ -338,3 +338,133 @@ def test_ivf_full_size():
     for j in range(32):
         want = exact._corpus.search(Q[j:j + 1], K, 0.3, 0.0, filter=exact._corpus.make_filter(_mask_of(ivf, cells[j])))
         assert _same((got_ids[j:j + 1], got_sc[j:j + 1]), want), j
+
+
+# ------------------------------------------------------------------------------------------------------- 10. > 1024 segments
+# nlist * G = 3000, 1200 and 8192 (cell, bucket) segments: the plan's scan takes 3, 2 and 8 rounds of 1024 (csrc/ivf.hip)
+MANY_CELLS = [(6000, 50, 1500, "cosine"), (6000, 129, 300, "l2"), (9000, 64, 2048, "cosine")]
+MANY_NPROBE = (4, 16, 64)
+_many_cells = {}
+
+
+def _many_cells_pair(n, dim, nlist, space):
+    """Built once per shape: -> (ivf, exact, queries)."""
+    key = (n, dim, nlist, space)
+    if key not in _many_cells:
+        _many_cells[key] = _pair(n, dim, space, seed=dim + 1, nlist=nlist, train_iters=4)[:3]
+    return _many_cells[key]
+
+
+def _probe_sizes(ivf, cells):
+    """|F_j| of every query (the probed cells of one query are distinct)."""
+    return ivf.cell_sizes[cells].sum(axis=1)
+
+
+@pytest.mark.parametrize("n,dim,nlist,space", MANY_CELLS)
+def test_more_than_1024_segments(n, dim, nlist, space):
+    ivf, exact, Q = _many_cells_pair(n, dim, nlist, space)
+    offsets, _, g = ivf.cell_lists()
+    assert nlist * g > 1024 and offsets.shape == (nlist * g + 1,) and offsets[-1] == n
+    for nprobe in MANY_NPROBE:
+        cells = ivf.probe(Q[:32], nprobe)
+        f = _probe_sizes(ivf, cells)
+        assert np.array_equal(f, [_mask_of(ivf, row).sum() for row in cells])
+        print(f"{n} x {dim}, nlist {nlist}, nprobe {nprobe}: |F_j| {f.min()} to {f.max()}, {int((f < 2 * K).sum())} short probes of 32")
+        assert f.min() > 0
+        kk = np.minimum(K, f)
+        want = [exact.search_batch(Q[j:j + 1], int(kk[j]), 0.4, 0.0, filter=_mask_of(ivf, cells[j])) for j in range(32)]
+        got = [ivf.search_batch(Q[j:j + 1], K, 0.4, 0.0, nprobe=nprobe) for j in range(4)]
+        where = list(range(4))
+        for b in (9, 32):
+            ids, sc = ivf.search_batch(Q[:b], K, 0.4, 0.0, nprobe=nprobe)
+            got += [(ids[j:j + 1], sc[j:j + 1]) for j in range(b)]
+            where += list(range(b))
+        for (ids, sc), j in zip(got, where):
+            assert ids.shape == (1, K) and np.all(ids[0, kk[j]:] == -1) and np.all(np.isnan(sc[0, kk[j]:])), (nprobe, j)
+            assert _same((ids[:, :kk[j]], sc[:, :kk[j]]), want[j]), (nprobe, j)
+    # the full probe is the unfiltered exact search
+    singles = [exact.search_batch(Q[j:j + 1], K, 0.4, 0.0) for j in range(32)]
+    assert _same(ivf.search_batch(Q[:1], K, 0.4, 0.0, nprobe=nlist), singles[0])
+    for b in (9, 32):
+        ids, sc = ivf.search_batch(Q[:b], K, 0.4, 0.0, nprobe=nlist)
+        for j in range(b):
+            assert _same((ids[j:j + 1], sc[j:j + 1]), singles[j]), (b, j)
+
+
+def test_more_than_1024_segments_mix_short_and_long_probes():
+    """The cases above take both ways through ``search_device``: some batch of 32 mixes probes below and above the cut of 2k
+    rows (the split), some batch is all long (the shared passes alone)."""
+    short = {}
+    for shape in MANY_CELLS:
+        ivf, _, Q = _many_cells_pair(*shape)
+        for nprobe in MANY_NPROBE:
+            short[shape + (nprobe,)] = int((_probe_sizes(ivf, ivf.probe(Q[:32], nprobe)) < 2 * K).sum())
+    assert any(0 < s < 32 for s in short.values()), short
+    assert any(s == 0 for s in short.values()), short
+
+
+# ------------------------------------------------------------------------------------------------------- 11. ties across segments
+def _reload_with_assignment(ivf, path, assign):
+    """Save, overwrite the saved assignment, load: ``load()`` takes the saved assignment as it is."""
+    from dewi.ivf import IVFIndex
+    ivf.save(path)
+    np.save(str(path / "ivf_assign.npy"), np.asarray(assign, dtype=np.int32))
+    return IVFIndex.load(path)
+
+
+@pytest.mark.parametrize("dim", [64, 50])
+def test_exact_ties_across_segments(dim, tmp_path):
+    """200 bit-identical copies of each of 100 vectors, scattered over 64 cells by a random assignment: a query's probe holds
+    about 50 copies of its vector in several segments of the list, all with one similarity, and the cut of c = 2k = 20 rows
+    falls inside them.  Ties on similarity go to the lower row (include/dewi_hip.h), wherever the row sits in the list."""
+    from dewi.backends import ExactIndex
+    from dewi.ivf import IVFIndex
+    n, n_base, nlist, nprobe = 20000, 100, 64, 16
+    r = np.random.RandomState(dim)
+    B = _unit(r.randn(n_base, dim))
+    X = B[np.arange(n) % n_base]
+    which = r.choice(n_base, 32, replace=False)
+    Q = _unit(B[which] + 0.05 * r.randn(32, dim))
+    cols = orc.synth_payload_columns(n, seed=dim)
+    ids = [f"doc_{i:07d}" for i in range(n)]
+    first = IVFIndex(dim, "cosine", nlist=nlist, train_iters=1)
+    first.add_batch_columns(ids, X, cols)
+    first.build()
+    assign = np.random.RandomState(0).randint(0, nlist, n).astype(np.int32)
+    ivf = _reload_with_assignment(first, tmp_path / "ivf", assign)
+    exact = ExactIndex(dim, "cosine")
+    exact.add_batch_columns(ids, X, cols)
+    exact.build()
+    E = exact._embeddings
+    assert np.array_equal(E[:n_base].view(np.uint32), E[n_base:2 * n_base].view(np.uint32))         # the stored copies are bit-equal
+
+    cells = ivf.probe(Q, nprobe)
+    assert np.array_equal(ivf.cell_of_row, assign)
+    lowest = []
+    for j in range(32):
+        copies = np.arange(which[j], n, n_base)
+        mine = copies[np.isin(assign[copies], cells[j])]                         # the copies of B[j] inside F_j, ascending
+        assert mine.size >= 2 * K + 1 and np.unique(assign[mine]).size >= 2, (j, mine.size)
+        lowest.append(mine[:2 * K])
+    want = [exact.search_batch(Q[j:j + 1], K, 0.4, 0.1, filter=_mask_of(ivf, cells[j])) for j in range(32)]
+    got = [ivf.search_batch(Q[j:j + 1], K, 0.4, 0.1, nprobe=nprobe) for j in range(32)]
+    for b in (9, 32):
+        ids_b, sc_b = ivf.search_batch(Q[:b], K, 0.4, 0.1, nprobe=nprobe)
+        got += [(ids_b[j:j + 1], sc_b[j:j + 1]) for j in range(b)]
+    for t, res in enumerate(got):
+        j = t if t < 32 else (t - 32 if t < 41 else t - 41)
+        assert _same(res, want[j]), (t, j)                                       # 1. the exact search on the mask of F_j
+        if dim == 64:
+            assert np.all(np.isin(res[0][0], lowest[j])), (t, j, res[0][0], lowest[j])   # 2. the cut took the 20 lowest copies
+    if dim == 64:
+        for j in range(32):
+            assert np.all(np.isin(want[j][0][0], lowest[j])), j
+
+
+def test_saved_assignment_outside_the_range_is_refused(tmp_path):
+    ivf, _, Q, _ = _pair(2000, D, seed=6, nlist=16, train_iters=1)
+    assign = ivf.cell_of_row.copy()
+    assign[[17, 1999]] = [-1, 16]
+    loaded = _reload_with_assignment(ivf, tmp_path / "ivf", assign)
+    with pytest.raises(ValueError, match=r"2 rows are assigned to cells outside \[0, 16\)"):
+        loaded.search_batch(Q[:2], K, 0.4, nprobe=2)
