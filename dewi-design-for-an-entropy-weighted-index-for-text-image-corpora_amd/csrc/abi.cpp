@@ -816,6 +816,33 @@ size_t dewi_knn_filtered_workspace_bytes(int64_t n_allowed, int dim, int n_queri
   return layout_knn(n_allowed, dim, 4, n_queries, c, dev.cus).total;
 }
 
+// the re-rank rule of the two filtered entry points: a similarity transform only together with a candidate count
+static int check_rerank_rule(int sim_transform, int n_candidates) {
+  if (sim_transform != DEWI_SIM_RAW && sim_transform != DEWI_SIM_ONE_MINUS_DIST && sim_transform != DEWI_SIM_INV_ONE_PLUS_DIST)
+    return fail(DEWI_ERR_INVALID_ARG, "unknown sim_transform %d", sim_transform);
+  if (sim_transform != DEWI_SIM_RAW && n_candidates <= 0)
+    return fail(DEWI_ERR_INVALID_ARG, "similarity transforms belong to the ANN re-rank rule: pass n_candidates as well");
+  return DEWI_OK;
+}
+
+// select + re-rank over the keys a filtered scan left in the workspace (local ids, no candidate records); `what` names the
+// launch in the error message
+static int select_filtered(const KnnLayout& L, char* ws, int n_queries, int c, int k, const dewi::RerankParams& rp,
+                           const float* d_dewi32, const float* d_ent32, int64_t* d_out_ids, float* d_out_scores, hipStream_t stream,
+                           const char* what) {
+  const uint64_t* keys = reinterpret_cast<const uint64_t*>(ws + L.keys_off);
+  hipError_t e;
+  if (c > dewi::kMaxSortCandidates) {
+    uint64_t* g1 = reinterpret_cast<uint64_t*>(ws + L.big_off);
+    e = dewi::launch_select_rerank_large(keys, L.plan.keys_per_query, n_queries, c, L.p2, k, rp, d_dewi32, d_ent32, 0, g1,
+                                         g1 + static_cast<size_t>(n_queries) * L.p2, d_out_ids, d_out_scores, nullptr, c, stream);
+  } else {
+    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, L.plan.slots == 1 ? L.plan.n_lists : 0, n_queries, c, k, rp,
+                                   d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr, nullptr, dewi::SegmentLayout{}, stream);
+  }
+  return e == hipSuccess ? DEWI_OK : hip_fail(e, what);
+}
+
 int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_allowed,
                              const float* d_Q, int n_queries, const float* d_dewi32, const float* d_ent32, int k, int n_candidates,
                              int sim_transform, double eta, double entropy_pref, int space, int64_t* d_out_ids,
@@ -828,10 +855,8 @@ int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int
   if (!d_filter) return fail(DEWI_ERR_INVALID_ARG, "null filter pointer");
   if (n_allowed < 0 || n_allowed > n_rows)
     return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
-  if (sim_transform != DEWI_SIM_RAW && sim_transform != DEWI_SIM_ONE_MINUS_DIST && sim_transform != DEWI_SIM_INV_ONE_PLUS_DIST)
-    return fail(DEWI_ERR_INVALID_ARG, "unknown sim_transform %d", sim_transform);
-  if (sim_transform != DEWI_SIM_RAW && n_candidates <= 0)
-    return fail(DEWI_ERR_INVALID_ARG, "similarity transforms belong to the ANN re-rank rule: pass n_candidates as well");
+  rc = check_rerank_rule(sim_transform, n_candidates);
+  if (rc) return rc;
   // the reference's rule on a score vector of length |A| (backends.py:439-441, 468): no candidates -> nothing; k > |A| -> error
   if (k <= 0 || n_allowed == 0) return DEWI_OK;
   if (k > n_allowed)
@@ -855,18 +880,8 @@ int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int
   char* ws = static_cast<char*>(d_workspace);
   rc = run_scan(L, d_E, 0, n_allowed, dim, d_Q, n_queries, c, space, ws, stream, static_cast<const uint32_t*>(d_filter));
   if (rc) return rc;
-  const dewi::RerankParams rp = make_rerank(eta, entropy_pref, sim_transform, space);
-  const uint64_t* keys = reinterpret_cast<const uint64_t*>(ws + L.keys_off);
-  hipError_t e;
-  if (c > dewi::kMaxSortCandidates) {
-    uint64_t* g1 = reinterpret_cast<uint64_t*>(ws + L.big_off);
-    e = dewi::launch_select_rerank_large(keys, L.plan.keys_per_query, n_queries, c, L.p2, k, rp, d_dewi32, d_ent32, 0, g1,
-                                         g1 + static_cast<size_t>(n_queries) * L.p2, d_out_ids, d_out_scores, nullptr, c, stream);
-  } else {
-    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, L.plan.slots == 1 ? L.plan.n_lists : 0, n_queries, c, k, rp,
-                                   d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr, nullptr, dewi::SegmentLayout{}, stream);
-  }
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "select launch (filtered)");
+  return select_filtered(L, ws, n_queries, c, k, make_rerank(eta, entropy_pref, sim_transform, space), d_dewi32, d_ent32, d_out_ids,
+                         d_out_scores, stream, "select launch (filtered)");
 }
 
 // ---- per-query filters (additive to ABI 6) ----------------------------------------------------------------------------
@@ -939,10 +954,8 @@ int dewi_knn_rerank_query_filtered(const void* d_E, int elem_type, int64_t n_row
   if (n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
   if (n_union < 0 || n_union > n_rows)
     return fail(DEWI_ERR_INVALID_ARG, "n_union %lld outside [0, %lld]", static_cast<long long>(n_union), static_cast<long long>(n_rows));
-  if (sim_transform != DEWI_SIM_RAW && sim_transform != DEWI_SIM_ONE_MINUS_DIST && sim_transform != DEWI_SIM_INV_ONE_PLUS_DIST)
-    return fail(DEWI_ERR_INVALID_ARG, "unknown sim_transform %d", sim_transform);
-  if (sim_transform != DEWI_SIM_RAW && n_candidates <= 0)
-    return fail(DEWI_ERR_INVALID_ARG, "similarity transforms belong to the ANN re-rank rule: pass n_candidates as well");
+  rc = check_rerank_rule(sim_transform, n_candidates);
+  if (rc) return rc;
   if (k <= 0) return DEWI_OK;
   if (n_candidates > 0 && n_candidates < k) return fail(DEWI_ERR_INVALID_ARG, "n_candidates %d must be at least k = %d", n_candidates, k);
   // one cut for the batch: c = 2k (or n_candidates), and every list at least that long — shorter lists are searched one by one
@@ -974,18 +987,8 @@ int dewi_knn_rerank_query_filtered(const void* d_E, int elem_type, int64_t n_row
   rc = run_scan(L, d_E, 0, n_union, dim, d_Q, n_queries, c, space, ws, stream, filt, filt + dewi::kFilterHeaderWords + n_rows,
                 n_union);
   if (rc) return rc;
-  const dewi::RerankParams rp = make_rerank(eta, entropy_pref, sim_transform, space);
-  const uint64_t* keys = reinterpret_cast<const uint64_t*>(ws + L.keys_off);
-  hipError_t e;
-  if (c > dewi::kMaxSortCandidates) {
-    uint64_t* g1 = reinterpret_cast<uint64_t*>(ws + L.big_off);
-    e = dewi::launch_select_rerank_large(keys, L.plan.keys_per_query, n_queries, c, L.p2, k, rp, d_dewi32, d_ent32, 0, g1,
-                                         g1 + static_cast<size_t>(n_queries) * L.p2, d_out_ids, d_out_scores, nullptr, c, stream);
-  } else {
-    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, L.plan.slots == 1 ? L.plan.n_lists : 0, n_queries, c, k, rp,
-                                   d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr, nullptr, dewi::SegmentLayout{}, stream);
-  }
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "select launch (query-filtered)");
+  return select_filtered(L, ws, n_queries, c, k, make_rerank(eta, entropy_pref, sim_transform, space), d_dewi32, d_ent32, d_out_ids,
+                         d_out_scores, stream, "select launch (query-filtered)");
 }
 
 // ---- IVF: cell lists and probe expansion (additive to ABI 6) -----------------------------------------------------------

@@ -71,11 +71,8 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
     }
   }
 
-  WaveList<DENSE ? 1 : S> lst[DENSE ? 1 : NQ];
-  if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) lst[qi].init(n_candidates, lane);
-  }
+  ScanLists<S, NQ> lst;
+  DEWI_INIT_LISTS(S, NQ, lst);
 
   const f32x4* Ev = reinterpret_cast<const f32x4*>(E);
   [[maybe_unused]] const uint32_t* __restrict__ list = filt + kFilterHeaderWords;
@@ -85,26 +82,11 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
     else return i;
   };
   // slot: where a dense key goes (the row; LIST: the list position)
-  auto consume = [&](const f32x4(&v)[U], int64_t row, int64_t slot) {
+  // QMASK: only the queries whose bit of qb (the row's query word: wave-uniform, a scalar branch) is set take the row
+  auto consume = [&](const f32x4(&v)[U], int64_t row, int64_t slot, [[maybe_unused]] uint32_t qb = 0u) {
 #pragma unroll
     for (int qi = 0; qi < NQ; ++qi) {
-      float acc = 0.f;
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc = accum4<SPACE>(v[u], qf[qi][u], acc);
-      float s = wave_sum_f32(acc);
-      if constexpr (SPACE == DEWI_SPACE_L2) s = -s;
-      if constexpr (DENSE) {
-        if (lane == 0) keys[qi * keys_per_query + slot] = make_key(s, static_cast<uint32_t>(row));
-      } else {
-        lst[qi].offer(s, static_cast<uint32_t>(row), lane);
-      }
-    }
-  };
-  // QMASK: the same for the queries whose bit of qb (the row's query word: wave-uniform, a scalar branch) is set
-  [[maybe_unused]] auto consume_q = [&](const f32x4(&v)[U], int64_t row, int64_t slot, uint32_t qb) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) {
-      if (((qb >> (qshift + qi)) & 1u) != 0u) {
+      if (!QMASK || ((qb >> (qshift + qi)) & 1u) != 0u) {
         float acc = 0.f;
 #pragma unroll
         for (int u = 0; u < U; ++u) acc = accum4<SPACE>(v[u], qf[qi][u], acc);
@@ -115,7 +97,7 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
         } else {
           lst[qi].offer(s, static_cast<uint32_t>(row), lane);
         }
-      } else if constexpr (DENSE) {
+      } else if constexpr (QMASK && DENSE) {
         if (lane == 0) keys[qi * keys_per_query + slot] = kKeyEmpty;
       }
     }
@@ -153,7 +135,7 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
         for (int u = 0; u < U; ++u) v[r][u] = load_x4<NT>(p + u * 64);
       }
 #pragma unroll
-      for (int r = 0; r < R; ++r) consume_q(v[r], rows[r], row0 + r, qbits[r]);
+      for (int r = 0; r < R; ++r) consume(v[r], rows[r], row0 + r, qbits[r]);
       slot = (slot + 1) & (kWave - 1);
     }
   } else if constexpr (LIST) {
@@ -201,20 +183,11 @@ __device__ __forceinline__ void scan_rows_f32_body(const float* __restrict__ E, 
     const f32x4* p = Ev + row_of(row) * D4 + lane;
 #pragma unroll
     for (int u = 0; u < U; ++u) v[u] = load_x4<NT>(p + u * 64);
-    if constexpr (QMASK) consume_q(v, row_of(row), row, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(qword[row]))));
+    if constexpr (QMASK) consume(v, row_of(row), row, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(qword[row]))));
     else consume(v, row_of(row), row);
   }
 
-  if constexpr (S == 1) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      block_merge_store(lst[qi], merge_buf, keys + qi * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates,
-                        n_candidates, lane, wave_in_block);
-  } else if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      lst[qi].store(keys + qi * keys_per_query + gwave * n_candidates, n_candidates, lane);
-  }
+  DEWI_STORE_LISTS(S, NQ, lst);
 }
 
 template <int U, int R, int NQ, int SPACE, int S, bool NT>
@@ -289,11 +262,8 @@ __global__ __launch_bounds__(kScanThreads) void scan_generic_f32(const float* __
   const int lg = lane % group;   // position inside the row group
   const int units = dim / VEC;
 
-  WaveList<DENSE ? 1 : S> lst[DENSE ? 1 : NQ];
-  if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) lst[qi].init(n_candidates, lane);
-  }
+  ScanLists<S, NQ> lst;
+  DEWI_INIT_LISTS(S, NQ, lst);
 
   const int64_t n_steps = (n_rows + rows_per_step - 1) / rows_per_step;
   for (int64_t st = gwave; st < n_steps; st += n_waves) {
@@ -341,16 +311,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_generic_f32(const float* __
       }
     }
   }
-  if constexpr (S == 1) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      block_merge_store(lst[qi], merge_buf, keys + qi * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates,
-                        n_candidates, lane, wave_in_block);
-  } else if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      lst[qi].store(keys + qi * keys_per_query + gwave * n_candidates, n_candidates, lane);
-  }
+  DEWI_STORE_LISTS(S, NQ, lst);
 }
 
 // Filtered scan: the same kernel over the list positions of a prepared filter (scan_common.hpp); the row comes from the
@@ -375,11 +336,8 @@ __global__ __launch_bounds__(kScanThreads) void scan_generic_f32_list(const floa
   const int64_t n_rows = filt[kFilterMaxBuckets];   // list positions (every bucket in order); the prepare step fills the
                                                     // offsets past the last bucket with the count
 
-  WaveList<DENSE ? 1 : S> lst[DENSE ? 1 : NQ];
-  if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) lst[qi].init(n_candidates, lane);
-  }
+  ScanLists<S, NQ> lst;
+  DEWI_INIT_LISTS(S, NQ, lst);
 
   const int64_t n_steps = (n_rows + rows_per_step - 1) / rows_per_step;
   for (int64_t st = gwave; st < n_steps; st += n_waves) {
@@ -427,16 +385,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_generic_f32_list(const floa
       }
     }
   }
-  if constexpr (S == 1) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      block_merge_store(lst[qi], merge_buf, keys + qi * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates,
-                        n_candidates, lane, wave_in_block);
-  } else if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      lst[qi].store(keys + qi * keys_per_query + gwave * n_candidates, n_candidates, lane);
-  }
+  DEWI_STORE_LISTS(S, NQ, lst);
 }
 
 // Per-query filtered scan (QMASK): the same over the union list `filt`; qword[p] holds list position p's query bits from bit
@@ -462,11 +411,8 @@ __global__ __launch_bounds__(kScanThreads) void scan_generic_f32_qmask(const flo
   const int64_t n_rows = filt[kFilterMaxBuckets];   // list positions (every bucket in order); the prepare step fills the
                                                     // offsets past the last bucket with the count
 
-  WaveList<DENSE ? 1 : S> lst[DENSE ? 1 : NQ];
-  if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) lst[qi].init(n_candidates, lane);
-  }
+  ScanLists<S, NQ> lst;
+  DEWI_INIT_LISTS(S, NQ, lst);
 
   const int64_t n_steps = (n_rows + rows_per_step - 1) / rows_per_step;
   for (int64_t st = gwave; st < n_steps; st += n_waves) {
@@ -521,16 +467,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_generic_f32_qmask(const flo
       }
     }
   }
-  if constexpr (S == 1) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      block_merge_store(lst[qi], merge_buf, keys + qi * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates,
-                        n_candidates, lane, wave_in_block);
-  } else if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      lst[qi].store(keys + qi * keys_per_query + gwave * n_candidates, n_candidates, lane);
-  }
+  DEWI_STORE_LISTS(S, NQ, lst);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -86,11 +86,8 @@ __device__ __forceinline__ void scan_rows_bf16_body(const uint16_t* __restrict__
     else return dot8<SPACE>(e, qf[qi][j], acc);
   };
 
-  WaveList<DENSE ? 1 : S> lst[DENSE ? 1 : NQ];
-  if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) lst[qi].init(n_candidates, lane);
-  }
+  ScanLists<S, NQ> lst;
+  DEWI_INIT_LISTS(S, NQ, lst);
 
   auto finish_row = [&](int qi, float acc, int64_t row) {
     float s = wave_sum_f32(acc);
@@ -161,16 +158,7 @@ __device__ __forceinline__ void scan_rows_bf16_body(const uint16_t* __restrict__
     consume_pair(v, 2 * n_pairs, false);
   }
 
-  if constexpr (S == 1) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      block_merge_store(lst[qi], merge_buf, keys + qi * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates,
-                        n_candidates, lane, wave_in_block);
-  } else if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      lst[qi].store(keys + qi * keys_per_query + gwave * n_candidates, n_candidates, lane);
-  }
+  DEWI_STORE_LISTS(S, NQ, lst);
 }
 
 template <int H, int NQ, int SPACE, int S, bool NT>
@@ -196,8 +184,8 @@ __global__ __launch_bounds__(kScanThreads) void scan_rows_bf16_flagged(const uin
 }
 
 // ---------------------------------------------------------------------------------------------
-// Generic path: any dim.  G lanes per row; queries arrive normalised and bf16-rounded as fp32.
-// VEC = 8 (16-byte loads) when dim % 8 == 0, else scalar.
+// Generic path: rows wider than 1024 units (since round 4 scan_any.hpp serves the rest).  G lanes per row; queries arrive
+// normalised and bf16-rounded as fp32.  VEC = 8 (16-byte loads) when dim % 8 == 0, else scalar.
 // ---------------------------------------------------------------------------------------------
 template <int VEC, int NQ, int SPACE, int S>
 __global__ __launch_bounds__(kScanThreads) void scan_generic_bf16(const uint16_t* __restrict__ E, int64_t n_rows, int dim,
@@ -214,11 +202,8 @@ __global__ __launch_bounds__(kScanThreads) void scan_generic_bf16(const uint16_t
   const int sub = lane / group, lg = lane % group;
   const int units = dim / VEC;
 
-  WaveList<DENSE ? 1 : S> lst[DENSE ? 1 : NQ];
-  if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) lst[qi].init(n_candidates, lane);
-  }
+  ScanLists<S, NQ> lst;
+  DEWI_INIT_LISTS(S, NQ, lst);
   const int64_t n_steps = (n_rows + rows_per_step - 1) / rows_per_step;
   for (int64_t st = gwave; st < n_steps; st += n_waves) {
     const int64_t row = st * rows_per_step + sub;
@@ -271,16 +256,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_generic_bf16(const uint16_t
       }
     }
   }
-  if constexpr (S == 1) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      block_merge_store(lst[qi], merge_buf, keys + qi * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates,
-                        n_candidates, lane, wave_in_block);
-  } else if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      lst[qi].store(keys + qi * keys_per_query + gwave * n_candidates, n_candidates, lane);
-  }
+  DEWI_STORE_LISTS(S, NQ, lst);
 }
 
 // ---------------------------------------------------------------------------------------------

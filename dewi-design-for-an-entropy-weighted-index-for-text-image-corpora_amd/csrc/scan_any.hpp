@@ -268,11 +268,8 @@ __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, 
     for (int u = 0; u < U; ++u) qf[qi][u].finish();
   }
 
-  WaveList<DENSE ? 1 : S> lst[DENSE ? 1 : NQ];
-  if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) lst[qi].init(n_candidates, lane);
-  }
+  ScanLists<S, NQ> lst;
+  DEWI_INIT_LISTS(S, NQ, lst);
 
   // i: index among this wave's rows (not PH: the row itself).  Consecutive rows of a wave are a whole number of units apart.
   // LIST: i is a position inside the wave's bucket, the row comes from the list (rows of a group are then anywhere).
@@ -350,16 +347,7 @@ __device__ __forceinline__ void scan_rows_any_body(const u32x4* __restrict__ E, 
     consume(v, row_of(i), slot_of(i), qbits_of(i));
   }
 
-  if constexpr (S == 1) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      block_merge_store(lst[qi], merge_buf, keys + qi * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates,
-                        n_candidates, lane, wave_in_block);
-  } else if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      lst[qi].store(keys + qi * keys_per_query + gwave * n_candidates, n_candidates, lane);
-  }
+  DEWI_STORE_LISTS(S, NQ, lst);
 }
 
 template <int ELEM, int U, int R, int NQ, int SPACE, int S, bool PH = false>
@@ -590,11 +578,8 @@ __device__ __forceinline__ void scan_short_rows_any_body(const u32x4* __restrict
     qf[qi].finish();
   }
 
-  WaveList<DENSE ? 1 : S> lst[DENSE ? 1 : NQ];
-  if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) lst[qi].init(n_candidates, lane);
-  }
+  ScanLists<S, NQ> lst;
+  DEWI_INIT_LISTS(S, NQ, lst);
 
   const int64_t rows_per_step = static_cast<int64_t>(rows_per_load) * R;
   if constexpr (LIST) {
@@ -685,16 +670,7 @@ __device__ __forceinline__ void scan_short_rows_any_body(const u32x4* __restrict
   }
   }
 
-  if constexpr (S == 1) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      block_merge_store(lst[qi], merge_buf, keys + qi * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates,
-                        n_candidates, lane, wave_in_block);
-  } else if constexpr (!DENSE) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi)
-      lst[qi].store(keys + qi * keys_per_query + gwave * n_candidates, n_candidates, lane);
-  }
+  DEWI_STORE_LISTS(S, NQ, lst);
 }
 
 template <int ELEM, int R, int NQ, int SPACE, int S, bool PH = false>

@@ -171,6 +171,34 @@ __device__ __forceinline__ void block_merge_store(const WaveList<1>& lst, MergeS
   }
 }
 
+// The lists of one pass of a row kernel: one per query of the pass with S key slots per lane (S = 0, dense keys: no list,
+// one placeholder).  DEWI_INIT_LISTS empties them; DEWI_STORE_LISTS writes them out at the end of the pass: S == 1 one sorted
+// list per workgroup, S > 1 one list per wave, dense nothing.  Both use the names every scan body gives its locals:
+// n_candidates, lane, wave_in_block, gwave, merge_buf, keys, keys_per_query.
+// (Macros, not functions: handed to an inlined function by reference, the lists change the instructions of the fast
+// kernels, which are kept identical to the parent's — profiles/r09/scan_bodies/README.md.)
+template <int S, int NQ>
+using ScanLists = WaveList<S == 0 ? 1 : S>[S == 0 ? 1 : NQ];
+
+#define DEWI_INIT_LISTS(S, NQ, lst)                                                                  \
+  {                                                                                                  \
+    if constexpr ((S) != 0) {                                                                        \
+      _Pragma("unroll") for (int qi_ = 0; qi_ < (NQ); ++qi_) lst[qi_].init(n_candidates, lane);      \
+    }                                                                                                \
+  }
+#define DEWI_STORE_LISTS(S, NQ, lst)                                                                                       \
+  {                                                                                                                        \
+    if constexpr ((S) == 1) {                                                                                              \
+      _Pragma("unroll") for (int qi_ = 0; qi_ < (NQ); ++qi_)                                                               \
+        block_merge_store(lst[qi_], merge_buf,                                                                             \
+                          keys + qi_ * keys_per_query + static_cast<int64_t>(blockIdx.x) * n_candidates, n_candidates, lane, \
+                          wave_in_block);                                                                                  \
+    } else if constexpr ((S) != 0) {                                                                                       \
+      _Pragma("unroll") for (int qi_ = 0; qi_ < (NQ); ++qi_)                                                               \
+        lst[qi_].store(keys + qi_ * keys_per_query + gwave * n_candidates, n_candidates, lane);                            \
+    }                                                                                                                      \
+  }
+
 // Repair launches: call f(q) for every query whose flag is set.  One vector load + one ballot per 64 queries (a loop of
 // scalar loads, one per query, cost a 256-query batch ~25 us of latency in every workgroup even with nothing to repair).
 template <class F>

@@ -33,12 +33,16 @@ def _setup(n, dim, seed):
 
 @pytest.mark.parametrize("dim,n", [(768, 4001), (768, 4000), (512, 3000), (256, 2501), (1024, 1501), (136, 2000),
                                    (100, 2000), (1280, 900), (8, 3000), (64, 3000), (200, 2000), (264, 2001), (384, 2001),
-                                   (1000, 1501), (3072, 800), (5120, 502), (8192, 301), (8200, 300)])
+                                   (1000, 1501), (3072, 800), (5120, 502), (8192, 301), (8200, 300), (8200, 701)])
 def test_bf16_search_vs_oracle(dim, n):
     """Pair-of-rows kernel (dim = 256*H, odd and even row counts); the any-width kernels (dim % 8 == 0: rows sharing a wave up
     to 256 columns, one row per step with a predicated tail up to 8192, two queries per pass beyond 4096); rows that are not whole
-    units (100: tests/test_hip_odd_rows.py has the sweep) and the 16-byte generic kernel beyond 8192 columns (8200)."""
+    units (100: tests/test_hip_odd_rows.py has the sweep) and the 16-byte generic kernel beyond 8192 columns (8200; with 701 rows every
+    wave takes several rows and k = 150 runs on dense keys.  701, not 700: the oracle alone leaves 5 / 5 / 5 / 4 of the 5 queries
+    decisive at the four k below; at 700 rows k = 100 has 3, which is the floor itself)."""
     cb, Eb, dewi32, ent32 = _setup(n, dim, seed=dim + n)
+    if dim > 8192:
+        assert cb.scan_kernel_name(1, 10).startswith("scan_generic"), cb.scan_kernel_name(1, 10)
     Q = orc.synth_queries(5, dim, seed=dim)
     Qp = device_prepared_queries(Q)
     for k, eta, pref in ((10, 0.3, 0.0), (1, 0.5, 0.0), (100, 0.25, 0.3), (150, 0.5, 0.0)):

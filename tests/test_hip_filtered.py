@@ -18,7 +18,7 @@ FAST_DIMS = [256, 768, 1536]
 ANY_DIMS = [384, 1000, 1280, 3072, 4096]
 SHORT_DIMS = [64, 100]
 ODD_DIMS = [5, 50, 129, 301, 1001, 3001]
-GENERIC_DIMS = [4101]
+GENERIC_DIMS = [4100, 4101]   # 1025 units per row: the generic kernel with 16-byte loads; 4101: with scalar loads
 ALL_DIMS = FAST_DIMS + ANY_DIMS + SHORT_DIMS + ODD_DIMS + GENERIC_DIMS
 
 
@@ -148,7 +148,7 @@ def test_filtered_equals_unfiltered_bits(dim):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. batch
-@pytest.mark.parametrize("dim", [100, 301, 768, 1000, 4101])
+@pytest.mark.parametrize("dim", [100, 301, 768, 1000, 4100, 4101])
 def test_filtered_batch_equals_singles(dim):
     n = 3001
     for space in ("cosine", "l2"):

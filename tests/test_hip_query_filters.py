@@ -17,7 +17,7 @@ FAST_DIMS = [256, 768, 1536]
 ANY_DIMS = [384, 1000, 3072]
 SHORT_DIMS = [64, 100]
 ODD_DIMS = [5, 50, 129, 301, 1001]
-GENERIC_DIMS = [4101]
+GENERIC_DIMS = [4100, 4101]   # 1025 units per row: the generic kernel with 16-byte loads; 4101: with scalar loads
 ALL_DIMS = FAST_DIMS + ANY_DIMS + SHORT_DIMS + ODD_DIMS + GENERIC_DIMS
 
 
@@ -99,7 +99,7 @@ def test_query_filters_equal_singles_bits(dim):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. oracle
-@pytest.mark.parametrize("dim", [100, 301, 768, 1000, 4101])
+@pytest.mark.parametrize("dim", [100, 301, 768, 1000, 4100, 4101])
 def test_query_filters_oracle_parity(dim):
     n = 2003 if dim <= 1600 else 1201
     k = 10
