@@ -29,6 +29,28 @@ int fail(int code, const char* fmt, ...) {
 int hip_fail(hipError_t e, const char* what) {
   return fail(DEWI_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
+// the tail of an entry point: the status of its last launch (`what` names it in the error message)
+int launched(hipError_t e, const char* what) { return e == hipSuccess ? DEWI_OK : hip_fail(e, what); }
+
+// ---- argument checks more than one entry point makes, each with the one message it has everywhere ----
+// the shape of an entry point that takes rows but no query batch (filters, IVF)
+int check_rows_dim(int64_t n_rows, int dim) {
+  if (n_rows <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
+  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  return DEWI_OK;
+}
+int check_elem_type(int elem_type) {
+  return elem_type == 0 || elem_type == 1 ? DEWI_OK : fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+}
+// entry points that serve fp32 corpora only; `feature`: "filtered search" / "IVF"
+int check_fp32_only(int elem_type, const char* feature) {
+  if (elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "%s serves fp32 corpora (bf16: not in this build)", feature);
+  return check_elem_type(elem_type);
+}
+int check_workspace(const void* d_ws, size_t ws_bytes, size_t need) {
+  if (!d_ws || ws_bytes < need) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
+  return DEWI_OK;
+}
 
 struct DeviceInfo {
   bool ready = false;
@@ -157,55 +179,85 @@ dewi::RerankParams make_rerank(double eta, double pref, int transform = DEWI_SIM
   return rp;
 }
 
+// What describes a query batch, filled once by the extern "C" function and read by every step of it: the matrix the row
+// kernels scan (`elem_type`: 0 fp32, 1 bf16), the caller's RAW queries, the space and the stream.
+struct Batch {
+  const void* d_E; int elem_type; int64_t n_rows; int dim;
+  const float* d_Q; int n_queries;
+  int space; hipStream_t stream;
+};
+
+// What a select step writes and what it blends.  k > 0: ids / scores of the re-ranked top k.  k == 0: n_candidates records
+// per query into d_out_cand (an overflowed query of a matrix-core path carries id -2 there, -1 in the id output).
+struct SelectOut {
+  int k; dewi::RerankParams rp;
+  const float* d_dewi32; const float* d_ent32; int64_t id_offset;
+  int64_t* d_out_ids; float* d_out_scores; dewi_candidate* d_out_cand;
+};
+
 // Steps 1-3 for every query: fills the keys region of the workspace.
 // d_filter (fp32 corpus only): scan the rows of that prepared filter instead (L planned on the filter's length).
 // d_qwords (with d_filter: the union of per-query lists): the query-word planes [ceil(n_queries / 32)][n_union] of a prepared
 // query-filter buffer — every pass takes its queries' bits (QMASK kernels).
-int run_scan(const KnnLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_Q,
-             int n_queries, int n_candidates, int space, char* ws, hipStream_t stream, const uint32_t* d_filter = nullptr,
+int run_scan(const KnnLayout& L, const Batch& B, int n_candidates, char* ws, const uint32_t* d_filter = nullptr,
              const uint32_t* d_qwords = nullptr, int64_t n_union = 0) {
   uint64_t* keys = reinterpret_cast<uint64_t*>(ws + L.keys_off);
   float* qn = reinterpret_cast<float*>(ws + L.qn_off);
   hipError_t e;
   if (!L.plan.raw_queries) {
-    e = dewi::launch_prepare_queries(d_Q, qn, n_queries, dim, space, elem_type ? 1 : 0, stream);
+    e = dewi::launch_prepare_queries(B.d_Q, qn, B.n_queries, B.dim, B.space, B.elem_type ? 1 : 0, B.stream);
     if (e != hipSuccess) return hip_fail(e, "prepare_queries");
   }
-  ScanTimer timer(stream);
+  ScanTimer timer(B.stream);
+  const float* q_prepared = L.plan.raw_queries ? nullptr : qn;
   int q = 0;
-  while (q < n_queries) {
+  while (q < B.n_queries) {
     // queries per corpus pass: 8 (fp32 row-per-wave kernel with one sorted list per workgroup), else 4, else 1
     static const bool nq8_enabled = [] { const char* e = getenv("DEWI_SCAN_NQ8"); return e == nullptr || atoi(e) != 0; }();
-    const bool can8 = !elem_type && L.plan.fast && L.plan.slots == 1 && nq8_enabled;
-    const int nq = (can8 && n_queries - q >= 8) ? 8 : ((L.plan.nq_max > 1 && n_queries - q >= L.plan.nq_max) ? L.plan.nq_max : 1);
+    const bool can8 = !B.elem_type && L.plan.fast && L.plan.slots == 1 && nq8_enabled;
+    const int left = B.n_queries - q;
+    const int nq = (can8 && left >= 8) ? 8 : ((L.plan.nq_max > 1 && left >= L.plan.nq_max) ? L.plan.nq_max : 1);
     if (d_filter) {
       dewi::QWords qw;
       if (d_qwords) {
         qw.words = d_qwords + static_cast<int64_t>(q / 32) * n_union;
         qw.shift = q % 32;
       }
-      e = dewi::launch_scan_f32_filtered(L.plan, static_cast<const float*>(d_E), dim, d_Q, L.plan.raw_queries ? nullptr : qn, q, nq,
-                                         n_candidates, space, keys, d_filter, stream, qw);
+      e = dewi::launch_scan_f32_filtered(L.plan, static_cast<const float*>(B.d_E), B.dim, B.d_Q, q_prepared, q, nq, n_candidates,
+                                         B.space, keys, d_filter, B.stream, qw);
+    } else if (B.elem_type) {
+      e = dewi::launch_scan_bf16(L.plan, static_cast<const uint16_t*>(B.d_E), B.n_rows, B.dim, B.d_Q, q_prepared, q, nq,
+                                 n_candidates, B.space, keys, B.stream);
+    } else {
+      e = dewi::launch_scan_f32(L.plan, static_cast<const float*>(B.d_E), B.n_rows, B.dim, B.d_Q, q_prepared, q, nq, n_candidates,
+                                B.space, keys, B.stream);
     }
-    else if (elem_type)
-      e = dewi::launch_scan_bf16(L.plan, static_cast<const uint16_t*>(d_E), n_rows, dim, d_Q, L.plan.raw_queries ? nullptr : qn,
-                                 q, nq, n_candidates, space, keys, stream);
-    else
-      e = dewi::launch_scan_f32(L.plan, static_cast<const float*>(d_E), n_rows, dim, d_Q, L.plan.raw_queries ? nullptr : qn, q,
-                                nq, n_candidates, space, keys, stream);
     if (e != hipSuccess) return hip_fail(e, "scan launch");
     q += nq;
   }
   return DEWI_OK;
 }
 
-int check_common(const void* d_E, int64_t n_rows, int dim, const float* d_Q, int n_queries, int space) {
-  if (!d_E || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "null embedding or query pointer");
-  if (n_rows <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_rows must be positive (got %lld)", static_cast<long long>(n_rows));
-  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
-  if (dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "dim must be positive (got %d)", dim);
-  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
-  if (space != DEWI_SPACE_COSINE && space != DEWI_SPACE_L2) return fail(DEWI_ERR_INVALID_ARG, "unknown space %d", space);
+int check_common(const Batch& B) {
+  if (!B.d_E || !B.d_Q) return fail(DEWI_ERR_INVALID_ARG, "null embedding or query pointer");
+  if (B.n_rows <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_rows must be positive (got %lld)", static_cast<long long>(B.n_rows));
+  if (B.n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(B.n_rows));
+  if (B.dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "dim must be positive (got %d)", B.dim);
+  if (B.n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", B.n_queries);
+  if (B.space != DEWI_SPACE_COSINE && B.space != DEWI_SPACE_L2) return fail(DEWI_ERR_INVALID_ARG, "unknown space %d", B.space);
+  return DEWI_OK;
+}
+
+// The similarity cut of a search over n rows: the reference's min(2k, n) (backends.py:439), or min(n_override, n) for
+// n_override > 0 (the ANN re-rank rule).
+int resolve_cut(int k, int64_t n, int n_override, int* c) {
+  int64_t c64 = (2ll * k < n) ? 2ll * k : n;
+  if (n_override > 0) {
+    if (n_override < k) return fail(DEWI_ERR_INVALID_ARG, "n_candidates %d must be at least k = %d", n_override, k);
+    c64 = n_override < n ? n_override : n;
+  }
+  if (c64 > (1ll << 30)) return fail(DEWI_ERR_UNSUPPORTED, "candidate count %lld exceeds 2^30", static_cast<long long>(c64));
+  *c = static_cast<int>(c64);
   return DEWI_OK;
 }
 
@@ -224,6 +276,7 @@ struct BatchPlan {
   KnnLayout rows;              // Rows: the batch itself; Depth / Big: the REPAIR of refused queries (same row kernels, keys from offset 0)
   dewi::MfmaF32Layout depth;
   dewi::MfmaLayout big;
+  bool shadow;                 // the pass pre-selects over the bf16 shadow of an fp32 corpus: the select re-scores from the rows (plan_shadow)
   size_t flags_off;            // Depth / Big: one u32 per query behind both layouts — raised by the select for a refused query
   size_t total;                // workspace bytes of the chosen path (+ its repair)
 };
@@ -233,15 +286,21 @@ struct BatchPlan {
 // too, behind the boundary: the select raises the query's flag instead of writing it off, and two fixed-shape launches on the
 // same stream — a row scan and a select that look at the flags and return at once when none is set — answer the flagged
 // queries exactly.  `corpus_elem_bytes` is the matrix the repair scans (the fp32 rows for a pre-selection over a bf16 shadow).
-void plan_repair(BatchPlan& P, size_t path_total, int64_t n_rows, int dim, int corpus_elem_bytes, int n_queries, int n_candidates,
+// false: this shape has no repair — its cut is beyond what the repair's select sorts, or its row kernel has no flagged form —
+// so the caller must not take a matrix-core pass (decided here, while planning: nothing has been launched yet).
+bool plan_repair(BatchPlan& P, size_t path_total, int64_t n_rows, int dim, int corpus_elem_bytes, int n_queries, int n_candidates,
                  int cus) {
+  if (n_candidates > dewi::kMaxSortCandidates) return false;
   P.rows = layout_knn(n_rows, dim, corpus_elem_bytes, n_queries, n_candidates, cus);
+  if (!dewi::scan_flagged_supported(P.rows.plan, corpus_elem_bytes)) return false;
   P.flags_off = align_up(path_total > P.rows.total ? path_total : P.rows.total, 256);
   P.total = P.flags_off + align_up(static_cast<size_t>(n_queries) * 4, 256);
+  return true;
 }
 
 BatchPlan plan_batch(int elem_type, int64_t n_rows, int dim, int n_queries, int n_candidates, int space, int cus) {
   BatchPlan P{};
+  const int elem_bytes = elem_type ? 2 : 4;
   P.c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
   // the matrix-core paths select exactly n_candidates rows: a shard with fewer rows stays on the row kernels (padding)
   // space l2 on the matrix cores is scored 2<e,q> - ||e||^2 - ||q||^2: absolute error ~ulp(||e||^2 + ||q||^2), where the
@@ -251,98 +310,88 @@ BatchPlan plan_batch(int elem_type, int64_t n_rows, int dim, int n_queries, int 
   // kernels' arithmetic: batch_select); over a bf16 corpus l2 batches take the exact row kernels unless the calling thread
   // opted in to the approximate form (dewi_tuning_set batched_mfma = 2).
   const bool mfma = g_tuning.mfma != 0 && P.c_local == n_candidates &&
-                    (space == DEWI_SPACE_COSINE || elem_type == 0 || g_tuning.mfma == 2) &&
-                    dewi::scan_flagged_supported(dewi::plan_scan(n_rows, dim, elem_type ? 2 : 4, n_candidates, cus, g_tuning),
-                                                 elem_type ? 2 : 4);
+                    (space == DEWI_SPACE_COSINE || elem_type == 0 || g_tuning.mfma == 2);
   const bool depth_ok = mfma && dewi::mfma_f32_path_supported(elem_type, n_rows, dim, n_queries, n_candidates, space);
   const bool big_ok = mfma && elem_type == 1 && dewi::mfma_path_supported(n_rows, dim, n_queries, n_candidates, space);
+  bool repairable = false;   // a pass is taken only together with its repair (plan_repair)
   if (depth_ok && (elem_type == 0 || n_queries <= 32 || !big_ok)) {
     P.path = BatchPath::Depth;
     P.depth = dewi::plan_mfma_f32(elem_type, n_rows, dim, n_queries, n_candidates, cus);
-    plan_repair(P, P.depth.total, n_rows, dim, elem_type ? 2 : 4, n_queries, n_candidates, cus);
+    repairable = plan_repair(P, P.depth.total, n_rows, dim, elem_bytes, n_queries, n_candidates, cus);
   } else if (big_ok) {
     P.path = BatchPath::Big;
     P.big = dewi::plan_mfma(n_rows, dim, n_queries, n_candidates, cus);
-    plan_repair(P, P.big.total, n_rows, dim, elem_type ? 2 : 4, n_queries, n_candidates, cus);
-  } else {
+    repairable = plan_repair(P, P.big.total, n_rows, dim, elem_bytes, n_queries, n_candidates, cus);
+  }
+  if (!repairable) {
     P.path = BatchPath::Rows;
-    P.rows = layout_knn(n_rows, dim, elem_type ? 2 : 4, n_queries, P.c_local, cus);
+    P.rows = layout_knn(n_rows, dim, elem_bytes, n_queries, P.c_local, cus);
     P.total = P.rows.total;
   }
   return P;
 }
 
-int batch_scan(const BatchPlan& P, const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_Q, int n_queries,
-               int n_candidates, int space, void* d_ws, size_t ws_bytes, int cus, hipStream_t stream) {
-  if (!d_ws || ws_bytes < P.total) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, P.total);
+int batch_scan(const BatchPlan& P, const Batch& B, int n_candidates, void* d_ws, size_t ws_bytes, int cus) {
+  if (int rc = check_workspace(d_ws, ws_bytes, P.total)) return rc;
   char* ws = static_cast<char*>(d_ws);
-  hipError_t e;
   switch (P.path) {
     case BatchPath::Depth:
-      e = dewi::launch_mfma_f32(P.depth, elem_type, d_E, n_rows, dim, d_Q, n_queries, n_candidates, space, ws, stream);
-      return e == hipSuccess ? DEWI_OK : hip_fail(e, "depth-split mfma scan launch");
+      return launched(dewi::launch_mfma_f32(P.depth, B.elem_type, B.d_E, B.n_rows, B.dim, B.d_Q, B.n_queries, n_candidates, B.space,
+                                            ws, B.stream),
+                      "depth-split mfma scan launch");
     case BatchPath::Big:   // the launcher brackets its filter pass for dewi_timing_read itself
-      e = dewi::launch_mfma_bf16(P.big, static_cast<const uint16_t*>(d_E), n_rows, dim, d_Q, n_queries, n_candidates, space, ws,
-                                 cus, stream);
-      return e == hipSuccess ? DEWI_OK : hip_fail(e, "mfma scan launch");
+      return launched(dewi::launch_mfma_bf16(P.big, static_cast<const uint16_t*>(B.d_E), B.n_rows, B.dim, B.d_Q, B.n_queries,
+                                             n_candidates, B.space, ws, cus, B.stream),
+                      "mfma scan launch");
     default:
-      return run_scan(P.rows, d_E, elem_type, n_rows, dim, d_Q, n_queries, P.c_local, space, ws, stream);
+      return run_scan(P.rows, B, P.c_local, ws);
   }
 }
 
-// k > 0: ids / scores of the re-ranked top k.  k == 0: n_candidates records per query into d_out_cand (an overflowed
-// query of a matrix-core path carries id -2 there, -1 in the id output).
-// d_E / elem_type / dim / space: the corpus the scan ran over — the exact-refine mode of l2 over an fp32 corpus re-scores
-// its candidates from the rows themselves.
-// The repair of a matrix-core batch (plan_repair): flagged queries once more on the exact row kernels over `d_E`
-// (`elem_type`: its element type), keys from offset 0 of the workspace — the pass's own regions are dead by now.
-int batch_repair(const BatchPlan& P, char* ws, const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_Q,
-                 int n_queries, int n_candidates, int space, int k, const dewi::RerankParams& rp, const float* d_dewi32,
-                 const float* d_ent32, int64_t id_offset, int64_t* d_out_ids, float* d_out_scores, dewi_candidate* d_out_cand,
-                 hipStream_t stream) {
+// The repair of a matrix-core batch (plan_repair): flagged queries once more on the exact row kernels over B.d_E, keys from
+// offset 0 of the workspace — the pass's own regions are dead by now.
+int batch_repair(const BatchPlan& P, char* ws, const Batch& B, const SelectOut& O, int n_candidates) {
   const KnnLayout& L = P.rows;
   uint32_t* flags = reinterpret_cast<uint32_t*>(ws + P.flags_off);
   uint64_t* keys = reinterpret_cast<uint64_t*>(ws + L.keys_off);
-  hipError_t e = elem_type ? dewi::launch_scan_flagged_bf16(L.plan, static_cast<const uint16_t*>(d_E), n_rows, dim, d_Q, n_queries,
-                                                            n_candidates, space, keys, flags, stream)
-                           : dewi::launch_scan_flagged_f32(L.plan, static_cast<const float*>(d_E), n_rows, dim, d_Q, n_queries,
-                                                           n_candidates, space, keys, flags, stream);
+  hipError_t e = B.elem_type ? dewi::launch_scan_flagged_bf16(L.plan, static_cast<const uint16_t*>(B.d_E), B.n_rows, B.dim, B.d_Q,
+                                                              B.n_queries, n_candidates, B.space, keys, flags, B.stream)
+                             : dewi::launch_scan_flagged_f32(L.plan, static_cast<const float*>(B.d_E), B.n_rows, B.dim, B.d_Q,
+                                                             B.n_queries, n_candidates, B.space, keys, flags, B.stream);
   if (e != hipSuccess) return hip_fail(e, "repair scan launch");
-  if (n_candidates > dewi::kMaxSortCandidates) return fail(DEWI_ERR_UNSUPPORTED, "repair beyond %d candidates", dewi::kMaxSortCandidates);
   const int sorted = L.plan.slots == 1 ? L.plan.n_lists : 0;
-  e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, sorted, n_queries, n_candidates, k, rp, d_dewi32, d_ent32, id_offset,
-                                 d_out_ids, d_out_scores, d_out_cand, nullptr, dewi::SegmentLayout{}, stream,
+  e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, sorted, B.n_queries, n_candidates, O.k, O.rp, O.d_dewi32, O.d_ent32,
+                                 O.id_offset, O.d_out_ids, O.d_out_scores, O.d_out_cand, nullptr, dewi::SegmentLayout{}, B.stream,
                                  dewi::RefineParams{nullptr, nullptr, nullptr, 0, 0.f, 0}, dewi::QueryFlags{flags, 2});
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "repair select launch");
+  return launched(e, "repair select launch");
 }
 
-// d_Q: the caller's RAW queries (the repair of a refused query scans for it again; exact-refine over a bf16 shadow
-// re-scores with them: `shadow`).
-int batch_select(const BatchPlan& P, void* d_ws, size_t ws_bytes, int n_queries, int n_candidates, int k,
-                 const dewi::RerankParams& rp, const float* d_dewi32, const float* d_ent32, int64_t id_offset,
-                 int64_t* d_out_ids, float* d_out_scores, dewi_candidate* d_out_cand, hipStream_t stream,
-                 const void* d_E, int elem_type, int64_t n_rows, int dim, int space, const float* d_Q, bool shadow = false) {
-  const float* d_Q_shadow = shadow ? d_Q : nullptr;
-  if (!d_ws || ws_bytes < P.total) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, P.total);
+// The select step of a batch whose scan (batch_scan, or the shadow entry's own pass) has filled the workspace.
+// B: the corpus the scan ran over and the caller's RAW queries — the exact-refine mode of l2 over an fp32 corpus re-scores
+// its candidates from the rows themselves, a pre-selection over a bf16 shadow (P.shadow) re-scores from the fp32 rows with
+// the raw queries, and the repair of a refused query scans for it again.
+int batch_select(const BatchPlan& P, const Batch& B, const SelectOut& O, int n_candidates, void* d_ws, size_t ws_bytes) {
+  if (int rc = check_workspace(d_ws, ws_bytes, P.total)) return rc;
   char* ws = static_cast<char*>(d_ws);
+  const int n_queries = B.n_queries, k = O.k;
   hipError_t e = hipSuccess;
   if (P.path == BatchPath::Rows && P.c_local > dewi::kMaxSortCandidates) {
     // k > 1024 (dense keys from the row kernels): the candidate arrays live in the workspace, not in LDS
     const KnnLayout& L = P.rows;
     uint64_t* g1 = reinterpret_cast<uint64_t*>(ws + L.big_off);
     e = dewi::launch_select_rerank_large(reinterpret_cast<const uint64_t*>(ws + L.keys_off), L.plan.keys_per_query, n_queries,
-                                         P.c_local, L.p2, k, rp, d_dewi32, d_ent32, id_offset, g1,
-                                         g1 + static_cast<size_t>(n_queries) * L.p2, d_out_ids, d_out_scores, d_out_cand,
-                                         n_candidates, stream);
-    return e == hipSuccess ? DEWI_OK : hip_fail(e, "select_rerank_large launch");
+                                         P.c_local, L.p2, k, O.rp, O.d_dewi32, O.d_ent32, O.id_offset, g1,
+                                         g1 + static_cast<size_t>(n_queries) * L.p2, O.d_out_ids, O.d_out_scores, O.d_out_cand,
+                                         n_candidates, B.stream);
+    return launched(e, "select_rerank_large launch");
   }
   if (P.path == BatchPath::Rows) {
     const KnnLayout& L = P.rows;
     const int sorted = (L.plan.slots == 1 && P.c_local == n_candidates) ? L.plan.n_lists : 0;
     e = dewi::launch_select_rerank(reinterpret_cast<const uint64_t*>(ws + L.keys_off), L.plan.keys_per_query, sorted, n_queries,
-                                   n_candidates, k, rp, d_dewi32, d_ent32, id_offset, d_out_ids, d_out_scores, d_out_cand,
-                                   nullptr, dewi::SegmentLayout{}, stream);
-    return e == hipSuccess ? DEWI_OK : hip_fail(e, "select launch");
+                                   n_candidates, k, O.rp, O.d_dewi32, O.d_ent32, O.id_offset, O.d_out_ids, O.d_out_scores,
+                                   O.d_out_cand, nullptr, dewi::SegmentLayout{}, B.stream);
+    return launched(e, "select launch");
   }
   // matrix-core paths: one select launch per query group (each group has its own survivor segments); up to 8192
   // survivors of a query (64 KiB) are staged in LDS
@@ -357,13 +406,12 @@ int batch_select(const BatchPlan& P, void* d_ws, size_t ws_bytes, int n_queries,
   // an fp32 corpus — its thresholds sit two error bounds lower, ~10 K survivors per query at k = 100)
   // DEWI_STAGE_KEYS (tests only): shrink the staging so that the over-capacity routes of the select kernel run on small inputs
   static const int stage_override = [] { const char* e = getenv("DEWI_STAGE_KEYS"); return e ? atoi(e) : 0; }();
-  const int stage_keys = stage_override > 0 ? stage_override : ((big && d_Q_shadow != nullptr) ? 12288 : 8192);
+  const int stage_keys = stage_override > 0 ? stage_override : ((big && P.shadow) ? 12288 : 8192);
   const dewi::SegmentLayout seg{n_seg, seg_cap, 1, static_cast<int64_t>(per) * seg_cap, big ? 1 : per, stage_keys, big ? n_seg : 1};
   // exact-refine modes: l2 on the depth-split pass over an fp32 corpus (queries and norms as the scan left them in the
-  // workspace), or the 256-query pass over the bf16 SHADOW of an fp32 corpus (d_Q_shadow = the caller's raw queries)
-  const bool refine_l2 = !big && space == DEWI_SPACE_L2 && elem_type == 0;
-  const bool refine_shadow = d_Q_shadow != nullptr;
-  if (!d_E || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "a matrix-core batch needs the corpus and the raw queries in its finish step (repair of refused queries)");
+  // workspace), or a pass over the bf16 SHADOW of an fp32 corpus (the caller's raw queries)
+  const bool refine_l2 = !big && B.space == DEWI_SPACE_L2 && B.elem_type == 0;
+  if (!B.d_E || !B.d_Q) return fail(DEWI_ERR_INVALID_ARG, "a matrix-core batch needs the corpus and the raw queries in its finish step (repair of refused queries)");
   uint32_t* flags = reinterpret_cast<uint32_t*>(ws + P.flags_off);
   for (int g = 0; g < groups && e == hipSuccess; ++g) {
     const int q0 = g * per;
@@ -372,54 +420,45 @@ int batch_select(const BatchPlan& P, void* d_ws, size_t ws_bytes, int n_queries,
     const uint32_t* counts = reinterpret_cast<const uint32_t*>(ws + cnt_off) + static_cast<int64_t>(g) * n_seg * per;
     dewi::RefineParams rf{nullptr, nullptr, nullptr, 0, 0.f, 0};
     if (refine_l2)   // the raw queries and their squared norms as the scan left them in the workspace
-      rf = dewi::RefineParams{static_cast<const float*>(d_E),
-                              reinterpret_cast<const float*>(ws + P.depth.qn_off) + static_cast<int64_t>(q0) * dim,
-                              reinterpret_cast<const float*>(ws + P.depth.qn2_off) + q0, dim, dewi::depth_l2_margin(dim),
+      rf = dewi::RefineParams{static_cast<const float*>(B.d_E),
+                              reinterpret_cast<const float*>(ws + P.depth.qn_off) + static_cast<int64_t>(q0) * B.dim,
+                              reinterpret_cast<const float*>(ws + P.depth.qn2_off) + q0, B.dim, dewi::depth_l2_margin(B.dim),
                               DEWI_SPACE_L2};
-    else if (refine_shadow)
-      rf = dewi::RefineParams{static_cast<const float*>(d_E), d_Q_shadow + static_cast<int64_t>(q0) * dim, nullptr, dim,
-                              dewi::shadow_margin(dim), DEWI_SPACE_COSINE};
-    e = dewi::launch_select_rerank(keys, 0, 0, nq, n_candidates, k, rp, d_dewi32, d_ent32, id_offset,
-                                   d_out_ids ? d_out_ids + static_cast<int64_t>(q0) * k : nullptr,
-                                   d_out_scores ? d_out_scores + static_cast<int64_t>(q0) * k : nullptr,
-                                   d_out_cand ? d_out_cand + static_cast<int64_t>(q0) * n_candidates : nullptr, counts, seg, stream,
-                                   rf, dewi::QueryFlags{flags + q0, 1});
+    else if (P.shadow)
+      rf = dewi::RefineParams{static_cast<const float*>(B.d_E), B.d_Q + static_cast<int64_t>(q0) * B.dim, nullptr, B.dim,
+                              dewi::shadow_margin(B.dim), DEWI_SPACE_COSINE};
+    e = dewi::launch_select_rerank(keys, 0, 0, nq, n_candidates, k, O.rp, O.d_dewi32, O.d_ent32, O.id_offset,
+                                   O.d_out_ids ? O.d_out_ids + static_cast<int64_t>(q0) * k : nullptr,
+                                   O.d_out_scores ? O.d_out_scores + static_cast<int64_t>(q0) * k : nullptr,
+                                   O.d_out_cand ? O.d_out_cand + static_cast<int64_t>(q0) * n_candidates : nullptr, counts, seg,
+                                   B.stream, rf, dewi::QueryFlags{flags + q0, 1});
   }
   if (e != hipSuccess) return hip_fail(e, "select launch");
-  return batch_repair(P, ws, d_E, elem_type, n_rows, dim, d_Q, n_queries, n_candidates, space, k, rp, d_dewi32, d_ent32, id_offset,
-                      d_out_ids, d_out_scores, d_out_cand, stream);
+  return batch_repair(P, ws, B, O, n_candidates);
 }
 
 // n_candidates_override <= 0: the reference's cut, min(2k, n_rows) (backends.py:439).
-int knn_rerank_impl(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_Q, int n_queries,
-                    const float* d_dewi32, const float* d_ent32, int k, double eta, double pref, int space,
-                    int64_t* d_out_ids, float* d_out_scores, void* d_ws, size_t ws_bytes, void* stream_,
-                    int n_candidates_override = 0, int transform = DEWI_SIM_RAW) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  int rc = check_common(d_E, n_rows, dim, d_Q, n_queries, space);
+int knn_rerank_impl(const Batch& B, const float* d_dewi32, const float* d_ent32, int k, double eta, double pref,
+                    int64_t* d_out_ids, float* d_out_scores, void* d_ws, size_t ws_bytes, int n_candidates_override = 0,
+                    int transform = DEWI_SIM_RAW) {
+  int rc = check_common(B);
   if (rc) return rc;
   if (k <= 0) return DEWI_OK;  // candidate_count <= 0 -> [] (reference backends.py:439-441)
-  if (k > n_rows)
-    return fail(DEWI_ERR_K_OUT_OF_BOUNDS, "kth(=%lld) out of bounds (%lld)", static_cast<long long>(n_rows - k),
-                static_cast<long long>(n_rows));
+  if (k > B.n_rows)
+    return fail(DEWI_ERR_K_OUT_OF_BOUNDS, "kth(=%lld) out of bounds (%lld)", static_cast<long long>(B.n_rows - k),
+                static_cast<long long>(B.n_rows));
   if (!d_dewi32 || !d_ent32 || !d_out_ids || !d_out_scores) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
-  int64_t c64 = (2ll * k < n_rows) ? 2ll * k : n_rows;
-  if (n_candidates_override > 0) {
-    if (n_candidates_override < k)
-      return fail(DEWI_ERR_INVALID_ARG, "n_candidates %d must be at least k = %d", n_candidates_override, k);
-    c64 = n_candidates_override < n_rows ? n_candidates_override : n_rows;
-  }
-  if (c64 > (1ll << 30)) return fail(DEWI_ERR_UNSUPPORTED, "candidate count %lld exceeds 2^30", static_cast<long long>(c64));
-  const int c = static_cast<int>(c64);
+  int c = 0;
+  rc = resolve_cut(k, B.n_rows, n_candidates_override, &c);
+  if (rc) return rc;
   DeviceInfo dev;
   rc = ensure_device(dev);
   if (rc) return rc;
-  const BatchPlan P = plan_batch(elem_type, n_rows, dim, n_queries, c, space, dev.cus);
-  rc = batch_scan(P, d_E, elem_type, n_rows, dim, d_Q, n_queries, c, space, d_ws, ws_bytes, dev.cus, stream);
+  const BatchPlan P = plan_batch(B.elem_type, B.n_rows, B.dim, B.n_queries, c, B.space, dev.cus);
+  rc = batch_scan(P, B, c, d_ws, ws_bytes, dev.cus);
   if (rc) return rc;
-  const dewi::RerankParams rp = make_rerank(eta, pref, transform, space);
-  return batch_select(P, d_ws, ws_bytes, n_queries, c, k, rp, d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr, stream, d_E,
-                      elem_type, n_rows, dim, space, d_Q);
+  const SelectOut O{k, make_rerank(eta, pref, transform, B.space), d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr};
+  return batch_select(P, B, O, c, d_ws, ws_bytes);
 }
 
 // Which route a search over an fp32 corpus WITH a bf16 shadow takes (dewi_knn_rerank_f32_shadow), from the shapes alone.
@@ -431,10 +470,14 @@ struct ShadowPlan {
   KnnLayout lists;    // Lists: that scan's layout
   BatchPlan P;        // the pass's layout (Big / Depth) and, for every mode but Plain, the repair + flags (plan_repair)
 };
+// (a mode is taken only together with its repair: a shape plan_repair refuses stays Plain — today none does: plan_shadow takes
+// Lists up to a cut of 32, Big up to 512 and Depth up to 256, all below kMaxSortCandidates, and every dim % 8 width from 136 to
+// 1536 has a flagged row kernel)
 
 ShadowPlan plan_shadow(bool have_shadow, int64_t n_rows, int dim, int n_queries, int k, int space, int cus) {
   ShadowPlan S{};
   S.mode = ShadowMode::Plain;
+  S.P.shadow = true;
   const int64_t c64 = (2ll * k < n_rows) ? 2ll * k : n_rows;
   S.c = static_cast<int>(c64 < (1ll << 30) ? c64 : (1ll << 30));
   // the shadow pre-selects only where a matrix-core pass runs over it and the one-query search of the same corpus takes the
@@ -461,24 +504,23 @@ ShadowPlan plan_shadow(bool have_shadow, int64_t n_rows, int dim, int n_queries,
   const int list_len = (n_queries == 1 && n_rows >= 64 * 1024) ? dewi::shadow_list_len(static_cast<int>(c64 < 64 ? c64 : 64)) : 0;
   if (list_len > 0) {
     S.lists = layout_knn(n_rows, dim, 2, 1, list_len, cus);
-    if (S.lists.plan.fast && S.lists.plan.slots == 1 && S.lists.plan.n_lists <= 4 * 64) {
+    if (S.lists.plan.fast && S.lists.plan.slots == 1 && S.lists.plan.n_lists <= 4 * 64 &&
+        plan_repair(S.P, S.lists.total, n_rows, dim, 4, 1, S.c, cus)) {   // the repair of a refused query: the plain fp32 scan
       S.mode = ShadowMode::Lists;
       S.list_len = list_len;
-      plan_repair(S.P, S.lists.total, n_rows, dim, 4, 1, S.c, cus);   // the repair of a refused query: the plain fp32 scan
       return S;
     }
   }
   S.P.c_local = S.c;
   if (use_big) {
-    S.mode = ShadowMode::Big;
     S.P.path = BatchPath::Big;
     S.P.big = dewi::plan_mfma(n_rows, dim, n_queries, S.c, cus, true);
-    plan_repair(S.P, S.P.big.total, n_rows, dim, 4, n_queries, S.c, cus);      // the repair scans the fp32 rows
+    if (plan_repair(S.P, S.P.big.total, n_rows, dim, 4, n_queries, S.c, cus)) S.mode = ShadowMode::Big;   // the repair scans the fp32 rows
   } else if (use_depth) {
-    S.mode = ShadowMode::Depth;    // 1..32 queries (and larger batches the 256-query pass does not take): passes of 32 over the shadow
+    // 1..32 queries (and larger batches the 256-query pass does not take): passes of 32 over the shadow
     S.P.path = BatchPath::Depth;
     S.P.depth = dewi::plan_mfma_f32(1, n_rows, dim, n_queries, S.c, cus, true);
-    plan_repair(S.P, S.P.depth.total, n_rows, dim, 4, n_queries, S.c, cus);
+    if (plan_repair(S.P, S.P.depth.total, n_rows, dim, 4, n_queries, S.c, cus)) S.mode = ShadowMode::Depth;
   }
   return S;
 }
@@ -504,24 +546,21 @@ int dewi_normalize_rows_f32(const float* d_src, float* d_dst, int64_t n_rows, in
   if (n_rows < 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
   if (n_rows == 0) return DEWI_OK;
   if (!d_src || !d_dst) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  hipError_t e = dewi::launch_normalize_rows(d_src, d_dst, n_rows, dim, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "normalize_rows launch");
+  return launched(dewi::launch_normalize_rows(d_src, d_dst, n_rows, dim, static_cast<hipStream_t>(stream)), "normalize_rows launch");
 }
 
 int dewi_row_cosine_f32(const float* d_a, const float* d_b, float* d_out, int64_t n_rows, int dim, void* stream) {
   if (n_rows < 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
   if (n_rows == 0) return DEWI_OK;
   if (!d_a || !d_b || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  hipError_t e = dewi::launch_row_cosine(d_a, d_b, d_out, n_rows, dim, 1e-8f, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "row_cosine launch");
+  return launched(dewi::launch_row_cosine(d_a, d_b, d_out, n_rows, dim, 1e-8f, static_cast<hipStream_t>(stream)), "row_cosine launch");
 }
 
 int dewi_convert_f32_to_bf16(const float* d_src, uint16_t* d_dst, int64_t n_elems, void* stream) {
   if (n_elems < 0) return fail(DEWI_ERR_INVALID_ARG, "negative element count");
   if (n_elems == 0) return DEWI_OK;
   if (!d_src || !d_dst) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  hipError_t e = dewi::launch_f32_to_bf16(d_src, d_dst, n_elems, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "f32_to_bf16 launch");
+  return launched(dewi::launch_f32_to_bf16(d_src, d_dst, n_elems, static_cast<hipStream_t>(stream)), "f32_to_bf16 launch");
 }
 
 int dewi_payload_soa_f64(const double* d_dewi, const double* d_ht_mean, const double* d_hi_mean, float* d_dewi32,
@@ -529,9 +568,8 @@ int dewi_payload_soa_f64(const double* d_dewi, const double* d_ht_mean, const do
   if (n_rows < 0) return fail(DEWI_ERR_INVALID_ARG, "negative row count");
   if (n_rows == 0) return DEWI_OK;
   if (!d_dewi || !d_ht_mean || !d_hi_mean || !d_dewi32 || !d_ent32) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  hipError_t e = dewi::launch_payload_soa(d_dewi, d_ht_mean, d_hi_mean, d_dewi32, d_ent32, n_rows,
-                                          static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "payload_soa launch");
+  return launched(dewi::launch_payload_soa(d_dewi, d_ht_mean, d_hi_mean, d_dewi32, d_ent32, n_rows, static_cast<hipStream_t>(stream)),
+                  "payload_soa launch");
 }
 
 size_t dewi_knn_workspace_bytes(int64_t n_rows, int dim, int n_queries, int n_candidates) {
@@ -605,41 +643,41 @@ int dewi_knn_rerank_f32(const float* d_E, int64_t n_rows, int dim, const float* 
                         const float* d_dewi32, const float* d_ent32, int k, double eta, double entropy_pref, int space,
                         int64_t* d_out_ids, float* d_out_scores, void* d_workspace, size_t workspace_bytes,
                         void* stream) {
-  return knn_rerank_impl(d_E, 0, n_rows, dim, d_Q, n_queries, d_dewi32, d_ent32, k, eta, entropy_pref, space,
-                         d_out_ids, d_out_scores, d_workspace, workspace_bytes, stream);
+  return knn_rerank_impl(Batch{d_E, 0, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream)}, d_dewi32, d_ent32, k,
+                         eta, entropy_pref, d_out_ids, d_out_scores, d_workspace, workspace_bytes);
 }
 
 int dewi_knn_rerank_f32_shadow(const float* d_E, const uint16_t* d_E_bf16, int64_t n_rows, int dim, const float* d_Q,
                                int n_queries, const float* d_dewi32, const float* d_ent32, int k, double eta,
                                double entropy_pref, int space, int64_t* d_out_ids, float* d_out_scores, void* d_workspace,
                                size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  int rc = check_common(d_E, n_rows, dim, d_Q, n_queries, space);
+  const Batch B{d_E, 0, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream_)};   // (the repair scans the fp32 rows)
+  int rc = check_common(B);
   if (rc) return rc;
   DeviceInfo dev;
   rc = ensure_device(dev);
   if (rc) return rc;
   const ShadowPlan S = plan_shadow(d_E_bf16 != nullptr, n_rows, dim, n_queries, k, space, dev.cus);
   if (S.mode == ShadowMode::Plain)
-    return knn_rerank_impl(d_E, 0, n_rows, dim, d_Q, n_queries, d_dewi32, d_ent32, k, eta, entropy_pref, space, d_out_ids,
-                           d_out_scores, d_workspace, workspace_bytes, stream_);
+    return knn_rerank_impl(B, d_dewi32, d_ent32, k, eta, entropy_pref, d_out_ids, d_out_scores, d_workspace, workspace_bytes);
   if (!d_dewi32 || !d_ent32 || !d_out_ids || !d_out_scores) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
   const BatchPlan& P = S.P;
-  if (!d_workspace || workspace_bytes < P.total) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, P.total);
+  rc = check_workspace(d_workspace, workspace_bytes, P.total);
+  if (rc) return rc;
   char* ws = static_cast<char*>(d_workspace);
-  const dewi::RerankParams rp = make_rerank(eta, entropy_pref, DEWI_SIM_RAW, space);
+  hipStream_t stream = B.stream;
+  const SelectOut O{k, make_rerank(eta, entropy_pref, DEWI_SIM_RAW, space), d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr};
   if (S.mode == ShadowMode::Lists) {
     const KnnLayout& L = S.lists;
-    rc = run_scan(L, d_E_bf16, 1, n_rows, dim, d_Q, 1, S.list_len, space, ws, stream);
+    rc = run_scan(L, Batch{d_E_bf16, 1, n_rows, dim, d_Q, 1, space, stream}, S.list_len, ws);
     if (rc) return rc;
     const dewi::RefineParams rf{d_E, d_Q, nullptr, dim, dewi::shadow_margin(dim), DEWI_SPACE_COSINE, S.list_len};
     const hipError_t e = dewi::launch_select_rerank(reinterpret_cast<const uint64_t*>(ws + L.keys_off), L.plan.keys_per_query,
-                                                    L.plan.n_lists, 1, S.c, k, rp, d_dewi32, d_ent32, 0, d_out_ids, d_out_scores,
+                                                    L.plan.n_lists, 1, S.c, k, O.rp, d_dewi32, d_ent32, 0, d_out_ids, d_out_scores,
                                                     nullptr, nullptr, dewi::SegmentLayout{}, stream, rf,
                                                     dewi::QueryFlags{reinterpret_cast<uint32_t*>(ws + P.flags_off), 1});
     if (e != hipSuccess) return hip_fail(e, "select launch (one query, bf16 shadow)");
-    return batch_repair(P, ws, d_E, 0, n_rows, dim, d_Q, 1, S.c, space, k, rp, d_dewi32, d_ent32, 0, d_out_ids, d_out_scores,
-                        nullptr, stream);
+    return batch_repair(P, ws, B, O, S.c);   // (Lists is planned for one query: B.n_queries == 1)
   }
   // scores from bf16(e), bf16(q) are within shadow_margin of the fp32 row kernels': the sample's c-th best minus the bound is
   // a lower bound of the exact c-th best, and a row may score that much lower here than exactly -> thresholds - 2 bounds
@@ -648,8 +686,7 @@ int dewi_knn_rerank_f32_shadow(const float* d_E, const uint16_t* d_E_bf16, int64
                      ? dewi::launch_mfma_bf16(P.big, d_E_bf16, n_rows, dim, d_Q, n_queries, S.c, space, ws, dev.cus, stream, bias)
                      : dewi::launch_mfma_f32(P.depth, 1, d_E_bf16, n_rows, dim, d_Q, n_queries, S.c, space, ws, stream, bias);
   if (e != hipSuccess) return hip_fail(e, "mfma scan launch (bf16 shadow)");
-  return batch_select(P, d_workspace, workspace_bytes, n_queries, S.c, k, rp, d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr,
-                      stream, d_E, 0, n_rows, dim, space, d_Q, true);
+  return batch_select(P, B, O, S.c, d_workspace, workspace_bytes);
 }
 
 int dewi_knn_refusal_flags(int elem_type, int through_shadow, int64_t n_rows, int dim, int n_queries, int k, int n_candidates,
@@ -682,21 +719,23 @@ int dewi_knn_rerank_candidates(const void* d_E, int elem_type, int64_t n_rows, i
   if (n_candidates <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_candidates must be positive (got %d)", n_candidates);
   if (sim_transform != DEWI_SIM_RAW && sim_transform != DEWI_SIM_ONE_MINUS_DIST && sim_transform != DEWI_SIM_INV_ONE_PLUS_DIST)
     return fail(DEWI_ERR_INVALID_ARG, "unknown sim_transform %d", sim_transform);
-  return knn_rerank_impl(d_E, elem_type, n_rows, dim, d_Q, n_queries, d_dewi32, d_ent32, k, eta, entropy_pref, space,
-                         d_out_ids, d_out_scores, d_workspace, workspace_bytes, stream, n_candidates, sim_transform);
+  return knn_rerank_impl(Batch{d_E, elem_type, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream)}, d_dewi32,
+                         d_ent32, k, eta, entropy_pref, d_out_ids, d_out_scores, d_workspace, workspace_bytes, n_candidates,
+                         sim_transform);
 }
 
 int dewi_prepare_queries_bf16(const float* d_Q, int n_queries, int dim, int space, uint16_t* d_out, void* stream) {
   if (!d_Q || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
   if (n_queries <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "non-positive size");
   if (space != DEWI_SPACE_COSINE && space != DEWI_SPACE_L2) return fail(DEWI_ERR_INVALID_ARG, "unknown space %d", space);
-  hipError_t e = dewi::launch_prepare_queries_bf16(d_Q, d_out, n_queries, n_queries, dim, space, nullptr, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "prepare_queries_bf16 launch");
+  return launched(dewi::launch_prepare_queries_bf16(d_Q, d_out, n_queries, n_queries, dim, space, nullptr, static_cast<hipStream_t>(stream)),
+                  "prepare_queries_bf16 launch");
 }
 
 int dewi_knn_scan(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_Q, int n_queries,
                   int n_candidates, int space, void* d_workspace, size_t workspace_bytes, void* stream_) {
-  int rc = check_common(d_E, n_rows, dim, d_Q, n_queries, space);
+  const Batch B{d_E, elem_type, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream_)};
+  int rc = check_common(B);
   if (rc) return rc;
   if (n_candidates <= 0) return DEWI_OK;
   if (n_candidates > (1 << 30)) return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds 2^30", n_candidates);
@@ -704,8 +743,7 @@ int dewi_knn_scan(const void* d_E, int elem_type, int64_t n_rows, int dim, const
   rc = ensure_device(dev);
   if (rc) return rc;
   const BatchPlan P = plan_batch(elem_type, n_rows, dim, n_queries, n_candidates, space, dev.cus);
-  return batch_scan(P, d_E, elem_type, n_rows, dim, d_Q, n_queries, n_candidates, space, d_workspace, workspace_bytes, dev.cus,
-                    static_cast<hipStream_t>(stream_));
+  return batch_scan(P, B, n_candidates, d_workspace, workspace_bytes, dev.cus);
 }
 
 int dewi_knn_finish(void* d_workspace, size_t workspace_bytes, const void* d_E, int elem_type, int64_t n_rows, int dim,
@@ -730,25 +768,25 @@ int dewi_knn_finish(void* d_workspace, size_t workspace_bytes, const void* d_E, 
   if (rc) return rc;
   // the same plan as dewi_knn_scan made (same shapes, same thread's tuning)
   const BatchPlan P = plan_batch(elem_type, n_rows, dim, n_queries, n_candidates, space, dev.cus);
-  return batch_select(P, d_workspace, workspace_bytes, n_queries, n_candidates, records ? 0 : k,
-                      make_rerank(records ? 0.0 : eta, records ? 0.0 : entropy_pref, DEWI_SIM_RAW, space), d_dewi32, d_ent32,
-                      id_offset, records ? nullptr : d_out_ids, records ? nullptr : d_out_scores, d_out_cand,
-                      static_cast<hipStream_t>(stream_), d_E, elem_type, n_rows, dim, space, d_Q);
+  const Batch B{d_E, elem_type, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream_)};
+  const SelectOut O{records ? 0 : k, make_rerank(records ? 0.0 : eta, records ? 0.0 : entropy_pref, DEWI_SIM_RAW, space), d_dewi32,
+                    d_ent32, id_offset, records ? nullptr : d_out_ids, records ? nullptr : d_out_scores, d_out_cand};
+  return batch_select(P, B, O, n_candidates, d_workspace, workspace_bytes);
 }
 
 int dewi_knn_rerank_bf16(const uint16_t* d_E, int64_t n_rows, int dim, const float* d_Q, int n_queries,
                          const float* d_dewi32, const float* d_ent32, int k, double eta, double entropy_pref, int space,
                          int64_t* d_out_ids, float* d_out_scores, void* d_workspace, size_t workspace_bytes,
                          void* stream) {
-  return knn_rerank_impl(d_E, 1, n_rows, dim, d_Q, n_queries, d_dewi32, d_ent32, k, eta, entropy_pref, space,
-                         d_out_ids, d_out_scores, d_workspace, workspace_bytes, stream);
+  return knn_rerank_impl(Batch{d_E, 1, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream)}, d_dewi32, d_ent32, k,
+                         eta, entropy_pref, d_out_ids, d_out_scores, d_workspace, workspace_bytes);
 }
 
 int dewi_knn_candidates(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_Q, int n_queries,
                         const float* d_dewi32, const float* d_ent32, int n_candidates, int space, int64_t id_offset,
                         dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  int rc = check_common(d_E, n_rows, dim, d_Q, n_queries, space);
+  const Batch B{d_E, elem_type, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream_)};
+  int rc = check_common(B);
   if (rc) return rc;
   if (n_candidates <= 0) return DEWI_OK;
   if (n_candidates > (1 << 30)) return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds 2^30", n_candidates);
@@ -762,10 +800,10 @@ int dewi_knn_candidates(const void* d_E, int elem_type, int64_t n_rows, int dim,
   // The select step writes n_candidates records per query; a shard with fewer rows than that selects every row and
   // pads the tail (id = -1, sim = -inf).
   const BatchPlan P = plan_batch(elem_type, n_rows, dim, n_queries, n_candidates, space, dev.cus);
-  rc = batch_scan(P, d_E, elem_type, n_rows, dim, d_Q, n_queries, n_candidates, space, d_workspace, workspace_bytes, dev.cus, stream);
+  rc = batch_scan(P, B, n_candidates, d_workspace, workspace_bytes, dev.cus);
   if (rc) return rc;
-  return batch_select(P, d_workspace, workspace_bytes, n_queries, n_candidates, 0, make_rerank(0.0, 0.0), d_dewi32, d_ent32,
-                      id_offset, nullptr, nullptr, d_out, stream, d_E, elem_type, n_rows, dim, space, d_Q);
+  return batch_select(P, B, SelectOut{0, make_rerank(0.0, 0.0), d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out}, n_candidates,
+                      d_workspace, workspace_bytes);
 }
 
 // ---- filtered search (ABI 6) ----------------------------------------------------------------------------------------
@@ -791,9 +829,8 @@ int dewi_filter_prepare(int elem_type, int64_t n_rows, int dim, const uint8_t* d
                         int64_t* out_n_allowed, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!d_mask || !d_filter || !out_n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  if (elem_type != 0 && elem_type != 1) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
-  if (n_rows <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
-  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (int rc = check_elem_type(elem_type)) return rc;
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
   const size_t need = dewi_filter_bytes(n_rows, dim, elem_type);
   if (filter_bytes < need) return fail(DEWI_ERR_WORKSPACE, "filter buffer %zu B < required %zu B", filter_bytes, need);
   uint32_t* filt = static_cast<uint32_t*>(d_filter);
@@ -825,33 +862,45 @@ static int check_rerank_rule(int sim_transform, int n_candidates) {
   return DEWI_OK;
 }
 
-// select + re-rank over the keys a filtered scan left in the workspace (local ids, no candidate records); `what` names the
-// launch in the error message
-static int select_filtered(const KnnLayout& L, char* ws, int n_queries, int c, int k, const dewi::RerankParams& rp,
-                           const float* d_dewi32, const float* d_ent32, int64_t* d_out_ids, float* d_out_scores, hipStream_t stream,
-                           const char* what) {
+// The two filtered searches from the device on: the row kernels of this dim planned on the n_scan listed rows (grid, lists or
+// dense keys, keys per query; no matrix-core pass), then select + re-rank over the keys they left in the workspace (local ids,
+// no candidate records).  d_qwords: see run_scan (n_scan doubles as its n_union: the stride of the query-word planes, read
+// only with d_qwords, so the one-filter caller's value is ignored).  `what` names the select launch in the error message.
+static int scan_select_filtered(const Batch& B, const SelectOut& O, int64_t n_scan, int c, const uint32_t* d_filter,
+                                const uint32_t* d_qwords, void* d_ws, size_t ws_bytes, const char* what) {
+  DeviceInfo dev;
+  int rc = ensure_device(dev);
+  if (rc) return rc;
+  const KnnLayout L = layout_knn(n_scan, B.dim, 4, B.n_queries, c, dev.cus);
+  rc = check_workspace(d_ws, ws_bytes, L.total);
+  if (rc) return rc;
+  char* ws = static_cast<char*>(d_ws);
+  rc = run_scan(L, B, c, ws, d_filter, d_qwords, n_scan);
+  if (rc) return rc;
   const uint64_t* keys = reinterpret_cast<const uint64_t*>(ws + L.keys_off);
   hipError_t e;
   if (c > dewi::kMaxSortCandidates) {
     uint64_t* g1 = reinterpret_cast<uint64_t*>(ws + L.big_off);
-    e = dewi::launch_select_rerank_large(keys, L.plan.keys_per_query, n_queries, c, L.p2, k, rp, d_dewi32, d_ent32, 0, g1,
-                                         g1 + static_cast<size_t>(n_queries) * L.p2, d_out_ids, d_out_scores, nullptr, c, stream);
+    e = dewi::launch_select_rerank_large(keys, L.plan.keys_per_query, B.n_queries, c, L.p2, O.k, O.rp, O.d_dewi32, O.d_ent32, 0, g1,
+                                         g1 + static_cast<size_t>(B.n_queries) * L.p2, O.d_out_ids, O.d_out_scores, nullptr, c,
+                                         B.stream);
   } else {
-    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, L.plan.slots == 1 ? L.plan.n_lists : 0, n_queries, c, k, rp,
-                                   d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr, nullptr, dewi::SegmentLayout{}, stream);
+    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, L.plan.slots == 1 ? L.plan.n_lists : 0, B.n_queries, c, O.k, O.rp,
+                                   O.d_dewi32, O.d_ent32, 0, O.d_out_ids, O.d_out_scores, nullptr, nullptr, dewi::SegmentLayout{},
+                                   B.stream);
   }
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, what);
+  return launched(e, what);
 }
 
 int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_allowed,
                              const float* d_Q, int n_queries, const float* d_dewi32, const float* d_ent32, int k, int n_candidates,
                              int sim_transform, double eta, double entropy_pref, int space, int64_t* d_out_ids,
                              float* d_out_scores, void* d_workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  int rc = check_common(d_E, n_rows, dim, d_Q, n_queries, space);
+  const Batch B{d_E, elem_type, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream_)};
+  int rc = check_common(B);
   if (rc) return rc;
-  if (elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "filtered search serves fp32 corpora (bf16: not in this build)");
-  if (elem_type != 0) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+  rc = check_fp32_only(elem_type, "filtered search");
+  if (rc) return rc;
   if (!d_filter) return fail(DEWI_ERR_INVALID_ARG, "null filter pointer");
   if (n_allowed < 0 || n_allowed > n_rows)
     return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
@@ -863,25 +912,12 @@ int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int
     return fail(DEWI_ERR_K_OUT_OF_BOUNDS, "kth(=%lld) out of bounds (%lld)", static_cast<long long>(n_allowed - k),
                 static_cast<long long>(n_allowed));
   if (!d_dewi32 || !d_ent32 || !d_out_ids || !d_out_scores) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
-  int64_t c64 = (2ll * k < n_allowed) ? 2ll * k : n_allowed;
-  if (n_candidates > 0) {
-    if (n_candidates < k) return fail(DEWI_ERR_INVALID_ARG, "n_candidates %d must be at least k = %d", n_candidates, k);
-    c64 = n_candidates < n_allowed ? n_candidates : n_allowed;
-  }
-  if (c64 > (1ll << 30)) return fail(DEWI_ERR_UNSUPPORTED, "candidate count %lld exceeds 2^30", static_cast<long long>(c64));
-  const int c = static_cast<int>(c64);
-  DeviceInfo dev;
-  rc = ensure_device(dev);
+  int c = 0;
+  rc = resolve_cut(k, n_allowed, n_candidates, &c);
   if (rc) return rc;
-  // the row kernels of this dim, planned on |A| rows (grid, lists or dense keys, keys per query); no matrix-core pass
-  const KnnLayout L = layout_knn(n_allowed, dim, 4, n_queries, c, dev.cus);
-  if (!d_workspace || workspace_bytes < L.total)
-    return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, L.total);
-  char* ws = static_cast<char*>(d_workspace);
-  rc = run_scan(L, d_E, 0, n_allowed, dim, d_Q, n_queries, c, space, ws, stream, static_cast<const uint32_t*>(d_filter));
-  if (rc) return rc;
-  return select_filtered(L, ws, n_queries, c, k, make_rerank(eta, entropy_pref, sim_transform, space), d_dewi32, d_ent32, d_out_ids,
-                         d_out_scores, stream, "select launch (filtered)");
+  const SelectOut O{k, make_rerank(eta, entropy_pref, sim_transform, space), d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr};
+  return scan_select_filtered(B, O, n_allowed, c, static_cast<const uint32_t*>(d_filter), nullptr, d_workspace, workspace_bytes,
+                              "select launch (filtered)");
 }
 
 // ---- per-query filters (additive to ABI 6) ----------------------------------------------------------------------------
@@ -912,9 +948,8 @@ int dewi_query_filter_prepare(int elem_type, int64_t n_rows, int dim, int n_quer
                               size_t filter_bytes, int64_t* out_n_union, int64_t* out_n_allowed, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!d_masks || !d_filter || !out_n_union || !out_n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  if (elem_type != 0 && elem_type != 1) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
-  if (n_rows <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
-  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (int rc = check_elem_type(elem_type)) return rc;
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
   if (n_queries <= 0 || n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
   const size_t need = dewi_query_filter_bytes(n_rows, dim, elem_type, n_queries);
   if (filter_bytes < need) return fail(DEWI_ERR_WORKSPACE, "query filter buffer %zu B < required %zu B", filter_bytes, need);
@@ -945,11 +980,11 @@ int dewi_knn_rerank_query_filtered(const void* d_E, int elem_type, int64_t n_row
                                    const float* d_ent32, int k, int n_candidates, int sim_transform, double eta,
                                    double entropy_pref, int space, int64_t* d_out_ids, float* d_out_scores, void* d_workspace,
                                    size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  int rc = check_common(d_E, n_rows, dim, d_Q, n_queries, space);
+  const Batch B{d_E, elem_type, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream_)};
+  int rc = check_common(B);
   if (rc) return rc;
-  if (elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "filtered search serves fp32 corpora (bf16: not in this build)");
-  if (elem_type != 0) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+  rc = check_fp32_only(elem_type, "filtered search");
+  if (rc) return rc;
   if (!d_filter || !n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null filter or count pointer");
   if (n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
   if (n_union < 0 || n_union > n_rows)
@@ -975,20 +1010,10 @@ int dewi_knn_rerank_query_filtered(const void* d_E, int elem_type, int64_t n_row
   if (!d_dewi32 || !d_ent32 || !d_out_ids || !d_out_scores) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
   if (c64 > (1ll << 30)) return fail(DEWI_ERR_UNSUPPORTED, "candidate count %lld exceeds 2^30", static_cast<long long>(c64));
   const int c = static_cast<int>(c64);
-  DeviceInfo dev;
-  rc = ensure_device(dev);
-  if (rc) return rc;
-  // the row kernels of this dim, planned on |U| rows; no matrix-core pass
-  const KnnLayout L = layout_knn(n_union, dim, 4, n_queries, c, dev.cus);
-  if (!d_workspace || workspace_bytes < L.total)
-    return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, L.total);
-  char* ws = static_cast<char*>(d_workspace);
-  const uint32_t* filt = static_cast<const uint32_t*>(d_filter);
-  rc = run_scan(L, d_E, 0, n_union, dim, d_Q, n_queries, c, space, ws, stream, filt, filt + dewi::kFilterHeaderWords + n_rows,
-                n_union);
-  if (rc) return rc;
-  return select_filtered(L, ws, n_queries, c, k, make_rerank(eta, entropy_pref, sim_transform, space), d_dewi32, d_ent32, d_out_ids,
-                         d_out_scores, stream, "select launch (query-filtered)");
+  const uint32_t* filt = static_cast<const uint32_t*>(d_filter);   // planned on |U| rows; the query words sit behind the union list
+  const SelectOut O{k, make_rerank(eta, entropy_pref, sim_transform, space), d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr};
+  return scan_select_filtered(B, O, n_union, c, filt, filt + dewi::kFilterHeaderWords + n_rows, d_workspace, workspace_bytes,
+                              "select launch (query-filtered)");
 }
 
 // ---- IVF: cell lists and probe expansion (additive to ABI 6) -----------------------------------------------------------
@@ -1010,17 +1035,15 @@ int dewi_ivf_lists_build(int elem_type, int64_t n_rows, int dim, int n_cells, co
                          size_t lists_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!d_assign || !d_lists) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  if (elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "IVF serves fp32 corpora (bf16: not in this build)");
-  if (elem_type != 0) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
-  if (n_rows <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
-  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (int rc = check_fp32_only(elem_type, "IVF")) return rc;
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
   if (n_cells <= 0 || n_cells > dewi::kIvfMaxCells || n_cells > n_rows)
     return fail(DEWI_ERR_INVALID_ARG, "n_cells %d outside [1, min(%d, n_rows)]", n_cells, dewi::kIvfMaxCells);
   const size_t need = dewi_ivf_lists_bytes(n_rows, dim, elem_type, n_cells);
   if (lists_bytes < need) return fail(DEWI_ERR_WORKSPACE, "cell-list buffer %zu B < required %zu B", lists_bytes, need);
-  hipError_t e = dewi::launch_ivf_lists_build(d_assign, n_rows, n_cells, filter_buckets(dim, elem_type),
-                                              static_cast<uint32_t*>(d_lists), stream);
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "ivf_lists_build launch");
+  return launched(dewi::launch_ivf_lists_build(d_assign, n_rows, n_cells, filter_buckets(dim, elem_type), static_cast<uint32_t*>(d_lists),
+                                               stream),
+                  "ivf_lists_build launch");
 }
 
 static size_t ivf_group_words(int64_t n_rows, int n_buckets, int group) {
@@ -1058,10 +1081,8 @@ int dewi_ivf_probe_prepare(int elem_type, int64_t n_rows, int dim, const void* d
                            int64_t* out_n_allowed, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!d_lists || !d_probe_ids || !d_out || !out_n_union || !out_n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  if (elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "IVF serves fp32 corpora (bf16: not in this build)");
-  if (elem_type != 0) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
-  if (n_rows <= 0 || dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape %lld x %d", static_cast<long long>(n_rows), dim);
-  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (int rc = check_fp32_only(elem_type, "IVF")) return rc;
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
   if (n_cells <= 0 || n_cells > dewi::kIvfMaxCells || n_cells > n_rows)
     return fail(DEWI_ERR_INVALID_ARG, "n_cells %d outside [1, min(%d, n_rows)]", n_cells, dewi::kIvfMaxCells);
   if (n_queries <= 0 || n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
@@ -1112,23 +1133,26 @@ size_t dewi_knn_range_workspace_bytes(int64_t n_scan, int dim, int elem_type, in
 int dewi_knn_range_count(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_allowed,
                          const float* d_Q, int n_queries, const float* d_thresholds, int space, int64_t* d_counts,
                          void* d_workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  int rc = check_common(d_E, n_rows, dim, d_Q, n_queries, space);
+  const Batch B{d_E, elem_type, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream_)};
+  hipStream_t stream = B.stream;
+  int rc = check_common(B);
   if (rc) return rc;
-  if (elem_type != 0 && elem_type != 1) return fail(DEWI_ERR_INVALID_ARG, "unknown elem_type %d", elem_type);
+  rc = check_elem_type(elem_type);
+  if (rc) return rc;
   if (n_queries > DEWI_RANGE_MAX_QUERIES)
     return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, %d]: split the batch", n_queries, DEWI_RANGE_MAX_QUERIES);
   if (!d_thresholds || !d_counts) return fail(DEWI_ERR_INVALID_ARG, "null threshold or count pointer");
-  if (d_filter && elem_type == 1) return fail(DEWI_ERR_UNSUPPORTED, "filtered search serves fp32 corpora (bf16: not in this build)");
+  if (d_filter && (rc = check_fp32_only(elem_type, "filtered search"))) return rc;
   if (d_filter && (n_allowed < 0 || n_allowed > n_rows))
     return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
   const int64_t n_scan = d_filter ? n_allowed : n_rows;
   if (n_scan == 0) {   // an empty allow-list: every query's answer is empty
     const hipError_t e = hipMemsetAsync(d_counts, 0, sizeof(int64_t) * static_cast<size_t>(n_queries), stream);
-    return e == hipSuccess ? DEWI_OK : hip_fail(e, "hipMemsetAsync (range counts)");
+    return launched(e, "hipMemsetAsync (range counts)");
   }
   const RangeLayout R = range_layout(n_scan, dim, n_queries);
-  if (!d_workspace || workspace_bytes < R.total) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, R.total);
+  rc = check_workspace(d_workspace, workspace_bytes, R.total);
+  if (rc) return rc;
   if (reinterpret_cast<uintptr_t>(d_workspace) % 16 != 0) return fail(DEWI_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
   DeviceInfo dev;
   rc = ensure_device(dev);
@@ -1139,12 +1163,11 @@ int dewi_knn_range_count(const void* d_E, int elem_type, int64_t n_rows, int dim
     return fail(DEWI_ERR_UNSUPPORTED, "no dense row scan for this shape");
   L.qn_off = R.qn_off;   // (the chunk counts sit between the keys and the prepared queries)
   char* ws = static_cast<char*>(d_workspace);
-  rc = run_scan(L, d_E, elem_type, n_scan, dim, d_Q, n_queries, kRangeDenseCandidates, space, ws, stream,
-                static_cast<const uint32_t*>(d_filter));
+  rc = run_scan(L, B, kRangeDenseCandidates, ws, static_cast<const uint32_t*>(d_filter));
   if (rc) return rc;
-  const hipError_t e = dewi::launch_range_count(reinterpret_cast<const uint64_t*>(ws), n_scan, n_queries, d_thresholds,
-                                                reinterpret_cast<uint32_t*>(ws + R.chunks_off), d_counts, stream);
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "range count launch");
+  return launched(dewi::launch_range_count(reinterpret_cast<const uint64_t*>(ws), n_scan, n_queries, d_thresholds,
+                                           reinterpret_cast<uint32_t*>(ws + R.chunks_off), d_counts, stream),
+                  "range count launch");
 }
 
 int dewi_knn_range_collect(const void* d_workspace, size_t workspace_bytes, int64_t n_scan, int n_queries,
@@ -1160,14 +1183,14 @@ int dewi_knn_range_collect(const void* d_workspace, size_t workspace_bytes, int6
     return fail(DEWI_ERR_INVALID_ARG, "null threshold, lims, payload or output pointer");
   const RangeLayout R = range_layout(n_scan, 1, n_queries);
   const size_t need = R.chunks_off + R.chunks_bytes;
-  if (!d_workspace || workspace_bytes < need) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
+  if (int rc = check_workspace(d_workspace, workspace_bytes, need)) return rc;
   if (reinterpret_cast<uintptr_t>(d_workspace) % 16 != 0) return fail(DEWI_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
   const char* ws = static_cast<const char*>(d_workspace);
-  const hipError_t e = dewi::launch_range_collect(reinterpret_cast<const uint64_t*>(ws), n_scan, n_queries, d_thresholds,
-                                                  reinterpret_cast<const uint32_t*>(ws + R.chunks_off), d_lims, capacity,
-                                                  make_rerank(eta, entropy_pref), d_dewi32, d_ent32, d_out_rows, d_out_sims,
-                                                  d_out_scores, static_cast<hipStream_t>(stream_));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "range collect launch");
+  return launched(dewi::launch_range_collect(reinterpret_cast<const uint64_t*>(ws), n_scan, n_queries, d_thresholds,
+                                             reinterpret_cast<const uint32_t*>(ws + R.chunks_off), d_lims, capacity,
+                                             make_rerank(eta, entropy_pref), d_dewi32, d_ent32, d_out_rows, d_out_sims, d_out_scores,
+                                             static_cast<hipStream_t>(stream_)),
+                  "range collect launch");
 }
 
 // ---- range search through the bf16 shadow (additive to ABI 6) ---------------------------------------------------------
@@ -1212,8 +1235,7 @@ static int range_shadow_check(int64_t n_rows, int dim, int64_t first_row, int n_
   if (rc) return rc;
   *L = dewi::plan_range_shadow(n_rows, dim, n_queries, seg_cap, dev.cus);
   if (!L->fits) return fail(DEWI_ERR_INVALID_ARG, "seg_cap %d: a group's records must stay below 2^32 bytes", seg_cap);
-  if (workspace_bytes < L->total) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, L->total);
-  return DEWI_OK;
+  return check_workspace(d_workspace, workspace_bytes, L->total);
 }
 
 int dewi_knn_range_shadow_count(const float* d_E, const uint16_t* d_E_bf16, int64_t n_rows, int dim, int64_t first_row,
@@ -1224,9 +1246,9 @@ int dewi_knn_range_shadow_count(const float* d_E, const uint16_t* d_E_bf16, int6
   dewi::RangeShadowLayout L;
   const int rc = range_shadow_check(n_rows, dim, first_row, n_queries, seg_cap, d_workspace, workspace_bytes, &L);
   if (rc) return rc;
-  const hipError_t e = dewi::launch_range_shadow_count(L, d_E, d_E_bf16, n_rows, dim, first_row, d_Q, n_queries, d_thresholds,
-                                                       d_counts, static_cast<char*>(d_workspace), static_cast<hipStream_t>(stream_));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "range shadow count launch");
+  return launched(dewi::launch_range_shadow_count(L, d_E, d_E_bf16, n_rows, dim, first_row, d_Q, n_queries, d_thresholds, d_counts,
+                                                  static_cast<char*>(d_workspace), static_cast<hipStream_t>(stream_)),
+                  "range shadow count launch");
 }
 
 int dewi_knn_range_shadow_collect(const void* d_workspace, size_t workspace_bytes, int64_t n_rows, int dim, int64_t first_row,
@@ -1240,10 +1262,10 @@ int dewi_knn_range_shadow_collect(const void* d_workspace, size_t workspace_byte
   const int rc = range_shadow_check(n_rows, dim, first_row, n_queries, seg_cap, d_workspace, workspace_bytes, &L);
   if (rc) return rc;
   if (capacity == 0) return DEWI_OK;
-  const hipError_t e = dewi::launch_range_shadow_collect(L, n_rows, first_row, n_queries, static_cast<const char*>(d_workspace), d_lims,
-                                                         capacity, make_rerank(eta, entropy_pref), d_dewi32, d_ent32, d_out_rows,
-                                                         d_out_sims, d_out_scores, static_cast<hipStream_t>(stream_));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "range shadow collect launch");
+  return launched(dewi::launch_range_shadow_collect(L, n_rows, first_row, n_queries, static_cast<const char*>(d_workspace), d_lims,
+                                                    capacity, make_rerank(eta, entropy_pref), d_dewi32, d_ent32, d_out_rows, d_out_sims,
+                                                    d_out_scores, static_cast<hipStream_t>(stream_)),
+                  "range shadow collect launch");
 }
 
 size_t dewi_merge_workspace_bytes(int n_lists, int n_queries, int list_len, int n_candidates) {
@@ -1273,7 +1295,7 @@ int dewi_merge_rerank(const dewi_candidate* d_lists, int n_lists, int n_queries,
     e = dewi::launch_merge_rerank_large(d_lists, n_lists, n_queries, list_len, n_candidates, k, make_rerank(eta, entropy_pref),
                                         d_workspace, d_out_ids, d_out_scores, static_cast<hipStream_t>(stream));
   }
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "merge_rerank launch");
+  return launched(e, "merge_rerank launch");
 }
 
 size_t dewi_robust_fit_workspace_bytes(int n_signals) {
@@ -1287,9 +1309,9 @@ int dewi_robust_fit_f32(const float* d_S, int64_t n, int64_t ld, int n_signals, 
                                                       static_cast<long long>(n), static_cast<long long>(ld), n_signals);
   if (n > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n exceeds 2^32-1");
   const size_t need = dewi::robust_fit_workspace_bytes(n_signals);
-  if (!d_workspace || workspace_bytes < need) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
-  hipError_t e = dewi::launch_robust_fit(d_S, n, ld, n_signals, d_med, d_mad, d_workspace, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "robust_fit launch");
+  if (int rc = check_workspace(d_workspace, workspace_bytes, need)) return rc;
+  return launched(dewi::launch_robust_fit(d_S, n, ld, n_signals, d_med, d_mad, d_workspace, static_cast<hipStream_t>(stream)),
+                  "robust_fit launch");
 }
 
 // ---- sharded robust fit: the select of dewi_robust_fit_f32 split at its histogram boundaries ----
@@ -1297,14 +1319,12 @@ static int check_fit_step(int n_signals, int phase, int pass, void* d_workspace,
   if (n_signals <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_signals %d", n_signals);
   if (phase < 0 || phase > 1 || pass < 0 || pass > 2) return fail(DEWI_ERR_INVALID_ARG, "phase %d / pass %d out of range", phase, pass);
   const size_t need = dewi::robust_fit_workspace_bytes(n_signals);
-  if (!d_workspace || workspace_bytes < need) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
-  return DEWI_OK;
+  return check_workspace(d_workspace, workspace_bytes, need);
 }
 
 int dewi_robust_fit_begin(int n_signals, void* d_workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_fit_step(n_signals, 0, 0, d_workspace, workspace_bytes)) return rc;
-  hipError_t e = dewi::launch_fit_begin(d_workspace, n_signals, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "robust_fit_begin");
+  return launched(dewi::launch_fit_begin(d_workspace, n_signals, static_cast<hipStream_t>(stream)), "robust_fit_begin");
 }
 
 int dewi_robust_fit_hist_f32(const float* d_S, int64_t n_local, int64_t ld, int n_signals, int phase, int pass,
@@ -1314,8 +1334,8 @@ int dewi_robust_fit_hist_f32(const float* d_S, int64_t n_local, int64_t ld, int 
   if (n_local > 0 && !d_S) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
   if (phase == 1 && !d_med) return fail(DEWI_ERR_INVALID_ARG, "the MAD phase needs the medians");
   if (n_local > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n exceeds 2^32-1");
-  hipError_t e = dewi::launch_fit_hist(d_S, n_local, ld, n_signals, phase, pass, d_med, d_workspace, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "robust_fit_hist launch");
+  return launched(dewi::launch_fit_hist(d_S, n_local, ld, n_signals, phase, pass, d_med, d_workspace, static_cast<hipStream_t>(stream)),
+                  "robust_fit_hist launch");
 }
 
 int dewi_robust_fit_region(int n_signals, int phase, int pass, int which, size_t* offset_bytes, size_t* count_u32) {
@@ -1329,16 +1349,16 @@ int dewi_robust_fit_pick(int64_t n_total, int n_signals, int phase, int pass, vo
                          void* stream) {
   if (int rc = check_fit_step(n_signals, phase, pass, d_workspace, workspace_bytes)) return rc;
   if (n_total <= 0 || n_total > 0xFFFFFFFFll) return fail(DEWI_ERR_INVALID_ARG, "n_total %lld", static_cast<long long>(n_total));
-  hipError_t e = dewi::launch_fit_pick(n_total, n_signals, phase, pass, d_workspace, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "robust_fit_pick launch");
+  return launched(dewi::launch_fit_pick(n_total, n_signals, phase, pass, d_workspace, static_cast<hipStream_t>(stream)),
+                  "robust_fit_pick launch");
 }
 
 int dewi_robust_fit_finish(int64_t n_total, int n_signals, int phase, void* d_workspace, size_t workspace_bytes,
                            float* d_out, void* stream) {
   if (int rc = check_fit_step(n_signals, phase, 0, d_workspace, workspace_bytes)) return rc;
   if (n_total <= 0 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "bad arguments");
-  hipError_t e = dewi::launch_fit_finish(n_total, n_signals, phase, d_workspace, d_out, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "robust_fit_finish launch");
+  return launched(dewi::launch_fit_finish(n_total, n_signals, phase, d_workspace, d_out, static_cast<hipStream_t>(stream)),
+                  "robust_fit_finish launch");
 }
 
 static int score_impl(const void* d_S, int signals_are_f64, int64_t n, int64_t ld, const double* med, const double* mad,
@@ -1356,8 +1376,8 @@ static int score_impl(const void* d_S, int signals_are_f64, int64_t n, int64_t l
   for (int i = 0; i < 5; ++i) sp.w[i] = weights[i];
   sp.delta = delta;
   sp.mode = mode;
-  hipError_t e = dewi::launch_score(d_S, signals_are_f64, n, ld, sp, d_med, d_mad, d_out, d_out32, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DEWI_OK : hip_fail(e, "score launch");
+  return launched(dewi::launch_score(d_S, signals_are_f64, n, ld, sp, d_med, d_mad, d_out, d_out32, static_cast<hipStream_t>(stream)),
+                  "score launch");
 }
 
 int dewi_score_f64(const void* d_S, int signals_are_f64, int64_t n, int64_t ld, const double* med, const double* mad,

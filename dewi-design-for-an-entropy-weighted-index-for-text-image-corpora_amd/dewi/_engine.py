@@ -38,6 +38,59 @@ def check_thresholds(thresholds, n_queries: int) -> np.ndarray:
     return np.ascontiguousarray(t)
 
 
+# ---- what every search entry point shares (host logic only: plain functions of shapes and values) ----------------------
+def check_search_args(q_shape, dim: int, k, candidates: Optional[int], similarity: str) -> Tuple[int, int]:
+    """The argument check of the three ``DeviceCorpus`` search paths and ``IVFIndex.search_device``, in one order: query
+    width, ``similarity``, "a transform needs ``candidates``" -> ``(batch, k)``.  ``k <= 0`` is the caller's next question."""
+    if q_shape[1] != dim:
+        raise ValueError(f"Expected query shape ({dim},), got {tuple(q_shape[1:])}")
+    if similarity not in nat.SIM_CODES:
+        raise ValueError(f"unknown similarity {similarity!r}")
+    if candidates is None and similarity != "ip":
+        raise ValueError("similarity transforms belong to the ANN re-rank rule: pass candidates=k as well")
+    return int(q_shape[0]), int(k)
+
+
+def cut_size(k: int, candidates: Optional[int], n: Optional[int] = None) -> int:
+    """The similarity cut that is re-ranked: the reference's ``2k`` (backends.py:439) or ``candidates``, at most the ``n``
+    rows there are to choose from (``None``: the caller has made sure of that already), never below 1."""
+    c = 2 * int(k) if candidates is None else int(candidates)
+    if n is not None:
+        c = min(c, int(n))
+    return max(c, 1)
+
+
+def library_size(size_fn, *args) -> int:
+    """``size_fn(*args)`` in bytes.  A size function of the library answers 0 for a shape it refuses: ``NativeLibraryError``
+    with its last error."""
+    need = int(size_fn(*args))
+    if need == 0:
+        raise nat.NativeLibraryError(f"{getattr(size_fn, '__name__', size_fn)} returned 0: " + nat.last_error())
+    return need
+
+
+def default_outputs(b: int, k: int, device, out_ids=None, out_scores=None):
+    """The caller's output tensors, or fresh ``[B, k]`` ones (ids int64, scores fp32) where it gave none."""
+    torch = _torch()
+    if out_ids is None:
+        out_ids = torch.empty((b, k), dtype=torch.int64, device=device)
+    if out_scores is None:
+        out_scores = torch.empty((b, k), dtype=torch.float32, device=device)
+    return out_ids, out_scores
+
+
+def empty_result(b: int, device):
+    """The ``[B, 0]`` answer of a search with nothing to return (k <= 0, an empty filter)."""
+    return default_outputs(b, 0, device)
+
+
+# The library's launch-shape overrides are thread-local, and the workspace sizes depend on them: ``tuning()`` stamps the
+# calling thread with a fresh process-wide number, a thread that never called it keeps 0 (the defaults).  Two threads with
+# the same number therefore have the same tuning, whatever their idents.
+_tuning_epochs = itertools.count(1)
+_thread_tuning = threading.local()
+
+
 def _order_key(x):
     """fp32 tensor -> int64 keys in the order of the kernels' ``ord_f32``: larger float, larger key; -0 == +0; NaN on top."""
     torch = _torch()
@@ -140,8 +193,7 @@ class DeviceCorpus:
         self.device = emb.device
         self.corpus_id = next(_corpus_ids)      # what a DeviceFilter is checked against
         self._lib = nat.load_library()
-        self._ws: Dict[Tuple[int, int], "torch.Tensor"] = {}
-        self._ws_need: Dict[Tuple[int, int, int], Tuple[int, int]] = {}     # (batch, cut, thread) -> (tuning epoch, bytes)
+        self._ws: Dict[tuple, tuple] = {}       # key -> (workspace, tuning epoch it was sized under): _cached_workspace
         self._q_pinned = None
         self._q_dev = None
         self.shadow = None            # bf16 copy of an fp32 matrix (enable_bf16_shadow): pre-selection over half the bytes
@@ -245,32 +297,39 @@ class DeviceCorpus:
     def is_bf16(self) -> bool:
         return self.emb.dtype == _torch().bfloat16
 
+    @property
+    def _elem(self) -> int:
+        """``elem_type`` of the ABI: 0 fp32, 1 bf16."""
+        return 1 if self.is_bf16 else 0
+
     def corpus_bytes(self) -> int:
         return self.emb.numel() * self.emb.element_size()
 
     # ------------------------------------------------------------------ helpers
-    def _workspace(self, n_queries: int, n_candidates: int):
-        # the required size depends on the launch plan (tunable): asked again whenever `tuning()` has been called since
-        # (the library call plans every path of the shape — a few microseconds that a 40 us search need not pay each time)
-        key = (n_queries, n_candidates)
-        nkey = (n_queries, n_candidates, threading.get_ident())      # (the library's tuning is thread-local)
-        cached = self._ws_need.get(nkey)
-        if cached is not None and cached[0] == _tuning_epoch:
-            need = cached[1]
-        else:
-            need = int(self._lib.dewi_knn_workspace_bytes(self.n_rows, self.dim, n_queries, n_candidates))
-            if need == 0:
-                raise nat.NativeLibraryError("dewi_knn_workspace_bytes returned 0: " + nat.last_error())
-            if len(self._ws_need) > 64:
-                self._ws_need.clear()
-            self._ws_need[nkey] = (_tuning_epoch, need)
-        ws = self._ws.get(key)
+    def _cached_workspace(self, key, size_fn, *size_args):
+        """The workspace of every entry point of this corpus: one tensor per ``key``.  The required size depends on the launch
+        plan (tunable), so an entry is good for the tuning it was sized under: a hit under the calling thread's current
+        tuning costs one lookup; otherwise ``size_fn(*size_args)`` asks the library again (it plans every path of the shape —
+        a few microseconds that a 40 us search need not pay each time) and the tensor grows if the size did.  More than 8
+        entries: the cache is dropped before the next allocation.  An entry holds ONE epoch: two threads under different
+        tunings that share a corpus and a key re-ask the size on every call (correct — the tensor only grows — and
+        ``search_device`` is one caller at a time per instance anyway); a size per thread was not worth a second table."""
+        epoch = getattr(_thread_tuning, "epoch", 0)
+        hit = self._ws.get(key)
+        if hit is not None and hit[1] == epoch:
+            return hit[0]
+        need = library_size(size_fn, *size_args)
+        ws = None if hit is None else hit[0]
         if ws is None or ws.numel() < need:
             if len(self._ws) > 8:
                 self._ws.clear()
             ws = _torch().empty(need, dtype=_torch().uint8, device=self.device)
-            self._ws[key] = ws
+        self._ws[key] = (ws, epoch)
         return ws
+
+    def _workspace(self, n_queries: int, n_candidates: int):
+        return self._cached_workspace((n_queries, n_candidates), self._lib.dewi_knn_workspace_bytes, self.n_rows, self.dim,
+                                      n_queries, n_candidates)
 
     def stage_queries(self, queries: ArrayLike):
         """Host or device query batch -> contiguous fp32 [B, d] tensor on this device."""
@@ -305,10 +364,8 @@ class DeviceCorpus:
             raise ValueError(f"filter mask must have shape ({self.n_rows},), got {tuple(m.shape)}")
         if m.dtype != torch.bool:
             raise ValueError(f"filter mask must be boolean, got {m.dtype}")
-        elem = 1 if self.is_bf16 else 0
-        need = int(self._lib.dewi_filter_bytes(self.n_rows, self.dim, elem))
-        if need == 0:
-            raise nat.NativeLibraryError("dewi_filter_bytes returned 0: " + nat.last_error())
+        elem = self._elem
+        need = library_size(self._lib.dewi_filter_bytes, self.n_rows, self.dim, elem)
         with torch.cuda.device(self.device):
             m8 = m.to(device=self.device).view(torch.uint8).contiguous()
             buf = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -338,10 +395,8 @@ class DeviceCorpus:
         if m.dtype != torch.bool:
             raise ValueError(f"query filter masks must be boolean, got {m.dtype}")
         b = int(m.shape[0])
-        elem = 1 if self.is_bf16 else 0
-        need = int(self._lib.dewi_query_filter_bytes(self.n_rows, self.dim, elem, b))
-        if need == 0:
-            raise nat.NativeLibraryError("dewi_query_filter_bytes returned 0: " + nat.last_error())
+        elem = self._elem
+        need = library_size(self._lib.dewi_query_filter_bytes, self.n_rows, self.dim, elem, b)
         with torch.cuda.device(self.device):
             m8 = m.to(device=self.device).view(torch.uint8).contiguous()
             buf = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -368,30 +423,19 @@ class DeviceCorpus:
         query with 0 < |F_j| < c runs the one-list search on a filter of its own list (its cut is |F_j|); an empty list
         gives id -1 / score NaN in that query's row.  Every query's result is bit-equal to its one-list search."""
         torch = _torch()
-        b = int(q_dev.shape[0])
-        self.check_query_filters(qf, b)
-        if q_dev.shape[1] != self.dim:
-            raise ValueError(f"Expected query shape ({self.dim},), got {tuple(q_dev.shape[1:])}")
-        if similarity not in nat.SIM_CODES:
-            raise ValueError(f"unknown similarity {similarity!r}")
-        if candidates is None and similarity != "ip":
-            raise ValueError("similarity transforms belong to the ANN re-rank rule: pass candidates=k as well")
+        self.check_query_filters(qf, int(q_dev.shape[0]))
+        b, k = check_search_args(q_dev.shape, self.dim, k, candidates, similarity)
         if self.is_bf16:
             raise NotImplementedError("filtered search serves fp32 corpora (bf16: not in this build)")
-        k = int(k)
         if k <= 0:
-            return (torch.empty((b, 0), dtype=torch.int64, device=self.device),
-                    torch.empty((b, 0), dtype=torch.float32, device=self.device))
+            return empty_result(b, self.device)
         counts = qf.n_allowed
         for j in range(b):
             if 0 < counts[j] < k:
                 raise ValueError(f"query {j}: kth(={int(counts[j]) - k}) out of bounds ({int(counts[j])}): k = {k} exceeds "
                                  f"the {int(counts[j])} rows its filter allows")
-        if out_ids is None:
-            out_ids = torch.empty((b, k), dtype=torch.int64, device=self.device)
-        if out_scores is None:
-            out_scores = torch.empty((b, k), dtype=torch.float32, device=self.device)
-        c = 2 * k if candidates is None else max(int(candidates), 1)
+        out_ids, out_scores = default_outputs(b, k, self.device, out_ids, out_scores)
+        c = cut_size(k, candidates)
         shared = [j for j in range(b) if counts[j] >= c]
         if len(shared) < b:
             out_ids.fill_(-1)
@@ -407,18 +451,10 @@ class DeviceCorpus:
                         qf._subsets.clear()
                     sub = qf._subsets[key] = self.make_query_filters(qf.masks[list(shared)].view(torch.bool))
                 q_sub = q_dev[shared].contiguous()
-                o_ids = torch.empty((len(shared), k), dtype=torch.int64, device=self.device)
-                o_sc = torch.empty((len(shared), k), dtype=torch.float32, device=self.device)
+                o_ids, o_sc = default_outputs(len(shared), k, self.device)
             nb = len(shared)
-            wkey = ("qfiltered", nb, sub.n_union, c)
-            ws = self._ws.get(wkey)
-            if ws is None:
-                need = int(self._lib.dewi_knn_query_filtered_workspace_bytes(sub.n_union, self.dim, nb, c))
-                if need == 0:
-                    raise nat.NativeLibraryError("dewi_knn_query_filtered_workspace_bytes returned 0: " + nat.last_error())
-                if len(self._ws) > 8:
-                    self._ws.clear()
-                ws = self._ws[wkey] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._cached_workspace(("qfiltered", nb, sub.n_union, c), self._lib.dewi_knn_query_filtered_workspace_bytes,
+                                        sub.n_union, self.dim, nb, c)
             self._last_call = (nb, k, c, False, ws)
             n_a = (ctypes.c_int64 * nb)(*[int(x) for x in sub.n_allowed])
             rc = self._lib.dewi_knn_rerank_query_filtered(
@@ -444,37 +480,17 @@ class DeviceCorpus:
                          candidates: Optional[int], similarity: str, filter: DeviceFilter):
         """``search_device`` over the rows of a prepared filter (``dewi_knn_rerank_filtered``): the row kernels of this
         dim over the list, then the same select / blend / top-k.  k <= 0 or an empty filter: empty results."""
-        torch = _torch()
         self.check_filter(filter)
-        b = int(q_dev.shape[0])
-        if q_dev.shape[1] != self.dim:
-            raise ValueError(f"Expected query shape ({self.dim},), got {tuple(q_dev.shape[1:])}")
-        if similarity not in nat.SIM_CODES:
-            raise ValueError(f"unknown similarity {similarity!r}")
-        if candidates is None and similarity != "ip":
-            raise ValueError("similarity transforms belong to the ANN re-rank rule: pass candidates=k as well")
-        k = int(k)
+        b, k = check_search_args(q_dev.shape, self.dim, k, candidates, similarity)
         n_a = filter.n_allowed
         if k <= 0 or n_a == 0:
-            return (torch.empty((b, 0), dtype=torch.int64, device=self.device),
-                    torch.empty((b, 0), dtype=torch.float32, device=self.device))
-        if out_ids is None:
-            out_ids = torch.empty((b, k), dtype=torch.int64, device=self.device)
-        if out_scores is None:
-            out_scores = torch.empty((b, k), dtype=torch.float32, device=self.device)
-        c = min(2 * k, n_a) if candidates is None else min(max(int(candidates), 1), n_a)
-        key = ("filtered", b, n_a, c)
-        ws = self._ws.get(key)
-        if ws is None:
-            need = int(self._lib.dewi_knn_filtered_workspace_bytes(n_a, self.dim, b, c))
-            if need == 0:
-                raise nat.NativeLibraryError("dewi_knn_filtered_workspace_bytes returned 0: " + nat.last_error())
-            if len(self._ws) > 8:
-                self._ws.clear()
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            return empty_result(b, self.device)
+        out_ids, out_scores = default_outputs(b, k, self.device, out_ids, out_scores)
+        c = cut_size(k, candidates, n_a)
+        ws = self._cached_workspace(("filtered", b, n_a, c), self._lib.dewi_knn_filtered_workspace_bytes, n_a, self.dim, b, c)
         self._last_call = (b, k, c, False, ws)
         rc = self._lib.dewi_knn_rerank_filtered(
-            nat.ptr(self.emb), 1 if self.is_bf16 else 0, self.n_rows, self.dim, nat.ptr(filter.buf), n_a, nat.ptr(q_dev), b,
+            nat.ptr(self.emb), self._elem, self.n_rows, self.dim, nat.ptr(filter.buf), n_a, nat.ptr(q_dev), b,
             nat.ptr(self.dewi32), nat.ptr(self.ent32), k, 0 if candidates is None else int(candidates), nat.SIM_CODES[similarity],
             float(eta), float(entropy_pref), nat.SPACE_CODES[self.space], nat.ptr(out_ids), nat.ptr(out_scores), nat.ptr(ws),
             ws.numel(), nat.stream_ptr())
@@ -508,26 +524,17 @@ class DeviceCorpus:
                                                filter)
         if filter is not None:
             return self._search_filtered(q_dev, k, eta, entropy_pref, out_ids, out_scores, candidates, similarity, filter)
-        torch = _torch()
-        b = int(q_dev.shape[0])
-        if q_dev.shape[1] != self.dim:
-            raise ValueError(f"Expected query shape ({self.dim},), got {tuple(q_dev.shape[1:])}")
-        k = int(k)
+        n, d = self.n_rows, self.dim
+        b, k = check_search_args(q_dev.shape, d, k, candidates, similarity)
         if k <= 0:
-            return (torch.empty((b, 0), dtype=torch.int64, device=self.device),
-                    torch.empty((b, 0), dtype=torch.float32, device=self.device))
-        c = min(2 * k, self.n_rows) if candidates is None else min(int(candidates), self.n_rows)
-        if out_ids is None:
-            out_ids = torch.empty((b, k), dtype=torch.int64, device=self.device)
-        if out_scores is None:
-            out_scores = torch.empty((b, k), dtype=torch.float32, device=self.device)
-        if similarity not in nat.SIM_CODES:
-            raise ValueError(f"unknown similarity {similarity!r}")
-        if candidates is None and similarity != "ip":
-            raise ValueError("similarity transforms belong to the ANN re-rank rule: pass candidates=k as well")
-        ws = self._workspace(b, max(c, 1))
+            return empty_result(b, self.device)
+        c = cut_size(k, candidates, n)
+        if out_ids is None or out_scores is None:
+            out_ids, out_scores = default_outputs(b, k, self.device, out_ids, out_scores)
+        # (the cache directly, with the shape read once: the hit path of the headline step)
+        ws = self._cached_workspace((b, c), self._lib.dewi_knn_workspace_bytes, n, d, b, c)
         through_shadow = candidates is None and self.shadow is not None and b >= self.shadow_min_batch and use_shadow
-        self._last_call = (b, k, max(c, 1), bool(through_shadow), ws)
+        self._last_call = (b, k, c, bool(through_shadow), ws)
         if through_shadow:
             rc = self._lib.dewi_knn_rerank_f32_shadow(
                 nat.ptr(self.emb), nat.ptr(self.shadow), self.n_rows, self.dim, nat.ptr(q_dev), b, nat.ptr(self.dewi32),
@@ -540,7 +547,7 @@ class DeviceCorpus:
                     nat.ptr(out_ids), nat.ptr(out_scores), nat.ptr(ws), ws.numel(), nat.stream_ptr())
         else:
             rc = self._lib.dewi_knn_rerank_candidates(
-                nat.ptr(self.emb), 1 if self.is_bf16 else 0, self.n_rows, self.dim, nat.ptr(q_dev), b, nat.ptr(self.dewi32),
+                nat.ptr(self.emb), self._elem, self.n_rows, self.dim, nat.ptr(q_dev), b, nat.ptr(self.dewi32),
                 nat.ptr(self.ent32), k, int(candidates), float(eta), float(entropy_pref), nat.SPACE_CODES[self.space],
                 nat.SIM_CODES[similarity], nat.ptr(out_ids), nat.ptr(out_scores), nat.ptr(ws), ws.numel(), nat.stream_ptr())
         nat.check(rc)
@@ -662,19 +669,11 @@ class DeviceCorpus:
         dev = self.device
         parts = []
         counts_h = np.zeros(b, dtype=np.int64)
-        elem = 1 if self.is_bf16 else 0
+        elem = self._elem
         lims_c = None
         for q0 in range(0, b if n_scan > 0 else 0, nat.RANGE_MAX_QUERIES):
             nb = min(nat.RANGE_MAX_QUERIES, b - q0)
-            wkey = ("range", nb, n_scan)
-            ws = self._ws.get(wkey)
-            if ws is None:
-                need = int(self._lib.dewi_knn_range_workspace_bytes(n_scan, self.dim, elem, nb))
-                if need == 0:
-                    raise nat.NativeLibraryError(f"dewi_knn_range_workspace_bytes returned 0 for {n_scan} x {self.dim}")
-                if len(self._ws) > 8:
-                    self._ws.clear()
-                ws = self._ws[wkey] = torch.empty(need, dtype=torch.uint8, device=dev)
+            ws = self._cached_workspace(("range", nb, n_scan), self._lib.dewi_knn_range_workspace_bytes, n_scan, self.dim, elem, nb)
             q_c, thr_c = q_dev[q0:q0 + nb], thr[q0:q0 + nb]
             counts_d = torch.empty(nb, dtype=torch.int64, device=dev)
             nat.check(self._lib.dewi_knn_range_count(
@@ -710,17 +709,8 @@ class DeviceCorpus:
         counts_h = np.zeros(b, dtype=np.int64)
         for q0 in range(0, b, nat.RANGE_SHADOW_MAX_QUERIES):
             nb = min(nat.RANGE_SHADOW_MAX_QUERIES, b - q0)
-            wkey = ("range_shadow", nb, seg_cap)
-            ws = self._ws.get(wkey)
-            if ws is None:
-                need = int(self._lib.dewi_knn_range_shadow_workspace_bytes(self.n_rows, self.dim, nat.SPACE_CODES[self.space], nb,
-                                                                           seg_cap))
-                if need == 0:
-                    raise nat.NativeLibraryError(f"dewi_knn_range_shadow_workspace_bytes returned 0 for {self.n_rows} x "
-                                                 f"{self.dim}, seg_cap {seg_cap}")
-                if len(self._ws) > 8:
-                    self._ws.clear()
-                ws = self._ws[wkey] = torch.empty(need, dtype=torch.uint8, device=dev)
+            ws = self._cached_workspace(("range_shadow", nb, seg_cap), self._lib.dewi_knn_range_shadow_workspace_bytes,
+                                        self.n_rows, self.dim, nat.SPACE_CODES[self.space], nb, seg_cap)
             q_c, thr_c = q_dev[q0:q0 + nb], thr[q0:q0 + nb]
             counts_d = torch.empty(nb, dtype=torch.int64, device=dev)
             nat.check(self._lib.dewi_knn_range_shadow_count(
@@ -829,7 +819,7 @@ class DeviceCorpus:
         b, k, c, through_shadow, ws = self._last_call
         off = ctypes.c_size_t(0)
         with torch.cuda.device(self.device):
-            nat.check(self._lib.dewi_knn_refusal_flags(1 if self.is_bf16 else 0, 1 if through_shadow else 0, self.n_rows, self.dim,
+            nat.check(self._lib.dewi_knn_refusal_flags(self._elem, 1 if through_shadow else 0, self.n_rows, self.dim,
                                                        b, k, c, nat.SPACE_CODES[self.space], ctypes.byref(off)))
             torch.cuda.current_stream().synchronize()
         if off.value == ctypes.c_size_t(-1).value:
@@ -838,10 +828,10 @@ class DeviceCorpus:
 
     def scan_kernel_name(self, n_queries: int, k: int, candidates: Optional[int] = None) -> str:
         """The kernel that streams the corpus for a batch of this size (``dewi_knn_scan_kernel``): measurement label."""
-        c = min(2 * int(k), self.n_rows) if candidates is None else min(int(candidates), self.n_rows)
+        c = cut_size(k, candidates, self.n_rows)
         buf = ctypes.create_string_buffer(128)
         with _torch().cuda.device(self.device):
-            nat.check(self._lib.dewi_knn_scan_kernel(1 if self.is_bf16 else 0, self.n_rows, self.dim, int(n_queries), max(c, 1),
+            nat.check(self._lib.dewi_knn_scan_kernel(self._elem, self.n_rows, self.dim, int(n_queries), c,
                                                      nat.SPACE_CODES[self.space], buf, 128))
         return buf.value.decode()
 
@@ -909,7 +899,7 @@ class DeviceCorpus:
         c_local = max(1, min(n_candidates, self.n_rows))
         ws = self._workspace(b, c_local)
         self._last_call = (b, max(1, c_local // 2), c_local, False, ws)
-        rc = self._lib.dewi_knn_candidates(nat.ptr(self.emb), 1 if self.is_bf16 else 0, self.n_rows, self.dim,
+        rc = self._lib.dewi_knn_candidates(nat.ptr(self.emb), self._elem, self.n_rows, self.dim,
                                            nat.ptr(q_dev), b, nat.ptr(self.dewi32), nat.ptr(self.ent32),
                                            int(n_candidates), nat.SPACE_CODES[self.space], self.id_offset, nat.ptr(out),
                                            nat.ptr(ws), ws.numel(), nat.stream_ptr())
@@ -941,10 +931,8 @@ class PipelinedSearcher:
         self.k, self.eta, self.pref, self.b = int(k), float(eta), float(entropy_pref), int(n_queries)
         self.c = int(n_candidates) if n_candidates is not None else min(2 * self.k, corpus.n_rows)
         self._lib = corpus._lib
-        need = int(self._lib.dewi_knn_workspace_bytes(corpus.n_rows, corpus.dim, self.b, max(1, min(self.c, corpus.n_rows))))
-        if need == 0:
-            raise nat.NativeLibraryError("dewi_knn_workspace_bytes returned 0: " + nat.last_error())
-        self._need = need
+        need = self._need = library_size(self._lib.dewi_knn_workspace_bytes, corpus.n_rows, corpus.dim, self.b,
+                                         cut_size(self.k, self.c, corpus.n_rows))
         with torch.cuda.device(corpus.device):
             # scan_streams > 1: consecutive scans alternate between streams, so the tail of one (block merge,
             # last workgroups) overlaps the ramp of the next (query preparation) — small shards only
@@ -958,7 +946,7 @@ class PipelinedSearcher:
             self._scan_done = [torch.cuda.Event() for _ in range(self.depth)]
             self._finish_done = [torch.cuda.Event() for _ in range(self.depth)]
         self._i = 0
-        self._elem = 1 if corpus.is_bf16 else 0
+        self._elem = corpus._elem
         self._space = nat.SPACE_CODES[corpus.space]
         self._emb, self._dewi, self._ent = nat.ptr(corpus.emb), nat.ptr(corpus.dewi32), nat.ptr(corpus.ent32)
         self._s_scans = [int(st.cuda_stream) for st in self._scan_streams]
@@ -1065,16 +1053,12 @@ def prepare_queries_bf16(q_dev, space: str = "cosine"):
     return out
 
 
-_tuning_epoch = 0      # bumped by tuning(): cached workspace sizes of every DeviceCorpus are asked for again
-
-
 def tuning(scan_blocks: int = 0, rows_per_iter: int = 0, nontemporal: int = -1, batched_mfma: int = 1) -> None:
     """Launch-shape overrides of the CALLING THREAD (the library keeps them thread-local).
     batched_mfma: 0 row kernels only; 1 (default) cosine batches on the matrix cores, ``space="l2"`` batches over an fp32
     corpus too (exact-refine mode: error-widened cut, candidates re-scored with the row kernels' arithmetic); 2 also l2
     batches over a bf16 corpus, unrefined (2<e,q> - ||e||^2 - ||q||^2: absolute error ~ulp(||e||^2+||q||^2) —
     near-duplicates of a query lose their near-zero distance; not the parity path)."""
-    global _tuning_epoch
-    _tuning_epoch += 1
+    _thread_tuning.epoch = next(_tuning_epochs)      # this thread's cached workspace sizes are asked for again
     nat.check(nat.load_library().dewi_tuning_set(int(scan_blocks), int(rows_per_iter), int(nontemporal),
                                                  int(batched_mfma)))

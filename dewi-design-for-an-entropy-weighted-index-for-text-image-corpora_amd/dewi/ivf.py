@@ -240,11 +240,10 @@ class IVFIndex(ExactIndex):
         return list(n_union), list(n_allowed), stride
 
     def _workspace_for(self, n_union: int, nq: int, c: int):
+        # one grow-only buffer, sized on every call: (n_union, nq) change with every probe, so there is nothing to cache by
         import torch
-        from . import _native as nat
-        need = int(self._corpus._lib.dewi_knn_filtered_workspace_bytes(n_union, self.dim, nq, c))
-        if need == 0:
-            raise nat.NativeLibraryError("dewi_knn_filtered_workspace_bytes returned 0: " + nat.last_error())
+        from ._engine import library_size
+        need = library_size(self._corpus._lib.dewi_knn_filtered_workspace_bytes, n_union, self.dim, nq, c)
         if self._ivf_ws is None or self._ivf_ws.numel() < need or self._ivf_ws.device != self._corpus.device:
             self._ivf_ws = torch.empty(need, dtype=torch.uint8, device=self._corpus.device)
         return self._ivf_ws
@@ -282,27 +281,20 @@ class IVFIndex(ExactIndex):
         score NaN.  One caller at a time (shared buffers)."""
         import torch
         from . import _native as nat
+        from ._engine import check_search_args, cut_size, default_outputs, empty_result
         self._ensure_built()
         corpus, st = self._corpus, self._ivf
         if corpus.is_bf16:
             raise NotImplementedError("IVFIndex serves fp32 corpora (bf16: not in this build)")
         npb = self._resolve_nprobe(nprobe, st.nlist)
-        if similarity not in nat.SIM_CODES:
-            raise ValueError(f"unknown similarity {similarity!r}")
-        if candidates is None and similarity != "ip":
-            raise ValueError("similarity transforms belong to the ANN re-rank rule: pass candidates=k as well")
-        b, k = int(q_dev.shape[0]), int(k)
-        if q_dev.shape[1] != self.dim:
-            raise ValueError(f"Expected query shape ({self.dim},), got {tuple(q_dev.shape[1:])}")
+        b, k = check_search_args(q_dev.shape, self.dim, k, candidates, similarity)
         if k <= 0:
-            return (torch.empty((b, 0), dtype=torch.int64, device=corpus.device),
-                    torch.empty((b, 0), dtype=torch.float32, device=corpus.device))
+            return empty_result(b, corpus.device)
         if candidates is not None and int(candidates) < k:
             raise ValueError(f"candidates = {candidates} must be at least k = {k}")
-        c = 2 * k if candidates is None else int(candidates)
+        c = cut_size(k, candidates)
         sim, eta, pref = nat.SIM_CODES[similarity], float(eta), float(entropy_pref)
-        out_ids = torch.empty((b, k), dtype=torch.int64, device=corpus.device)
-        out_scores = torch.empty((b, k), dtype=torch.float32, device=corpus.device)
+        out_ids, out_scores = default_outputs(b, k, corpus.device)
         probe_ids, _ = st.coarse.search_device(q_dev, npb, 0.0, 0.0, candidates=npb)
         n_union, n_allowed, stride = self._prepare_probe(probe_ids, b, npb)
         short = [j for j in range(b) if n_allowed[j] < c]
@@ -316,8 +308,7 @@ class IVFIndex(ExactIndex):
         if shared:
             idx = torch.tensor(shared, dtype=torch.int64, device=corpus.device)
             pid_s, q_s = probe_ids[idx].contiguous(), q_dev[idx].contiguous()
-            o_ids = torch.empty((len(shared), k), dtype=torch.int64, device=corpus.device)
-            o_sc = torch.empty((len(shared), k), dtype=torch.float32, device=corpus.device)
+            o_ids, o_sc = default_outputs(len(shared), k, corpus.device)
             u_s, a_s, stride = self._prepare_probe(pid_s, len(shared), npb)
             self._search_groups(q_s, u_s, a_s, stride, k, c, candidates, sim, eta, pref, o_ids, o_sc)
             out_ids.index_copy_(0, idx, o_ids)
@@ -327,8 +318,7 @@ class IVFIndex(ExactIndex):
                 continue
             kk = min(k, n_allowed[j])
             u_1, a_1, stride = self._prepare_probe(probe_ids[j:j + 1], 1, npb)
-            o_ids = torch.empty((1, kk), dtype=torch.int64, device=corpus.device)
-            o_sc = torch.empty((1, kk), dtype=torch.float32, device=corpus.device)
+            o_ids, o_sc = default_outputs(1, kk, corpus.device)
             self._search_groups(q_dev[j:j + 1], u_1, a_1, stride, kk, c, candidates, sim, eta, pref, o_ids, o_sc)
             out_ids[j, :kk] = o_ids[0]
             out_scores[j, :kk] = o_sc[0]

@@ -313,3 +313,31 @@ def test_filtered_full_size():
     ids, sc = c.search(Q, k, 0.3, 0.0, filter=c.make_filter(mask))
     check_batch(E[rows], Q, dewi32[rows], ent32[rows], k, 0.3, 0.0, "cosine", np.searchsorted(rows, ids), sc,
                 min_decisive_frac=0.75)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7. tuning
+def test_filtered_workspace_follows_tuning():
+    """The workspace of a filtered search is sized from the calling thread's launch plan: a corpus that served the search
+    under ``tuning(scan_blocks=8)`` (8 lists per query) serves it again under the defaults (8192 listed rows at dim 256: 64
+    workgroups, 64 lists) — asked for again and grown, not reused too small — and answers as a fresh corpus does."""
+    eng = _eng()
+    n, dim, k, b = 16384, 256, 10, 3
+    mask = rows_mask(n, np.arange(0, n, 2))                            # 8192 rows
+    Q = orc.synth_queries(b, dim, seed=97)
+    c, _, _, _ = _corpus(n, dim, "cosine", seed=95)
+    f = c.make_filter(mask)
+    assert f.n_allowed == 8192
+    try:
+        eng.tuning(scan_blocks=8)
+        need_8 = int(c._lib.dewi_knn_filtered_workspace_bytes(8192, dim, b, 2 * k))
+        c.search(Q, k, 0.3, 0.0, filter=f)
+        eng.tuning()
+        need_default = int(c._lib.dewi_knn_filtered_workspace_bytes(8192, dim, b, 2 * k))
+        print(f"filtered workspace: {need_8} B under scan_blocks=8, {need_default} B under the defaults")
+        assert need_8 != need_default and need_8 > 0 and need_default > 0
+        got = c.search(Q, k, 0.3, 0.0, filter=f)
+    finally:
+        eng.tuning()
+    fresh, _, _, _ = _corpus(n, dim, "cosine", seed=95)
+    want = fresh.search(Q, k, 0.3, 0.0, filter=fresh.make_filter(mask))
+    assert got[0].shape == (b, k) and _same(got, want)

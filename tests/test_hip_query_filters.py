@@ -278,3 +278,34 @@ def test_query_filters_full_size():
     for j in (0, 9, 18, 31):
         want = c.search(Q[j:j + 1], k, 0.3, 0.0, filter=c.make_filter(masks[j]))
         assert _same((ids[j:j + 1], sc[j:j + 1]), want), j
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7. tuning
+def test_query_filters_workspace_follows_tuning():
+    """As ``test_filtered_workspace_follows_tuning`` for per-query lists: two lists of 8192 rows each share one pass, whose
+    workspace is sized from the calling thread's launch plan — after ``tuning()`` it is asked for again and grown."""
+    eng = _eng()
+    n, dim, k, b = 16384, 256, 10, 2
+    masks = np.zeros((b, n), bool)
+    masks[0, ::2] = True                                               # 8192 rows
+    masks[1, :8192] = True                                             # 8192 rows, half of them the other list's
+    Q = orc.synth_queries(b, dim, seed=99)
+    c, _, _, _ = _corpus(n, dim, "cosine", seed=98)
+    qf = c.make_query_filters(masks)
+    assert qf.n_allowed.tolist() == [8192, 8192] and qf.n_union == 12288
+    try:
+        eng.tuning(scan_blocks=8)
+        need_8 = [int(c._lib.dewi_knn_filtered_workspace_bytes(8192, dim, b, 2 * k)),
+                  int(c._lib.dewi_knn_query_filtered_workspace_bytes(qf.n_union, dim, b, 2 * k))]
+        c.search(Q, k, 0.3, 0.0, filter=qf)
+        eng.tuning()
+        need_default = [int(c._lib.dewi_knn_filtered_workspace_bytes(8192, dim, b, 2 * k)),
+                        int(c._lib.dewi_knn_query_filtered_workspace_bytes(qf.n_union, dim, b, 2 * k))]
+        print(f"query-filtered workspace: {need_8} B under scan_blocks=8, {need_default} B under the defaults")
+        assert need_8[0] != need_default[0] and need_8[1] != need_default[1] and min(need_8 + need_default) > 0
+        got = c.search(Q, k, 0.3, 0.0, filter=qf)
+    finally:
+        eng.tuning()
+    fresh, _, _, _ = _corpus(n, dim, "cosine", seed=98)
+    want = fresh.search(Q, k, 0.3, 0.0, filter=fresh.make_query_filters(masks))
+    assert got[0].shape == (b, k) and _same(got, want)
