@@ -1268,6 +1268,89 @@ int dewi_knn_range_shadow_collect(const void* d_workspace, size_t workspace_byte
                   "range shadow collect launch");
 }
 
+// ---- near-duplicate groups: union-find over the rows (additive to ABI 6) ------------------------------------------------
+constexpr int64_t kGroupsMaxRows = 0x7FFFFFFFll;        // parents are int32
+constexpr int64_t kGroupsMaxEdges = 1ll << 38;          // one thread per edge, 256 per workgroup: the grid stays below 2^31
+
+size_t dewi_groups_workspace_bytes(int64_t n_rows) {
+  if (n_rows <= 0 || n_rows > kGroupsMaxRows) return 0;
+  return dewi::groups_layout(n_rows).total;
+}
+
+// the checks every groups entry point shares, all before any device work
+static int groups_check(int64_t n_rows, const void* d_workspace, size_t workspace_bytes, dewi::GroupsLayout* L) {
+  if (n_rows <= 0 || n_rows > kGroupsMaxRows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_rows %lld outside [1, 2^31 - 1]", static_cast<long long>(n_rows));
+  if (!d_workspace) return fail(DEWI_ERR_WORKSPACE, "null workspace");
+  if (reinterpret_cast<uintptr_t>(d_workspace) % 16 != 0) return fail(DEWI_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+  *L = dewi::groups_layout(n_rows);
+  return check_workspace(d_workspace, workspace_bytes, L->total);
+}
+
+int dewi_groups_begin(int64_t n_rows, void* d_workspace, size_t workspace_bytes, void* stream_) {
+  dewi::GroupsLayout L;
+  if (int rc = groups_check(n_rows, d_workspace, workspace_bytes, &L)) return rc;
+  return launched(dewi::launch_groups_begin(L, n_rows, static_cast<char*>(d_workspace), static_cast<hipStream_t>(stream_)),
+                  "groups begin launch");
+}
+
+int dewi_groups_union_lists(int64_t n_rows, const int64_t* d_lims, const int64_t* d_rows, int n_queries, int64_t n_results,
+                            int64_t first_row, void* d_workspace, size_t workspace_bytes, void* stream_) {
+  if (!d_lims || (!d_rows && n_results != 0)) return fail(DEWI_ERR_INVALID_ARG, "null lims or rows pointer");
+  if (n_queries <= 0 || n_queries > DEWI_RANGE_SHADOW_MAX_QUERIES)
+    return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, %d]: split the batch", n_queries, DEWI_RANGE_SHADOW_MAX_QUERIES);
+  if (n_results < 0 || n_results > kGroupsMaxEdges)
+    return fail(DEWI_ERR_INVALID_ARG, "n_results %lld outside [0, 2^38]", static_cast<long long>(n_results));
+  dewi::GroupsLayout L;
+  if (int rc = groups_check(n_rows, d_workspace, workspace_bytes, &L)) return rc;
+  if (first_row < 0 || first_row > n_rows - n_queries)
+    return fail(DEWI_ERR_INVALID_ARG, "queries [%lld, %lld + %d) are not rows of [0, %lld)", static_cast<long long>(first_row),
+                static_cast<long long>(first_row), n_queries, static_cast<long long>(n_rows));
+  if (n_results == 0) return DEWI_OK;
+  return launched(dewi::launch_groups_union_lists(L, n_rows, d_lims, d_rows, n_queries, n_results, first_row,
+                                                  static_cast<char*>(d_workspace), static_cast<hipStream_t>(stream_)),
+                  "groups union (lists) launch");
+}
+
+int dewi_groups_union_pairs(int64_t n_rows, const int64_t* d_a, const int64_t* d_b, int64_t n_pairs, void* d_workspace,
+                            size_t workspace_bytes, void* stream_) {
+  if (n_pairs < 0 || n_pairs > kGroupsMaxEdges)
+    return fail(DEWI_ERR_INVALID_ARG, "n_pairs %lld outside [0, 2^38]", static_cast<long long>(n_pairs));
+  if ((!d_a || !d_b) && n_pairs != 0) return fail(DEWI_ERR_INVALID_ARG, "null pair pointer");
+  dewi::GroupsLayout L;
+  if (int rc = groups_check(n_rows, d_workspace, workspace_bytes, &L)) return rc;
+  if (n_pairs == 0) return DEWI_OK;
+  return launched(dewi::launch_groups_union_pairs(L, n_rows, d_a, d_b, n_pairs, static_cast<char*>(d_workspace),
+                                                  static_cast<hipStream_t>(stream_)),
+                  "groups union (pairs) launch");
+}
+
+int dewi_groups_finish(int64_t n_rows, int keep, const float* d_key, int64_t id_offset, int64_t* d_labels, int64_t* d_sizes,
+                       int64_t* d_representatives, int64_t* out_n_groups, int64_t* out_bad_endpoints, void* d_workspace,
+                       size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (keep != DEWI_GROUPS_KEEP_FIRST && keep != DEWI_GROUPS_KEEP_MAX_KEY) return fail(DEWI_ERR_INVALID_ARG, "unknown keep rule %d", keep);
+  if (keep == DEWI_GROUPS_KEEP_MAX_KEY && !d_key) return fail(DEWI_ERR_INVALID_ARG, "keep = max key needs a key column");
+  if (!d_labels || !d_sizes || !d_representatives || !out_n_groups || !out_bad_endpoints)
+    return fail(DEWI_ERR_INVALID_ARG, "null output pointer");
+  dewi::GroupsLayout L;
+  if (int rc = groups_check(n_rows, d_workspace, workspace_bytes, &L)) return rc;
+  char* ws = static_cast<char*>(d_workspace);
+  hipError_t e = dewi::launch_groups_finish(L, n_rows, keep, d_key, id_offset, d_labels, d_sizes, d_representatives, ws, stream);
+  if (e != hipSuccess) return hip_fail(e, "groups finish launch");
+  uint32_t err[2] = {0, 0}, n_groups = 0;
+  e = hipMemcpyAsync(err, ws, sizeof(err), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&n_groups, ws + L.count_off, sizeof(n_groups), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hip_fail(e, "groups read-back");
+  *out_n_groups = static_cast<int64_t>(n_groups);
+  *out_bad_endpoints = static_cast<int64_t>(err[dewi::kGroupsErrBadRow]);
+  if (err[dewi::kGroupsErrGaveUp] != 0)
+    return fail(DEWI_ERR_HIP, "groups: an edge was given up (compare-and-swap retry cap, or a parent word above its row: was the "
+                              "workspace written between begin and finish?); the groups are incomplete");
+  return DEWI_OK;
+}
+
 size_t dewi_merge_workspace_bytes(int n_lists, int n_queries, int list_len, int n_candidates) {
   if (n_lists <= 0 || n_queries <= 0 || list_len <= 0 || n_candidates <= 0) return 0;
   if (static_cast<int64_t>(n_lists) * list_len <= dewi::kMaxSortCandidates) return 0;   // sorted in LDS

@@ -391,6 +391,23 @@ hipError_t launch_range_shadow_collect(const RangeShadowLayout& L, int64_t n_row
                                        const float* d_ent32, int64_t* d_out_rows, float* d_out_sims, float* d_out_scores,
                                        hipStream_t stream);
 
+// ---- groups.hip: connected components of an edge set over the rows (union-find in the caller's workspace)
+constexpr int kGroupsHeaderWords = 16;   // u32 words at the workspace's start; begin zeroes them
+constexpr int kGroupsErrBadRow = 0;      // edges dropped because an endpoint lay outside [0, n_rows)
+constexpr int kGroupsErrGaveUp = 1;      // != 0: an edge was given up (CAS cap, or a parent word that breaks parent[i] <= i)
+struct GroupsLayout {
+  size_t parent_off, count_off, members_off, best_off, total;   // bytes; [count_off, total) is what finish zeroes
+};
+GroupsLayout groups_layout(int64_t n_rows);
+hipError_t launch_groups_begin(const GroupsLayout& L, int64_t n_rows, char* ws, hipStream_t stream);
+hipError_t launch_groups_union_lists(const GroupsLayout& L, int64_t n_rows, const int64_t* d_lims, const int64_t* d_rows,
+                                     int n_queries, int64_t n_results, int64_t first_row, char* ws, hipStream_t stream);
+hipError_t launch_groups_union_pairs(const GroupsLayout& L, int64_t n_rows, const int64_t* d_a, const int64_t* d_b, int64_t n_pairs,
+                                     char* ws, hipStream_t stream);
+// keep 0: representative = the root (lowest row); 1: the member with the highest d_key (ties: lowest row; NaN loses)
+hipError_t launch_groups_finish(const GroupsLayout& L, int64_t n_rows, int keep, const float* d_key, int64_t id_offset,
+                                int64_t* d_labels, int64_t* d_sizes, int64_t* d_reps, char* ws, hipStream_t stream);
+
 // ---- ingest.hip ---------------------------------------------------------------------------
 hipError_t launch_normalize_rows(const float* d_src, float* d_dst, int64_t n_rows, int dim, hipStream_t stream);
 hipError_t launch_row_cosine(const float* d_a, const float* d_b, float* d_out, int64_t n_rows, int dim, float eps,

@@ -811,6 +811,81 @@ class DeviceCorpus:
             a, rows = a + self.id_offset, rows + self.id_offset
         return a, rows, sims
 
+    # ------------------------------------------------------------------ near-duplicate groups
+    def _groups_begin(self, n: int):
+        """A union-find over rows ``0 .. n - 1`` in this corpus's cached workspace, every row its own group."""
+        if not 1 <= int(n) < (1 << 31):
+            raise ValueError(f"groups need between 1 and 2^31 - 1 rows, got {n}")
+        ws = self._cached_workspace(("groups", int(n)), self._lib.dewi_groups_workspace_bytes, int(n))
+        nat.check(self._lib.dewi_groups_begin(int(n), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+        return ws
+
+    def _groups_finish(self, ws, n: int, keep: str):
+        """``((labels, sizes, representatives) int64 [n] on the device, n_groups)`` of the workspace's edges so far; the one
+        synchronisation of a grouping.  Edges with an endpoint outside the rows: ``ValueError``."""
+        torch = _torch()
+        if keep not in nat.KEEP_CODES:
+            raise ValueError(f"unknown keep rule {keep!r}: one of {sorted(nat.KEEP_CODES)}")
+        if keep == "dewi" and int(n) != self.n_rows:
+            raise ValueError(f"keep='dewi' reads this corpus's dewi column: {self.n_rows} rows, not {n}")
+        labels, sizes, reps = (torch.empty(int(n), dtype=torch.int64, device=self.device) for _ in range(3))
+        n_groups, bad = ctypes.c_int64(0), ctypes.c_int64(0)
+        nat.check(self._lib.dewi_groups_finish(int(n), nat.KEEP_CODES[keep], nat.ptr(self.dewi32) if keep == "dewi" else None,
+                                               self.id_offset, nat.ptr(labels), nat.ptr(sizes), nat.ptr(reps), ctypes.byref(n_groups),
+                                               ctypes.byref(bad), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+        if bad.value:
+            raise ValueError(f"{bad.value} edges have an endpoint outside the {n} rows")
+        return (labels, sizes, reps), int(n_groups.value)
+
+    def duplicate_groups_device(self, threshold: float, chunk: int = 2048, use_shadow: bool = True, keep: str = "first"):
+        """The near-duplicate GROUPS of the stored rows: ``((labels, sizes, representatives), n_groups)`` — three int64 [N]
+        device tensors and the number of groups (singletons included).
+
+        DEFINITION: the groups are the connected components of the graph whose edges are exactly the pairs
+        ``near_duplicates_device(threshold)`` reports (single linkage: a chain of pairwise-similar rows is one group).
+        ``labels[i]``: the smallest row of row i's group (``id_offset`` added) — the same whatever the chunking or the order
+        the device took the edges in; ``sizes[i]``: the group's number of rows; ``representatives[i]``: the one row that stands
+        for the group (``id_offset`` added) — ``keep="first"`` its smallest row, ``keep="dewi"`` the row with the highest
+        ``dewi32`` (ties to the lower row; a NaN loses to every number).
+
+        The chunk loop, the ``_range_rows`` call and the routes are those of ``near_duplicates_device``; every chunk's result
+        lists go straight into ``dewi_groups_union_lists`` (which skips each query's own and lower rows) and are dropped: no
+        pair is kept, so there is no ``max_pairs`` — memory is O(N) plus one chunk's results.  One synchronisation per chunk
+        (the range search's) and one at the end.  The workspace is this corpus's: NOT thread-safe on one instance."""
+        n = self.n_rows
+        chunk = max(1, min(int(chunk), nat.RANGE_SHADOW_MAX_QUERIES))
+        thr = float(threshold)
+        if keep not in nat.KEEP_CODES:
+            raise ValueError(f"unknown keep rule {keep!r}: one of {sorted(nat.KEEP_CODES)}")
+        ws = self._groups_begin(n)
+        for s in range(0, n - 1, chunk):
+            e = min(n, s + chunk)
+            q = self.emb[s:e] if not self.is_bf16 else self.emb[s:e].float()
+            lims, rows, _, _, _ = self._range_rows(q, thr, 0.0, 0.0, None, None, use_shadow, first_row=s)
+            if rows.shape[0]:
+                nat.check(self._lib.dewi_groups_union_lists(n, nat.ptr(lims), nat.ptr(rows), e - s, int(rows.shape[0]), s,
+                                                            nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+        return self._groups_finish(ws, n, keep)
+
+    def groups_from_pairs_device(self, a, b, n_rows: Optional[int] = None, keep: str = "first"):
+        """``duplicate_groups_device``'s result for the caller's own edges: ``a``, ``b`` int64 [P] device tensors of row ids as
+        ``near_duplicates_device`` returns them (``id_offset`` included), in any order, repeats and ``a == b`` allowed.
+        ``n_rows`` (default: this corpus's): the ids' range; ``keep="dewi"`` needs the corpus's own.  An id outside the
+        range: ``ValueError``."""
+        torch = _torch()
+        n = self.n_rows if n_rows is None else int(n_rows)
+        if keep not in nat.KEEP_CODES:
+            raise ValueError(f"unknown keep rule {keep!r}: one of {sorted(nat.KEEP_CODES)}")
+        a, b = (torch.as_tensor(x, dtype=torch.int64, device=self.device).reshape(-1).contiguous() for x in (a, b))
+        if a.shape != b.shape:
+            raise ValueError(f"a and b must have the same length, got {tuple(a.shape)} and {tuple(b.shape)}")
+        if self.id_offset:
+            a, b = a - self.id_offset, b - self.id_offset
+        ws = self._groups_begin(n)
+        nat.check(self._lib.dewi_groups_union_pairs(n, nat.ptr(a), nat.ptr(b), int(a.shape[0]), nat.ptr(ws), ws.numel(),
+                                                    nat.stream_ptr()))
+        return self._groups_finish(ws, n, keep)
+
     def refused_by_last_call(self) -> np.ndarray:
         """Monitoring / tests: bool [B] — which queries of the LAST ``search_device`` call a matrix-core pass refused (and the
         repair launches inside the same library call answered).  All False for a shape that takes the row kernels.

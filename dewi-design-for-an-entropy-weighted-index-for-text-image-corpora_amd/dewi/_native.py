@@ -36,6 +36,8 @@ ABI_VERSION = 6
 RANGE_MAX_QUERIES = 32
 #: most queries one dewi_knn_range_shadow_count call takes (DEWI_RANGE_SHADOW_MAX_QUERIES: 8 groups of 256)
 RANGE_SHADOW_MAX_QUERIES = 2048
+#: which row of a group represents it (include/dewi_hip.h DEWI_GROUPS_KEEP_*): the lowest row / the highest key (the dewi column)
+KEEP_CODES = {"first": 0, "dewi": 1}
 
 #: every symbol include/dewi_hip.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -52,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "dewi_knn_range_workspace_bytes", "dewi_knn_range_count", "dewi_knn_range_collect",
     "dewi_knn_range_shadow_supported", "dewi_knn_range_shadow_workspace_bytes", "dewi_knn_range_shadow_count",
     "dewi_knn_range_shadow_collect",
+    "dewi_groups_workspace_bytes", "dewi_groups_begin", "dewi_groups_union_lists", "dewi_groups_union_pairs", "dewi_groups_finish",
 )
 
 
@@ -180,6 +183,16 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_knn_range_shadow_count.argtypes = [vp, vp, i64, i32, i64, vp, i32, vp, i32, vp, vp, sz, vp]
     lib.dewi_knn_range_shadow_collect.restype = i32
     lib.dewi_knn_range_shadow_collect.argtypes = [vp, sz, i64, i32, i64, i32, i32, vp, i64, vp, vp, f64, f64, vp, vp, vp, vp]
+    lib.dewi_groups_workspace_bytes.restype = sz
+    lib.dewi_groups_workspace_bytes.argtypes = [i64]
+    lib.dewi_groups_begin.restype = i32
+    lib.dewi_groups_begin.argtypes = [i64, vp, sz, vp]
+    lib.dewi_groups_union_lists.restype = i32
+    lib.dewi_groups_union_lists.argtypes = [i64, vp, vp, i32, i64, i64, vp, sz, vp]
+    lib.dewi_groups_union_pairs.restype = i32
+    lib.dewi_groups_union_pairs.argtypes = [i64, vp, vp, i64, vp, sz, vp]
+    lib.dewi_groups_finish.restype = i32
+    lib.dewi_groups_finish.argtypes = [i64, i32, vp, i64, vp, vp, vp, c.POINTER(i64), c.POINTER(i64), vp, sz, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

@@ -15,6 +15,7 @@ construction, which is what the reference does when those libraries are not inst
 """
 from __future__ import annotations
 
+import dataclasses
 import enum
 import json
 import logging
@@ -49,6 +50,30 @@ class IndexBackend(enum.Enum):
 
 
 SearchResult = List[Tuple[str, float, Payload]]
+
+
+def clusters_from_labels(labels: np.ndarray, doc_ids: Sequence[str]) -> List[List[str]]:
+    """Group labels int64 [N] -> the groups as lists of doc ids: ordered by label, members by ascending row, singletons
+    included.  Host logic only."""
+    labels = np.asarray(labels)
+    if labels.size == 0:
+        return []
+    order = np.argsort(labels, kind="stable")
+    cuts = np.flatnonzero(np.diff(labels[order])) + 1
+    return [[doc_ids[i] for i in grp.tolist()] for grp in np.split(order, cuts)]
+
+
+@dataclasses.dataclass
+class DuplicateGroups:
+    """``ExactIndex.duplicate_groups``: per row the group's label (its smallest row), its size and its representative row —
+    numpy int64 [N] — the number of groups (singletons included), and with ``doc_ids=True`` the groups as lists of doc ids
+    (ordered by label, members by ascending row, singletons included), else ``None``."""
+
+    labels: np.ndarray
+    sizes: np.ndarray
+    representatives: np.ndarray
+    n_groups: int
+    clusters: Optional[List[List[str]]] = None
 
 
 class BaseIndex:
@@ -631,6 +656,51 @@ class ExactIndex(BaseIndex):
             ids = self._doc_ids
             return [ids[i] for i in a.tolist()], [ids[i] for i in b.tolist()], sims
         return a, b, sims
+
+    # ---------------------------------------------------------------- near-duplicate groups (additive)
+    def duplicate_groups(self, threshold: float, keep: str = "dewi", doc_ids: bool = False) -> DuplicateGroups:
+        """The near-duplicate groups of the index (additive; the reference has no such method): the connected components of
+        the graph whose edges are the pairs ``near_duplicates(threshold)`` reports — computed on the device without ever
+        holding the pairs, so a cluster of m copies costs m rows of memory, not m (m - 1) / 2 pairs, and there is no
+        ``max_pairs``.  Single linkage: a chain of pairwise-similar documents is one group.
+
+        Returns a ``DuplicateGroups``: ``labels[i]`` the smallest row of document i's group, ``sizes[i]`` the group's number of
+        documents, ``representatives[i]`` the one row to keep of it — ``keep="dewi"`` the member with the highest ``dewi``
+        (ties to the lower row), ``keep="first"`` the smallest row — and ``n_groups``, singletons included.  ``doc_ids=True``
+        adds ``clusters``: the groups as lists of doc ids, ordered by label, members by ascending row, singletons included —
+        the shape the reference's ``metrics.duplicate_rate`` / ``cluster_coverage`` take.  An empty index has no groups, one
+        document is its own; neither builds anything.  (``IVFIndex`` inherits this unchanged: it is exact, the cells are not
+        consulted.)"""
+        from . import _native as nat
+        if keep not in nat.KEEP_CODES:
+            raise ValueError(f"unknown keep rule {keep!r}: one of {sorted(nat.KEEP_CODES)}")
+        n = len(self._doc_ids)
+        if n < 2:
+            labels = np.arange(n, dtype=np.int64)
+            sizes, reps, n_groups = np.ones(n, np.int64), labels.copy(), n
+        else:
+            self._ensure_built()
+            import torch
+            corpus = self._corpus
+            with corpus._lock, torch.cuda.device(corpus.device):
+                out, n_groups = corpus.duplicate_groups_device(float(threshold), keep=keep)
+                labels, sizes, reps = (t.cpu().numpy() for t in out)
+        return DuplicateGroups(labels, sizes, reps, int(n_groups), clusters_from_labels(labels, self._doc_ids) if doc_ids else None)
+
+    def dedup_filter(self, threshold: float, keep: str = "dewi"):
+        """``make_filter`` of the rows that are their group's representative in ``duplicate_groups(threshold, keep)``: a
+        normal ``DeviceFilter``, so ``search(..., filter=index.dedup_filter(0.95))`` is the filtered exact search with every
+        near-duplicate group collapsed to one document.  fp32 corpora, as every filter (bf16: ``NotImplementedError``).  On an
+        ``IVFIndex`` a user filter already runs the parent's exact filtered search, and so does this one."""
+        self._ensure_built()
+        import torch
+        corpus = self._corpus
+        if corpus.is_bf16:
+            raise NotImplementedError("filtered search serves fp32 corpora (bf16: not in this build)")
+        with corpus._lock, torch.cuda.device(corpus.device):
+            (_, _, reps), _ = corpus.duplicate_groups_device(float(threshold), keep=keep)
+            mask = reps == torch.arange(corpus.id_offset, corpus.id_offset + corpus.n_rows, dtype=torch.int64, device=corpus.device)
+        return self.make_filter(mask)
 
     def results_for(self, rows: np.ndarray, scores: np.ndarray) -> List[SearchResult]:
         """Row indices/scores of ``search_batch`` -> the reference's (doc_id, score, Payload) tuples."""

@@ -4,7 +4,8 @@ Same constructor, defaults and methods as the reference (index.py:22-166): it va
 the query, fills in the default ``eta`` / ``entropy_pref`` and delegates to a backend.  In
 this build every backend choice resolves to the HIP ``ExactIndex`` (ANN graph libraries
 are out of scope), with the reference's own warning when an ANN backend was asked for.
-Additions: ``add_batch``, ``search_batch``, ``range_search``, ``range_search_batch`` and ``near_duplicates``.
+Additions: ``add_batch``, ``search_batch``, ``range_search``, ``range_search_batch``, ``near_duplicates``, ``duplicate_groups`` and
+``dedup_filter``.
 """
 from __future__ import annotations
 
@@ -150,6 +151,21 @@ class DewiIndex(BaseIndex):
         out = self._backend.near_duplicates(threshold, max_pairs=max_pairs, doc_ids=doc_ids)
         if len(self) > 1:
             self._built = True
+        return out
+
+    def duplicate_groups(self, threshold: float, keep: str = "dewi", doc_ids: bool = False):
+        """The near-duplicate groups (additive; ``ExactIndex.duplicate_groups``): labels, sizes, representatives, the number
+        of groups and, with ``doc_ids=True``, the clusters as lists of doc ids.  Exact, whatever the backend probes."""
+        out = self._backend.duplicate_groups(threshold, keep=keep, doc_ids=doc_ids)
+        if len(self) > 1:
+            self._built = True
+        return out
+
+    def dedup_filter(self, threshold: float, keep: str = "dewi"):
+        """An allow-list of one document per near-duplicate group (additive; ``ExactIndex.dedup_filter``) for
+        ``search`` / ``search_batch`` / ``range_search(filter=...)``."""
+        out = self._backend.dedup_filter(threshold, keep=keep)
+        self._built = True
         return out
 
     # ------------------------------------------------------------------ accessors (index.py:95-119)

@@ -56,6 +56,9 @@ class IVFIndex(ExactIndex):
     ``range_search`` / ``range_search_batch`` are ``ExactIndex``'s, unchanged: they scan EVERY row (or every row of
     ``filter``) and are exact — the cells are not consulted and there is no ``nprobe`` argument.  A range search over the
     probed cells only is not part of this build.
+
+    ``duplicate_groups`` / ``dedup_filter`` are inherited as well and exact.  ``search(..., filter=dedup_filter(...))`` on
+    this class is what any user filter is here: the parent's exact filtered search over the whole allow-list, not a probe.
     """
 
     def __init__(self, dim: int, space: str = "cosine", nlist: Optional[int] = None, nprobe: Optional[int] = None,

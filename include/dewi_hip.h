@@ -346,6 +346,44 @@ int dewi_knn_range_shadow_collect(const void* d_workspace, size_t workspace_byte
                                   const float* d_ent32, double eta, double entropy_pref, int64_t* d_out_rows, float* d_out_sims,
                                   float* d_out_scores, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Near-duplicate GROUPS (additive to ABI 6): the connected components of a set of edges over the rows 0 .. n_rows - 1, by
+ * a lock-free union-find in the caller's workspace.  begin, any number of union calls, finish; all on one stream.
+ *
+ * n_rows: 1 .. 2^31 - 1.  Workspace: dewi_groups_workspace_bytes (0 for an n_rows outside that range; needs no device),
+ * 16-byte aligned; it belongs to the computation from begin to finish.
+ * dewi_groups_begin: every row is its own group; the error words are cleared.
+ * dewi_groups_union_lists: one self-join chunk as the range entry points leave it — d_lims DEVICE int64 [n_queries + 1],
+ * d_rows DEVICE int64 [n_results] LOCAL rows, queries = the stored rows first_row .. first_row + n_queries - 1 (all inside
+ * [0, n_rows), n_queries <= DEWI_RANGE_SHADOW_MAX_QUERIES).  Result e of query j (lims[j] <= e < lims[j + 1]) is the edge
+ * (first_row + j, rows[e]); it is taken only when rows[e] > first_row + j (the row itself and lower rows are skipped), and
+ * a row >= n_rows is counted as a bad endpoint and never used.  Results outside [lims[0], lims[n_queries]) are ignored.
+ * dewi_groups_union_pairs: edges (a[p], b[p]), DEVICE int64 [n_pairs], in any order.  An endpoint outside [0, n_rows) is
+ * counted as a bad endpoint and the edge dropped (it is never dereferenced); otherwise a == b is no edge.
+ * Both union calls are asynchronous; calls on one workspace may be split or merged at will: the result depends on the SET of
+ * edges only.  A count of 0 is DEWI_OK with nothing launched.
+ * dewi_groups_finish: per row i, d_labels[i] = the smallest row of i's group + id_offset (so labels are deterministic),
+ * d_sizes[i] = the group's number of rows, d_representatives[i] = one row of the group + id_offset, the same for all its
+ * rows: keep = DEWI_GROUPS_KEEP_FIRST the smallest row; DEWI_GROUPS_KEEP_MAX_KEY the row with the largest d_key (DEVICE fp32
+ * [n_rows]; -0 == +0, ties go to the lower row, a NaN key loses to every number).  All three DEVICE int64 [n_rows].
+ * *out_n_groups, *out_bad_endpoints: HOST.  finish SYNCHRONISES the stream (it is the only call that does) and may be
+ * repeated with another keep rule.  Integer atomics only: the same edge set gives the same bytes, whatever the order.
+ * DEWI_ERR_HIP from finish: a union kernel gave an edge up — its compare-and-swap retry reached its cap, or it met a parent
+ * word that nothing of this library writes; no loop in these kernels is unbounded and none waits for another thread.
+ * Bad arguments and a short workspace are reported before any device work.
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_GROUPS_KEEP_FIRST 0
+#define DEWI_GROUPS_KEEP_MAX_KEY 1
+size_t dewi_groups_workspace_bytes(int64_t n_rows);
+int dewi_groups_begin(int64_t n_rows, void* d_workspace, size_t workspace_bytes, void* stream);
+int dewi_groups_union_lists(int64_t n_rows, const int64_t* d_lims, const int64_t* d_rows, int n_queries, int64_t n_results,
+                            int64_t first_row, void* d_workspace, size_t workspace_bytes, void* stream);
+int dewi_groups_union_pairs(int64_t n_rows, const int64_t* d_a, const int64_t* d_b, int64_t n_pairs, void* d_workspace,
+                            size_t workspace_bytes, void* stream);
+int dewi_groups_finish(int64_t n_rows, int keep, const float* d_key, int64_t id_offset, int64_t* d_labels, int64_t* d_sizes,
+                       int64_t* d_representatives, int64_t* out_n_groups, int64_t* out_bad_endpoints, void* d_workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* Step 1 of the bf16 search alone (backends.py:420-424 followed by the bf16 rounding of config C3): q / ||q||
  * in fp32 unless the norm is 0 (cosine), then round-to-nearest-even to bf16.  This is the kernel the batched
  * matrix-core path runs on its queries; exposed so that parity tests can check the normalisation on its own
