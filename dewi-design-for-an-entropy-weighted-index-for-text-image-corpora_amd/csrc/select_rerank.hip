@@ -3,7 +3,7 @@
 // Replaces steps 3-9 of ExactIndex.search (reference src/dewi/backends.py:439-481):
 //   top = argpartition(scores, -c)[-c:]                    -> block radix-select over the scan's keys
 //   adj = (1-eta)*scores[top] + eta*dewi[top] (+pref*ent)  -> fp32, two rounded products + one add
-//   argpartition(adj, -k)[-k:], argsort(-adj)              -> bitonic sort in LDS, first k
+//   argpartition(adj, -k)[-k:], argsort(-adj)              -> bitonic sort in LDS, first k (NaN scores: in the k, written last)
 // One workgroup per query.  The work is O(keys) with keys << corpus bytes; this kernel is
 // latency-bound, not bandwidth-bound, and is kept to a handful of passes over L2-resident keys.
 #include <stdlib.h>
@@ -19,13 +19,26 @@ __device__ __forceinline__ int pow2_at_least(int v) {
   return p;
 }
 
+// Where sorted position j (< kk, the number of results) of the adjusted keys is written.  A NaN adjusted score has the
+// largest key (ord_f32), so the NaN ones sit at the front of the sorted order and stay in the first kk like in the
+// reference's argpartition (NaN sorts as the largest value), but the reference's final argsort(-adj) puts them LAST
+// (backends.py:468-471: -NaN is NaN, and argsort sorts NaN to the end).  z of the first kk keys are NaN: the numbers move
+// up by z, the NaN ones go behind them in their own order (the candidate rank).
+constexpr uint32_t kOrdNaN = 0xFFFFFFFFu;   // ord_f32(NaN)
+__device__ __forceinline__ int emit_position(int j, bool is_nan, int kk, uint32_t n_nan) {
+  const int z = n_nan < static_cast<uint32_t>(kk) ? static_cast<int>(n_nan) : kk;
+  return is_nan ? kk - z + j : j - z;
+}
+
 // After sh.sel[0..n_sel) holds the candidates sorted by (sim desc, row asc) and dewi/ent of entry t
-// are available through `fetch(t, &dewi, &ent, &id)`: blend, sort, emit the first k.
+// are available through `fetch(t, &dewi, &ent, &id)`: blend, sort, emit the first k (NaN scores last).
+// `n_nan` (LDS) counts the NaN adjusted scores: the kernel zeroes it at its start, with a barrier before this call.
 template <class Fetch>
-__device__ void rerank_and_emit(SelectShared& sh, int n_sel, int k, const RerankParams& rp, Fetch fetch,
+__device__ void rerank_and_emit(SelectShared& sh, uint32_t& n_nan, int n_sel, int k, const RerankParams& rp, Fetch fetch,
                                 int64_t* __restrict__ out_ids, float* __restrict__ out_scores) {
   const int tid = static_cast<int>(threadIdx.x), nt = static_cast<int>(blockDim.x);
   const int p2 = pow2_at_least(n_sel);
+  const int kk = k < n_sel ? k : n_sel;
   int64_t my_id = -1;  // id of candidate t == tid, kept in a register for the one-candidate-per-thread case
   for (int t = tid; t < p2; t += nt) {
     uint64_t k2 = kKeyEmpty;
@@ -35,6 +48,7 @@ __device__ void rerank_and_emit(SelectShared& sh, int n_sel, int k, const Rerank
       fetch(t, dewi, ent, id);
       if (t == tid) my_id = id;
       const float adj = blend(rp, key_score(sh.sel[t]), dewi, ent);
+      if (adj != adj) atomicAdd(&n_nan, 1u);   // rare: a workgroup without NaN scores pays the compare only
       // ties on the adjusted score: the candidate that ranked higher on similarity first
       k2 = (static_cast<uint64_t>(ord_f32(adj)) << 32) | static_cast<uint64_t>(0xFFFFFFFFu - static_cast<uint32_t>(t));
     }
@@ -56,8 +70,10 @@ __device__ void rerank_and_emit(SelectShared& sh, int n_sel, int k, const Rerank
             float dewi, ent;
             fetch(t, dewi, ent, id);
           }
-          out_ids[rank] = id;
-          out_scores[rank] = unord_f32(static_cast<uint32_t>(mine >> 32));
+          const uint32_t hi = static_cast<uint32_t>(mine >> 32);
+          const int at = emit_position(rank, hi == kOrdNaN, kk, n_nan);
+          out_ids[at] = id;
+          out_scores[at] = unord_f32(hi);
         }
       }
     } else {
@@ -77,22 +93,26 @@ __device__ void rerank_and_emit(SelectShared& sh, int n_sel, int k, const Rerank
           float dewi, ent;
           int64_t id;
           fetch(t, dewi, ent, id);
-          out_ids[rank] = id;
-          out_scores[rank] = unord_f32(static_cast<uint32_t>(mine >> 32));
+          const uint32_t hi = static_cast<uint32_t>(mine >> 32);
+          const int at = emit_position(rank, hi == kOrdNaN, kk, n_nan);
+          out_ids[at] = id;
+          out_scores[at] = unord_f32(hi);
         }
       }
     }
     return;
   }
   bitonic_sort_desc<false>(sh.sel2, nullptr, p2);
-  for (int j = tid; j < k && j < n_sel; j += nt) {
+  for (int j = tid; j < kk; j += nt) {
     const uint64_t k2 = sh.sel2[j];
     const int t = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(k2));
     float dewi, ent;
     int64_t id;
     fetch(t, dewi, ent, id);
-    out_ids[j] = id;
-    out_scores[j] = unord_f32(static_cast<uint32_t>(k2 >> 32));
+    const uint32_t hi = static_cast<uint32_t>(k2 >> 32);
+    const int at = emit_position(j, hi == kOrdNaN, kk, n_nan);
+    out_ids[at] = id;
+    out_scores[at] = unord_f32(hi);
   }
 }
 
@@ -177,7 +197,7 @@ __device__ int top_candidates_lds(const uint64_t* keys, int n, int n_candidates,
 // compacted.
 // Part 1 (two sources): find the cut and compact the candidates into sh.sel2; returns their number.
 __device__ __forceinline__ float refine_bound(const RefineParams& rf, float q2, float a) {
-  const float d = a < 0.f ? -a : 0.f;              // M(a); NaN scores (NaN rows rank first) get an infinite bound
+  const float d = a < 0.f ? -a : 0.f;              // M(a); NaN scores (NaN rows are on top of every cut) get an infinite bound
   return a == a ? (rf.space == DEWI_SPACE_L2 ? rf.margin * (3.f * q2 + 2.f * d) * 1.01f : rf.margin) : __builtin_inff();
 }
 __device__ __forceinline__ float refine_low(const RefineParams& rf, float q2, uint64_t thr) {
@@ -304,7 +324,7 @@ __device__ __forceinline__ int refine_from_sorted_lists(const uint64_t* __restri
       const int j = st * kGroup + sub;
       const uint64_t key = (l < n_lists && j < list_len) ? keys[static_cast<int64_t>(l) * list_len + j] : kKeyEmpty;
       const float a = key_score(key);
-      const bool pass = key != kKeyEmpty && !(a < low);      // NaN scores pass (NaN rows rank first)
+      const bool pass = key != kKeyEmpty && !(a < low);      // NaN scores pass (NaN rows are on top of every cut)
       if (pass && j == list_len - 1) sh.total = 1;            // the whole list is inside the band
       if (__builtin_amdgcn_ballot_w64(pass) == 0ull) break;
       refine_append(sh, pass, key, lane);
@@ -572,10 +592,12 @@ __global__ __launch_bounds__(kSelectThreads) void select_rerank_kernel(
     int64_t* __restrict__ out_ids, float* __restrict__ out_scores, dewi_candidate* __restrict__ out_cand,
     const uint32_t* __restrict__ counts, SegmentLayout seg, RefineParams refine, QueryFlags flags) {
   __shared__ SelectShared sh;
+  __shared__ uint32_t n_nan;       // NaN adjusted scores of this query (rerank_and_emit)
   const int tid = static_cast<int>(threadIdx.x), nt = static_cast<int>(blockDim.x);
   const int q = static_cast<int>(blockIdx.x);
   const uint64_t* keys = keys_all + static_cast<int64_t>(q) * keys_per_query;
   int n_sel;
+  if (tid == 0) n_nan = 0;         // every route to rerank_and_emit passes a barrier first
   if (flags.mode == 2) {           // repair launch: only the queries the approximate pass refused (block-uniform)
     if (flags.p[q] == 0u) return;
   } else if (flags.mode == 1 && tid == 0) {
@@ -759,7 +781,7 @@ __global__ __launch_bounds__(kSelectThreads) void select_rerank_kernel(
     ent = ent32[row];
     id = static_cast<int64_t>(row) + id_offset;
   };
-  rerank_and_emit(sh, n_sel, k, rp, fetch, out_ids + static_cast<int64_t>(q) * k,
+  rerank_and_emit(sh, n_nan, n_sel, k, rp, fetch, out_ids + static_cast<int64_t>(q) * k,
                   out_scores + static_cast<int64_t>(q) * k);
 }
 
@@ -772,6 +794,7 @@ __global__ __launch_bounds__(kSelectThreads) void merge_rerank_kernel(const dewi
                                                                       int64_t* __restrict__ out_ids,
                                                                       float* __restrict__ out_scores) {
   __shared__ SelectShared sh;
+  __shared__ uint32_t n_nan;       // NaN adjusted scores of this query (rerank_and_emit)
   const int tid = static_cast<int>(threadIdx.x), nt = static_cast<int>(blockDim.x);
   const int q = static_cast<int>(blockIdx.x);
   const int m = n_lists * list_len;
@@ -779,6 +802,7 @@ __global__ __launch_bounds__(kSelectThreads) void merge_rerank_kernel(const dewi
   if (tid == 0) {
     sh.count = 0;
     sh.total = 0;
+    n_nan = 0;
   }
   __syncthreads();
   const bool small = m <= kRankSortMax;   // the usual case (8 shards x 2k records): one ranking pass
@@ -835,7 +859,7 @@ __global__ __launch_bounds__(kSelectThreads) void merge_rerank_kernel(const dewi
     ent = rec.ent;
     id = rec.id;
   };
-  rerank_and_emit(sh, n_sel, k, rp, fetch, out_ids + static_cast<int64_t>(q) * k,
+  rerank_and_emit(sh, n_nan, n_sel, k, rp, fetch, out_ids + static_cast<int64_t>(q) * k,
                   out_scores + static_cast<int64_t>(q) * k);
 }
 
@@ -873,8 +897,10 @@ __global__ __launch_bounds__(kSelectThreads) void select_rerank_large_kernel(
     uint64_t* __restrict__ g2_all, int64_t* __restrict__ out_ids, float* __restrict__ out_scores,
     dewi_candidate* __restrict__ out_cand, int n_out) {
   __shared__ SelectShared sh;
+  __shared__ uint32_t n_nan;       // NaN adjusted scores of this query
   const int tid = static_cast<int>(threadIdx.x), nt = static_cast<int>(blockDim.x);
   const int q = static_cast<int>(blockIdx.x);
+  if (tid == 0) n_nan = 0;         // (barriers of the radix select lie between this and the first count)
   const ArrayKeys keys{keys_all + static_cast<int64_t>(q) * keys_per_query, keys_per_query};
   uint64_t* g1 = g1_all + static_cast<int64_t>(q) * p2;
   uint64_t* g2 = g2_all + static_cast<int64_t>(q) * p2;
@@ -917,16 +943,20 @@ __global__ __launch_bounds__(kSelectThreads) void select_rerank_large_kernel(
     if (t < n_sel) {
       const uint32_t row = key_row(g1[t]);
       const float adj = blend(rp, key_score(g1[t]), dewi32[row], ent32[row]);
+      if (adj != adj) atomicAdd(&n_nan, 1u);
       k2 = (static_cast<uint64_t>(ord_f32(adj)) << 32) | static_cast<uint64_t>(0xFFFFFFFFu - static_cast<uint32_t>(t));
     }
     g2[t] = k2;
   }
   bitonic_sort_desc_global(g2, p2);
-  for (int j = tid; j < k && j < n_sel; j += nt) {
+  const int kk = k < n_sel ? k : n_sel;
+  for (int j = tid; j < kk; j += nt) {     // NaN scores last: see emit_position
     const uint64_t k2 = g2[j];
     const uint32_t t = 0xFFFFFFFFu - static_cast<uint32_t>(k2);
-    out_ids[static_cast<int64_t>(q) * k + j] = static_cast<int64_t>(key_row(g1[t])) + id_offset;
-    out_scores[static_cast<int64_t>(q) * k + j] = unord_f32(static_cast<uint32_t>(k2 >> 32));
+    const uint32_t hi = static_cast<uint32_t>(k2 >> 32);
+    const int at = emit_position(j, hi == kOrdNaN, kk, n_nan);
+    out_ids[static_cast<int64_t>(q) * k + at] = static_cast<int64_t>(key_row(g1[t])) + id_offset;
+    out_scores[static_cast<int64_t>(q) * k + at] = unord_f32(hi);
   }
 }
 
@@ -958,7 +988,7 @@ __global__ __launch_bounds__(kSelectThreads) void merge_rerank_large_kernel(
     const dewi_candidate* __restrict__ lists, int n_lists, int n_queries, int list_len, int n_candidates, int p2, int k,
     RerankParams rp, uint64_t* __restrict__ g1_all, uint64_t* __restrict__ g2_all, uint32_t* __restrict__ src_all,
     int64_t* __restrict__ out_ids, float* __restrict__ out_scores) {
-  __shared__ uint32_t n_valid, refused;
+  __shared__ uint32_t n_valid, refused, n_nan;
   const int tid = static_cast<int>(threadIdx.x), nt = static_cast<int>(blockDim.x);
   const int q = static_cast<int>(blockIdx.x);
   uint64_t* g1 = g1_all + static_cast<int64_t>(q) * p2;
@@ -968,6 +998,7 @@ __global__ __launch_bounds__(kSelectThreads) void merge_rerank_large_kernel(
   if (tid == 0) {
     n_valid = 0;
     refused = 0;
+    n_nan = 0;
   }
   for (int t = tid; t < p2; t += nt) g1[t] = kKeyEmpty;
   __syncthreads();
@@ -1015,16 +1046,20 @@ __global__ __launch_bounds__(kSelectThreads) void merge_rerank_large_kernel(
     if (t < n_sel) {
       const dewi_candidate rec = record_at(t);
       const float adj = blend(rp, rec.sim, rec.dewi, rec.ent);
+      if (adj != adj) atomicAdd(&n_nan, 1u);
       k2 = (static_cast<uint64_t>(ord_f32(adj)) << 32) | static_cast<uint64_t>(0xFFFFFFFFu - static_cast<uint32_t>(t));
     }
     g2[t] = k2;
   }
   bitonic_sort_desc_global(g2, p2);
-  for (int j = tid; j < k && j < n_sel; j += nt) {
+  const int kk = k < n_sel ? k : n_sel;
+  for (int j = tid; j < kk; j += nt) {     // NaN scores last: see emit_position
     const uint64_t k2 = g2[j];
     const int t = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(k2));
-    out_ids[static_cast<int64_t>(q) * k + j] = record_at(t).id;
-    out_scores[static_cast<int64_t>(q) * k + j] = unord_f32(static_cast<uint32_t>(k2 >> 32));
+    const uint32_t hi = static_cast<uint32_t>(k2 >> 32);
+    const int at = emit_position(j, hi == kOrdNaN, kk, n_nan);
+    out_ids[static_cast<int64_t>(q) * k + at] = record_at(t).id;
+    out_scores[static_cast<int64_t>(q) * k + at] = unord_f32(hi);
   }
 }
 

@@ -272,7 +272,7 @@ class DeviceCorpus:
             raise ValueError("the bf16 shadow serves cosine corpora (stored rows of unit norm)")
         if self.shadow is None:
             # the error bound of the pre-selection (2^-8 of ||e|| ||q|| + accumulation) is proven for rows of norm <= 1.0001:
-            # the stored form of a cosine corpus.  Checked once (NaN rows — zero embeddings — are fine: they rank first).
+            # the stored form of a cosine corpus.  Checked once (NaN rows — zero embeddings — are fine: they are in every cut and come last in every result).
             worst = float(torch.nan_to_num(torch.linalg.vector_norm(self.emb, dim=1), nan=0.0).max()) if self.n_rows else 0.0
             if worst > 1.0001:
                 raise ValueError(f"rows are not normalised (largest norm {worst:.6f}): the bf16 shadow's error bound "

@@ -107,6 +107,10 @@ int dewi_payload_soa_f64(const double* d_dewi, const double* d_ht_mean, const do
  *   4. adj = fp32(1-eta)*sim + fp32(eta)*dewi32[i]         (:461)       two rounded products, one add
  *      adj += fp32(pref)*ent32[i]   if pref != 0           (:464-465)
  *   5. k best by adj, descending                           (:468-481)   ties: higher sim, then lower row
+ *      A NaN similarity (a zero-norm row of a cosine corpus is stored as a NaN row, no guard, as in the reference) or a NaN
+ *      adj (NaN payload value, 0 * inf) counts as the LARGEST value in steps 3 and 5 — np.argpartition's order: such rows
+ *      stay in the cut and among the k best — and is written LAST: the numbers first, descending, then the NaN scores in
+ *      the order of step 3 (:469-471, argsort(-adj) sorts NaN to the end).  -0 == +0 in both orders.
  * d_E  [n_rows][dim] row-major; d_Q [n_queries][dim] raw (un-normalised) fp32 queries.
  *      ANY dim, as the reference's one BLAS call (:431-433).  Rows that are whole 16-byte units (fp32 dim % 4 == 0, bf16
  *      dim % 8 == 0): d_E 16-byte aligned (hipMalloc gives 256).  Other widths: d_E may be any element-aligned address — a
@@ -441,7 +445,12 @@ int dewi_knn_candidates(const void* d_E, int elem_type, int64_t n_rows, int dim,
  * are sorted in LDS and need no workspace (dewi_merge_workspace_bytes returns 0, d_workspace may be NULL);
  * beyond that (k > 128 at eight shards) the sorted shard lists are rank-merged through a caller-owned workspace
  * of dewi_merge_workspace_bytes(...) bytes, so that a sharded search answers every k the single device
- * answers (the reference has no limit: backends.py:439-471).  (ABI 4: workspace arguments added.) */
+ * answers (the reference has no limit: backends.py:439-471).  (ABI 4: workspace arguments added.)
+ * Records with id < 0 are padding; each list sorted by (sim desc, id asc; NaN sims first, -0 == +0) with its padding at
+ * the tail.  With n_valid records of id >= 0 in a query's lists, kk = min(k, n_candidates, n_valid) results are written
+ * in the order of step 5 above (numbers descending, then the NaN scores); positions kk .. k-1 of BOTH outputs are NOT
+ * written — they keep what the caller put there (the package prefills ids -1 / scores NaN and relies on it).  The same
+ * holds for every search entry point whose cut holds fewer than k rows (filters, probes). */
 size_t dewi_merge_workspace_bytes(int n_lists, int n_queries, int list_len, int n_candidates);
 
 int dewi_merge_rerank(const dewi_candidate* d_lists, int n_lists, int n_queries, int list_len,

@@ -13,6 +13,7 @@ Vector families:
   g3  edge cases: k==N, k>N raises, zero query, l2, pref != 0, N < 2k
   g4  scorer: fit medians/MADs + score/score_conditional, N in {1,2,101,10000}
   g5  persistence: ExactIndex.save and DewiIndex.save directories
+  g7  NaN adjusted scores: zero rows (cosine), NaN payload values, k below and above the NaN count
 """
 from __future__ import annotations
 
@@ -292,8 +293,51 @@ def g6():
     (OUT / "g6_api_surface.json").write_text(json.dumps(surface, indent=1, sort_keys=True))
 
 
+def g7():
+    """Rows whose adjusted score is NaN: zero rows of a cosine corpus (stored as NaN rows, no guard), NaN payload values.
+    The reference keeps them in the cut and in the top k and returns them LAST (backends.py:468-471).  k above the NaN count:
+    the tail is determined as a set; k below it: which NaN candidates come back is an artefact of introselect
+    (``tail_is_a_choice``), the file lists the candidates."""
+    rs = np.random.RandomState(77)
+    n, d = 120, 24
+    base = rs.randn(n, d).astype(np.float32)
+    Q = rs.randn(6, d).astype(np.float32)
+    flat, names = {}, []
+
+    def put(name, space, zero_rows, k, eta, pref, q, nan_dewi=0, nan_ht=0):
+        raw = base.copy()
+        raw[zero_rows] = 0.0
+        cols = {key: v.copy() for key, v in orc.synth_payload_columns(n, seed=9).items()}
+        with np.errstate(invalid="ignore", divide="ignore"):
+            E = orc.build_matrix(raw, space)
+            s = orc.similarities(E, orc.prepare_query(q, space), space)
+        best = [int(r) for r in np.argsort(-np.where(np.isnan(s), -np.inf, s))]       # finite similarities, best first
+        cols["dewi"][best[1:1 + nan_dewi]] = np.nan
+        cols["ht_mean"][best[3:3 + nan_ht]] = np.nan
+        idx, pos = build_ref(raw, payloads_from_columns(cols, n), space)
+        with np.errstate(invalid="ignore"):
+            ids, sc = run(idx, pos, q, k, eta, pref)
+        cand = ([int(r) for r in zero_rows] if space == "cosine" else []) + best[1:1 + nan_dewi] + (best[3:3 + nan_ht] if pref != 0 else [])
+        z = int(np.isnan(sc).sum())
+        assert z == min(k, len(cand)) and z > 0 and np.isnan(sc[k - z:]).all(), (name, z, cand, sc)
+        names.append(name)
+        flat.update({f"{name}__raw": raw, f"{name}__query": q, f"{name}__k": np.int64(k), f"{name}__eta": np.float64(eta),
+                     f"{name}__pref": np.float64(pref), f"{name}__dewi": cols["dewi"], f"{name}__ht_mean": cols["ht_mean"],
+                     f"{name}__hi_mean": cols["hi_mean"], f"{name}__ids": ids, f"{name}__scores": sc,
+                     f"{name}__tail_is_a_choice": np.bool_(len(cand) > k), f"{name}__nan_candidates": np.array(sorted(cand), np.int64)})
+
+    put("cos_zero_rows_k5", "cosine", [17, 80], 5, 0.3, 0.0, Q[0])
+    put("cos_zero_rows_k2_below", "cosine", [0, 63, 119], 2, 0.3, 0.0, Q[1])
+    put("cos_zero_row_nan_dewi_k6", "cosine", [64], 6, 0.4, 0.0, Q[2], nan_dewi=2)
+    put("cos_nan_ht_pref_k5", "cosine", [31], 5, 0.3, 0.25, Q[3], nan_ht=1)
+    put("l2_zero_rows_nan_dewi_k5", "l2", [17, 80], 5, 0.3, 0.0, Q[4], nan_dewi=2)
+    put("l2_nan_dewi_k1_below", "l2", [], 1, 0.5, 0.0, Q[5], nan_dewi=2)
+    np.savez_compressed(OUT / "g7_nan_rows.npz", cases=np.array(names), **flat)
+    print("g7 ok", names)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7"]
     for name in which:
         globals()[name]()
     for p in sorted(OUT.rglob("*")):

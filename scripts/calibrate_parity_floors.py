@@ -139,3 +139,80 @@ X, Q, _, _ = corpora.embedding_like(n, dim, seed, n_queries=nq)
 sel = corpora.oracle_queries(nq)
 for k, eta, pref in ((10, 0.3, 0.1), (10, 0.0, 0.0), (100, 0.3, 0.1), (100, 0.0, 0.0)):
     print("embedding-like k", k, "eta", eta, "pref", pref, both(X, Q[sel], seed, k, eta, pref), "/", sel.size)
+print("== non-finite order (tests/test_hip_nonfinite_order.py, and the NaN-row tests of test_hip_search / test_hip_mfma_f32)")
+import test_hip_nonfinite_order as nf  # noqa: E402
+def build(raw, space):
+    with np.errstate(all="ignore"):
+        if space != "cosine":
+            return raw
+        return (raw / np.linalg.norm(raw, axis=1, keepdims=True)).astype(np.float32)   # rows as orc.build_matrix, vectorised
+def bf16_inputs(E, Q, space="cosine"):
+    return orc.bf16_round(E), np.stack([orc.bf16_round(orc.prepare_query(q, space)) for q in Q])
+for space in ("cosine", "l2"):
+    for dim in (256, 100, 10):
+        out = []
+        for k in (5, 40, 150):
+            raw, cols, Q, bad = nf.corpus(300, dim, space, seed=dim + k, n_bad=3 if k == 5 else 7)
+            d, e = soa(cols)
+            out.append(parity.count_decisive(build(raw, space), Q, d, e, k, nf.ETA, nf.PREF, space))
+        print("one query f32", space, dim, "k 5/40/150:", out, "/ 4")
+raw, cols, Q, bad = nf.corpus(3000, 64, "cosine", seed=71, n_bad=9, b=2); d, e = soa(cols)
+print("k 1025:", parity.count_decisive(build(raw, "cosine"), Q, d, e, 1025, nf.ETA, 0.1, "cosine"), "/ 2")
+for dim in (256, 100):
+    raw, cols, Q, bad = nf.corpus(300, dim, "cosine", seed=dim + 3, n_bad=4); d, e = soa(cols)
+    Eb, Qp = bf16_inputs(build(raw, "cosine"), Q)
+    print("one query bf16", dim, parity.count_decisive(Eb, Qp, d, e, 10, nf.ETA, nf.PREF, "cosine", gap=G, prepared=True, exact_gaps=False), "/ 4")
+for route in nf.BATCH_ROUTES:
+    raw, cols, Q, bad, elem, space, kernel = nf.batch_case(route); d, e = soa(cols)
+    sel = np.linspace(0, Q.shape[0] - 1, nf.BATCH_CHECKED).astype(int)
+    E = build(raw, space)
+    if elem == "bf16":
+        Eb, Qp = bf16_inputs(E, Q[sel], space)
+        nd = parity.count_decisive(Eb, Qp, d, e, nf.BATCH_K, nf.ETA, 0.1, space, gap=G, prepared=True, exact_gaps=False)
+    else:
+        nd = parity.count_decisive(E, Q[sel], d, e, nf.BATCH_K, nf.ETA, 0.1, space, exact_gaps=False)
+    print("batch", route, nd, "/", sel.size)
+raw, cols, Q, bad = nf.corpus(3000, 96, "cosine", seed=96, n_bad=5, b=6); d, e = soa(cols); E = build(raw, "cosine")
+masks = np.random.RandomState(4).rand(6, 3000) < 0.4; masks[:, bad[:3]] = True; masks[:, bad[3:]] = False; masks[1, bad[3]] = True
+print("lists:", sum(parity.count_decisive(E[masks[j]], Q[j:j + 1], d[masks[j]], e[masks[j]], 10, nf.ETA, nf.PREF, "cosine") for j in range(6)), "/ 6 (each compared twice)")
+for n, dim, k in ((3000, 96, 10), (6000, 64, 200)):
+    raw, cols, Q, bad = nf.corpus(n, dim, "cosine", seed=dim + k, n_bad=7, b=4); d, e = soa(cols)
+    print("shards", n, dim, k, parity.count_decisive(build(raw, "cosine"), Q, d, e, k, nf.ETA, nf.PREF, "cosine"), "/ 4")
+raw, cols, Q, rows = nf.payload_case(300, 100, 4, seed=8); d, e = soa(cols)
+print("NaN dewi, one query:", parity.count_decisive(build(raw, "cosine"), Q, d, e, 5, nf.ETA, nf.PREF, "cosine"), "/ 4")
+raw, cols, Q, rows = nf.payload_case(66_000, 128, 32, seed=9); d, e = soa(cols)
+sel = np.linspace(0, 31, nf.BATCH_CHECKED).astype(int)
+print("NaN dewi, batch:", parity.count_decisive(build(raw, "cosine"), Q[sel], d, e, 10, nf.ETA, nf.PREF, "cosine", exact_gaps=False), "/", sel.size)
+# tests/test_hip_search.py::test_nan_rows_rank_last_like_numpy
+rs = np.random.RandomState(6); raw = rs.randn(300, 256).astype(np.float32); raw[17] = 0
+cols = orc.synth_payload_columns(300, seed=6); d, e = soa(cols); q = rs.randn(256).astype(np.float32)
+print("test_nan_rows_rank_last_like_numpy:", parity.count_decisive(build(raw, "cosine"), q[None, :], d, e, 5, 0.3, 0.0, "cosine"), "/ 1",
+      "gaps", orc.decision_gaps(np.delete(build(raw, "cosine"), 17, axis=0), q, np.delete(d, 17), np.delete(e, 17), 4, 0.3))
+# tests/test_hip_mfma_f32.py::test_partial_chunk_keeps_a_nan_row_out_of_its_neighbours (k = 5, eta = 0, 16 queries, 3 NaN rows)
+for dim in (384, 96, 800, 200, 1000, 300, 100, 260, 1284):
+    n, k, b = 70_000, 5, 16
+    raw = orc.synth_corpus(n, dim, seed=dim)
+    for i in (1000, 31 + 32 * 7, n - 1):
+        raw[i] = 0.0
+    cols = orc.synth_payload_columns(n, seed=dim); d, e = soa(cols)
+    Q = orc.synth_queries(b, dim, seed=3); Q[0], Q[1], Q[2] = raw[999], raw[30 + 32 * 7], raw[n - 2]
+    E = build(raw, "cosine")
+    Eb, Qp = bf16_inputs(E, Q)
+    print("partial chunk", dim, "f32", parity.count_decisive(E, Q, d, e, k, 0.0, 0.0, "cosine", exact_gaps=False),
+          "bf16", parity.count_decisive(Eb, Qp, d, e, k, 0.0, 0.0, "cosine", gap=G, prepared=True, exact_gaps=False), "/", b)
+# tests/test_hip_mfma_f32.py::test_mfma_depth_pass_edge_rows (k = 10, eta = 0, 16 queries)
+for space, bf16 in (("cosine", False), ("l2", False), ("l2", True)):
+    n, dim, b, k = 70_003, 512, 16, 10
+    rng = np.random.default_rng(11)
+    raw = orc.synth_corpus(n, dim, seed=11) * rng.uniform(0.5, 2.0, size=(n, 1)).astype(np.float32)
+    raw[40_000] = np.nan if space == "l2" else 0.0
+    raw[123] = 0.0 if space == "l2" else raw[123]
+    Q = orc.synth_queries(b, dim, seed=12) * np.float32(0.05); Q[:4] = raw[[5, 69_999, 70_002, 31_000]]
+    cols = orc.synth_payload_columns(n, seed=11); d, e = soa(cols)
+    E = build(raw, space)
+    if bf16:
+        Eb, Qp = bf16_inputs(E, Q, space)
+        nd = parity.count_decisive(Eb, Qp, d, e, k, 0.0, 0.0, space, gap=G, prepared=True, exact_gaps=False)
+    else:
+        nd = parity.count_decisive(E, Q, d, e, k, 0.0, 0.0, space, exact_gaps=False)
+    print("edge rows", space, "bf16" if bf16 else "f32", nd, "/", b)

@@ -193,7 +193,8 @@ def test_filtered_neighbours_do_not_leak(dim):
 
 @pytest.mark.parametrize("dim", [100, 301, 768])
 def test_filtered_zero_norm_rows_inside(dim):
-    """Zero rows of a cosine corpus are NaN after normalisation and rank first, unfiltered as filtered."""
+    """Zero rows of a cosine corpus are NaN after normalisation: they stay in the cut and in the top k and come last, as in
+    the reference (``argsort(-adjusted)`` sorts NaN to the end), unfiltered as filtered."""
     n = 2003
     raw = orc.synth_corpus(n, dim, seed=dim + 41)
     raw[[3, 500, 1999]] = 0.0
@@ -206,7 +207,8 @@ def test_filtered_zero_norm_rows_inside(dim):
         rows = _topc_superset(E, Q[j:j + 1], 10, "cosine", 30) | {3, 500, 1999, 7, 8, 9}
         got = c.search(Q[j:j + 1], 10, 0.3, 0.0, filter=c.make_filter(rows_mask(n, sorted(rows))))
         assert _same(got, want), j
-        assert {3, 500, 1999} <= set(got[0][0].tolist())
+        assert set(got[0][0, 7:].tolist()) == {3, 500, 1999} and np.isnan(got[1][0, 7:]).all()
+        assert not np.isnan(got[1][0, :7]).any()
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5. rules

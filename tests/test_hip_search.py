@@ -200,16 +200,25 @@ def test_ties_prefer_lower_row_and_zero_query():
     assert ids[0].tolist() == [0, 1, 2, 3, 4] and np.all(sc[0] == 0)
 
 
-def test_nan_rows_rank_first_like_numpy():
-    """A zero-norm row becomes NaN at build (reference has no guard); NumPy's partition ranks NaN
-    as the largest value, so the reference returns such rows first with a NaN score."""
+def test_nan_rows_rank_last_like_numpy():
+    """A zero-norm row becomes NaN at build (reference has no guard).  NumPy's partition ranks NaN as the largest value,
+    so the row stays in the cut and in the top k; the reference's final ``argsort(-adjusted)`` then sorts it to the END
+    (backends.py:468-471): the numbers come first, id for id as the oracle has them, the NaN row last."""
     rs = np.random.RandomState(6)
     raw = rs.randn(300, 256).astype(np.float32)
     raw[17] = 0
     cols = orc.synth_payload_columns(300, seed=6)
     c = _corpus(raw, cols)
-    ids, sc = c.search(rs.randn(256).astype(np.float32), 5, 0.3, 0.0)
-    assert ids[0, 0] == 17 and np.isnan(sc[0, 0]) and not np.any(np.isnan(sc[0, 1:]))
+    q = rs.randn(256).astype(np.float32)
+    ids, sc = c.search(q, 5, 0.3, 0.0)
+    assert ids[0, 4] == 17 and np.isnan(sc[0, 4]) and not np.any(np.isnan(sc[0, :4]))
+    E = c.emb.cpu().numpy()
+    dewi32, ent32 = orc.payload_soa(cols["dewi"], cols["ht_mean"], cols["hi_mean"])
+    want_ids, want_sc = orc.search(E, q, dewi32, ent32, 5, 0.3, 0.0)
+    assert want_ids[4] == 17 and np.isnan(want_sc[4])
+    decisive, msg = compare_query(E, q, dewi32, ent32, 5, 0.3, 0.0, "cosine", ids[0], sc[0])
+    assert msg is None and decisive                       # (decisive by the oracle alone: scripts/calibrate_parity_floors.py)
+    assert ids[0, :4].tolist() == want_ids[:4].tolist()
 
 
 def test_sharded_candidates_and_merge_equal_single_device():

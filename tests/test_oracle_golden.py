@@ -127,3 +127,30 @@ def test_decision_gaps_are_sane(golden):
     dewi32, ent32 = orc.payload_soa(cols["dewi"], cols["ht_mean"], cols["hi_mean"])
     cut, rank = orc.decision_gaps(g["stored"], g["Q"][0], dewi32, ent32, 10, 0.3)
     assert cut > 0 and rank > 0
+
+
+def test_g7_nan_rows_come_last(golden):
+    """The reference on corpora with zero rows (cosine: stored as NaN rows) and NaN payload values: such rows stay in the cut
+    and in the top k and come LAST (``argsort(-adjusted)``, backends.py:468-471).  The oracle must give the numbers bit for
+    bit and the NaN tail as a set; with k below the NaN count (``tail_is_a_choice``) any k of the NaN candidates."""
+    g = golden("g7_nan_rows.npz")
+    names = [str(s) for s in g["cases"]]
+    assert len(names) == 6 and {n.split("_")[0] for n in names} == {"cos", "l2"}
+    for name in names:
+        space = "l2" if name.startswith("l2") else "cosine"
+        k, eta, pref = int(g[f"{name}__k"]), float(g[f"{name}__eta"]), float(g[f"{name}__pref"])
+        dewi32, ent32 = orc.payload_soa(g[f"{name}__dewi"], g[f"{name}__ht_mean"], g[f"{name}__hi_mean"])
+        E = orc.build_matrix(g[f"{name}__raw"], space)
+        with np.errstate(invalid="ignore"):
+            ids, sc = orc.search(E, g[f"{name}__query"], dewi32, ent32, k, eta, pref, space)
+        want_ids, want_sc = g[f"{name}__ids"], g[f"{name}__scores"]
+        z = int(np.isnan(want_sc).sum())
+        assert z > 0 and np.isnan(want_sc[k - z:]).all() and not np.isnan(want_sc[: k - z]).any(), name
+        assert np.array_equal(sc.view(np.uint32)[: k - z], want_sc.view(np.uint32)[: k - z]) and np.isnan(sc[k - z:]).all(), name
+        assert np.array_equal(ids[: k - z], want_ids[: k - z]), name
+        cand = set(g[f"{name}__nan_candidates"].tolist())
+        if bool(g[f"{name}__tail_is_a_choice"]):
+            assert z == k < len(cand) and set(ids.tolist()) <= cand and set(want_ids.tolist()) <= cand, name
+        else:
+            assert set(ids[k - z:].tolist()) == set(want_ids[k - z:].tolist()) == cand, name
+    assert any(bool(g[f"{n}__tail_is_a_choice"]) for n in names) and not all(bool(g[f"{n}__tail_is_a_choice"]) for n in names)

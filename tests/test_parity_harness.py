@@ -121,3 +121,82 @@ def test_l2_and_prepared_modes():
     out = [orc.search_prepared(Eb, q, dewi32[:400], ent32[:400], 5, 0.3, 0.0) for q in Qp]
     ids, sc = np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
     parity.check_batch(Eb, Qp, dewi32[:400], ent32[:400], 5, 0.3, 0.0, "cosine", ids, sc, prepared=True, min_decisive_frac=0.5)
+
+
+def _nan_case(space="cosine", k=5, eta=0.3):
+    """300 x 64 rows, rows 17 and 200 zero (cosine: stored as NaN rows) or NaN (l2), a NaN dewi on a row inside the cut of
+    query 0."""
+    rs = np.random.RandomState(9)
+    raw = rs.randn(300, 64).astype(np.float32)
+    raw[[17, 200]] = 0.0 if space == "cosine" else np.nan
+    E = orc.build_matrix(raw, space)
+    cols = orc.synth_payload_columns(300, seed=9)
+    dewi32, ent32 = orc.payload_soa(cols["dewi"], cols["ht_mean"], cols["hi_mean"])
+    Q = rs.randn(6, 64).astype(np.float32)
+    out = [orc.search(E, q, dewi32, ent32, k, eta, 0.0, space) for q in Q]
+    return E, dewi32, ent32, Q, np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
+
+
+@pytest.mark.parametrize("space", ["cosine", "l2"])
+def test_nan_rows_oracle_answer_passes_and_is_decisive(space):
+    k, eta = 5, 0.3
+    E, dewi32, ent32, Q, ids, sc = _nan_case(space, k, eta)
+    assert np.isnan(sc[:, -2:]).all() and not np.isnan(sc[:, :-2]).any()           # the reference: NaN last
+    assert all(set(r[-2:].tolist()) == {17, 200} for r in ids)
+    n_dec = parity.check_batch(E, Q, dewi32, ent32, k, eta, 0.0, space, ids, sc)
+    assert n_dec == Q.shape[0] == parity.count_decisive(E, Q, dewi32, ent32, k, eta, 0.0, space)
+    # the tail is compared as a set: its internal order is an artefact of the reference's introselect
+    sw = ids.copy()
+    sw[:, [-2, -1]] = sw[:, [-1, -2]]
+    assert parity.check_batch(E, Q, dewi32, ent32, k, eta, 0.0, space, sw, sc) == Q.shape[0]
+
+
+@pytest.mark.parametrize("gap", [parity.GAP, 0.5])        # decisive, and every query forced onto the near-tie rules
+def test_nan_rows_rotated_to_the_front_fail(gap):
+    k, eta = 5, 0.3
+    E, dewi32, ent32, Q, ids, sc = _nan_case("cosine", k, eta)
+    for j in range(Q.shape[0]):
+        dec, msg = parity.compare_query(E, Q[j], dewi32, ent32, k, eta, 0.0, "cosine", np.roll(ids[j], 2), np.roll(sc[j], 2), gap=gap)
+        assert dec == (gap == parity.GAP) and msg is not None and "not the tail" in msg
+        # one NaN in front, one behind
+        dec, msg = parity.compare_query(E, Q[j], dewi32, ent32, k, eta, 0.0, "cosine", np.roll(ids[j], 1), np.roll(sc[j], 1), gap=gap)
+        assert msg is not None and "not the tail" in msg
+
+
+@pytest.mark.parametrize("gap", [parity.GAP, 0.5])
+def test_nan_row_dropped_fails(gap):
+    k, eta = 5, 0.3
+    E, dewi32, ent32, Q, ids, sc = _nan_case("cosine", k, eta)
+    for j in range(Q.shape[0]):
+        # the next best number takes the place of NaN row 17 (or 200): a well-formed result that lost a NaN candidate
+        more_ids, more_sc = orc.search(E, Q[j], dewi32, ent32, k + 1, eta, 0.0)
+        numbers = [(int(i), s) for i, s in zip(more_ids, more_sc) if not np.isnan(s)]
+        extra = next((i, s) for i, s in numbers if i not in set(ids[j].tolist()))
+        front = sorted(list(zip(ids[j][:3].tolist(), sc[j][:3].tolist())) + [extra], key=lambda r: -r[1])
+        wrong_ids = np.array([r[0] for r in front] + ids[j][4:].tolist(), np.int64)
+        wrong_sc = np.array([r[1] for r in front] + sc[j][4:].tolist(), np.float32)
+        msg = parity.compare_query(E, Q[j], dewi32, ent32, k, eta, 0.0, "cosine", wrong_ids, wrong_sc, gap=gap)[1]
+        assert msg is not None and ("missing from the tail" in msg or "ids differ" in msg), msg
+        # a number claimed for a NaN row
+        fake_sc = sc[j].copy()
+        fake_sc[3] = fake_sc[2] - 1e-3
+        msg = parity.compare_query(E, Q[j], dewi32, ent32, k, eta, 0.0, "cosine", ids[j], fake_sc, gap=gap)[1]
+        assert msg is not None
+
+
+def test_nan_payload_values_form_the_tail_too():
+    """NaN dewi on rows with a finite similarity inside the cut; eta = 0 with an infinite dewi (0 * inf); NaN ent with pref."""
+    k = 6
+    E, dewi32, ent32, Q, _, _ = _nan_case("cosine", k, 0.3)
+    for eta, pref, column, value in [(0.3, 0.0, "dewi", np.nan), (0.0, 0.0, "dewi", np.inf), (0.4, 0.2, "ent", np.nan)]:
+        for j in range(Q.shape[0]):
+            d, e = dewi32.copy(), ent32.copy()
+            s = orc.similarities(E, orc.prepare_query(Q[j]))
+            row = int(np.argsort(-np.where(np.isnan(s), -np.inf, s))[2])       # third best finite similarity
+            (d if column == "dewi" else e)[row] = value
+            ids, sc = orc.search(E, Q[j], d, e, k, eta, pref)
+            assert set(ids[-3:].tolist()) == {17, 200, row} and np.isnan(sc[-3:]).all()
+            dec, msg = parity.compare_query(E, Q[j], d, e, k, eta, pref, "cosine", ids, sc)
+            assert msg is None
+            dec, msg = parity.compare_query(E, Q[j], d, e, k, eta, pref, "cosine", np.roll(ids, 3), np.roll(sc, 3))
+            assert msg is not None and "not the tail" in msg
