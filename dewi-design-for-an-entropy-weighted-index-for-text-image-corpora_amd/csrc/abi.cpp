@@ -1381,6 +1381,37 @@ int dewi_merge_rerank(const dewi_candidate* d_lists, int n_lists, int n_queries,
   return launched(e, "merge_rerank launch");
 }
 
+// The lazy MMR re-rank keeps all of a query's state in LDS: no workspace for any shape it takes (and 0 for a bad one).
+size_t dewi_diverse_workspace_bytes(int n_queries, int n_candidates, int dim) {
+  (void)n_queries; (void)n_candidates; (void)dim;
+  return 0;
+}
+
+int dewi_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows, int dim, const dewi_candidate* d_cand, int n_queries,
+                        int n_candidates, int k, double eta, double entropy_pref, double mmr_lambda, double max_sim,
+                        int64_t id_offset, int64_t* d_out_ids, float* d_out_scores, float* d_out_mmr, void* d_workspace,
+                        size_t workspace_bytes, void* stream) {
+  if (!d_E || !d_cand || !d_out_ids || !d_out_scores) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
+  if (n_queries <= 0 || n_candidates <= 0)
+    return fail(DEWI_ERR_INVALID_ARG, "non-positive size (%d queries, %d candidates)", n_queries, n_candidates);
+  if (int rc = check_elem_type(elem_type)) return rc;
+  if (!(mmr_lambda >= 0.0 && mmr_lambda <= 1.0)) return fail(DEWI_ERR_INVALID_ARG, "mmr_lambda %g outside [0, 1]", mmr_lambda);
+  if (max_sim != max_sim) return fail(DEWI_ERR_INVALID_ARG, "max_sim is NaN");
+  if (k <= 0) return DEWI_OK;
+  if (k > n_candidates) return fail(DEWI_ERR_K_OUT_OF_BOUNDS, "k %d exceeds candidate count %d", k, n_candidates);
+  if (n_candidates > DEWI_DIVERSE_MAX_CANDIDATES)
+    return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds the %d a diverse re-rank takes", n_candidates,
+                DEWI_DIVERSE_MAX_CANDIDATES);
+  if (const size_t need = dewi_diverse_workspace_bytes(n_queries, n_candidates, dim))
+    if (int rc = check_workspace(d_workspace, workspace_bytes, need)) return rc;
+  return launched(dewi::launch_diverse_rerank(d_E, elem_type, n_rows, dim, d_cand, n_queries, n_candidates, k,
+                                              make_rerank(eta, entropy_pref), static_cast<float>(mmr_lambda),
+                                              static_cast<float>(1.0 - mmr_lambda), static_cast<float>(max_sim), id_offset,
+                                              d_out_ids, d_out_scores, d_out_mmr, static_cast<hipStream_t>(stream)),
+                  "diverse_rerank launch");
+}
+
 size_t dewi_robust_fit_workspace_bytes(int n_signals) {
   return n_signals > 0 ? dewi::robust_fit_workspace_bytes(n_signals) : 0;
 }

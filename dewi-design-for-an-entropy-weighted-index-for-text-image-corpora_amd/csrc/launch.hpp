@@ -408,6 +408,15 @@ hipError_t launch_groups_union_pairs(const GroupsLayout& L, int64_t n_rows, cons
 hipError_t launch_groups_finish(const GroupsLayout& L, int64_t n_rows, int keep, const float* d_key, int64_t id_offset,
                                 int64_t* d_labels, int64_t* d_sizes, int64_t* d_reps, char* ws, hipStream_t stream);
 
+// ---- diverse.hip: greedy MMR re-rank of candidate records, one workgroup per query (no workspace)
+constexpr int kDiverseMaxCandidates = DEWI_DIVERSE_MAX_CANDIDATES;
+// lam / one_minus_lam / max_sim: fp32(lambda), fp32(1 - lambda), fp32(max_sim) (+inf: no cut); d_out_mmr may be NULL.
+// 1 <= k <= n_candidates <= kDiverseMaxCandidates.
+hipError_t launch_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows, int dim, const dewi_candidate* d_cand,
+                                 int n_queries, int n_candidates, int k, const RerankParams& rp, float lam, float one_minus_lam,
+                                 float max_sim, int64_t id_offset, int64_t* d_out_ids, float* d_out_scores, float* d_out_mmr,
+                                 hipStream_t stream);
+
 // ---- ingest.hip ---------------------------------------------------------------------------
 hipError_t launch_normalize_rows(const float* d_src, float* d_dst, int64_t n_rows, int dim, hipStream_t stream);
 hipError_t launch_row_cosine(const float* d_a, const float* d_b, float* d_out, int64_t n_rows, int dim, float eps,

@@ -981,6 +981,67 @@ class DeviceCorpus:
         nat.check(rc)
         return out
 
+    # ------------------------------------------------------------------ diverse search (MMR)
+    def search_diverse_device(self, q_dev, k: int, eta: float, entropy_pref: float, mmr_lambda: float = 0.5,
+                              candidates: Optional[int] = None, max_sim: Optional[float] = None, out_ids=None,
+                              out_scores=None):
+        """Enqueue one DIVERSE search on the current stream; returns device tensors ``(ids, scores)`` [B, k], no sync.
+
+        The pool is the search's own candidate cut — ``candidates_device``: the ``candidates`` most similar rows of every
+        query (default ``4k``, at most N and ``DIVERSE_MAX_CANDIDATES``) — and ``dewi_diverse_rerank`` picks from it
+        greedily by maximal marginal relevance: ``mmr_lambda * adjusted score - (1 - mmr_lambda) * (largest inner product
+        with a row already picked)``; a candidate at least ``max_sim`` similar to a picked row is struck out (``None``: no
+        such cut).  Results are in PICK order; ``scores`` are the adjusted scores ``search_device`` returns.  ``mmr_lambda =
+        1`` without ``max_sim`` is the plain search over that pool.  A query with fewer than k eligible rows leaves id -1 /
+        score NaN in the tail of its row.  Cosine corpora (``space="l2"``: ``NotImplementedError`` — the
+        penalty is an inner product of unit rows), fp32 and bf16.  NOT thread-safe on one instance (shared workspaces)."""
+        torch = _torch()
+        n = self.n_rows
+        b, k = check_search_args(q_dev.shape, self.dim, k, None, "ip")
+        if self.space == "l2":
+            raise NotImplementedError("diverse search penalises the inner product of unit rows: space='l2' is not in this build")
+        lam = float(mmr_lambda)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"mmr_lambda must lie in [0, 1], got {mmr_lambda}")
+        cut = float("inf") if max_sim is None else float(max_sim)
+        if cut != cut:
+            raise ValueError("max_sim must not be NaN")
+        if candidates is not None and int(candidates) > nat.DIVERSE_MAX_CANDIDATES:
+            raise NotImplementedError(f"diverse search takes pools of at most {nat.DIVERSE_MAX_CANDIDATES} candidates, "
+                                      f"got {int(candidates)}")
+        if k <= 0:
+            return empty_result(b, self.device)
+        c = min(cut_size(k, 4 * k if candidates is None else int(candidates), n), nat.DIVERSE_MAX_CANDIDATES)
+        if k > c:
+            raise ValueError(f"k = {k} exceeds the pool of {c} candidates")
+        out_ids, out_scores = default_outputs(b, k, self.device, out_ids, out_scores)
+        if max_sim is not None:         # (without the cut every query picks k of its c >= k records: nothing is left unwritten)
+            out_ids.fill_(-1)
+            out_scores.fill_(float("nan"))
+        recs = self.candidates_device(q_dev, c)
+        need = int(self._lib.dewi_diverse_workspace_bytes(b, c, self.dim))    # 0: the re-rank keeps its state on chip
+        ws = None
+        if need:
+            ws = self._cached_workspace(("diverse", b, c), self._lib.dewi_diverse_workspace_bytes, b, c, self.dim)
+        rc = self._lib.dewi_diverse_rerank(
+            nat.ptr(self.emb), self._elem, n, self.dim, nat.ptr(recs), b, c, k, float(eta), float(entropy_pref), lam, cut,
+            self.id_offset, nat.ptr(out_ids), nat.ptr(out_scores), None, nat.ptr(ws) if ws is not None else None,
+            ws.numel() if ws is not None else 0, nat.stream_ptr())
+        nat.check(rc)
+        return out_ids, out_scores
+
+    def search_diverse(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                       mmr_lambda: float = 0.5, candidates: Optional[int] = None,
+                       max_sim: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Blocking twin of ``search`` for ``search_diverse_device``: (ids int64 [B, k] — global, as the candidate records
+        carry them —, scores fp32 [B, k]) on the host, in pick order; the tail of a short row holds id -1 / score NaN.  Safe to
+        call from several threads on one instance (serialised by the per-corpus lock)."""
+        torch = _torch()
+        with self._lock, torch.cuda.device(self.device):
+            q = self.stage_queries(queries)
+            ids_d, sc_d = self.search_diverse_device(q, k, eta, entropy_pref, mmr_lambda, candidates, max_sim)
+            return ids_d.cpu().numpy(), sc_d.cpu().numpy()
+
 
 class PipelinedSearcher:
     """Two query batches in flight on one GPU (throughput mode).

@@ -36,6 +36,8 @@ ABI_VERSION = 6
 RANGE_MAX_QUERIES = 32
 #: most queries one dewi_knn_range_shadow_count call takes (DEWI_RANGE_SHADOW_MAX_QUERIES: 8 groups of 256)
 RANGE_SHADOW_MAX_QUERIES = 2048
+#: largest candidate pool of a diverse (MMR) re-rank (include/dewi_hip.h DEWI_DIVERSE_MAX_CANDIDATES)
+DIVERSE_MAX_CANDIDATES = 1024
 #: which row of a group represents it (include/dewi_hip.h DEWI_GROUPS_KEEP_*): the lowest row / the highest key (the dewi column)
 KEEP_CODES = {"first": 0, "dewi": 1}
 
@@ -55,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "dewi_knn_range_shadow_supported", "dewi_knn_range_shadow_workspace_bytes", "dewi_knn_range_shadow_count",
     "dewi_knn_range_shadow_collect",
     "dewi_groups_workspace_bytes", "dewi_groups_begin", "dewi_groups_union_lists", "dewi_groups_union_pairs", "dewi_groups_finish",
+    "dewi_diverse_workspace_bytes", "dewi_diverse_rerank",
 )
 
 
@@ -193,6 +196,10 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_groups_union_pairs.argtypes = [i64, vp, vp, i64, vp, sz, vp]
     lib.dewi_groups_finish.restype = i32
     lib.dewi_groups_finish.argtypes = [i64, i32, vp, i64, vp, vp, vp, c.POINTER(i64), c.POINTER(i64), vp, sz, vp]
+    lib.dewi_diverse_workspace_bytes.restype = sz
+    lib.dewi_diverse_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.dewi_diverse_rerank.restype = i32
+    lib.dewi_diverse_rerank.argtypes = [vp, i32, i64, i32, vp, i32, i32, i32, f64, f64, f64, f64, i64, vp, vp, vp, vp, sz, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

@@ -589,6 +589,38 @@ class ExactIndex(BaseIndex):
         return self._corpus.search(q, int(k), float(eta), float(entropy_pref), candidates=candidates,
                                    similarity=similarity)
 
+    # ---------------------------------------------------------------- diverse search (additive)
+    def search_diverse(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                       mmr_lambda: float = 0.5, candidates: Optional[int] = None,
+                       max_sim: Optional[float] = None) -> SearchResult:
+        """``search`` with a per-query guard against near-duplicates (additive; the reference has no such method): maximal
+        marginal relevance (Carbonell & Goldstein 1998) over the query's ``candidates`` most similar documents (default
+        ``4k``, at most 1024).  Results are picked one by one, each the candidate with the largest ``mmr_lambda * adjusted
+        score - (1 - mmr_lambda) * (largest similarity to a document already picked)``; a candidate at least ``max_sim``
+        similar to a picked document is struck out, so the answer may be shorter than k.  Returns ``(doc_id, adjusted score,
+        Payload)`` tuples like ``search``, here IN PICK ORDER.  ``mmr_lambda=1.0, max_sim=0.95`` is the plain ranking of the
+        pool with every later copy of an earlier result removed; ``mmr_lambda=1.0`` alone is ``search(candidates=...)``.
+        Cosine indexes (``space="l2"``: ``NotImplementedError``); no ``filter`` in this build."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        rows, scores = self.search_diverse_batch(q[:1], k, eta, entropy_pref, mmr_lambda, candidates, max_sim)
+        keep = rows[0] >= 0             # (fewer than k eligible documents: the tail is padded with id -1)
+        return self.results_for(rows[:1][:, keep], scores[:1][:, keep])[0]
+
+    def search_diverse_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                             mmr_lambda: float = 0.5, candidates: Optional[int] = None,
+                             max_sim: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k]) in pick order; a query with fewer
+        than k eligible documents pads its row with id -1 and score NaN, as per-query filters do.  See ``search_diverse``."""
+        if self.space == "l2":
+            raise NotImplementedError("diverse search penalises the inner product of unit rows: space='l2' is not in this build")
+        self._ensure_built()
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        return self._corpus.search_diverse(q, int(k), float(eta), float(entropy_pref), float(mmr_lambda), candidates, max_sim)
+
     # ---------------------------------------------------------------- range search (additive)
     def range_search(self, query: np.ndarray, threshold: float, eta: float = 0.5, entropy_pref: float = 0.0, filter=None,
                      max_results: Optional[int] = None) -> SearchResult:

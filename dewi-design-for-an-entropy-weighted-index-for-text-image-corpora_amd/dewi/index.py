@@ -117,6 +117,34 @@ class DewiIndex(BaseIndex):
             rows, scores = self._backend.search_batch(q, k, eta, entropy_pref)
         return self._backend.results_for(rows, scores)
 
+    def search_diverse(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
+                       entropy_pref: Optional[float] = None, mmr_lambda: float = 0.5, candidates: Optional[int] = None,
+                       max_sim: Optional[float] = None) -> List[Tuple[str, float, Payload]]:
+        """``search`` re-ranked for diversity (additive; ``ExactIndex.search_diverse``): maximal marginal relevance over
+        the ``candidates`` most similar documents (default ``4k``), results in pick order, possibly fewer than k when
+        ``max_sim`` strikes candidates out."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.shape != (self.dim,):
+            raise ValueError(f"Expected query shape ({self.dim},), got {q.shape}")
+        return self.search_diverse_batch(q.reshape(1, -1), k, eta, entropy_pref, mmr_lambda, candidates, max_sim)[0]
+
+    def search_diverse_batch(self, queries: np.ndarray, k: int = 10, eta: Optional[float] = None,
+                             entropy_pref: Optional[float] = None, mmr_lambda: float = 0.5, candidates: Optional[int] = None,
+                             max_sim: Optional[float] = None) -> List[List[Tuple[str, float, Payload]]]:
+        """One call for B queries ([B, dim]); each result list equals ``search_diverse`` of that row."""
+        eta, entropy_pref = self._defaults(eta, entropy_pref)
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        if self.space == "l2":
+            raise NotImplementedError("diverse search penalises the inner product of unit rows: space='l2' is not in this build")
+        if not self._built:
+            self.build()
+        rows, scores = self._backend.search_diverse_batch(q, k, eta, entropy_pref, mmr_lambda, candidates, max_sim)
+        n_real = (rows >= 0).sum(axis=1)           # fewer than k eligible documents: the tail is padded with id -1
+        res = self._backend.results_for(np.where(rows < 0, 0, rows), scores)
+        return [r[:int(m)] for r, m in zip(res, n_real)]
+
     def range_search(self, query: np.ndarray, threshold: float, eta: Optional[float] = None,
                      entropy_pref: Optional[float] = None, filter=None,
                      max_results: Optional[int] = None) -> List[Tuple[str, float, Payload]]:

@@ -59,6 +59,10 @@ class IVFIndex(ExactIndex):
 
     ``duplicate_groups`` / ``dedup_filter`` are inherited as well and exact.  ``search(..., filter=dedup_filter(...))`` on
     this class is what any user filter is here: the parent's exact filtered search over the whole allow-list, not a probe.
+
+    ``search_diverse`` / ``search_diverse_batch`` are ``ExactIndex``'s too, in their EXACT form: the candidate pool is the
+    exact cut over every row, not over the probed cells, and there is no ``nprobe`` argument.  A diverse search over an IVF
+    probe is not part of this build.
     """
 
     def __init__(self, dim: int, space: str = "cosine", nlist: Optional[int] = None, nprobe: Optional[int] = None,

@@ -458,6 +458,62 @@ int dewi_merge_rerank(const dewi_candidate* d_lists, int n_lists, int n_queries,
                       float* d_out_scores, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Diverse search (additive to ABI 6; the reference has no such method): a greedy MMR re-rank (maximal marginal relevance,
+ * Carbonell & Goldstein 1998) of the candidate cut a search has already computed.  It picks results one by one, trading each
+ * candidate's blended score against its similarity to what is already picked.
+ *
+ * Input per query: `n_candidates` = c candidate records in dewi_knn_candidates' layout and order (d_cand [n_queries][c]).
+ * Records with id < 0 are padding at the tail.
+ * Padding and rank:
+ *   - A record whose id - id_offset lies outside [0, n_rows) is treated as padding.  The kernel never forms that row's address.
+ *   - Candidate rank t is the position among the valid records, t = 0 .. n_sel - 1.
+ * Arithmetic:
+ *   1. adj_t = blend(sim, dewi, ent), exactly as step 4 of the search with DEWI_SIM_RAW.  Products are rounded once; the ent
+ *      term is added only if entropy_pref != 0.
+ *   2. g(t, s) is the fp32 inner product of the stored rows (d_E, elem_type 0 fp32 / 1 bf16) of candidates t and s.  bf16
+ *      corpus: elements are widened to fp32, products are exact, accumulation is fp32.  The summation order is fixed, the same
+ *      for every pair and symmetric in (t, s): units of 16 bytes' worth of elements (4 fp32 / 8 bf16), unit u on lane u % 16
+ *      of 16, a lane's elements in ascending order with acc = fma(a, b, acc), the 16 sums added by the xor butterfly 8, 4, 2,
+ *      1.  It does not depend on k, c, the batch size, the query's position in the batch, the step at which the pair is
+ *      evaluated, or the alignment of d_E.
+ *   3. Greedy selection over steps j = 0, 1, ...
+ *      - pen_t = max over already picked s of g(t, s), ignoring NaN values (fmaxf semantics).
+ *      - If no picked row gave a number (including step 0): m_t = fp32(lambda) * adj_t.
+ *      - Otherwise: m_t = fp32(lambda) * adj_t - fp32(1 - lambda) * pen_t.  That is two products, each rounded once, and one
+ *        subtraction; no contraction.
+ *      - A candidate is INELIGIBLE while pen_t is a number and pen_t >= fp32(max_sim).  max_sim = +inf (any max_sim that
+ *        rounds to +inf in fp32) disables this rule.
+ *      - Pick the eligible unpicked candidate first in the order (ord(m_t) desc, t asc).  NaN counts as the largest value and
+ *        -0 == +0, exactly as step 5 of the search.
+ *      - Stop after k picks or when nothing is eligible.  Call the number of picks kk.
+ *   4. Output.
+ *      - The picks are written in pick order, with the picks whose m was NaN moved behind the numbers, keeping their own pick
+ *        order.
+ *      - d_out_ids [n_queries][k] holds the global id as in the record.
+ *      - d_out_scores [n_queries][k] holds adj_t, the same quantity the search returns, with -0 written as +0 as there.
+ *      - If d_out_mmr is not NULL, it receives m_t as it stood at the pick.
+ *      - Positions kk .. k-1 of every output are NOT written, as everywhere else in this ABI.
+ * Two consequences: lambda = 1 with max_sim = +inf returns exactly what dewi_merge_rerank returns for the same records with
+ * n_candidates = c (ids and scores, NaN rows included); lambda = 1 with max_sim = tau returns the plain ranking with every
+ * result dropped that lies within tau of an earlier result.
+ *
+ * One workgroup per query; after every pick each candidate that can still be picked takes one dot product against the
+ * picked row (k * c dots, no c^2 table), so dewi_diverse_workspace_bytes is 0 for every shape and d_workspace may be NULL.
+ * Any dim, any element-aligned d_E (16-byte loads where dim is whole 16-byte units and d_E is 16-byte aligned, element loads
+ * otherwise; nothing outside the rows is touched).  1 <= k <= n_candidates <= DEWI_DIVERSE_MAX_CANDIDATES.
+ * Asynchronous on `stream`; no allocation, no synchronisation.  Argument errors are reported before any device work: null
+ * pointers, a bad shape, an unknown elem_type, mmr_lambda outside [0, 1] or NaN, a NaN max_sim: DEWI_ERR_INVALID_ARG;
+ * k > n_candidates: DEWI_ERR_K_OUT_OF_BOUNDS; n_candidates > DEWI_DIVERSE_MAX_CANDIDATES: DEWI_ERR_UNSUPPORTED; a workspace
+ * below dewi_diverse_workspace_bytes: DEWI_ERR_WORKSPACE.  k <= 0 writes nothing and returns DEWI_OK.
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_DIVERSE_MAX_CANDIDATES 1024
+size_t dewi_diverse_workspace_bytes(int n_queries, int n_candidates, int dim);
+int dewi_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows, int dim, const dewi_candidate* d_cand, int n_queries,
+                        int n_candidates, int k, double eta, double entropy_pref, double mmr_lambda, double max_sim,
+                        int64_t id_offset, int64_t* d_out_ids, float* d_out_scores, float* d_out_mmr, void* d_workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A6  robust statistics — replaces scorer.RobustStats.fit (scorer.py:18-26) for n_signals
  * columns of n fp32 values each, stored SoA: column s starts at d_S + s*ld.
  *   med[s] = np.median(col)            exact fp32 order statistic; even n: fp32 (a+b)/2
