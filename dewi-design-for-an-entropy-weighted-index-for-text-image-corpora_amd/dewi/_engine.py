@@ -327,6 +327,22 @@ class DeviceCorpus:
         self._ws[key] = (ws, epoch)
         return ws
 
+    def cached_workspaces(self) -> Dict[tuple, "torch.Tensor"]:  # noqa: F821
+        """Tests / diagnostics: key -> workspace tensor of every entry ``_cached_workspace`` holds (a copy of the table)."""
+        return {key: hit[0] for key, hit in self._ws.items()}
+
+    def replace_cached_workspace(self, key, ws) -> None:
+        """Tests: put ``ws`` (uint8, at least as large as the entry it replaces) under ``key``, keeping the tuning epoch the
+        entry was sized under — the next call under that tuning runs in ``ws`` without asking the size again."""
+        old, epoch = self._ws[key]
+        if ws.numel() < old.numel():
+            raise ValueError(f"workspace {key}: {ws.numel()} bytes replace {old.numel()}")
+        self._ws[key] = (ws, epoch)
+
+    def drop_cached_workspaces(self) -> None:
+        """Tests: forget every cached workspace (the next call of each shape allocates afresh)."""
+        self._ws.clear()
+
     def _workspace(self, n_queries: int, n_candidates: int):
         return self._cached_workspace((n_queries, n_candidates), self._lib.dewi_knn_workspace_bytes, self.n_rows, self.dim,
                                       n_queries, n_candidates)

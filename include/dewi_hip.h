@@ -126,6 +126,12 @@ int dewi_payload_soa_f64(const double* d_dewi, const double* d_ht_mean, const do
  * dewi_knn_finish, dewi_knn_candidates — enqueues, behind the pass's select and on the same stream, two fixed-shape
  * REPAIR launches that read the per-query refusal flags from the workspace and answer the flagged queries on the
  * exact row kernels (they return at once when no flag is set).  No id -1 / -2 marker ever reaches the caller.
+ *
+ * WORKSPACE CONTRACT (this and every other dewi_*_workspace_bytes / dewi_*_bytes buffer a call works in): a workspace's
+ * contents on entry are undefined — each call writes or zeroes every region before it reads it, so a buffer may arrive
+ * holding anything ("Workspace regions"; the two-call forms — scan / finish, count / collect, the dewi_groups_*
+ * and dewi_robust_fit_* steps — keep their state in it between their own calls only).  No call reads or writes outside
+ * [d_workspace, d_workspace + workspace_bytes) or outside its declared outputs.
  * ------------------------------------------------------------------------------------------ */
 size_t dewi_knn_workspace_bytes(int64_t n_rows, int dim, int n_queries, int n_candidates);
 

@@ -157,6 +157,37 @@ def test_workspace_cache_eviction_beyond_eight_entries():
     assert cached(c, (1, 20), size, 1) is not first[0] and len(c._ws) == 2
 
 
+def test_workspace_cache_accessors(tuning):
+    """``cached_workspaces`` / ``replace_cached_workspace`` / ``drop_cached_workspaces`` (what tests/wsguard.py swaps the
+    tensors through): a copy of the table, the tuning epoch of the entry kept, a smaller tensor refused, the cache emptied."""
+    import torch
+    dc = _eng().DeviceCorpus
+    c, size = _corpus(), _Sizes(100)
+    tuning(scan_blocks=8)                             # an epoch other than the defaults' 0
+    ws = dc._cached_workspace(c, (2, 20), size, 2)
+    other = dc._cached_workspace(c, ("range", 3, 9), size, 3)
+    epoch = c._ws[(2, 20)][1]
+    assert epoch != 0
+    table = dc.cached_workspaces(c)
+    assert list(table) == [(2, 20), ("range", 3, 9)] and table[(2, 20)] is ws and table[("range", 3, 9)] is other
+    table.clear()                                     # a copy: the cache itself is untouched
+    assert len(c._ws) == 2
+    big = torch.zeros(4096 + 100 + 4096, dtype=torch.uint8)
+    view = big[4096: 4096 + 100]
+    dc.replace_cached_workspace(c, (2, 20), view)
+    assert c._ws[(2, 20)][0] is view and c._ws[(2, 20)][1] == epoch
+    assert dc._cached_workspace(c, (2, 20), size, 2) is view and len(size.calls) == 2          # a hit: no size call, the view stays
+    assert c._ws[("range", 3, 9)][0] is other
+    with pytest.raises(ValueError, match=r"99 bytes replace 100"):
+        dc.replace_cached_workspace(c, (2, 20), big[:99])
+    assert c._ws[(2, 20)][0] is view
+    with pytest.raises(KeyError):
+        dc.replace_cached_workspace(c, (7, 7), view)
+    dc.drop_cached_workspaces(c)
+    assert c._ws == {} and dc.cached_workspaces(c) == {}
+    assert dc._cached_workspace(c, (2, 20), size, 2) is not view and len(size.calls) == 3      # allocated afresh
+
+
 def test_workspace_cache_epochs_belong_to_threads(tuning):
     """A tuning() in another thread leaves this thread's entry valid, and the other way round; a fresh thread — whatever
     ident it gets — starts from the defaults' epoch, not from a dead thread's."""
