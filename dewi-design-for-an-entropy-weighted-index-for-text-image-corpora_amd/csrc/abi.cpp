@@ -1506,6 +1506,48 @@ int dewi_score_f64_dev(const void* d_S, int signals_are_f64, int64_t n, int64_t 
   return score_impl(d_S, signals_are_f64, n, ld, nullptr, nullptr, d_med, d_mad, weights, delta, mode, d_out, d_out32, stream);
 }
 
+// ---- in-place mutation (mutate.hip): additive, the reference has no counterpart ------------------------------------------
+int dewi_rows_move(void* d_E, int elem_type, void* d_E_bf16, float* d_dewi32, float* d_ent32, int32_t* d_aux_i32,
+                   int64_t n_rows, int dim, int64_t n_keep, const int64_t* d_src, const int64_t* d_dst, int64_t n_moves,
+                   int32_t* d_error, void* stream) {
+  if (int rc = check_elem_type(elem_type)) return rc;
+  if (dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "dim must be positive (got %d)", dim);
+  if (n_rows < 0 || n_keep < 0 || n_moves < 0)
+    return fail(DEWI_ERR_INVALID_ARG, "negative count (n_rows %lld, n_keep %lld, n_moves %lld)", static_cast<long long>(n_rows),
+                static_cast<long long>(n_keep), static_cast<long long>(n_moves));
+  if (n_keep > n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_keep %lld exceeds n_rows %lld", static_cast<long long>(n_keep), static_cast<long long>(n_rows));
+  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (elem_type == 1 && d_E_bf16) return fail(DEWI_ERR_INVALID_ARG, "a bf16 main matrix takes no bf16 shadow");
+  if (n_moves > n_rows - n_keep || n_moves > n_keep)
+    return fail(DEWI_ERR_INVALID_ARG, "n_moves %lld exceeds the %lld rows above n_keep or the %lld below it", static_cast<long long>(n_moves),
+                static_cast<long long>(n_rows - n_keep), static_cast<long long>(n_keep));
+  if (n_moves == 0) return DEWI_OK;
+  if (!d_E || !d_dewi32 || !d_ent32 || !d_src || !d_dst || !d_error) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  return launched(dewi::launch_rows_move(d_E, elem_type, static_cast<uint16_t*>(d_E_bf16), d_dewi32, d_ent32, d_aux_i32, n_rows, dim,
+                                         n_keep, d_src, d_dst, n_moves, d_error, static_cast<hipStream_t>(stream)),
+                  "rows_move launch");
+}
+
+int dewi_rows_put_f32(float* d_E, void* d_E_bf16, float* d_dewi32, float* d_ent32, int64_t capacity_rows, int dim, int normalize,
+                      const float* d_raw, const double* d_dewi, const double* d_ht_mean, const double* d_hi_mean,
+                      const int64_t* d_rows, int64_t n_put, int32_t* d_error, void* stream) {
+  if (dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "dim must be positive (got %d)", dim);
+  if (capacity_rows < 0 || n_put < 0)
+    return fail(DEWI_ERR_INVALID_ARG, "negative count (capacity_rows %lld, n_put %lld)", static_cast<long long>(capacity_rows),
+                static_cast<long long>(n_put));
+  if (capacity_rows > 0xFFFFFFFFll)
+    return fail(DEWI_ERR_UNSUPPORTED, "capacity_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(capacity_rows));
+  if (n_put > capacity_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_put %lld exceeds capacity_rows %lld", static_cast<long long>(n_put), static_cast<long long>(capacity_rows));
+  if (n_put == 0) return DEWI_OK;
+  if (!d_E || !d_dewi32 || !d_ent32 || !d_raw || !d_dewi || !d_ht_mean || !d_hi_mean || !d_rows || !d_error)
+    return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  return launched(dewi::launch_rows_put(d_E, static_cast<uint16_t*>(d_E_bf16), d_dewi32, d_ent32, capacity_rows, dim, normalize, d_raw,
+                                        d_dewi, d_ht_mean, d_hi_mean, d_rows, n_put, d_error, static_cast<hipStream_t>(stream)),
+                  "rows_put launch");
+}
+
 int dewi_timing_enable(int every) {
   g_timing.every = every > 0 ? every : 0;
   g_timing.calls = 0;

@@ -142,6 +142,22 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
   return (static_cast<uint64_t>(mhi) << 32) | mlo;
 }
 
+// ---------------------------------------------------------------------------------------------
+// What the ingest kernels (ingest.hip) and the row writer (mutate.hip) store, defined once so that a row written in place
+// holds the bits a fresh build would have given it.
+// ---------------------------------------------------------------------------------------------
+// fp32 -> bf16, round to nearest even; NaN stays NaN (quiet bit forced).
+__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
+  const uint32_t u = __float_as_uint(f);
+  if (f != f) return static_cast<uint16_t>((u >> 16) | 0x0040u);
+  return static_cast<uint16_t>((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+// The two fp32 payload columns of the re-rank from the float64 triple (dewi_payload_soa_f64).
+__device__ __forceinline__ float payload_dewi32(double dewi) { return static_cast<float>(dewi); }
+__device__ __forceinline__ float payload_ent32(double ht_mean, double hi_mean) {
+  return static_cast<float>(__dmul_rn(__dadd_rn(ht_mean, hi_mean), 0.5));
+}
+
 __device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & (kWave - 1); }
 
 }  // namespace dewi

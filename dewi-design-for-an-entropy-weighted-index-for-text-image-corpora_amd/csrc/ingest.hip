@@ -191,13 +191,6 @@ hipError_t launch_row_cosine(const float* d_a, const float* d_b, float* d_out, i
   return hipGetLastError();
 }
 
-// fp32 -> bf16, round to nearest even; NaN stays NaN (quiet bit forced).
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if (f != f) return static_cast<uint16_t>((u >> 16) | 0x0040u);
-  return static_cast<uint16_t>((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst,
                                                           int64_t n) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
@@ -219,8 +212,8 @@ __global__ __launch_bounds__(256) void payload_soa_kernel(const double* __restri
                                                           float* __restrict__ ent32, int64_t n) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
-    dewi32[i] = static_cast<float>(dewi[i]);
-    ent32[i] = static_cast<float>(__dmul_rn(__dadd_rn(ht[i], hi[i]), 0.5));
+    dewi32[i] = payload_dewi32(dewi[i]);
+    ent32[i] = payload_ent32(ht[i], hi[i]);
   }
 }
 

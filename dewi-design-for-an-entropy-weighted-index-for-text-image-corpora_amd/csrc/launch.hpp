@@ -417,6 +417,15 @@ hipError_t launch_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows,
                                  float max_sim, int64_t id_offset, int64_t* d_out_ids, float* d_out_scores, float* d_out_mmr,
                                  hipStream_t stream);
 
+// ---- mutate.hip (in-place removal / upsert of rows; the reference has no counterpart) --------
+// d_error: an int32 the kernels INCREMENT for every pair / slot outside the contract (the caller zeroes it).
+hipError_t launch_rows_move(void* d_E, int elem_type, uint16_t* d_shadow, float* d_dewi32, float* d_ent32, int32_t* d_aux,
+                            int64_t n_rows, int dim, int64_t n_keep, const int64_t* d_src, const int64_t* d_dst,
+                            int64_t n_moves, int32_t* d_error, hipStream_t stream);
+hipError_t launch_rows_put(float* d_E, uint16_t* d_shadow, float* d_dewi32, float* d_ent32, int64_t capacity_rows, int dim,
+                           int normalize, const float* d_raw, const double* d_dewi, const double* d_ht, const double* d_hi,
+                           const int64_t* d_rows, int64_t n_put, int32_t* d_error, hipStream_t stream);
+
 // ---- ingest.hip ---------------------------------------------------------------------------
 hipError_t launch_normalize_rows(const float* d_src, float* d_dst, int64_t n_rows, int dim, hipStream_t stream);
 hipError_t launch_row_cosine(const float* d_a, const float* d_b, float* d_out, int64_t n_rows, int dim, float eps,

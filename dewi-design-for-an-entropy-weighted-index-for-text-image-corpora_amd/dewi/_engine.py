@@ -99,6 +99,39 @@ def _order_key(x):
     return torch.where(torch.isnan(x), torch.full_like(k, 1 << 31), k)
 
 
+#: an append beyond the capacity grows the storage to ``max(needed, capacity + capacity // CAPACITY_GROWTH_DIVISOR)`` rows
+CAPACITY_GROWTH_DIVISOR = 4
+
+
+def plan_remove(n_rows: int, rows) -> Tuple[np.ndarray, np.ndarray, int]:
+    """The moves of a removal: ``(src int64 [p], dst int64 [p], n_keep)``.  Host logic only (NumPy).
+
+    Rows are not shifted down; the tail fills the holes.  With ``n_keep = n_rows - len(rows)``: the holes are the deleted
+    rows below ``n_keep``, ascending; the movers are the surviving rows of ``[n_keep, n_rows)``, ascending; there are as
+    many of one as of the other, mover i goes to hole i (``src[i] -> dst[i]``) and the corpus is cut to ``n_keep`` rows.
+    Sources lie at or above ``n_keep`` and destinations below it, so the move is in place and touches at most ``len(rows)``
+    rows.  ``ValueError``: rows that are not integers, out of range or repeated, or a removal of every row."""
+    n = int(n_rows)
+    r = np.asarray(rows).reshape(-1)
+    if r.size and not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"rows to remove must be integers, got {r.dtype}")
+    r = np.sort(r.astype(np.int64))
+    m = int(r.size)
+    if m and (int(r[0]) < 0 or int(r[-1]) >= n):
+        raise ValueError(f"rows to remove must lie in [0, {n})")
+    if m > 1 and bool((np.diff(r) == 0).any()):
+        raise ValueError("rows to remove must be distinct")
+    if m >= n and n > 0:
+        raise ValueError(f"cannot remove every row ({m} of {n}): an index keeps at least one document")
+    n_keep = n - m
+    first_tail = int(np.searchsorted(r, n_keep))
+    dst = r[:first_tail].copy()
+    survives = np.ones(m, dtype=bool)
+    survives[r[first_tail:] - n_keep] = False
+    src = n_keep + np.flatnonzero(survives).astype(np.int64)
+    return src, dst, n_keep
+
+
 class DeviceFilter:
     """A prepared allow-list of corpus rows (``DeviceCorpus.make_filter``): the device buffer the filtered row kernels walk
     (``dewi_filter_prepare``: the allowed rows, sorted, grouped by the residue of their offset inside a 16-byte unit), the
@@ -206,6 +239,8 @@ class DeviceCorpus:
         # query, cached result buffers, workspaces): one caller at a time.  The reference's ExactIndex.search is
         # read-only and therefore safe under concurrent callers; this lock keeps that property for a threaded server.
         self._lock = threading.RLock()
+        self._store = None            # [emb, dewi32, ent32, shadow] storage tensors once the corpus was mutated or reserved
+        self.reallocations = 0        # how often the storage grew (reserve / an append beyond the capacity)
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -304,6 +339,156 @@ class DeviceCorpus:
 
     def corpus_bytes(self) -> int:
         return self.emb.numel() * self.emb.element_size()
+
+    # ------------------------------------------------------------------ mutation (additive; the reference only rebuilds)
+    @property
+    def capacity(self) -> int:
+        """Rows the storage holds without reallocating; ``n_rows`` for a corpus built as ever."""
+        return self.n_rows if self._store is None else int(self._store[0].shape[0])
+
+    def _stores(self):
+        """[emb, dewi32, ent32, shadow or None]: the storage tensors whose first ``n_rows`` rows are the corpus."""
+        st = self._store
+        if st is None:
+            st = self._store = [self.emb, self.dewi32, self.ent32, self.shadow]
+        if self.shadow is not None and (st[3] is None or int(st[3].shape[0]) < int(st[0].shape[0])):
+            sh = self.shadow                   # enabled after the storage was made: give it the storage's capacity
+            if int(sh.shape[0]) < int(st[0].shape[0]):
+                sh = _torch().empty((int(st[0].shape[0]), self.dim), dtype=sh.dtype, device=self.device)
+                sh[: self.n_rows].copy_(self.shadow)
+            st[3] = sh
+            self.shadow = sh[: self.n_rows]
+        return st
+
+    def _set_rows(self, n: int) -> None:
+        st = self._stores()
+        self.emb, self.dewi32, self.ent32 = st[0][:n], st[1][:n], st[2][:n]
+        if st[3] is not None:
+            self.shadow = st[3][:n]
+
+    def _grow(self, rows: int) -> None:
+        torch = _torch()
+        n = self.n_rows
+        old = self._stores()
+        new = []
+        for t in old:
+            if t is None:
+                new.append(None)
+                continue
+            g = torch.empty((int(rows),) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device)
+            g[:n].copy_(t[:n])
+            new.append(g)
+        self._store = new
+        self._set_rows(n)
+        self.reallocations += 1
+
+    def reserve(self, rows: int) -> None:
+        """Make room for ``rows`` rows: the matrix, the shadow and the payload columns become prefixes (``storage[:n]``, still
+        contiguous) of storage tensors of that many rows, so later appends up to there do not reallocate.  Growth is a
+        device-to-device copy into new tensors: peak memory is the old storage plus the new, and a caller's tensor the
+        build adopted in place (device-resident ingest) is no longer aliased afterwards.  The content does not change, so
+        prepared filters stay valid; a ``PipelinedSearcher`` made before holds the old pointers and must be made again.
+        The storage never shrinks."""
+        with self._lock, _torch().cuda.device(self.device):
+            self._check_mutable()
+            if int(rows) > self.capacity:
+                self._grow(int(rows))
+
+    def _check_mutable(self) -> None:
+        if self.is_bf16:
+            raise NotImplementedError("in-place mutation serves fp32 corpora (a bf16 main matrix: not in this build)")
+
+    def _after_mutation(self) -> None:
+        """The corpus is another one now: filters prepared before are refused, cached workspaces and result buffers go."""
+        self.corpus_id = next(_corpus_ids)
+        self._ws.clear()
+        self._io.clear()
+        self._last_call = None
+
+    def _read_error(self, err, what: str) -> None:
+        bad = int(err.item())                  # the call's one synchronisation
+        if bad:
+            raise nat.NativeLibraryError(f"{what}: {bad} rows outside the contract were skipped (corpus state is undefined)")
+
+    def remove_rows(self, rows, aux=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Delete ``rows`` in place (``plan_remove``: the tail fills the holes) and return the ``(src, dst)`` pairs applied;
+        the corpus then has ``n_rows - len(rows)`` rows.  One ``dewi_rows_move`` launch on the current stream moves the
+        matrix rows, the shadow rows, both payload columns and ``aux`` (an int32 device tensor of one word per row, e.g. the
+        IVF cells; the caller cuts it to the new ``n_rows``) together; the error word is read once (one synchronisation).
+        Afterwards the corpus has a new ``corpus_id`` — filters prepared before raise ``ValueError`` — and the cached
+        workspaces and result buffers are dropped.  The storage keeps its capacity.  fp32 corpora; the payload columns of a
+        ``to_bf16()`` copy made before alias this corpus's and are not kept consistent."""
+        torch = _torch()
+        with self._lock, torch.cuda.device(self.device):
+            self._check_mutable()
+            n = self.n_rows
+            src, dst, n_keep = plan_remove(n, rows)
+            if n_keep == n:
+                return src, dst
+            if aux is not None:
+                assert aux.is_cuda and aux.dtype == torch.int32 and aux.is_contiguous() and int(aux.numel()) >= n
+            st = self._stores()
+            if src.size:
+                pairs = torch.from_numpy(np.stack([src, dst])).to(self.device)
+                err = torch.zeros(1, dtype=torch.int32, device=self.device)
+                nat.check(self._lib.dewi_rows_move(
+                    nat.ptr(st[0]), 0, nat.ptr(st[3]), nat.ptr(st[1]), nat.ptr(st[2]), nat.ptr(aux), n, self.dim, n_keep,
+                    nat.ptr(pairs[0]), nat.ptr(pairs[1]), int(src.size), nat.ptr(err), nat.stream_ptr()))
+                self._read_error(err, "dewi_rows_move")
+            self._set_rows(n_keep)
+            self._after_mutation()
+            return src, dst
+
+    def put_rows(self, rows, raw, dewi, ht_mean, hi_mean, normalize: Optional[bool] = None) -> int:
+        """Write raw embeddings and payloads into ``rows`` — existing rows (replaced in place) and/or exactly the next ``a``
+        rows ``n_rows .. n_rows + a - 1`` (appended) — and return ``a``.  ``raw``: [m, dim], a host array or a CUDA fp32
+        tensor; ``dewi`` / ``ht_mean`` / ``hi_mean``: [m] float64 values, host or device.  One ``dewi_rows_put_f32`` launch
+        on the current stream stores what a fresh build stores for these rows, bit for bit (``normalize``: default for
+        ``space="cosine"``), shadow and payload columns included; the error word is read once.  An append beyond the
+        capacity first grows the storage to ``max(needed, capacity + capacity // CAPACITY_GROWTH_DIVISOR)`` (see
+        ``reserve``).  Afterwards: a new ``corpus_id``, no cached workspaces, as ``remove_rows``."""
+        torch = _torch()
+        with self._lock, torch.cuda.device(self.device):
+            self._check_mutable()
+            n = self.n_rows
+            r = np.asarray(rows).reshape(-1)
+            if r.size and not np.issubdtype(r.dtype, np.integer):
+                raise ValueError(f"rows to put must be integers, got {r.dtype}")
+            r = np.ascontiguousarray(r, dtype=np.int64)
+            m = int(r.size)
+            if m == 0:
+                return 0
+            new = np.sort(r[r >= n])
+            a = int(new.size)
+            if int(r.min()) < 0 or np.unique(r).size != m or not np.array_equal(new, np.arange(n, n + a)):
+                raise ValueError(f"rows to put must be distinct rows of [0, {n}) and/or exactly the next rows from {n} on")
+            if isinstance(raw, torch.Tensor):
+                x = raw.to(device=self.device, dtype=torch.float32).contiguous()
+            else:
+                x = torch.from_numpy(np.ascontiguousarray(raw, dtype=np.float32)).to(self.device)
+            if x.dim() != 2 or tuple(x.shape) != (m, self.dim):
+                raise ValueError(f"Expected embeddings of shape ({m}, {self.dim}), got {tuple(x.shape)}")
+            cols = [(c.to(device=self.device, dtype=torch.float64) if isinstance(c, torch.Tensor)
+                     else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float64)).to(self.device)).reshape(-1).contiguous()
+                    for c in (dewi, ht_mean, hi_mean)]
+            if any(int(c.numel()) != m for c in cols):
+                raise ValueError("payload columns must have one value per row")
+            if normalize is None:
+                normalize = self.space == "cosine"
+            need = n + a
+            if need > self.capacity:
+                self._grow(max(need, self.capacity + self.capacity // CAPACITY_GROWTH_DIVISOR))
+            st = self._stores()
+            slots = torch.from_numpy(r).to(self.device)
+            err = torch.zeros(1, dtype=torch.int32, device=self.device)
+            nat.check(self._lib.dewi_rows_put_f32(
+                nat.ptr(st[0]), nat.ptr(st[3]), nat.ptr(st[1]), nat.ptr(st[2]), need, self.dim, 1 if normalize else 0,
+                nat.ptr(x), nat.ptr(cols[0]), nat.ptr(cols[1]), nat.ptr(cols[2]), nat.ptr(slots), m, nat.ptr(err),
+                nat.stream_ptr()))
+            self._read_error(err, "dewi_rows_put_f32")
+            self._set_rows(need)
+            self._after_mutation()
+            return a
 
     # ------------------------------------------------------------------ helpers
     def _cached_workspace(self, key, size_fn, *size_args):

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "dewi_knn_range_shadow_collect",
     "dewi_groups_workspace_bytes", "dewi_groups_begin", "dewi_groups_union_lists", "dewi_groups_union_pairs", "dewi_groups_finish",
     "dewi_diverse_workspace_bytes", "dewi_diverse_rerank",
+    "dewi_rows_move", "dewi_rows_put_f32",
 )
 
 
@@ -200,6 +201,10 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_diverse_workspace_bytes.argtypes = [i32, i32, i32]
     lib.dewi_diverse_rerank.restype = i32
     lib.dewi_diverse_rerank.argtypes = [vp, i32, i64, i32, vp, i32, i32, i32, f64, f64, f64, f64, i64, vp, vp, vp, vp, sz, vp]
+    lib.dewi_rows_move.restype = i32
+    lib.dewi_rows_move.argtypes = [vp, i32, vp, vp, vp, vp, i64, i32, i64, vp, vp, i64, vp, vp]
+    lib.dewi_rows_put_f32.restype = i32
+    lib.dewi_rows_put_f32.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

@@ -188,6 +188,7 @@ class ExactIndex(BaseIndex):
         self._batch_shadow: bool = bool(kwargs.get("batch_shadow", False))
         # with batch_shadow: search() of ONE query goes through the shadow too (same answers; see enable_bf16_shadow)
         self._shadow_single: bool = bool(kwargs.get("shadow_single_query", False))
+        self._id_rows: Optional[Dict[str, int]] = None  # doc_id -> row of remove / upsert: made once, then kept per call
 
     # ---------------------------------------------------------------- ingest (A1)
     def add(self, doc_id: str, embedding: np.ndarray, payload: Payload) -> None:
@@ -269,6 +270,157 @@ class ExactIndex(BaseIndex):
     def _invalidate(self) -> None:
         self._is_trained = False
         self._host_rows = None
+        self._id_rows = None
+
+    # ---------------------------------------------------------------- remove / upsert in place (additive)
+    @property
+    def capacity(self) -> int:
+        """Rows the device storage holds without reallocating (0 before the first build)."""
+        return 0 if self._corpus is None else self._corpus.capacity
+
+    def reserve(self, rows: int) -> None:
+        """Make room on the device for ``rows`` documents, so that upserts of new ids up to there do not reallocate
+        (``DeviceCorpus.reserve``: a device-to-device copy, peak memory old plus new; the storage never shrinks)."""
+        self._ensure_built()
+        self._corpus.reserve(int(rows))
+
+    def _row_map(self) -> Dict[str, int]:
+        """doc_id -> row: built once in O(N), then maintained by every remove / upsert (``add`` drops it).  An index that
+        holds an id twice cannot be mutated by id: ``ValueError``."""
+        m = self._id_rows
+        if m is None:
+            m = {d: i for i, d in enumerate(self._doc_ids)}
+            if len(m) != len(self._doc_ids):
+                seen, twice = set(), []
+                for d in self._doc_ids:
+                    if d in seen and len(twice) < 5:
+                        twice.append(d)
+                    seen.add(d)
+                raise ValueError(f"the index holds doc ids more than once (e.g. {twice}): remove / upsert need unique ids")
+            self._id_rows = m
+        return m
+
+    def rows_of(self, doc_ids: Sequence[str]) -> np.ndarray:
+        """The row of every given doc id as the index stands now (int64; an unknown id raises ``KeyError``).  Rows change
+        with every ``remove``: the tail fills the holes."""
+        self._ensure_built()
+        ids = [doc_ids] if isinstance(doc_ids, str) else list(doc_ids)
+        m = self._row_map()
+        missing = [d for d in ids if d not in m]
+        if missing:
+            raise KeyError(f"unknown doc ids: {sorted(missing, key=str)[:5]}")
+        return np.fromiter((m[d] for d in ids), dtype=np.int64, count=len(ids))
+
+    def _corpus_remove(self, rows: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        return self._corpus.remove_rows(rows)
+
+    def _corpus_put(self, rows: np.ndarray, embeddings, triple) -> None:
+        self._corpus.put_rows(rows, embeddings, triple["dewi"], triple["ht_mean"], triple["hi_mean"], normalize=self._normalize)
+
+    def _check_removal(self, n_keep: int) -> None:
+        if n_keep <= 0:
+            raise ValueError(f"cannot remove every document ({len(self._doc_ids)}): an index keeps at least one")
+
+    def remove(self, doc_ids: Sequence[str]) -> int:
+        """Delete documents from the built index in place and return how many (additive; the reference cannot delete).
+
+        Nothing is rebuilt or copied to the host.  Rows are not shifted: with n documents and m of them deleted, the
+        surviving documents of the last m rows move into the holes below ``n - m`` (``_engine.plan_remove``), on the device in
+        one launch, and ``_doc_ids``, the payloads and ``rows_of`` follow — so row order is no longer insertion order, and
+        ``save`` / ``load`` keep the order the index has.  Pending ``add``s are built in first.  Everything is checked before
+        any device work, so a failing call leaves the index as it was: an unknown id raises ``KeyError``; an id given twice,
+        an index that holds an id twice, or a removal of every document ``ValueError``.  Filters prepared before are refused
+        afterwards (``ValueError``), as after a rebuild.  The device storage keeps its size.  The first mutation of an index
+        with column-ingested payloads costs O(N) host work (``PayloadStore.follow`` re-gathers the columns into one block
+        of its own); later ones O(rows touched)."""
+        self._ensure_built()
+        ids = [doc_ids] if isinstance(doc_ids, str) else list(doc_ids)
+        if len(set(ids)) != len(ids):
+            raise ValueError("doc ids to remove must be distinct")
+        rows = self.rows_of(ids)
+        if not ids:
+            return 0
+        n_old = len(self._doc_ids)
+        self._check_removal(n_old - len(ids))
+        src, dst = self._corpus_remove(rows)
+        n_keep = n_old - len(ids)
+        m, all_ids = self._id_rows, self._doc_ids
+        for d in ids:
+            del m[d]
+        for s_, d_ in zip(src.tolist(), dst.tolist()):
+            all_ids[d_] = all_ids[s_]
+            m[all_ids[d_]] = d_
+        del all_ids[n_keep:]
+        self._payloads.follow_remove(src, dst, n_old, all_ids, ids, rows)
+        self._host_rows = None
+        return len(ids)
+
+    def upsert(self, doc_id: str, embedding: np.ndarray, payload: Payload) -> None:
+        """Replace the embedding and payload of ``doc_id`` in place, or append it if the index does not hold it (additive)."""
+        if embedding.shape != (self.dim,):
+            raise ValueError(f"Expected embedding of shape {(self.dim,)}, got {embedding.shape}")
+        self.upsert_batch([doc_id], np.asarray(embedding).reshape(1, -1), [payload])
+
+    def upsert_batch(self, doc_ids: Sequence[str], embeddings: np.ndarray, payloads: Sequence[Payload]) -> Tuple[int, int]:
+        """``upsert`` of m documents in one launch: returns ``(n_replaced, n_appended)``.  A known id keeps its row; new ids
+        are appended in call order at rows ``N, N + 1, ...``.  The stored rows, the bf16 shadow and the payload columns get
+        the bits a fresh ``build`` would give them (``dewi_rows_put_f32``).  Checked before any device work like ``remove``
+        (an id twice in the call, or held twice: ``ValueError``; shapes: ``add_batch``'s messages)."""
+        self._ensure_built()
+        emb = np.asarray(embeddings)
+        if emb.ndim != 2 or emb.shape[1] != self.dim:
+            raise ValueError(f"Expected embeddings of shape (m, {self.dim}), got {emb.shape}")
+        if not (len(doc_ids) == emb.shape[0] == len(payloads)):
+            raise ValueError("doc_ids, embeddings and payloads must have the same length")
+        payloads = list(payloads)
+        return self._upsert(list(doc_ids), emb, payload_columns(payloads, ("dewi", "ht_mean", "hi_mean")), payloads, None)
+
+    def upsert_batch_columns(self, doc_ids: Sequence[str], embeddings, columns: Dict[str, np.ndarray]) -> Tuple[int, int]:
+        """``upsert_batch`` with the payloads as one array per ``Payload`` field (missing fields are 0.0), as
+        ``add_batch_columns`` takes them; ``embeddings`` may be a CUDA fp32 tensor [m, dim] and the columns CUDA tensors."""
+        self._ensure_built()
+        from . import _native as nat
+        shape = tuple(embeddings.shape) if hasattr(embeddings, "shape") else np.shape(embeddings)
+        if len(shape) != 2 or int(shape[1]) != self.dim:
+            raise ValueError(f"Expected embeddings of shape (m, {self.dim}), got {tuple(shape)}")
+        if len(doc_ids) != int(shape[0]):
+            raise ValueError("doc_ids and embeddings must have the same length")
+        unknown = [name for name in columns if name not in PAYLOAD_FIELDS]
+        if unknown:
+            raise ValueError(f"unknown payload columns {unknown}")
+        m = len(doc_ids)
+        cols = {}
+        for name in PAYLOAD_FIELDS:
+            if name in columns:
+                c = columns[name] if nat.is_device_tensor(columns[name]) else np.asarray(columns[name], dtype=np.float64)
+                if tuple(c.shape) != (m,):
+                    raise ValueError(f"payload column {name!r} has shape {tuple(c.shape)}, expected ({m},)")
+                cols[name] = c
+        triple = {name: cols.get(name, np.zeros(m, dtype=np.float64)) for name in ("dewi", "ht_mean", "hi_mean")}
+        emb = embeddings if nat.is_device_tensor(embeddings) else np.asarray(embeddings)
+        return self._upsert(list(doc_ids), emb, triple, None, cols)
+
+    def _upsert(self, ids: List[str], emb, triple, payloads, cols) -> Tuple[int, int]:
+        if len(set(ids)) != len(ids):
+            raise ValueError("doc ids to upsert must be distinct")
+        m = self._row_map()
+        if not ids:
+            return 0, 0
+        n = len(self._doc_ids)
+        rows = np.empty(len(ids), dtype=np.int64)
+        fresh: List[str] = []
+        for i, d in enumerate(ids):
+            r = m.get(d)
+            if r is None:
+                r = n + len(fresh)
+                fresh.append(d)
+            rows[i] = r
+        self._corpus_put(rows, emb, triple)
+        self._doc_ids.extend(fresh)
+        m.update(zip(fresh, range(n, n + len(fresh))))
+        self._payloads.follow_put(rows, n, self._doc_ids, ids, objects=payloads, columns=cols)
+        self._host_rows = None
+        return len(ids) - len(fresh), len(fresh)
 
     # ---------------------------------------------------------------- build (A2)
     def _raw_matrix(self) -> Tuple[np.ndarray, int]:

@@ -4,8 +4,8 @@ Same constructor, defaults and methods as the reference (index.py:22-166): it va
 the query, fills in the default ``eta`` / ``entropy_pref`` and delegates to a backend.  In
 this build every backend choice resolves to the HIP ``ExactIndex`` (ANN graph libraries
 are out of scope), with the reference's own warning when an ANN backend was asked for.
-Additions: ``add_batch``, ``search_batch``, ``range_search``, ``range_search_batch``, ``near_duplicates``, ``duplicate_groups`` and
-``dedup_filter``.
+Additions: ``add_batch``, ``search_batch``, ``range_search``, ``range_search_batch``, ``near_duplicates``, ``duplicate_groups``,
+``dedup_filter`` and the in-place ``remove`` / ``upsert`` / ``upsert_batch`` / ``upsert_batch_columns`` / ``rows_of`` / ``reserve``.
 """
 from __future__ import annotations
 
@@ -66,6 +66,46 @@ class DewiIndex(BaseIndex):
     def build(self) -> None:
         self._backend.build()
         self._built = True
+
+    # ------------------------------------------------------------------ remove / upsert in place (additive)
+    def remove(self, doc_ids: Sequence[str]) -> int:
+        """Delete documents from the built index in place (``ExactIndex.remove``): no rebuild; the metadata goes too, and
+        ``get_payload`` / ``get_embedding`` / ``get_metadata`` of a removed id return ``None``."""
+        ids = [doc_ids] if isinstance(doc_ids, str) else list(doc_ids)
+        n = self._backend.remove(ids)
+        for d in ids:
+            self._meta.pop(d, None)
+        self._built = True
+        return n
+
+    def upsert(self, doc_id: str, embedding: np.ndarray, payload: Payload, meta: Optional[Dict[str, Any]] = None) -> None:
+        """Replace ``doc_id``'s embedding and payload in place, or append it (``ExactIndex.upsert``); ``meta`` sets its
+        metadata."""
+        self._backend.upsert(doc_id, np.asarray(embedding, dtype=np.float32), payload)
+        if meta is not None:
+            self._meta[doc_id] = meta
+        self._built = True
+
+    def upsert_batch(self, doc_ids: Sequence[str], embeddings: np.ndarray, payloads: Sequence[Payload]) -> Tuple[int, int]:
+        out = self._backend.upsert_batch(doc_ids, np.asarray(embeddings, dtype=np.float32), payloads)
+        self._built = True
+        return out
+
+    def upsert_batch_columns(self, doc_ids: Sequence[str], embeddings, columns: Dict[str, np.ndarray]) -> Tuple[int, int]:
+        out = self._backend.upsert_batch_columns(doc_ids, embeddings, columns)
+        self._built = True
+        return out
+
+    def rows_of(self, doc_ids: Sequence[str]) -> np.ndarray:
+        return self._backend.rows_of(doc_ids)
+
+    def reserve(self, rows: int) -> None:
+        self._backend.reserve(rows)
+        self._built = True
+
+    @property
+    def capacity(self) -> int:
+        return self._backend.capacity
 
     # ------------------------------------------------------------------ search (A5)
     def _defaults(self, eta: Optional[float], entropy_pref: Optional[float]) -> Tuple[float, float]:

@@ -63,6 +63,11 @@ class IVFIndex(ExactIndex):
     ``search_diverse`` / ``search_diverse_batch`` are ``ExactIndex``'s too, in their EXACT form: the candidate pool is the
     exact cut over every row, not over the probed cells, and there is no ``nprobe`` argument.  A diverse search over an IVF
     probe is not part of this build.
+
+    ``remove`` / ``upsert`` / ``upsert_batch`` / ``upsert_batch_columns`` maintain the cells instead of retraining: the
+    centroids stay as trained, a surviving document keeps its cell, a replaced or appended one goes to the centroid nearest to
+    its stored row, and the lists are rebuilt.  The cells therefore DRIFT from what k-means would give the changed corpus as
+    documents come and go; ``build()`` retrains, as ever.  A removal that would leave fewer documents than cells is refused.
     """
 
     def __init__(self, dim: int, space: str = "cosine", nlist: Optional[int] = None, nprobe: Optional[int] = None,
@@ -120,20 +125,62 @@ class IVFIndex(ExactIndex):
             st = _IvfState()
             st.nlist = nlist
             st.buckets = int(lib.dewi_ivf_buckets(self.dim, 0))
-            need = int(lib.dewi_ivf_lists_bytes(n, self.dim, 0, nlist))
-            if need == 0 or st.buckets == 0:
-                raise nat.NativeLibraryError(f"dewi_ivf_lists_bytes returned 0 for {n} x {self.dim}, {nlist} cells")
-            st.lists = torch.empty(need, dtype=torch.uint8, device=dev)
-            nat.check(lib.dewi_ivf_lists_build(0, n, self.dim, nlist, nat.ptr(assign), nat.ptr(st.lists), need, nat.stream_ptr()))
-            words = st.lists.view(torch.int32)
-            dropped = int(words[nlist * st.buckets + 1 + n].item())           # the error word (synchronises)
-            if dropped:
-                raise ValueError(f"{dropped} rows are assigned to cells outside [0, {nlist})")
+            self._make_lists(st, assign, n)
             zeros = torch.zeros(nlist, dtype=torch.float32, device=dev)
             st.centroids, st.assign = centroids, assign
             st.coarse = DeviceCorpus(centroids, zeros, zeros.clone(), self.space)
             st.corpus_id = corpus.corpus_id
         self._ivf = st
+
+    def _make_lists(self, st: _IvfState, assign, n: int) -> None:
+        """``st.lists``: the per-cell row lists of ``assign`` (int32 [n] on the device), by ``dewi_ivf_lists_build``."""
+        import torch
+        from . import _native as nat
+        lib = nat.load_library()
+        nlist = st.nlist
+        need = int(lib.dewi_ivf_lists_bytes(n, self.dim, 0, nlist))
+        if need == 0 or st.buckets == 0:
+            raise nat.NativeLibraryError(f"dewi_ivf_lists_bytes returned 0 for {n} x {self.dim}, {nlist} cells")
+        st.lists = torch.empty(need, dtype=torch.uint8, device=assign.device)
+        nat.check(lib.dewi_ivf_lists_build(0, n, self.dim, nlist, nat.ptr(assign), nat.ptr(st.lists), need, nat.stream_ptr()))
+        words = st.lists.view(torch.int32)
+        dropped = int(words[nlist * st.buckets + 1 + n].item())           # the error word (synchronises)
+        if dropped:
+            raise ValueError(f"{dropped} rows are assigned to cells outside [0, {nlist})")
+
+    # ---------------------------------------------------------------- remove / upsert in place
+    # Mutations maintain the cells instead of retraining: the centroids are untouched, a surviving row keeps its cell (the
+    # cell column travels with the row mover), a replaced or appended row goes to the centroid nearest to its stored row, and
+    # the lists are rebuilt from the cell column.  The cells therefore DRIFT from what k-means would give the changed corpus
+    # as documents come and go; ``build()`` retrains, as ever.
+    def _check_removal(self, n_keep: int) -> None:
+        super()._check_removal(n_keep)
+        if self._ivf is not None and n_keep < self._ivf.nlist:
+            raise ValueError(f"cannot remove down to {n_keep} documents: the index has {self._ivf.nlist} cells")
+
+    def _corpus_remove(self, rows: np.ndarray):
+        import torch
+        st, corpus = self._ivf, self._corpus
+        with corpus._lock, torch.cuda.device(corpus.device):
+            src, dst = corpus.remove_rows(rows, aux=st.assign)
+            st.assign = st.assign[: corpus.n_rows].contiguous()
+            self._make_lists(st, st.assign, corpus.n_rows)
+            st.corpus_id = corpus.corpus_id
+        return src, dst
+
+    def _corpus_put(self, rows: np.ndarray, embeddings, triple) -> None:
+        import torch
+        st, corpus = self._ivf, self._corpus
+        with corpus._lock, torch.cuda.device(corpus.device):
+            super()._corpus_put(rows, embeddings, triple)
+            at = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(corpus.device)
+            cells = self._assign(corpus.emb.index_select(0, at), st.centroids).to(torch.int32)
+            grown = corpus.n_rows - int(st.assign.shape[0])
+            if grown > 0:
+                st.assign = torch.cat([st.assign, torch.zeros(grown, dtype=torch.int32, device=corpus.device)])
+            st.assign[at] = cells
+            self._make_lists(st, st.assign, corpus.n_rows)
+            st.corpus_id = corpus.corpus_id
 
     def _assign(self, X, C):
         """Nearest centroid of every row of X (int64): largest inner product (cosine) / smallest distance (l2)."""

@@ -101,6 +101,7 @@ class PayloadStore(dict):
         self._made: List[Dict[int, "Payload"]] = []      # per block: rows that already have an object
         self._id_rows: Optional[Dict[str, int]] = None    # doc_id -> global row of column-ingested docs (lazy)
         self._lazy_count = 0
+        self._owned = False                                # the blocks' arrays and id lists are the store's own (follow made them)
 
     # ---- ingest -----------------------------------------------------------------------------
     def add_columns(self, row0: int, doc_ids: Sequence[str], columns: Mapping[str, np.ndarray]) -> None:
@@ -119,6 +120,177 @@ class PayloadStore(dict):
         self._made.append({})
         self._id_rows = None
         self._lazy_count += n
+        self._owned = False
+
+    # ---- in-place mutation of the index (ExactIndex.remove / upsert) ----------------------------
+    def _own_block(self, n_old: int) -> bool:
+        """True when the store is ONE block over all ``n_old`` rows that ``follow`` made (its arrays and id list are the
+        store's own): a mutation is then applied to it in place, O(rows touched) instead of a re-gather."""
+        return self._owned and len(self._blocks) == 1 and self._blocks[0][0] == 0 and self._blocks[0][1] == int(n_old)
+
+    def follow_remove(self, src: np.ndarray, dst: np.ndarray, n_old: int, doc_ids: Sequence[str], removed_ids: Sequence[str],
+                      removed_rows: np.ndarray) -> None:
+        """Follow ``ExactIndex.remove``: the documents ``removed_ids`` at rows ``removed_rows`` left, row ``src[i]`` moved to
+        ``dst[i]``, ``doc_ids`` are the new ids in row order.  See ``follow``."""
+        n_keep = int(n_old) - len(removed_ids)
+        if not self._blocks:                               # a store of objects only: a plain dict
+            for d in removed_ids:
+                dict.pop(self, d, None)
+            return
+        if not self._own_block(n_old):
+            order = np.arange(n_keep, dtype=np.int64)
+            order[dst] = src
+            return self.follow(order, n_old, doc_ids, removed=removed_ids)
+        for d in removed_ids:
+            dict.pop(self, d, None)
+        _, _, ids, cols = self._blocks[0]
+        made = self._made[0]
+        for name, c in list(cols.items()):
+            if len(src):
+                if getattr(c, "is_cuda", False):
+                    import torch
+                    s_t, d_t = torch.from_numpy(np.ascontiguousarray(src)).to(c.device), torch.from_numpy(np.ascontiguousarray(dst)).to(c.device)
+                    c.index_copy_(0, d_t, c.index_select(0, s_t))
+                else:
+                    c[dst] = c[src]
+            cols[name] = c[:n_keep]
+        for r in np.asarray(removed_rows).tolist():
+            made.pop(r, None)
+        for s, d in zip(np.asarray(src).tolist(), np.asarray(dst).tolist()):
+            p = made.pop(s, None)
+            if p is not None:
+                made[d] = p
+            ids[d] = ids[s]
+        del ids[n_keep:]
+        self._blocks[0] = (0, n_keep, ids, cols)
+        self._id_rows = None
+        self._lazy_count = n_keep - len(made)
+
+    def follow_put(self, rows: np.ndarray, n_old: int, doc_ids: Sequence[str], ids: Sequence[str], objects=None, columns=None) -> None:
+        """Follow ``ExactIndex.upsert_batch`` / ``upsert_batch_columns``: document ``ids[i]`` was written to row ``rows[i]``
+        (rows from ``n_old`` on are new), with ``objects[i]`` as its ``Payload`` or row i of ``columns`` ({field: values}, host
+        or CUDA).  See ``follow``."""
+        rows = np.asarray(rows, dtype=np.int64)
+        n_new = len(doc_ids)
+        if not self._blocks and columns is None:
+            for d, p in zip(ids, objects):
+                dict.__setitem__(self, d, p)
+            return
+        if not self._own_block(n_old):
+            order = np.concatenate([np.arange(int(n_old), dtype=np.int64), np.full(n_new - int(n_old), -1, dtype=np.int64)])
+            order[rows] = -1
+            if objects is not None:
+                return self.follow(order, n_old, doc_ids, objects=list(zip(rows.tolist(), ids, objects)))
+            return self.follow(order, n_old, doc_ids, columns=(rows, ids, columns))
+        _, _, own_ids, cols = self._blocks[0]
+        made = self._made[0]
+        grown = n_new - int(n_old)
+        names = [name for name in PAYLOAD_FIELDS if name in cols or (columns is not None and name in columns)]
+        for name in names:
+            c = cols.get(name)
+            vals = None if columns is None else columns.get(name)
+            if c is None:
+                c = np.zeros(int(n_old), dtype=np.float64)
+            if getattr(vals, "is_cuda", False) and not getattr(c, "is_cuda", False):
+                import torch
+                c = torch.from_numpy(c).to(vals.device)           # a column with device values lives on the device from now on
+            if getattr(c, "is_cuda", False):
+                import torch
+                if grown:
+                    c = torch.cat([c, torch.zeros(grown, dtype=c.dtype, device=c.device)])
+                at = torch.from_numpy(rows).to(c.device)
+                v = (torch.zeros(len(rows), dtype=c.dtype, device=c.device) if vals is None
+                     else (vals if getattr(vals, "is_cuda", False) else torch.from_numpy(np.asarray(vals, dtype=np.float64))).to(device=c.device, dtype=c.dtype))
+                c.index_copy_(0, at, v)
+            else:
+                if grown:
+                    c = np.concatenate([c, np.zeros(grown, dtype=np.float64)])
+                c[rows] = 0.0 if vals is None else np.asarray(vals, dtype=np.float64)
+            cols[name] = c
+        if objects is not None:
+            for r, d, p in zip(rows.tolist(), ids, objects):
+                dict.__setitem__(self, d, p)
+                made[r] = p
+        else:
+            for r, d in zip(rows.tolist(), ids):
+                dict.pop(self, d, None)       # a replaced document's old object: the next lookup makes one from the new columns
+                made.pop(r, None)
+        own_ids.extend(doc_ids[int(n_old):])
+        self._blocks[0] = (0, n_new, own_ids, cols)
+        self._id_rows = None
+        self._lazy_count = n_new - len(made)
+
+    def follow(self,order: np.ndarray, n_old: int, doc_ids: Sequence[str], removed: Iterable[str] = (),
+               objects: Sequence[Tuple[int, str, "Payload"]] = (), columns=None) -> None:
+        """Follow a mutation of the index.  ``order`` int64 [n_new]: the OLD row whose document now sits at each new row, or
+        -1 where the row's payload is new; ``n_old``: rows before; ``doc_ids``: the new ids in row order; ``removed``: ids
+        that left; ``objects``: ``(row, doc_id, Payload)`` of new payloads given as objects; ``columns``: ``(rows, doc_ids,
+        {field: values})`` of new payloads given as columns (host arrays or CUDA tensors).
+
+        Dict entries are deleted or replaced; ``Payload`` objects already handed out for surviving documents stay the same
+        objects.  Column blocks are re-gathered into the new row order — host columns with NumPy, device columns with
+        ``index_select``, both as float64 (exact for fp32 columns) — into ONE block over all rows, in which rows that have an
+        object are listed as made.  That is O(N) host work per call (not per row), plus one gather per column.  The block it
+        leaves is the store's own, and ``follow_remove`` / ``follow_put`` apply later mutations to it in place, in O(rows
+        touched) (an append copies the columns once more to make room)."""
+        order = np.asarray(order, dtype=np.int64)
+        n_new = int(order.shape[0])
+        for d in removed:
+            dict.pop(self, d, None)
+        for _, d, p in objects:
+            dict.__setitem__(self, d, p)
+        if columns is not None:
+            for d in columns[1]:
+                dict.pop(self, d, None)       # a replaced document's old object: the next lookup makes one from the new columns
+        if not self._blocks and columns is None:
+            return
+        alive = order >= 0
+        inv = np.full(int(n_old), -1, dtype=np.int64)
+        inv[order[alive]] = np.flatnonzero(alive)
+        # per old block: the new rows it fills and the block-local rows they come from
+        takes = []
+        in_block = np.zeros(n_new, dtype=bool)
+        for row0, row1, _, _ in self._blocks:
+            dst = np.flatnonzero(alive & (order >= row0) & (order < row1))
+            takes.append((dst, order[dst] - row0))
+            in_block[dst] = True
+        names = [name for name in PAYLOAD_FIELDS
+                 if any(name in b[3] for b in self._blocks) or (columns is not None and name in columns[2])]
+        new_cols: Dict[str, np.ndarray] = {}
+        for name in names:
+            parts = [(dst, src, b[3][name]) for (dst, src), b in zip(takes, self._blocks) if name in b[3]]
+            if columns is not None and name in columns[2]:
+                parts.append((np.asarray(columns[0], dtype=np.int64), None, columns[2][name]))
+            dev = next((c.device for _, _, c in parts if getattr(c, "is_cuda", False)), None)
+            if dev is None:
+                out = np.zeros(n_new, dtype=np.float64)
+                for dst, src, c in parts:
+                    c = np.asarray(c, dtype=np.float64)
+                    out[dst] = c if src is None else c[src]
+            else:
+                import torch
+                out = torch.zeros(n_new, dtype=torch.float64, device=dev)
+                for dst, src, c in parts:
+                    c = c if getattr(c, "is_cuda", False) else torch.from_numpy(np.asarray(c, dtype=np.float64)).to(dev)
+                    if src is not None:
+                        c = c.index_select(0, torch.from_numpy(src).to(dev))
+                    out.index_copy_(0, torch.from_numpy(np.ascontiguousarray(dst)).to(dev), c.to(torch.float64))
+            new_cols[name] = out
+        made: Dict[int, "Payload"] = {}
+        for old_made in self._made:
+            for row, p in old_made.items():
+                if inv[row] >= 0:
+                    made[int(inv[row])] = p
+        for row in np.flatnonzero(alive & ~in_block).tolist():       # documents that came with an object
+            made[row] = dict.__getitem__(self, doc_ids[row])
+        for row, _, p in objects:
+            made[int(row)] = p
+        self._starts = [0]
+        self._blocks = [(0, n_new, list(doc_ids), new_cols)]
+        self._made = [made]
+        self._id_rows = None
+        self._lazy_count = n_new - len(made)
+        self._owned = True
 
     # ---- row access (search results: no doc_id -> row map needed) -----------------------------
     def _block_of(self, row: int) -> int:

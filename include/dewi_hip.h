@@ -520,6 +520,42 @@ int dewi_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows, int dim,
                         size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * In-place mutation of a built corpus (ABI 6, additive; the reference has no counterpart: its indexes only append and
+ * rebuild).  A removal does not shift rows: the tail fills the holes.  With n rows, m of them deleted and n_keep = n - m,
+ * the holes are the deleted rows below n_keep (ascending), the movers the surviving rows at or above n_keep (ascending),
+ * mover i goes to hole i and the corpus is truncated to n_keep by the caller.
+ *
+ * dewi_rows_move: one wavefront per pair copies row d_src[i] -> row d_dst[i] of the matrix (elem_type 0: fp32, 1: bf16),
+ * of the bf16 shadow of an fp32 matrix (d_E_bf16, may be NULL; must be NULL for elem_type 1), of both payload columns and
+ * of d_aux_i32 (one int32 per row — the IVF cell —, may be NULL).  16-byte loads and stores where a row's byte size and
+ * the base are multiples of 16, element accesses otherwise: any dim, any element-aligned base.  A pair with d_src[i]
+ * outside [n_keep, n_rows) or d_dst[i] outside [0, n_keep) writes nothing and INCREMENTS *d_error (a device int32 the caller
+ * zeroes and reads).  Distinct sources and distinct destinations are the caller's contract; rows at and above n_keep are
+ * left as they are.
+ *
+ * dewi_rows_put_f32: one wavefront per row reads raw row i of d_raw [n_put][dim] and writes slot d_rows[i] of an fp32
+ * matrix of capacity_rows rows: with normalize != 0 divided by its norm exactly as dewi_normalize_rows_f32 does on a fresh,
+ * 16-byte-aligned matrix of this dim (float64 squares, the same lanes' partial sums, one rounding after the square root,
+ * IEEE division, no zero-norm guard: a zero row becomes NaN); the bf16 shadow (may be NULL) with dewi_convert_f32_to_bf16's
+ * rounding of the stored value; the payload pair with dewi_payload_soa_f64's arithmetic from d_dewi / d_ht_mean /
+ * d_hi_mean [n_put].  A slot outside [0, capacity_rows) writes nothing and increments *d_error.  Distinct slots are the
+ * caller's contract.
+ *
+ * After either call the bits in HBM equal those of dewi_normalize_rows_f32 + dewi_convert_f32_to_bf16 +
+ * dewi_payload_soa_f64 over the same rows in the same order.  Asynchronous on `stream`; no allocation, no synchronisation.
+ * Argument errors are reported before any device work: a non-positive dim, negative counts, n_keep > n_rows, more moves
+ * than rows on either side of n_keep, n_put > capacity_rows, a shadow given with elem_type 1, an unknown elem_type, null
+ * pointers: DEWI_ERR_INVALID_ARG; 2^32 rows or more: DEWI_ERR_UNSUPPORTED.  n_moves == 0 / n_put == 0 launch nothing and
+ * return DEWI_OK.
+ * ------------------------------------------------------------------------------------------ */
+int dewi_rows_move(void* d_E, int elem_type, void* d_E_bf16, float* d_dewi32, float* d_ent32, int32_t* d_aux_i32,
+                   int64_t n_rows, int dim, int64_t n_keep, const int64_t* d_src, const int64_t* d_dst, int64_t n_moves,
+                   int32_t* d_error, void* stream);
+int dewi_rows_put_f32(float* d_E, void* d_E_bf16, float* d_dewi32, float* d_ent32, int64_t capacity_rows, int dim,
+                      int normalize, const float* d_raw, const double* d_dewi, const double* d_ht_mean,
+                      const double* d_hi_mean, const int64_t* d_rows, int64_t n_put, int32_t* d_error, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A6  robust statistics — replaces scorer.RobustStats.fit (scorer.py:18-26) for n_signals
  * columns of n fp32 values each, stored SoA: column s starts at d_S + s*ld.
  *   med[s] = np.median(col)            exact fp32 order statistic; even n: fp32 (a+b)/2
