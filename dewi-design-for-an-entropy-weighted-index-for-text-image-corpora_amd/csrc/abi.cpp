@@ -1412,6 +1412,110 @@ int dewi_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows, int dim,
                   "diverse_rerank launch");
 }
 
+// ---- approximate search over an int8 copy of the corpus (additive to ABI 6; knn_scan_i8.hip) ---------------------------------
+// the shape checks the int8 entry points share, in one order: rows, 2^32, dim, the unit (16 codes; the re-scoring: 4 floats)
+static int check_i8_shape(int64_t n_rows, int dim, int unit) {
+  if (n_rows <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_rows must be positive (got %lld)", static_cast<long long>(n_rows));
+  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "dim must be positive (got %d)", dim);
+  if (dim % unit != 0 || dim > DEWI_I8_MAX_DIM)
+    return fail(DEWI_ERR_UNSUPPORTED, "dim %d: the int8 route takes dim %% %d == 0 up to %d columns", dim, unit, DEWI_I8_MAX_DIM);
+  return DEWI_OK;
+}
+static int check_i8_candidates(int n_candidates) {
+  if (n_candidates <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_candidates must be positive (got %d)", n_candidates);
+  if (n_candidates > DEWI_I8_MAX_CANDIDATES)
+    return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds the %d the int8 route takes", n_candidates, DEWI_I8_MAX_CANDIDATES);
+  return DEWI_OK;
+}
+static int check_aligned16(const void* p, const char* what) {
+  if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return fail(DEWI_ERR_INVALID_ARG, "%s must be 16-byte aligned", what);
+  return DEWI_OK;
+}
+
+int dewi_quantize_rows_i8(const float* d_E, int64_t n_rows, int dim, int8_t* d_codes, float* d_scales, void* stream) {
+  if (n_rows == 0 && dim > 0) return DEWI_OK;
+  if (int rc = check_i8_shape(n_rows, dim, 16)) return rc;
+  if (!d_E || !d_codes || !d_scales) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (int rc = check_aligned16(d_E, "the rows")) return rc;
+  if (int rc = check_aligned16(d_codes, "the codes")) return rc;
+  return launched(dewi::launch_quantize_rows_i8(d_E, n_rows, dim, d_codes, d_scales, static_cast<hipStream_t>(stream)),
+                  "quantize_rows_i8 launch");
+}
+
+int dewi_prepare_queries_i8(const float* d_Q, int n_queries, int dim, int8_t* d_codes, float* d_scales, float* d_qn,
+                            void* stream) {
+  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
+  if (int rc = check_i8_shape(n_queries, dim, 16)) return rc;
+  if (!d_Q || !d_codes || !d_scales) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
+  if (int rc = check_aligned16(d_codes, "the codes")) return rc;
+  if (d_qn != nullptr)
+    if (int rc = check_aligned16(d_qn, "the normalised queries")) return rc;
+  return launched(dewi::launch_prepare_queries_i8(d_Q, n_queries, dim, d_codes, d_scales, d_qn, static_cast<hipStream_t>(stream)),
+                  "prepare_queries_i8 launch");
+}
+
+// keys of every query of the batch; the queries are prepared in registers, the select needs nothing else
+static size_t i8_workspace(const dewi::ScanPlan& plan, int n_queries) {
+  return align_up(static_cast<size_t>(n_queries) * static_cast<size_t>(plan.keys_per_query) * 8, 256);
+}
+
+size_t dewi_knn_i8_workspace_bytes(int64_t n_rows, int dim, int n_queries, int n_candidates) {
+  if (n_rows <= 0 || n_rows > 0xFFFFFFFFll || dim <= 0 || dim % 16 != 0 || dim > DEWI_I8_MAX_DIM || n_queries <= 0 ||
+      n_candidates <= 0 || n_candidates > DEWI_I8_MAX_CANDIDATES)
+    return 0;
+  const int c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
+  return i8_workspace(dewi::plan_scan_i8(n_rows, dim, c_local), n_queries);
+}
+
+int dewi_knn_candidates_i8(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const float* d_Q,
+                           int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
+                           dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, void* stream_) {
+  if (!d_codes || !d_scales || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "null codes, scales or query pointer");
+  if (int rc = check_i8_shape(n_rows, dim, 16)) return rc;
+  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
+  if (int rc = check_i8_candidates(n_candidates)) return rc;
+  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
+  if (int rc = check_aligned16(d_codes, "the codes")) return rc;
+  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
+  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
+                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
+  // a shard with fewer rows than n_candidates selects every row and pads the tail (id = -1, sim = -inf), as dewi_knn_candidates
+  const int c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
+  const dewi::ScanPlan plan = dewi::plan_scan_i8(n_rows, dim, c_local);
+  if (int rc = check_workspace(d_workspace, workspace_bytes, i8_workspace(plan, n_queries))) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  uint64_t* keys = static_cast<uint64_t*>(d_workspace);
+  {
+    ScanTimer timer(stream);
+    for (int q = 0; q < n_queries;) {           // four queries per corpus pass, then one by one
+      const int nq = n_queries - q >= 4 ? 4 : 1;
+      const hipError_t e = dewi::launch_scan_i8(plan, d_codes, d_scales, n_rows, dim, d_Q, q, nq, c_local, keys, stream);
+      if (e != hipSuccess) return hip_fail(e, "int8 scan launch");
+      q += nq;
+    }
+  }
+  const int sorted = (plan.slots == 1 && c_local == n_candidates) ? plan.n_lists : 0;
+  return launched(dewi::launch_select_rerank(keys, plan.keys_per_query, sorted, n_queries, n_candidates, 0, make_rerank(0.0, 0.0),
+                                             d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out, nullptr, dewi::SegmentLayout{},
+                                             stream),
+                  "select launch");
+}
+
+int dewi_rescore_candidates_f32(const float* d_E, int64_t n_rows, int dim, const float* d_Q, int n_queries,
+                                dewi_candidate* d_cand, int n_candidates, int64_t id_offset, void* stream) {
+  if (!d_E || !d_Q || !d_cand) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (int rc = check_i8_shape(n_rows, dim, 4)) return rc;
+  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
+  if (int rc = check_i8_candidates(n_candidates)) return rc;
+  if (int rc = check_aligned16(d_E, "the rows")) return rc;
+  return launched(dewi::launch_rescore_candidates_f32(d_E, n_rows, dim, d_Q, n_queries, d_cand, n_candidates, id_offset,
+                                                      static_cast<hipStream_t>(stream)),
+                  "rescore_candidates_f32 launch");
+}
+
 size_t dewi_robust_fit_workspace_bytes(int n_signals) {
   return n_signals > 0 ? dewi::robust_fit_workspace_bytes(n_signals) : 0;
 }

@@ -417,6 +417,23 @@ hipError_t launch_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows,
                                  float max_sim, int64_t id_offset, int64_t* d_out_ids, float* d_out_scores, float* d_out_mmr,
                                  hipStream_t stream);
 
+// ---- knn_scan_i8.hip: the approximate route over an int8 copy of the corpus (include/dewi_hip.h, "INT8 copy") ----
+constexpr int kI8MaxCandidates = DEWI_I8_MAX_CANDIDATES;
+constexpr int kI8MaxDim = DEWI_I8_MAX_DIM;
+constexpr int kI8MaxBlocks = 256;      // workgroups of the scan: one per compute unit of an MI355X, whatever the device (the
+                                       // plan, and with it the workspace size, needs no device)
+// fills blocks / waves, slots (1 / 4 / dense 0), n_lists, keys_per_query, nq_per_launch, kind (kScanAnyLong / kScanAnyShort),
+// units (16 codes each), u_pad, log2p, level, rows_per_iter — by plan_scan's rules for c <= 64, c <= 256 and above
+ScanPlan plan_scan_i8(int64_t n_rows, int dim, int n_candidates);
+hipError_t launch_quantize_rows_i8(const float* d_E, int64_t n_rows, int dim, int8_t* d_codes, float* d_scales, hipStream_t stream);
+hipError_t launch_prepare_queries_i8(const float* d_Q, int n_queries, int dim, int8_t* d_codes, float* d_scales, float* d_qn,
+                                     hipStream_t stream);
+// one corpus pass for queries [q0, q0 + nq), nq = 1 or 4 (raw queries; keys at d_keys + q * plan.keys_per_query)
+hipError_t launch_scan_i8(const ScanPlan& plan, const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim,
+                          const float* d_q_raw, int q0, int nq, int n_candidates, uint64_t* d_keys, hipStream_t stream);
+hipError_t launch_rescore_candidates_f32(const float* d_E, int64_t n_rows, int dim, const float* d_Q, int n_queries,
+                                         dewi_candidate* d_cand, int n_candidates, int64_t id_offset, hipStream_t stream);
+
 // ---- mutate.hip (in-place removal / upsert of rows; the reference has no counterpart) --------
 // d_error: an int32 the kernels INCREMENT for every pair / slot outside the contract (the caller zeroes it).
 hipError_t launch_rows_move(void* d_E, int elem_type, uint16_t* d_shadow, float* d_dewi32, float* d_ent32, int32_t* d_aux,

@@ -60,6 +60,30 @@ def cut_size(k: int, candidates: Optional[int], n: Optional[int] = None) -> int:
     return max(c, 1)
 
 
+def check_int8_shape(space: str, is_bf16: bool, dim: int) -> None:
+    """What the int8 route serves: cosine, an fp32 main matrix, ``dim % 16 == 0`` up to 4096 columns — anything else is a
+    ``ValueError``.  Host logic only."""
+    if space != "cosine":
+        raise ValueError(f"the int8 shadow serves cosine corpora, not space={space!r}")
+    if is_bf16:
+        raise ValueError("the int8 shadow is made from an fp32 main matrix (this corpus is bf16)")
+    if int(dim) % 16 != 0 or not 16 <= int(dim) <= nat.I8_MAX_DIM:
+        raise ValueError(f"the int8 shadow takes dim % 16 == 0 from 16 to {nat.I8_MAX_DIM} columns, got dim = {dim}")
+
+
+def approx_cut(k: int, candidates: Optional[int], n: int) -> int:
+    """The cut of an approximate search: the project's one rule (``cut_size``: ``min(2k, n)``, or ``candidates``), which the
+    int8 route serves up to ``I8_MAX_CANDIDATES``; ``k`` must fit into it.  ``ValueError`` otherwise.  Host logic only."""
+    if candidates is not None and int(candidates) > nat.I8_MAX_CANDIDATES:
+        raise ValueError(f"the int8 route re-ranks at most {nat.I8_MAX_CANDIDATES} candidates, got candidates = {int(candidates)}")
+    c = cut_size(k, candidates, n)
+    if c > nat.I8_MAX_CANDIDATES:
+        raise ValueError(f"the int8 route re-ranks at most {nat.I8_MAX_CANDIDATES} candidates, k = {int(k)} asks for {c}")
+    if int(k) > c:
+        raise ValueError(f"k = {int(k)} exceeds the cut of {c} candidates")
+    return c
+
+
 def library_size(size_fn, *args) -> int:
     """``size_fn(*args)`` in bytes.  A size function of the library answers 0 for a shape it refuses: ``NativeLibraryError``
     with its last error."""
@@ -241,6 +265,9 @@ class DeviceCorpus:
         self._lock = threading.RLock()
         self._store = None            # [emb, dewi32, ent32, shadow] storage tensors once the corpus was mutated or reserved
         self.reallocations = 0        # how often the storage grew (reserve / an append beyond the capacity)
+        self.i8_codes = None          # int8 copy of an fp32 matrix (enable_int8_shadow): [N, dim] codes ...
+        self.i8_scales = None         # ... and one fp32 scale per row
+        self._i8_stale = False        # the rows changed since the copy was made: the next approximate search re-quantises
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -318,6 +345,112 @@ class DeviceCorpus:
             self.shadow = out
         self.shadow_min_batch = 1 if single_query else 2
         return self
+
+    # ------------------------------------------------------------------ int8 shadow (approximate route)
+    def enable_int8_shadow(self) -> "DeviceCorpus":
+        """Keep an int8 copy of this fp32 matrix next to it — one byte per element and one fp32 scale per row: +25 % memory —
+        for the APPROXIMATE route ``search_approx_device`` (``dewi_quantize_rows_i8``: a symmetric per-row quantisation,
+        ``scale = max|x| / 127``).  Cosine, an fp32 main matrix, ``dim % 16 == 0`` up to 4096 columns; anything else raises
+        ``ValueError``.  Nothing else changes: every exact search of the corpus runs as before.
+
+        ``remove_rows`` / ``put_rows`` mark the copy stale; the next approximate search re-quantises the WHOLE matrix (one
+        pass over the fp32 rows, about the cost of one exact search) — so a mutated corpus and a freshly built one hold the
+        same codes bit for bit.  Incremental re-quantisation is not part of this build."""
+        check_int8_shape(self.space, self.is_bf16, self.dim)
+        with self._lock, _torch().cuda.device(self.device):
+            if self.i8_codes is None or self._i8_stale:
+                self._quantize_int8()
+        return self
+
+    @property
+    def has_int8_shadow(self) -> bool:
+        return self.i8_codes is not None
+
+    def _quantize_int8(self) -> None:
+        torch = _torch()
+        n = self.n_rows
+        codes = torch.empty((n, self.dim), dtype=torch.int8, device=self.device)
+        scales = torch.empty(n, dtype=torch.float32, device=self.device)
+        nat.check(self._lib.dewi_quantize_rows_i8(nat.ptr(self.emb), n, self.dim, nat.ptr(codes), nat.ptr(scales),
+                                                  nat.stream_ptr()))
+        self.i8_codes, self.i8_scales, self._i8_stale = codes, scales, False
+
+    def _int8(self):
+        """(codes, scales) of the int8 copy, re-quantised first if the rows changed since it was made."""
+        if self.i8_codes is None:
+            raise ValueError("this corpus has no int8 shadow: call enable_int8_shadow() (ExactIndex(int8_shadow=True))")
+        if self._i8_stale:
+            self._quantize_int8()
+        return self.i8_codes, self.i8_scales
+
+    def to_int8(self) -> "Int8Corpus":
+        """A stand-alone corpus of the codes, the scales and the payload columns only (0.26 x the memory of the fp32 rows):
+        it serves ``search_approx_device(rescore=False)`` / ``search_approx(rescore=False)``; everything else on it raises
+        ``NotImplementedError``.  The tensors are shared with this corpus's shadow when it has one."""
+        check_int8_shape(self.space, self.is_bf16, self.dim)
+        with self._lock, _torch().cuda.device(self.device):
+            if self.i8_codes is not None:
+                codes, scales = self._int8()
+            else:
+                self._quantize_int8()
+                codes, scales = self.i8_codes, self.i8_scales
+                self.i8_codes = self.i8_scales = None
+        return Int8Corpus(codes, scales, self.dewi32, self.ent32, self.id_offset)
+
+    def candidates_i8_device(self, q_dev, n_candidates: int, out=None, id_offset: Optional[int] = None):
+        """The ``n_candidates`` best rows of every query BY THE INT8 SCORES as candidate records, int32 view
+        [B, n_candidates, 4], in ``candidates_device``'s layout and order (``dewi_knn_candidates_i8``).  ``id_offset``:
+        default the corpus's."""
+        codes, scales = self._int8()
+        b, c = int(q_dev.shape[0]), int(n_candidates)
+        if out is None:
+            out = _torch().empty((b, c, 4), dtype=_torch().int32, device=self.device)
+        n = int(codes.shape[0])
+        ws = self._cached_workspace(("i8", b, c), self._lib.dewi_knn_i8_workspace_bytes, n, self.dim, b, c)
+        nat.check(self._lib.dewi_knn_candidates_i8(
+            nat.ptr(codes), nat.ptr(scales), n, self.dim, nat.ptr(q_dev), b, nat.ptr(self.dewi32), nat.ptr(self.ent32), c,
+            self.id_offset if id_offset is None else int(id_offset), nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+        return out
+
+    def rescore_candidates_device(self, q_dev, recs, id_offset: Optional[int] = None):
+        """In place: the similarity of every record of ``recs`` ([B, c, 4] int32 view) becomes the fp32 inner product of its
+        stored fp32 row and the normalised query, and each query's list is sorted again (``dewi_rescore_candidates_f32``)."""
+        if self.is_bf16:
+            raise NotImplementedError("candidates are re-scored from fp32 rows (this corpus is bf16)")
+        nat.check(self._lib.dewi_rescore_candidates_f32(
+            nat.ptr(self.emb), self.n_rows, self.dim, nat.ptr(q_dev), int(recs.shape[0]), nat.ptr(recs), int(recs.shape[1]),
+            self.id_offset if id_offset is None else int(id_offset), nat.stream_ptr()))
+        return recs
+
+    def search_approx_device(self, q_dev, k: int, eta: float, entropy_pref: float, candidates: Optional[int] = None,
+                             rescore: bool = True, out_ids=None, out_scores=None):
+        """Enqueue one APPROXIMATE search on the current stream; returns device tensors ``(ids, scores)`` [B, k] (local row
+        ids, as ``search_device``), no sync.  The cut — ``min(2k, N)``, or ``candidates`` (up to 1024) — is taken by the int8
+        scores of the shadow (a quarter of the fp32 rows' bytes), then — ``rescore=True`` — re-scored from the fp32 rows,
+        then blended and cut to k exactly as every search (``dewi_knn_candidates_i8`` -> ``dewi_rescore_candidates_f32`` ->
+        ``dewi_merge_rerank``).  With ``rescore`` the returned scores are fp32 similarities' blends; a document is missed
+        only when the int8 scores drop it from the cut (recall: DESIGN.md 4.1q).  ``k`` above the cut and a cut above 1024
+        raise ``ValueError``.  NOT thread-safe on one instance (shared workspaces)."""
+        b, k = check_search_args(q_dev.shape, self.dim, k, None, "ip")
+        if k <= 0:
+            return empty_result(b, self.device)
+        c = approx_cut(k, candidates, self.n_rows)
+        recs = self.candidates_i8_device(q_dev, c, id_offset=0)
+        if rescore:
+            self.rescore_candidates_device(q_dev, recs, id_offset=0)
+        return merge_rerank_device(recs.view(1, b, c, 4), c, k, eta, entropy_pref, out_ids, out_scores)
+
+    def search_approx(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                      candidates: Optional[int] = None, rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """Blocking twin of ``search`` for ``search_approx_device``: (ids int64 [B, k] including id_offset, scores fp32
+        [B, k]) on the host.  Serialised by the per-corpus lock."""
+        with self._lock, _torch().cuda.device(self.device):
+            q = self.stage_queries(queries)
+            ids_d, sc_d = self.search_approx_device(q, k, eta, entropy_pref, candidates, rescore)
+            ids_h, scores_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
+        if self.id_offset:
+            ids_h = ids_h + self.id_offset
+        return ids_h, scores_h
 
     # ------------------------------------------------------------------ properties
     @property
@@ -404,6 +537,8 @@ class DeviceCorpus:
         self._ws.clear()
         self._io.clear()
         self._last_call = None
+        if self.i8_codes is not None:
+            self._i8_stale = True              # re-quantised as a whole by the next approximate search (_int8)
 
     def _read_error(self, err, what: str) -> None:
         bad = int(err.item())                  # the call's one synchronisation
@@ -1196,6 +1331,20 @@ class DeviceCorpus:
         1`` without ``max_sim`` is the plain search over that pool.  A query with fewer than k eligible rows leaves id -1 /
         score NaN in the tail of its row.  Cosine corpora (``space="l2"``: ``NotImplementedError`` — the
         penalty is an inner product of unit rows), fp32 and bf16.  NOT thread-safe on one instance (shared workspaces)."""
+        return self._search_diverse(q_dev, k, eta, entropy_pref, mmr_lambda, candidates, max_sim, out_ids, out_scores)
+
+    def search_diverse_approx_device(self, q_dev, k: int, eta: float, entropy_pref: float, mmr_lambda: float = 0.5,
+                                     candidates: Optional[int] = None, max_sim: Optional[float] = None, rescore: bool = True,
+                                     out_ids=None, out_scores=None):
+        """``search_diverse_device`` with the pool taken by the int8 scores of the shadow (``candidates_i8_device``) and —
+        ``rescore=True`` — re-scored from the fp32 rows; the same records then go to ``dewi_diverse_rerank`` with the fp32
+        rows.  (A method of its own: the parameter list of ``search_diverse_device`` is fixed.)"""
+        self._int8()
+        return self._search_diverse(q_dev, k, eta, entropy_pref, mmr_lambda, candidates, max_sim, out_ids, out_scores,
+                                    approx=True, rescore=rescore)
+
+    def _search_diverse(self, q_dev, k, eta, entropy_pref, mmr_lambda, candidates, max_sim, out_ids, out_scores,
+                        approx: bool = False, rescore: bool = True):
         torch = _torch()
         n = self.n_rows
         b, k = check_search_args(q_dev.shape, self.dim, k, None, "ip")
@@ -1219,7 +1368,12 @@ class DeviceCorpus:
         if max_sim is not None:         # (without the cut every query picks k of its c >= k records: nothing is left unwritten)
             out_ids.fill_(-1)
             out_scores.fill_(float("nan"))
-        recs = self.candidates_device(q_dev, c)
+        if approx:
+            recs = self.candidates_i8_device(q_dev, c)
+            if rescore:
+                self.rescore_candidates_device(q_dev, recs)
+        else:
+            recs = self.candidates_device(q_dev, c)
         need = int(self._lib.dewi_diverse_workspace_bytes(b, c, self.dim))    # 0: the re-rank keeps its state on chip
         ws = None
         if need:
@@ -1242,6 +1396,74 @@ class DeviceCorpus:
             q = self.stage_queries(queries)
             ids_d, sc_d = self.search_diverse_device(q, k, eta, entropy_pref, mmr_lambda, candidates, max_sim)
             return ids_d.cpu().numpy(), sc_d.cpu().numpy()
+
+    def search_diverse_approx(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                              mmr_lambda: float = 0.5, candidates: Optional[int] = None, max_sim: Optional[float] = None,
+                              rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """Blocking twin of ``search_diverse`` for ``search_diverse_approx_device``."""
+        torch = _torch()
+        with self._lock, torch.cuda.device(self.device):
+            q = self.stage_queries(queries)
+            ids_d, sc_d = self.search_diverse_approx_device(q, k, eta, entropy_pref, mmr_lambda, candidates, max_sim, rescore)
+            return ids_d.cpu().numpy(), sc_d.cpu().numpy()
+
+
+class Int8Corpus(DeviceCorpus):
+    """The int8 form of a corpus on its own (``DeviceCorpus.to_int8``): codes, scales and the two payload columns — no fp32
+    rows.  Serves ``search_approx_device`` / ``search_approx`` with ``rescore=False``; every other public method of
+    ``DeviceCorpus`` raises ``NotImplementedError``."""
+
+    _SERVED = frozenset({"search_approx_device", "search_approx", "candidates_i8_device", "stage_queries", "corpus_bytes",
+                         "cached_workspaces", "replace_cached_workspace", "drop_cached_workspaces"})
+
+    def __init__(self, codes, scales, dewi32, ent32, id_offset: int = 0):
+        torch = _torch()
+        assert codes.is_cuda and codes.dim() == 2 and codes.is_contiguous() and codes.dtype == torch.int8
+        assert scales.dtype == torch.float32 and int(scales.numel()) == int(codes.shape[0]) == int(dewi32.numel())
+        self.emb = None
+        self.i8_codes, self.i8_scales, self._i8_stale = codes, scales.contiguous(), False
+        self.dewi32, self.ent32 = dewi32.contiguous(), ent32.contiguous()
+        self.space = "cosine"
+        self.id_offset = int(id_offset)
+        self.device = codes.device
+        self.corpus_id = next(_corpus_ids)
+        self._lib = nat.load_library()
+        self._ws = {}
+        self._q_pinned = None
+        self._q_dev = None
+        self.shadow = None
+        self._lock = threading.RLock()
+        self._store = None
+
+    def __getattribute__(self, name):
+        if not name.startswith("_") and name not in Int8Corpus._SERVED and callable(getattr(DeviceCorpus, name, None)):
+            raise NotImplementedError(f"{name}: a stand-alone int8 corpus serves search_approx(rescore=False) only")
+        return object.__getattribute__(self, name)
+
+    @property
+    def n_rows(self) -> int:
+        return int(self.i8_codes.shape[0])
+
+    @property
+    def dim(self) -> int:
+        return int(self.i8_codes.shape[1])
+
+    @property
+    def is_bf16(self) -> bool:
+        return False
+
+    def corpus_bytes(self) -> int:
+        return self.i8_codes.numel() + 4 * self.i8_scales.numel()
+
+    def search_approx_device(self, q_dev, k: int, eta: float, entropy_pref: float, candidates: Optional[int] = None,
+                             rescore: bool = False, out_ids=None, out_scores=None):
+        if rescore:
+            raise NotImplementedError("a stand-alone int8 corpus has no fp32 rows to re-score from: pass rescore=False")
+        return DeviceCorpus.search_approx_device(self, q_dev, k, eta, entropy_pref, candidates, False, out_ids, out_scores)
+
+    def search_approx(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                      candidates: Optional[int] = None, rescore: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        return DeviceCorpus.search_approx(self, queries, k, eta, entropy_pref, candidates, rescore)
 
 
 class PipelinedSearcher:

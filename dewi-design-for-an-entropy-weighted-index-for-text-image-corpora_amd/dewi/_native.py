@@ -38,6 +38,9 @@ RANGE_MAX_QUERIES = 32
 RANGE_SHADOW_MAX_QUERIES = 2048
 #: largest candidate pool of a diverse (MMR) re-rank (include/dewi_hip.h DEWI_DIVERSE_MAX_CANDIDATES)
 DIVERSE_MAX_CANDIDATES = 1024
+#: largest candidate cut and widest row of the int8 route (include/dewi_hip.h DEWI_I8_MAX_CANDIDATES / DEWI_I8_MAX_DIM)
+I8_MAX_CANDIDATES = 1024
+I8_MAX_DIM = 4096
 #: which row of a group represents it (include/dewi_hip.h DEWI_GROUPS_KEEP_*): the lowest row / the highest key (the dewi column)
 KEEP_CODES = {"first": 0, "dewi": 1}
 
@@ -59,6 +62,8 @@ EXPORTED_SYMBOLS = (
     "dewi_groups_workspace_bytes", "dewi_groups_begin", "dewi_groups_union_lists", "dewi_groups_union_pairs", "dewi_groups_finish",
     "dewi_diverse_workspace_bytes", "dewi_diverse_rerank",
     "dewi_rows_move", "dewi_rows_put_f32",
+    "dewi_quantize_rows_i8", "dewi_prepare_queries_i8", "dewi_knn_i8_workspace_bytes", "dewi_knn_candidates_i8",
+    "dewi_rescore_candidates_f32",
 )
 
 
@@ -205,6 +210,16 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_rows_move.argtypes = [vp, i32, vp, vp, vp, vp, i64, i32, i64, vp, vp, i64, vp, vp]
     lib.dewi_rows_put_f32.restype = i32
     lib.dewi_rows_put_f32.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp]
+    lib.dewi_quantize_rows_i8.restype = i32
+    lib.dewi_quantize_rows_i8.argtypes = [vp, i64, i32, vp, vp, vp]
+    lib.dewi_prepare_queries_i8.restype = i32
+    lib.dewi_prepare_queries_i8.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.dewi_knn_i8_workspace_bytes.restype = sz
+    lib.dewi_knn_i8_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_knn_candidates_i8.restype = i32
+    lib.dewi_knn_candidates_i8.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i32, i64, vp, vp, sz, vp]
+    lib.dewi_rescore_candidates_f32.restype = i32
+    lib.dewi_rescore_candidates_f32.argtypes = [vp, i64, i32, vp, i32, vp, i32, i64, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

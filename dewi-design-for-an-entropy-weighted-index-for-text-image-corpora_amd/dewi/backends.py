@@ -188,6 +188,14 @@ class ExactIndex(BaseIndex):
         self._batch_shadow: bool = bool(kwargs.get("batch_shadow", False))
         # with batch_shadow: search() of ONE query goes through the shadow too (same answers; see enable_bf16_shadow)
         self._shadow_single: bool = bool(kwargs.get("shadow_single_query", False))
+        # additive: keep an int8 copy of the fp32 matrix (+25 % HBM) for the APPROXIMATE route — search(approx=...) takes the
+        # candidate cut by integer scores over a quarter of the bytes and re-scores it from the fp32 rows
+        # (DeviceCorpus.enable_int8_shadow).  remove / upsert* mark the copy stale: the next approximate search re-quantises
+        # the whole matrix (one pass over the fp32 rows), so a mutated index and a fresh one answer bit-equally.
+        self._int8_shadow: bool = bool(kwargs.get("int8_shadow", False))
+        if self._int8_shadow:
+            from ._engine import check_int8_shape
+            check_int8_shape(space, False, dim)
         self._id_rows: Optional[Dict[str, int]] = None  # doc_id -> row of remove / upsert: made once, then kept per call
 
     # ---------------------------------------------------------------- ingest (A1)
@@ -496,6 +504,8 @@ class ExactIndex(BaseIndex):
         self._corpus = DeviceCorpus(emb, dewi32, ent32, self.space)
         if self._batch_shadow and self.space == "cosine":
             self._corpus.enable_bf16_shadow(single_query=self._shadow_single)
+        if self._int8_shadow:
+            self._corpus.enable_int8_shadow()
         self._pending = []
         self._pending_rows = 0
         self._loaded_rows = None
@@ -531,6 +541,8 @@ class ExactIndex(BaseIndex):
             corpus = head
         self._corpus = (corpus.enable_bf16_shadow(single_query=self._shadow_single)
                         if self._batch_shadow and self.space == "cosine" else corpus)
+        if self._int8_shadow:
+            self._corpus.enable_int8_shadow()
         self._pending = []
         self._pending_rows = 0
         self._loaded_rows = None
@@ -700,8 +712,35 @@ class ExactIndex(BaseIndex):
             return self.make_query_filters(filter)
         return self.make_filter(**filter_kwargs(filter))
 
+    #: largest batch ``approx=None`` sends through the int8 route: it scans the corpus once per FOUR queries (no matrix-core
+    #: pass), so it wins for one query and small batches and loses to the exact matrix-core batch beyond (1 M x 768, k = 10:
+    #: 4 queries 0.34 ms against 0.50 exact, 32 queries 2.58 ms against 0.55 — DESIGN.md 4.1q)
+    APPROX_AUTO_MAX_BATCH = 4
+
+    def _use_approx(self, approx: Optional[bool], similarity: str, filter, k: int, candidates: Optional[int],
+                    n_queries: int = 1) -> bool:
+        """Whether a search takes the int8 route.  ``approx=True``: it must (``ValueError`` without an int8 shadow, with a
+        ``filter`` or with a similarity transform); ``None``: it does where the index has an int8 shadow and the route
+        serves the call (no filter, no transform, a cut of at most 1024, at most ``APPROX_AUTO_MAX_BATCH`` queries);
+        ``False``: never."""
+        if approx is None:
+            if not self._int8_shadow or filter is not None or similarity != "ip" or int(n_queries) > self.APPROX_AUTO_MAX_BATCH:
+                return False
+            from . import _native as nat
+            return (2 * int(k) if candidates is None else int(candidates)) <= nat.I8_MAX_CANDIDATES
+        if not approx:
+            return False
+        if not self._int8_shadow:
+            raise ValueError("approx=True needs an index built with int8_shadow=True")
+        if filter is not None:
+            raise ValueError("approx=True does not take a filter: filtered searches run on the fp32 rows (approx=False)")
+        if similarity != "ip":
+            raise ValueError("approx=True does not take a similarity transform")
+        return True
+
     def search(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
-               candidates: Optional[int] = None, similarity: str = "ip", filter=None) -> SearchResult:
+               candidates: Optional[int] = None, similarity: str = "ip", *, approx: Optional[bool] = None,
+               rescore: bool = True, filter=None) -> SearchResult:
         """Reference ``ExactIndex.search`` (backends.py:414-481) for one query.
 
         ``candidates`` (additive): how many nearest rows are re-ranked.  Default ``min(2k, N)``, the
@@ -716,25 +755,44 @@ class ExactIndex(BaseIndex):
         ``make_filter`` takes.  The result is the reference's search applied to the allowed rows only: c = min(2k, |A|),
         ``[]`` for an empty filter, ``ValueError`` for k > |A|.  Per-query filters (``make_query_filters``) of one query
         are accepted as well.
+
+        ``approx`` / ``rescore`` (additive, keyword-only like ``filter``): see ``search_batch``.
         """
         q = np.asarray(query, dtype=np.float32)
         if q.ndim == 1:
             q = q.reshape(1, -1)
-        rows, scores = self.search_batch(q, k, eta, entropy_pref, candidates, similarity, filter=filter)
+        rows, scores = self.search_batch(q, k, eta, entropy_pref, candidates, similarity, approx=approx, rescore=rescore,
+                                         filter=filter)
         keep = rows[:1] >= 0            # (per-query filters: an empty list pads its row with id -1)
         return self.results_for(rows[:1][:, keep[0]], scores[:1][:, keep[0]])[0]
 
     def search_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
-                     candidates: Optional[int] = None, similarity: str = "ip", filter=None) -> Tuple[np.ndarray, np.ndarray]:
+                     candidates: Optional[int] = None, similarity: str = "ip", *, approx: Optional[bool] = None,
+                     rescore: bool = True, filter=None) -> Tuple[np.ndarray, np.ndarray]:
         """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k]).  ``filter``: see ``search``
         (one allow-list for every query of the batch; [B, 0] results when it is empty or k <= 0).  Per-query filters —
         a ``DeviceQueryFilters`` of B lists (``make_query_filters``) or a bool [B, N] mask — restrict query j to its own
         list F_j, with the rules of one list per query (c = min(2k, |F_j|), ``ValueError`` naming the query for
-        k > |F_j| > 0); the row of a query whose list is empty is padded with id -1 and score NaN."""
+        k > |F_j| > 0); the row of a query whose list is empty is padded with id -1 and score NaN.
+
+        ``approx`` (additive; an index built with ``int8_shadow=True``): take the candidate cut — ``min(2k, N)``, or
+        ``candidates`` up to 1024 — by the INT8 scores of the shadow (a quarter of the bytes of the fp32 rows), re-score it
+        from the fp32 rows (``rescore=True``; ``False`` blends the int8 scores as they are) and finish as ever.  Approximate:
+        a document is missed when the int8 scores drop it from the cut (measured recall: DESIGN.md 4.1q).  ``None`` (default)
+        means "the index has an int8 shadow" — where the route serves the call (no filter, no similarity transform, a cut
+        of at most 1024, at most ``APPROX_AUTO_MAX_BATCH`` = 4 queries: the route scans the corpus once per four queries and
+        loses to the exact matrix-core batch beyond; ``approx=True`` takes it for any batch); ``True`` without a shadow, with ``filter=`` or with a transform raises ``ValueError``; ``False`` is
+        the exact path, bit for bit.  After ``remove`` / ``upsert*`` the next approximate search re-quantises the whole
+        matrix (one pass over the fp32 rows), so a mutated index answers as a freshly built one."""
+        use_approx = self._use_approx(approx, similarity, filter, k, candidates,      # (argument errors before any build)
+                                      np.shape(queries)[0] if np.ndim(queries) == 2 else 1)
         self._ensure_built()
         q = np.asarray(queries, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        if use_approx:
+            return self._corpus.search_approx(q, int(k), float(eta), float(entropy_pref), candidates=candidates,
+                                              rescore=bool(rescore))
         if filter is not None:
             return self._corpus.search(q, int(k), float(eta), float(entropy_pref), candidates=candidates,
                                        similarity=similarity, filter=self._prepared(filter))
@@ -772,6 +830,33 @@ class ExactIndex(BaseIndex):
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
         return self._corpus.search_diverse(q, int(k), float(eta), float(entropy_pref), float(mmr_lambda), candidates, max_sim)
+
+    def search_diverse_approx(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                              mmr_lambda: float = 0.5, candidates: Optional[int] = None, max_sim: Optional[float] = None,
+                              rescore: bool = True) -> SearchResult:
+        """``search_diverse`` with the pool taken by the int8 scores of the shadow and — ``rescore=True`` — re-scored from the
+        fp32 rows (an index built with ``int8_shadow=True``; ``ValueError`` otherwise).  A method of its own: the parameter
+        lists of ``search_diverse`` / ``search_diverse_batch`` are fixed."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        rows, scores = self.search_diverse_approx_batch(q[:1], k, eta, entropy_pref, mmr_lambda, candidates, max_sim, rescore)
+        keep = rows[0] >= 0
+        return self.results_for(rows[:1][:, keep], scores[:1][:, keep])[0]
+
+    def search_diverse_approx_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                                    mmr_lambda: float = 0.5, candidates: Optional[int] = None,
+                                    max_sim: Optional[float] = None, rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k]) in pick order, padded with id -1 /
+        score NaN: ``search_diverse_batch`` over the int8 route's pool.  See ``search_diverse_approx``."""
+        if not self._int8_shadow:
+            raise ValueError("an approximate diverse search needs an index built with int8_shadow=True")
+        self._ensure_built()
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        return self._corpus.search_diverse_approx(q, int(k), float(eta), float(entropy_pref), float(mmr_lambda), candidates,
+                                                  max_sim, bool(rescore))
 
     # ---------------------------------------------------------------- range search (additive)
     def range_search(self, query: np.ndarray, threshold: float, eta: float = 0.5, entropy_pref: float = 0.0, filter=None,

@@ -44,7 +44,7 @@ class DewiIndex(BaseIndex):
             # index.py:58-60: requested ANN library missing -> warn, use the exact index
             logger.warning("ANN backend unavailable; falling back to ExactIndex.")
         # (additive switches of the exact backend; everything else in **kwargs is accepted and ignored as in the reference)
-        exact_kwargs = {k: v for k, v in kwargs.items() if k in ("device", "batch_shadow", "shadow_single_query")}
+        exact_kwargs = {k: v for k, v in kwargs.items() if k in ("device", "batch_shadow", "shadow_single_query", "int8_shadow")}
         self._backend: BaseIndex = ExactIndex(dim, space, **exact_kwargs)
 
     # ------------------------------------------------------------------ ingest / build
@@ -123,10 +123,18 @@ class DewiIndex(BaseIndex):
             self.build()
         return self._backend.make_query_filters(masks, doc_ids=doc_ids, rows=rows)
 
+    def _approx_kwargs(self, approx: Optional[bool], rescore: bool) -> Dict[str, Any]:
+        """The int8 route's keywords for the backend: nothing for a call that leaves them at their defaults (the backend then
+        sees exactly the call it always saw)."""
+        return {} if approx is None and rescore else {"approx": approx, "rescore": rescore}
+
     def search(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
-               entropy_pref: Optional[float] = None, filter=None) -> List[Tuple[str, float, Payload]]:
+               entropy_pref: Optional[float] = None, *, approx: Optional[bool] = None, rescore: bool = True,
+               filter=None) -> List[Tuple[str, float, Payload]]:
         """``filter`` (additive): search only an allow-list — a prepared filter (``make_filter``), a bool mask, doc ids
-        or row positions."""
+        or row positions.  ``approx`` / ``rescore`` (additive; an index made with ``int8_shadow=True``): the approximate
+        int8 route of ``ExactIndex.search_batch`` — ``None``: taken where the index has an int8 shadow; ``True`` without
+        one, or together with ``filter``, raises ``ValueError``; ``False``: the exact path."""
         if not self._built:
             self.build()
         eta, entropy_pref = self._defaults(eta, entropy_pref)
@@ -134,13 +142,15 @@ class DewiIndex(BaseIndex):
         if q.shape != (self.dim,):
             raise ValueError(f"Expected query shape ({self.dim},), got {q.shape}")
         if filter is not None:
-            return self._backend.search(q, k, eta, entropy_pref, filter=filter)
-        return self._backend.search(q, k, eta, entropy_pref)
+            return self._backend.search(q, k, eta, entropy_pref, filter=filter, **self._approx_kwargs(approx, rescore))
+        return self._backend.search(q, k, eta, entropy_pref, **self._approx_kwargs(approx, rescore))
 
     def search_batch(self, queries: np.ndarray, k: int = 10, eta: Optional[float] = None,
-                     entropy_pref: Optional[float] = None, filter=None) -> List[List[Tuple[str, float, Payload]]]:
-        """One call for B queries ([B, dim]); each result list equals ``search`` of that row (``filter``: see ``search``;
-        per-query filters — ``make_query_filters`` or a bool [B, N] mask — give ``[]`` for a query whose list is empty)."""
+                     entropy_pref: Optional[float] = None, *, approx: Optional[bool] = None, rescore: bool = True,
+                     filter=None) -> List[List[Tuple[str, float, Payload]]]:
+        """One call for B queries ([B, dim]); each result list equals ``search`` of that row (``filter``, ``approx``,
+        ``rescore``: see ``search``; per-query filters — ``make_query_filters`` or a bool [B, N] mask — give ``[]`` for a
+        query whose list is empty)."""
         if not self._built:
             self.build()
         eta, entropy_pref = self._defaults(eta, entropy_pref)
@@ -148,14 +158,43 @@ class DewiIndex(BaseIndex):
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
         if filter is not None:
-            rows, scores = self._backend.search_batch(q, k, eta, entropy_pref, filter=filter)
+            rows, scores = self._backend.search_batch(q, k, eta, entropy_pref, filter=filter,
+                                                      **self._approx_kwargs(approx, rescore))
             if rows.size and (rows < 0).any():     # per-query filters: an empty list pads its row with id -1
                 n_real = (rows >= 0).sum(axis=1)
                 res = self._backend.results_for(np.where(rows < 0, 0, rows), scores)
                 return [r[:int(m)] for r, m in zip(res, n_real)]
         else:
-            rows, scores = self._backend.search_batch(q, k, eta, entropy_pref)
+            rows, scores = self._backend.search_batch(q, k, eta, entropy_pref, **self._approx_kwargs(approx, rescore))
         return self._backend.results_for(rows, scores)
+
+    def search_diverse_approx(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
+                              entropy_pref: Optional[float] = None, mmr_lambda: float = 0.5, candidates: Optional[int] = None,
+                              max_sim: Optional[float] = None, rescore: bool = True) -> List[Tuple[str, float, Payload]]:
+        """``search_diverse`` over the pool the int8 route picks (``ExactIndex.search_diverse_approx``; an index made with
+        ``int8_shadow=True``)."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.shape != (self.dim,):
+            raise ValueError(f"Expected query shape ({self.dim},), got {q.shape}")
+        return self.search_diverse_approx_batch(q.reshape(1, -1), k, eta, entropy_pref, mmr_lambda, candidates, max_sim,
+                                                rescore)[0]
+
+    def search_diverse_approx_batch(self, queries: np.ndarray, k: int = 10, eta: Optional[float] = None,
+                                    entropy_pref: Optional[float] = None, mmr_lambda: float = 0.5,
+                                    candidates: Optional[int] = None, max_sim: Optional[float] = None,
+                                    rescore: bool = True) -> List[List[Tuple[str, float, Payload]]]:
+        """One call for B queries ([B, dim]); each result list equals ``search_diverse_approx`` of that row."""
+        eta, entropy_pref = self._defaults(eta, entropy_pref)
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        if not self._built:
+            self.build()
+        rows, scores = self._backend.search_diverse_approx_batch(q, k, eta, entropy_pref, mmr_lambda, candidates, max_sim,
+                                                                 rescore)
+        n_real = (rows >= 0).sum(axis=1)
+        res = self._backend.results_for(np.where(rows < 0, 0, rows), scores)
+        return [r[:int(m)] for r, m in zip(res, n_real)]
 
     def search_diverse(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
                        entropy_pref: Optional[float] = None, mmr_lambda: float = 0.5, candidates: Optional[int] = None,
@@ -270,7 +309,10 @@ class DewiIndex(BaseIndex):
                 json.dump(self._meta, fh)
 
     @classmethod
-    def load(cls, path: Union[str, Path]) -> "DewiIndex":
+    def load(cls, path: Union[str, Path], **kwargs: Any) -> "DewiIndex":
+        """``kwargs`` (additive): the exact backend's switches, e.g. ``int8_shadow=True`` — nothing of the int8 shadow is on
+        disk; it is made again from the fp32 rows at the first build, and quantisation is deterministic, so a loaded index
+        answers bit-equally."""
         root = Path(path)
         with open(root / "config.json", "r", encoding="utf-8") as fh:
             cfg = json.load(fh)
@@ -280,7 +322,8 @@ class DewiIndex(BaseIndex):
         inst = cls(dim=cfg["dim"], space=cfg["space"], backend="exact", use_ann=cfg.get("use_ann", True),
                    ef_query=cfg.get("ef_query", 200), rerank_eta=cfg.get("rerank_eta", 0.25),
                    entropy_pref=cfg.get("entropy_pref", 0.0))
-        inst._backend = backend_cls.load(root / "ann_index")
+        exact_kwargs = {k: v for k, v in kwargs.items() if k in ("device", "batch_shadow", "shadow_single_query", "int8_shadow")}
+        inst._backend = backend_cls.load(root / "ann_index", **exact_kwargs)
         inst._built = False  # device copy is rebuilt on first use
         meta_path = root / "meta.json"
         if meta_path.exists():

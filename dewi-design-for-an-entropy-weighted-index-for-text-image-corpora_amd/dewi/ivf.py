@@ -80,6 +80,8 @@ class IVFIndex(ExactIndex):
             raise ValueError(f"train_iters must not be negative, got {train_iters}")
         if max_train_rows is not None and int(max_train_rows) < 1:
             raise ValueError(f"max_train_rows must be at least 1, got {max_train_rows}")
+        if kwargs.get("int8_shadow"):
+            raise ValueError("IVFIndex does not take int8_shadow: the int8 route scans every row (not in this build)")
         super().__init__(dim, space, **kwargs)
         self.nlist = None if nlist is None else int(nlist)
         self.nprobe = None if nprobe is None else int(nprobe)
@@ -379,17 +381,20 @@ class IVFIndex(ExactIndex):
         return out_ids, out_scores
 
     def search_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
-                     candidates: Optional[int] = None, similarity: str = "ip", filter=None, *,
-                     nprobe: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+                     candidates: Optional[int] = None, similarity: str = "ip", *, approx: Optional[bool] = None,
+                     rescore: bool = True, filter=None, nprobe: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k]); query j searches the rows F_j of its
         ``nprobe`` nearest cells with the rules of ``ExactIndex.search`` on those rows (cut ``min(2k, |F_j|)`` or
         ``candidates``, blend, top-k).  An approximate index does not raise when the probe is short: with ``|F_j| < k`` the
         row holds ``|F_j|`` results and is padded with id -1 / score NaN.
 
         ``filter=`` together with IVF is not supported: passing one runs the parent's EXACT filtered search over the whole
-        allow-list (``nprobe`` is then ignored)."""
+        allow-list (``nprobe`` is then ignored).  ``approx`` / ``rescore`` are ``ExactIndex``'s int8 route, which an
+        ``IVFIndex`` does not have: ``approx=True`` raises ``ValueError``."""
         if nprobe is not None and int(nprobe) < 1:
             raise ValueError(f"nprobe must be at least 1, got {nprobe}")
+        if approx:
+            raise ValueError("approx=True needs an index built with int8_shadow=True (IVFIndex has no int8 route)")
         if filter is not None:
             return super().search_batch(queries, k, eta, entropy_pref, candidates, similarity, filter=filter)
         self._ensure_built()
@@ -404,14 +409,15 @@ class IVFIndex(ExactIndex):
             return ids.cpu().numpy(), scores.cpu().numpy()
 
     def search(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
-               candidates: Optional[int] = None, similarity: str = "ip", filter=None, *,
-               nprobe: Optional[int] = None) -> SearchResult:
+               candidates: Optional[int] = None, similarity: str = "ip", *, approx: Optional[bool] = None,
+               rescore: bool = True, filter=None, nprobe: Optional[int] = None) -> SearchResult:
         """``ExactIndex.search`` over the rows of the query's ``nprobe`` nearest cells (see ``search_batch``); fewer than k
         results when those cells hold fewer than k rows."""
         q = np.asarray(query, dtype=np.float32)
         if q.ndim == 1:
             q = q.reshape(1, -1)
-        rows, scores = self.search_batch(q, k, eta, entropy_pref, candidates, similarity, filter=filter, nprobe=nprobe)
+        rows, scores = self.search_batch(q, k, eta, entropy_pref, candidates, similarity, approx=approx, rescore=rescore,
+                                         filter=filter, nprobe=nprobe)
         keep = rows[0] >= 0
         return self.results_for(rows[:1][:, keep], scores[:1][:, keep])[0]
 

@@ -520,6 +520,62 @@ int dewi_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows, int dim,
                         size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Approximate search over an INT8 copy of the corpus (additive to ABI 6; the reference has no counterpart).  One byte per
+ * element instead of four: a symmetric per-row scalar quantisation, integer inner products, and — optionally — the candidate
+ * cut re-scored from the fp32 rows.  Unlike the bf16 shadow this route is NOT exact: no error band of a useful width is
+ * proven for it; it is opt-in, its arithmetic is defined below bit for bit (tests/int8_model.py restates it in NumPy), and
+ * its recall is measured.  Cosine only.
+ *
+ * Quantisation Q(x) of an fp32 vector x of `dim` elements -> (codes int8[dim], scale fp32):
+ *   a = max_i |x_i|.  Any element NaN or +-inf: scale = NaN, every code 0.  Otherwise scale = a / 127 (fp32, round to
+ *   nearest); scale == 0: every code 0; otherwise code_i = clamp(rint(x_i / scale), -127, 127), the division in fp32 round to
+ *   nearest, rint = round half to even.  -128 is never produced.
+ * Score of a row against a query: D = sum_i code_row,i * code_q,i in exact int32 (|D| <= 127^2 * 4096 < 2^31), ONE int32 ->
+ *   fp32 conversion (round to nearest), then two fp32 products in this order: sim = fl(fl(float(D) * scale_row) * scale_q).
+ *   A NaN row gives 0 * NaN = NaN: it ranks largest and is emitted last, exactly as in the fp32 search.
+ *
+ * dewi_quantize_rows_i8: Q per stored row of d_E [n_rows][dim] -> d_codes [n_rows][dim] row-major, d_scales [n_rows] (a
+ *   separate array, so that rows stay whole 16-byte units).  n_rows == 0: DEWI_OK, nothing launched.
+ * dewi_prepare_queries_i8: a raw query is normalised as every other kernel does it (the float64-summed norm, one rounding
+ *   after the square root, IEEE division, left alone when the norm is 0 — or NaN), then Q.  d_codes [n_queries][dim], d_scales
+ *   [n_queries]; d_qn (may be NULL) receives the normalised fp32 queries [n_queries][dim].  This is the preparation
+ *   dewi_knn_candidates_i8 makes in registers; exposed so that tests can check it on its own and feed the model the very
+ *   same prepared queries.
+ * dewi_knn_i8_workspace_bytes: 0 for a shape the route does not take; needs no device.
+ * dewi_knn_candidates_i8: steps 1-3 of the search on the scores above; d_out [n_queries][n_candidates] in exactly
+ *   dewi_knn_candidates' layout and order — sorted by (ord(sim) desc, id asc), NaN first, -0 == +0 (written as +0), padding
+ *   (id = -1, sim = -inf) behind min(n_candidates, n_rows) — with the payload pair of each row and id_offset added.
+ *   dim % 16 == 0, 16 <= dim <= 4096, d_codes 16-byte aligned, 1 <= n_candidates <= DEWI_I8_MAX_CANDIDATES, n_rows <= 2^32-1.
+ *   Nothing is read outside [d_codes, d_codes + n_rows * dim) or outside d_scales [n_rows].  Batches take the row kernel four
+ *   queries per corpus pass (no matrix-core pass: nothing is refused).
+ * dewi_rescore_candidates_f32: IN PLACE, for every record whose id - id_offset lies in [0, n_rows) (the rule of
+ *   dewi_diverse_rerank: no address is formed for any other row) `sim` becomes the fp32 inner product of the stored fp32 row
+ *   and the normalised fp32 query (normalised as in dewi_prepare_queries_i8), in the summation order of dewi_diverse_rerank's
+ *   g: 16-byte units, unit u on lane u % 16 of 16, a lane's elements ascending with acc = fma(e, q, acc), xor butterfly 8, 4,
+ *   2, 1.  Each query's list is then sorted again: the records with id >= 0 by (ord(sim) desc, id asc) — a record with
+ *   id >= 0 outside the rows keeps its sim —, the records with id < 0 behind them in their old order; dewi / ent / id of a
+ *   record never change.  The result is a list dewi_merge_rerank and dewi_diverse_rerank accept.  One workgroup per query, the
+ *   sort in LDS; dim % 4 == 0, dim <= 4096, d_E 16-byte aligned, 1 <= n_candidates <= DEWI_I8_MAX_CANDIDATES; needs no
+ *   workspace.
+ * All five are asynchronous on `stream`, allocate nothing and synchronise nothing; argument errors are reported before any
+ * device work: null pointers and bad shapes DEWI_ERR_INVALID_ARG; dim % 16 != 0 (rescore: dim % 4), dim > 4096, n_candidates
+ * above the limit, 2^32 rows or more: DEWI_ERR_UNSUPPORTED; a short workspace: DEWI_ERR_WORKSPACE.  n_candidates > n_rows is
+ * not an error (padding).  Steps 3-5 of the search are dewi_merge_rerank(d_out, 1, n_queries, c, c, k, ...) on the records; a
+ * diverse search is dewi_diverse_rerank on the same records with the fp32 rows.
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_I8_MAX_CANDIDATES 1024
+#define DEWI_I8_MAX_DIM 4096
+int dewi_quantize_rows_i8(const float* d_E, int64_t n_rows, int dim, int8_t* d_codes, float* d_scales, void* stream);
+int dewi_prepare_queries_i8(const float* d_Q, int n_queries, int dim, int8_t* d_codes, float* d_scales, float* d_qn,
+                            void* stream);
+size_t dewi_knn_i8_workspace_bytes(int64_t n_rows, int dim, int n_queries, int n_candidates);
+int dewi_knn_candidates_i8(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const float* d_Q,
+                           int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
+                           dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, void* stream);
+int dewi_rescore_candidates_f32(const float* d_E, int64_t n_rows, int dim, const float* d_Q, int n_queries,
+                                dewi_candidate* d_cand, int n_candidates, int64_t id_offset, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-place mutation of a built corpus (ABI 6, additive; the reference has no counterpart: its indexes only append and
  * rebuild).  A removal does not shift rows: the tail fills the holes.  With n rows, m of them deleted and n_keep = n - m,
  * the holes are the deleted rows below n_keep (ascending), the movers the surviving rows at or above n_keep (ascending),
