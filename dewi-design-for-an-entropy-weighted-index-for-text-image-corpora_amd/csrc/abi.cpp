@@ -1504,6 +1504,108 @@ int dewi_knn_candidates_i8(const int8_t* d_codes, const float* d_scales, int64_t
                   "select launch");
 }
 
+// ---- the int8 scan over the rows of a prepared filter / of per-query lists (additive to ABI 6) -----------------
+size_t dewi_knn_i8_filtered_workspace_bytes(int64_t n_scan, int dim, int n_queries, int n_candidates) {
+  // today what the unfiltered call needs on n_scan rows (keys of every query: lists, or one dense key per list position)
+  if (n_scan <= 0 || n_scan > 0xFFFFFFFFll || dim <= 0 || dim % 16 != 0 || dim > DEWI_I8_MAX_DIM || n_queries <= 0 ||
+      n_candidates <= 0 || n_candidates > DEWI_I8_MAX_CANDIDATES)
+    return 0;
+  const int c_local = n_candidates < n_scan ? n_candidates : static_cast<int>(n_scan);
+  return i8_workspace(dewi::plan_scan_i8(n_scan, dim, c_local), n_queries);
+}
+
+// the argument checks the two filtered int8 entry points share, in the order of dewi_knn_candidates_i8 (the filter pointer
+// after the payload pointers)
+static int check_i8_filtered(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const void* d_filter,
+                             const float* d_Q, int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates,
+                             int64_t id_offset, const dewi_candidate* d_out) {
+  if (!d_codes || !d_scales || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "null codes, scales or query pointer");
+  if (int rc = check_i8_shape(n_rows, dim, 16)) return rc;
+  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
+  if (int rc = check_i8_candidates(n_candidates)) return rc;
+  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
+  if (!d_filter) return fail(DEWI_ERR_INVALID_ARG, "null filter pointer");
+  if (int rc = check_aligned16(d_codes, "the codes")) return rc;
+  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
+  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
+                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
+  return DEWI_OK;
+}
+
+// Both entry points from the device on: the LIST (d_qwords: QMASK) kernels planned on the n_scan listed rows, four queries
+// per pass and then one by one, then the select of dewi_knn_candidates_i8 over the keys they left.
+static int scan_select_i8_filtered(const int8_t* d_codes, const float* d_scales, int dim, const uint32_t* d_filter,
+                                   const uint32_t* d_qwords, int64_t n_scan, const float* d_Q, int n_queries,
+                                   const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
+                                   dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, hipStream_t stream) {
+  const int c_local = n_candidates < n_scan ? n_candidates : static_cast<int>(n_scan);
+  const dewi::ScanPlan plan = dewi::plan_scan_i8(n_scan, dim, c_local);
+  if (int rc = check_workspace(d_workspace, workspace_bytes, i8_workspace(plan, n_queries))) return rc;
+  uint64_t* keys = static_cast<uint64_t*>(d_workspace);
+  {
+    ScanTimer timer(stream);
+    for (int q = 0; q < n_queries;) {           // passes of four start at multiples of 4: inside one query word
+      const int nq = n_queries - q >= 4 ? 4 : 1;
+      dewi::QWords qw;
+      if (d_qwords) {
+        qw.words = d_qwords + static_cast<int64_t>(q / 32) * n_scan;
+        qw.shift = q % 32;
+      }
+      const hipError_t e = dewi::launch_scan_i8_list(plan, d_codes, d_scales, dim, d_Q, q, nq, c_local, keys, d_filter, stream, qw);
+      if (e != hipSuccess) return hip_fail(e, "int8 filtered scan launch");
+      q += nq;
+    }
+  }
+  const int sorted = (plan.slots == 1 && c_local == n_candidates) ? plan.n_lists : 0;
+  return launched(dewi::launch_select_rerank(keys, plan.keys_per_query, sorted, n_queries, n_candidates, 0, make_rerank(0.0, 0.0),
+                                             d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out, nullptr, dewi::SegmentLayout{},
+                                             stream),
+                  "select launch (int8 filtered)");
+}
+
+int dewi_knn_candidates_i8_filtered(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const void* d_filter,
+                                    int64_t n_allowed, const float* d_Q, int n_queries, const float* d_dewi32,
+                                    const float* d_ent32, int n_candidates, int64_t id_offset, dewi_candidate* d_out,
+                                    void* d_workspace, size_t workspace_bytes, void* stream_) {
+  if (int rc = check_i8_filtered(d_codes, d_scales, n_rows, dim, d_filter, d_Q, n_queries, d_dewi32, d_ent32, n_candidates,
+                                 id_offset, d_out))
+    return rc;
+  if (n_allowed < 0 || n_allowed > n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+  if (n_allowed == 0) return DEWI_OK;           // nothing launched, nothing written (dewi_knn_rerank_filtered's rule)
+  return scan_select_i8_filtered(d_codes, d_scales, dim, static_cast<const uint32_t*>(d_filter), nullptr, n_allowed, d_Q, n_queries,
+                                 d_dewi32, d_ent32, n_candidates, id_offset, d_out, d_workspace, workspace_bytes,
+                                 static_cast<hipStream_t>(stream_));
+}
+
+int dewi_knn_candidates_i8_query_filtered(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim,
+                                          const void* d_filter, int64_t n_union, const int64_t* n_allowed, const float* d_Q,
+                                          int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates,
+                                          int64_t id_offset, dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes,
+                                          void* stream_) {
+  if (int rc = check_i8_filtered(d_codes, d_scales, n_rows, dim, d_filter, d_Q, n_queries, d_dewi32, d_ent32, n_candidates,
+                                 id_offset, d_out))
+    return rc;
+  if (!n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null count pointer");
+  if (n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
+  if (n_union < 0 || n_union > n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_union %lld outside [0, %lld]", static_cast<long long>(n_union), static_cast<long long>(n_rows));
+  // one cut for the batch, and every list at least that long: a shorter list is searched on its own (the caller's split)
+  for (int j = 0; j < n_queries; ++j) {
+    if (n_allowed[j] < 0 || n_allowed[j] > n_union)
+      return fail(DEWI_ERR_INVALID_ARG, "query %d: n_allowed %lld outside [0, %lld]", j, static_cast<long long>(n_allowed[j]),
+                  static_cast<long long>(n_union));
+    if (n_allowed[j] < n_candidates)
+      return fail(DEWI_ERR_INVALID_ARG, "query %d: %lld allowed rows < the batch's cut %d (search it on its own filter)", j,
+                  static_cast<long long>(n_allowed[j]), n_candidates);
+  }
+  const uint32_t* filt = static_cast<const uint32_t*>(d_filter);   // the query words sit behind the union list's n_rows slots
+  return scan_select_i8_filtered(d_codes, d_scales, dim, filt, filt + dewi::kFilterHeaderWords + n_rows, n_union, d_Q, n_queries,
+                                 d_dewi32, d_ent32, n_candidates, id_offset, d_out, d_workspace, workspace_bytes,
+                                 static_cast<hipStream_t>(stream_));
+}
+
 int dewi_rescore_candidates_f32(const float* d_E, int64_t n_rows, int dim, const float* d_Q, int n_queries,
                                 dewi_candidate* d_cand, int n_candidates, int64_t id_offset, void* stream) {
   if (!d_E || !d_Q || !d_cand) return fail(DEWI_ERR_INVALID_ARG, "null pointer");

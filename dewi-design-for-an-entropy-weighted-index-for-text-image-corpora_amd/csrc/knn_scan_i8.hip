@@ -15,8 +15,11 @@
 // Each wave prepares the query codes once and keeps them in registers (4 dwords per unit and query, 1 or 4 queries per corpus
 // pass).  A row's scale is loaded WITH the row's codes (wave-uniform for long rows), not after the reduction.  The lists, the
 // workgroup merge and the select that follows are scan_common.hpp's and select_rerank.hip's, unchanged.
+// scan_rows_i8_list / scan_short_rows_i8_list are the same two scans over the rows of a prepared filter (LIST) or of per-query
+// lists (QMASK): allow-lists and IVF probes on the codes.
 //
-// Roofline: HBM.  Algorithmic bytes per pass = n_rows * (dim + 4) + n_queries * dim * 4.
+// Roofline: HBM.  Algorithmic bytes per pass = n_rows * (dim + 4) + n_queries * dim * 4 (a list of |A| rows: |A| * (dim + 4) +
+// 4 * |A| + n_queries * dim * 4).
 #include "scan_any.hpp"
 #include "select_common.hpp"
 
@@ -366,6 +369,233 @@ __global__ __launch_bounds__(kScanThreads) void scan_short_rows_i8(const u32x4* 
   DEWI_STORE_LISTS(S, NQ, lst);
 }
 
+// ---------------------------------------------------------------------------------------------
+// LIST / QMASK forms: the rows of a prepared filter instead of 0 .. n_rows, with the meaning of the LIST /
+// QMASK forms of scan_any.hpp.  dim % 16 == 0 means whole 16-byte fp32 units: a filter of this corpus has ONE bucket.  The
+// key carries the global row; a dense key goes to its list position.  Kernels of their own: the unfiltered kernels above
+// keep their instructions.
+// ---------------------------------------------------------------------------------------------
+// QMASK: qword[p] holds the query bits of list position p, query qi of the pass owns bit qshift + qi.
+template <int U, int R, int NQ, int S, bool QMASK>
+__global__ __launch_bounds__(kScanThreads) void scan_rows_i8_list(const u32x4* __restrict__ C, const float* __restrict__ scales,
+                                                                  const uint32_t* __restrict__ filt,
+                                                                  const uint32_t* __restrict__ qword, int qshift, int units,
+                                                                  const float* __restrict__ Q, int n_candidates,
+                                                                  uint64_t* __restrict__ keys, int64_t keys_per_query) {
+  constexpr bool DENSE = S == 0;
+  __shared__ MergeShared merge_buf;
+  const int lane = lane_id();
+  // (wave-uniform on purpose: list positions, row numbers, row addresses and the rows' scales then live in scalar registers)
+  const int wave_in_block = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+  const int64_t gwave = static_cast<int64_t>(blockIdx.x) * (kScanThreads / kWave) + wave_in_block;
+  const int64_t n_waves = static_cast<int64_t>(gridDim.x) * (kScanThreads / kWave);
+  const int dim = units * kUnitCodes;
+  const ListPart part = list_part(filt, 1, gwave, n_waves);
+  const uint32_t* __restrict__ list = filt + kFilterHeaderWords + part.base;
+  // (dense keys go to list positions: never past the keys the plan gave a query)
+  const int64_t n_mine = DENSE && part.count > keys_per_query ? keys_per_query : part.count;
+  bool act[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) act[u] = lane + 64 * u < units;
+
+  // the query codes, prepared here exactly as dewi_prepare_queries_i8 prepares them
+  uint32_t qc[NQ][U][4];
+  float qs[NQ];
+#pragma unroll
+  for (int qi = 0; qi < NQ; ++qi) {
+    const float* qrow = Q + static_cast<int64_t>(qi) * dim;
+    float x[U][kUnitCodes];
+#pragma unroll
+    for (int u = 0; u < U; ++u) load_unit_f32(qrow, lane + 64 * u, act[u], x[u]);
+    normalize_wave<U>(x, true);
+    qs[qi] = quantize_wave<U>(x, qc[qi]);
+  }
+
+  ScanLists<S, NQ> lst;
+  DEWI_INIT_LISTS(S, NQ, lst);
+
+  auto fetch = [&](u32x4(&v)[U], const u32x4* p) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      v[u] = u32x4{0u, 0u, 0u, 0u};
+      if (act[u]) v[u] = load_u4<true>(p + 64 * u);
+    }
+  };
+  auto qbits_of = [&](int64_t i) -> uint32_t {   // QMASK: the query bits of the wave's i-th row (wave-uniform)
+    if constexpr (QMASK) return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(qword[part.base + i])));
+    else return 0u;
+  };
+  auto consume = [&](const u32x4(&v)[U], float scale_row, int64_t row, int64_t slot, [[maybe_unused]] uint32_t qb) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) {
+      if constexpr (QMASK) {
+        if (((qb >> (qshift + qi)) & 1u) == 0u) {   // (wave-uniform: a scalar branch)
+          if constexpr (DENSE) {
+            if (lane == 0) keys[qi * keys_per_query + slot] = kKeyEmpty;
+          }
+          continue;
+        }
+      }
+      int acc = 0;
+#pragma unroll
+      for (int u = 0; u < U; ++u) acc = dot16_i8(v[u], qc[qi][u], acc);
+      const int d = static_cast<int>(wave_sum_u32(static_cast<uint32_t>(acc)));
+      const float s = score_i8(d, scale_row, qs[qi]);
+      if constexpr (DENSE) {
+        if (lane == 0) keys[qi * keys_per_query + slot] = make_key(s, static_cast<uint32_t>(row));
+      } else {
+        lst[qi].offer(s, static_cast<uint32_t>(row), lane);
+      }
+    }
+  };
+
+  // i: a position inside the list; the rows of a group are anywhere
+  const int64_t n_groups = n_mine / R;
+  for (int64_t g = part.wave_pos; g < n_groups; g += part.wave_cnt) {
+    u32x4 v[R][U];
+    float sc[R];
+    int64_t row[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) row[r] = list_row(list, g * R + r);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      fetch(v[r], C + row[r] * units + lane);
+      sc[r] = scales[row[r]];
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) consume(v[r], sc[r], row[r], part.base + g * R + r, qbits_of(g * R + r));
+  }
+  for (int64_t i = n_groups * R + part.wave_pos; i < n_mine; i += part.wave_cnt) {   // fewer than R rows left
+    u32x4 v[U];
+    const int64_t row = list_row(list, i);
+    fetch(v, C + row * units + lane);
+    const float sc = scales[row];
+    consume(v, sc, row, part.base + i, qbits_of(i));
+  }
+
+  DEWI_STORE_LISTS(S, NQ, lst);
+}
+
+// Short rows: list position j = st * rows_per_step + r * rows_per_load + sub belongs to lane group sub, load r of step st —
+// one list entry and one address per lane group; positions past the end of the list take row -1 (no address, no offer).
+// QMASK: one word per lane group, so a query's bit joins the lane predicate instead of a branch.
+template <int R, int NQ, int S, bool QMASK>
+__global__ __launch_bounds__(kScanThreads) void scan_short_rows_i8_list(const u32x4* __restrict__ C, const float* __restrict__ scales,
+                                                                        const uint32_t* __restrict__ filt,
+                                                                        const uint32_t* __restrict__ qword, int qshift, int units,
+                                                                        int log2p, const float* __restrict__ Q, int n_candidates,
+                                                                        uint64_t* __restrict__ keys, int64_t keys_per_query) {
+  constexpr bool DENSE = S == 0;
+  __shared__ MergeShared merge_buf;
+  const int lane = lane_id();
+  const int wave_in_block = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+  const int64_t gwave = static_cast<int64_t>(blockIdx.x) * (kScanThreads / kWave) + wave_in_block;
+  const int64_t n_waves = static_cast<int64_t>(gridDim.x) * (kScanThreads / kWave);
+  const int dim = units * kUnitCodes;
+  const int group = 1 << log2p;           // lanes per row
+  const int rows_per_load = kWave >> log2p;
+  const int sub = lane >> log2p;          // which row of the load
+  const int pos = lane & (group - 1);     // which unit of the row
+  const bool act = pos < units;
+  const bool holder = pos == group - 1;   // the lane group_sum_i32 leaves the row's sum in
+  const ListPart part = list_part(filt, 1, gwave, n_waves);
+  const uint32_t* __restrict__ list = filt + kFilterHeaderWords + part.base;
+  const int64_t n_mine = DENSE && part.count > keys_per_query ? keys_per_query : part.count;   // (see scan_rows_i8_list)
+
+  // every lane group holds a copy of the query codes; the first group alone feeds the norm
+  uint32_t qc[NQ][4];
+  float qs[NQ];
+#pragma unroll
+  for (int qi = 0; qi < NQ; ++qi) {
+    float x[1][kUnitCodes];
+    load_unit_f32(Q + static_cast<int64_t>(qi) * dim, pos, act, x[0]);
+    normalize_wave<1>(x, sub == 0);
+    uint32_t code[1][4];
+    qs[qi] = quantize_wave<1>(x, code);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) qc[qi][j] = code[0][j];
+  }
+
+  ScanLists<S, NQ> lst;
+  DEWI_INIT_LISTS(S, NQ, lst);
+
+  const int64_t rows_per_step = static_cast<int64_t>(rows_per_load) * R;
+  const int64_t n_steps = (n_mine + rows_per_step - 1) / rows_per_step;
+  for (int64_t st = part.wave_pos; st < n_steps; st += part.wave_cnt) {
+    u32x4 v[R];
+    float sc[R];
+    int64_t row[R];
+    [[maybe_unused]] uint32_t qb[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t j = st * rows_per_step + static_cast<int64_t>(r) * rows_per_load + sub;
+      row[r] = j < n_mine ? static_cast<int64_t>(list[j]) : -1;
+      if constexpr (QMASK) qb[r] = j < n_mine ? qword[part.base + j] >> qshift : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      v[r] = u32x4{0u, 0u, 0u, 0u};
+      sc[r] = 0.f;
+      if (act && row[r] >= 0) v[r] = load_u4<true>(C + row[r] * units + pos);
+      if (holder && row[r] >= 0) sc[r] = scales[row[r]];
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const bool mine = holder && row[r] >= 0;
+#pragma unroll
+      for (int qi = 0; qi < NQ; ++qi) {
+        const int d = group_sum_i32(dot16_i8(v[r], qc[qi], 0), log2p);
+        const float s = score_i8(d, sc[r], qs[qi]);
+        bool take = true;   // QMASK: query qi may take this lane group's row
+        if constexpr (QMASK) take = ((qb[r] >> qi) & 1u) != 0u;
+        if constexpr (DENSE) {
+          if (mine)
+            keys[qi * keys_per_query + part.base + st * rows_per_step + static_cast<int64_t>(r) * rows_per_load + sub] =
+                take ? make_key(s, static_cast<uint32_t>(row[r])) : kKeyEmpty;
+        } else {
+          // rows worth an offer: not below the list's current worst (NaN rows pass, as in WaveList::offer)
+          unsigned long long m = __ballot(mine && take && !(s < lst[qi].thr_s));
+          while (m != 0ull) {
+            const int src = __ffsll(m) - 1;
+            m &= m - 1ull;
+            const float sv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), src));
+            const uint32_t rw = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(row[r])), src));
+            lst[qi].offer(sv, rw, lane);
+          }
+        }
+      }
+    }
+  }
+
+  DEWI_STORE_LISTS(S, NQ, lst);
+}
+
+template <int NQ, int S, bool QMASK>
+hipError_t launch_kind_list(const ScanPlan& plan, const u32x4* C, const float* scales, const uint32_t* filt, QWords qw,
+                            const float* Q, int c, uint64_t* keys, hipStream_t stream) {
+  if (plan.kind == kScanAnyShort) {
+    hipLaunchKernelGGL((scan_short_rows_i8_list<kAnyShortRows, NQ, S, QMASK>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, C,
+                       scales, filt, qw.words, qw.shift, plan.units, plan.log2p, Q, c, keys, plan.keys_per_query);
+    return hipGetLastError();
+  }
+#define DEWI_I8_LONG(UU, RR)                                                                                                  \
+  if (plan.u_pad == UU && plan.rows_per_iter == RR) {                                                                         \
+    hipLaunchKernelGGL((scan_rows_i8_list<UU, RR, NQ, S, QMASK>), dim3(plan.blocks), dim3(kScanThreads), 0, stream, C, scales, \
+                       filt, qw.words, qw.shift, plan.units, Q, c, keys, plan.keys_per_query);                                \
+    return hipGetLastError();                                                                                                 \
+  }
+  DEWI_I8_LONG(1, 12)
+  DEWI_I8_LONG(1, 8)
+  DEWI_I8_LONG(2, 6)
+  DEWI_I8_LONG(2, 4)
+  DEWI_I8_LONG(2, 3)
+  DEWI_I8_LONG(3, 2)
+  DEWI_I8_LONG(4, 2)
+  DEWI_I8_LONG(4, 1)
+#undef DEWI_I8_LONG
+  return hipErrorInvalidValue;
+}
+
 template <int NQ, int S>
 hipError_t launch_kind(const ScanPlan& plan, const u32x4* C, const float* scales, int64_t n_rows, const float* Q, int c,
                        uint64_t* keys, hipStream_t stream) {
@@ -539,6 +769,37 @@ hipError_t launch_scan_i8(const ScanPlan& plan, const int8_t* d_codes, const flo
     DEWI_I8_S(1)
   } else if (nq == 4) {
     DEWI_I8_S(4)
+  }
+#undef DEWI_I8_S
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_scan_i8_list(const ScanPlan& plan, const int8_t* d_codes, const float* d_scales, int dim, const float* d_q_raw,
+                               int q0, int nq, int n_candidates, uint64_t* d_keys, const uint32_t* d_filter, hipStream_t stream,
+                               QWords qw) {
+  // a pass takes its bits from ONE query word: four queries start at a multiple of 4, so they never straddle two
+  if (qw.words != nullptr && (qw.shift < 0 || qw.shift + nq > 32 || (nq == 4 && qw.shift % 4 != 0))) return hipErrorInvalidValue;
+  const u32x4* C = reinterpret_cast<const u32x4*>(d_codes);
+  const float* Q = d_q_raw + static_cast<int64_t>(q0) * dim;
+  uint64_t* keys = d_keys + static_cast<int64_t>(q0) * plan.keys_per_query;
+#define DEWI_I8_S(NQ, QM)                                                                                            \
+  switch (plan.slots) {                                                                                              \
+    case 0: return launch_kind_list<NQ, 0, QM>(plan, C, d_scales, d_filter, qw, Q, n_candidates, keys, stream);      \
+    case 1: return launch_kind_list<NQ, 1, QM>(plan, C, d_scales, d_filter, qw, Q, n_candidates, keys, stream);      \
+    default: return launch_kind_list<NQ, kMaxSlots, QM>(plan, C, d_scales, d_filter, qw, Q, n_candidates, keys, stream); \
+  }
+  if (qw.words != nullptr) {
+    if (nq == 1) {
+      DEWI_I8_S(1, true)
+    } else if (nq == 4) {
+      DEWI_I8_S(4, true)
+    }
+  } else {
+    if (nq == 1) {
+      DEWI_I8_S(1, false)
+    } else if (nq == 4) {
+      DEWI_I8_S(4, false)
+    }
   }
 #undef DEWI_I8_S
   return hipErrorInvalidValue;

@@ -431,6 +431,12 @@ hipError_t launch_prepare_queries_i8(const float* d_Q, int n_queries, int dim, i
 // one corpus pass for queries [q0, q0 + nq), nq = 1 or 4 (raw queries; keys at d_keys + q * plan.keys_per_query)
 hipError_t launch_scan_i8(const ScanPlan& plan, const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim,
                           const float* d_q_raw, int q0, int nq, int n_candidates, uint64_t* d_keys, hipStream_t stream);
+// the same pass over the rows of a prepared filter (elem_type 0, this dim: one bucket) — plan made on the list's length,
+// dense keys at list positions; qw.words set: the per-query (QMASK) form, the pass's bits shift .. shift + nq - 1 of ONE word
+// (hipErrorInvalidValue for a pass that would straddle two)
+hipError_t launch_scan_i8_list(const ScanPlan& plan, const int8_t* d_codes, const float* d_scales, int dim, const float* d_q_raw,
+                               int q0, int nq, int n_candidates, uint64_t* d_keys, const uint32_t* d_filter, hipStream_t stream,
+                               QWords qw = {});
 hipError_t launch_rescore_candidates_f32(const float* d_E, int64_t n_rows, int dim, const float* d_Q, int n_queries,
                                          dewi_candidate* d_cand, int n_candidates, int64_t id_offset, hipStream_t stream);
 

@@ -452,6 +452,128 @@ class DeviceCorpus:
             ids_h = ids_h + self.id_offset
         return ids_h, scores_h
 
+    # ------------------------------------------------------------------ approximate route over allow-lists
+    def candidates_i8_filtered_device(self, q_dev, n_candidates: int, filter, out=None, id_offset: Optional[int] = None):
+        """``candidates_i8_device`` over the rows of ``filter`` only: a ``DeviceFilter`` of this corpus (one list for every
+        query: ``dewi_knn_candidates_i8_filtered``) or a ``DeviceQueryFilters`` of B lists, every one of them at least
+        ``n_candidates`` long (``dewi_knn_candidates_i8_query_filtered``; shorter lists are the caller's split).  Ids are rows
+        of the whole corpus.  An empty ``DeviceFilter`` writes nothing: ``out`` is returned filled with padding."""
+        torch = _torch()
+        codes, scales = self._int8()
+        b, c = int(q_dev.shape[0]), int(n_candidates)
+        n = int(codes.shape[0])
+        off = self.id_offset if id_offset is None else int(id_offset)
+        if isinstance(filter, DeviceQueryFilters):
+            self.check_query_filters(filter, b)
+            if out is None:
+                out = torch.empty((b, c, 4), dtype=torch.int32, device=self.device)
+            ws = self._cached_workspace(("i8qf", b, filter.n_union, c), self._lib.dewi_knn_i8_filtered_workspace_bytes,
+                                        filter.n_union, self.dim, b, c)
+            n_a = (ctypes.c_int64 * b)(*[int(x) for x in filter.n_allowed])
+            nat.check(self._lib.dewi_knn_candidates_i8_query_filtered(
+                nat.ptr(codes), nat.ptr(scales), n, self.dim, nat.ptr(filter.buf), filter.n_union, n_a, nat.ptr(q_dev), b,
+                nat.ptr(self.dewi32), nat.ptr(self.ent32), c, off, nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+            return out
+        self.check_filter(filter)
+        if out is None:
+            out = torch.empty((b, c, 4), dtype=torch.int32, device=self.device)
+        if filter.n_allowed == 0:
+            # the padding record (sim -inf, dewi 0, ent 0, id -1) as int32 words
+            out.copy_(torch.tensor([-0x800000, 0, 0, -1], dtype=torch.int32, device=self.device).expand(b, c, 4))
+            return out
+        ws = self._cached_workspace(("i8f", b, filter.n_allowed, c), self._lib.dewi_knn_i8_filtered_workspace_bytes,
+                                    filter.n_allowed, self.dim, b, c)
+        nat.check(self._lib.dewi_knn_candidates_i8_filtered(
+            nat.ptr(codes), nat.ptr(scales), n, self.dim, nat.ptr(filter.buf), filter.n_allowed, nat.ptr(q_dev), b,
+            nat.ptr(self.dewi32), nat.ptr(self.ent32), c, off, nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+        return out
+
+    def _approx_one_list(self, q_dev, k: int, eta: float, entropy_pref: float, candidates: Optional[int], rescore: bool,
+                         f: DeviceFilter, out_ids, out_scores):
+        c = approx_cut(k, candidates, f.n_allowed)
+        b = int(q_dev.shape[0])
+        recs = self.candidates_i8_filtered_device(q_dev, c, f, id_offset=0)
+        if rescore:
+            self.rescore_candidates_device(q_dev, recs, id_offset=0)
+        return merge_rerank_device(recs.view(1, b, c, 4), c, k, eta, entropy_pref, out_ids, out_scores)
+
+    def search_approx_filtered_device(self, q_dev, k: int, eta: float, entropy_pref: float, filter,
+                                      candidates: Optional[int] = None, rescore: bool = True, out_ids=None, out_scores=None):
+        """``search_approx_device`` over the rows of ``filter`` only (a ``DeviceFilter`` or a ``DeviceQueryFilters`` of this
+        corpus; stale filters raise ``ValueError``): the cut ``approx_cut(k, candidates, |A|)`` is taken by the int8 scores of
+        the listed rows — a quarter of the bytes ``search_device(filter=)`` reads —, re-scored from the fp32 rows unless
+        ``rescore=False``, then blended and cut to k.  Local row ids, no sync.  ``k`` above ``|A|`` raises ``ValueError``; an
+        empty ``DeviceFilter`` gives [B, 0].  ``DeviceQueryFilters``: the host split of ``search_device``: lists at least as
+        long as the cut share one pass over the union, a shorter list runs on a filter of its own (its cut is ``|F_j|``), an
+        empty list leaves id -1 / score NaN in its row."""
+        torch = _torch()
+        if isinstance(filter, DeviceQueryFilters):
+            qf = filter
+            self.check_query_filters(qf, int(q_dev.shape[0]))
+        else:
+            self.check_filter(filter)
+        b, k = check_search_args(q_dev.shape, self.dim, k, None, "ip")
+        self._int8()
+        if k <= 0:
+            return empty_result(b, self.device)
+        if not isinstance(filter, DeviceQueryFilters):
+            if filter.n_allowed == 0:
+                return empty_result(b, self.device)
+            if k > filter.n_allowed:
+                raise ValueError(f"k = {k} exceeds the {filter.n_allowed} rows the filter allows")
+            return self._approx_one_list(q_dev, k, eta, entropy_pref, candidates, rescore, filter, out_ids, out_scores)
+        counts = qf.n_allowed
+        for j in range(b):
+            if 0 < counts[j] < k:
+                raise ValueError(f"query {j}: k = {k} exceeds the {int(counts[j])} rows its filter allows")
+        c = approx_cut(k, candidates, self.n_rows)
+        out_ids, out_scores = default_outputs(b, k, self.device, out_ids, out_scores)
+        shared = [j for j in range(b) if counts[j] >= c]
+        if len(shared) < b:
+            out_ids.fill_(-1)
+            out_scores.fill_(float("nan"))
+        if shared:
+            if len(shared) == b:
+                sub, q_sub, o_ids, o_sc = qf, q_dev, out_ids, out_scores
+            else:
+                key = tuple(shared)
+                sub = qf._subsets.get(key)
+                if sub is None:
+                    if len(qf._subsets) > 8:
+                        qf._subsets.clear()
+                    sub = qf._subsets[key] = self.make_query_filters(qf.masks[list(shared)].view(torch.bool))
+                q_sub = q_dev[shared].contiguous()
+                o_ids, o_sc = default_outputs(len(shared), k, self.device)
+            nb = len(shared)
+            recs = self.candidates_i8_filtered_device(q_sub, c, sub, id_offset=0)
+            if rescore:
+                self.rescore_candidates_device(q_sub, recs, id_offset=0)
+            merge_rerank_device(recs.view(1, nb, c, 4), c, k, eta, entropy_pref, o_ids, o_sc)
+            if o_ids is not out_ids:
+                idx = torch.tensor(shared, dtype=torch.int64, device=self.device)
+                out_ids.index_copy_(0, idx, o_ids)
+                out_scores.index_copy_(0, idx, o_sc)
+        for j in range(b):
+            if 0 < counts[j] < c:          # a short list: on a filter of its own (cut |F_j|)
+                f = qf._singles.get(j)
+                if f is None:
+                    f = qf._singles[j] = self.make_filter(qf.masks[j].view(torch.bool))
+                self._approx_one_list(q_dev[j:j + 1], k, eta, entropy_pref, candidates, rescore, f, out_ids[j:j + 1],
+                                      out_scores[j:j + 1])
+        return out_ids, out_scores
+
+    def search_approx_filtered(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, *, filter,
+                               candidates: Optional[int] = None, rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """Blocking twin of ``search_approx_filtered_device``: (ids int64 [B, k] including id_offset — -1 stays -1 —, scores
+        fp32 [B, k]) on the host.  Serialised by the per-corpus lock."""
+        with self._lock, _torch().cuda.device(self.device):
+            q = self.stage_queries(queries)
+            ids_d, sc_d = self.search_approx_filtered_device(q, k, eta, entropy_pref, filter, candidates, rescore)
+            ids_h, scores_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
+        if self.id_offset:
+            ids_h = np.where(ids_h >= 0, ids_h + self.id_offset, ids_h)
+        return ids_h, scores_h
+
     # ------------------------------------------------------------------ properties
     @property
     def n_rows(self) -> int:

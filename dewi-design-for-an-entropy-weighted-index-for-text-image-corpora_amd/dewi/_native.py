@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = (
     "dewi_rows_move", "dewi_rows_put_f32",
     "dewi_quantize_rows_i8", "dewi_prepare_queries_i8", "dewi_knn_i8_workspace_bytes", "dewi_knn_candidates_i8",
     "dewi_rescore_candidates_f32",
+    "dewi_knn_i8_filtered_workspace_bytes", "dewi_knn_candidates_i8_filtered", "dewi_knn_candidates_i8_query_filtered",
 )
 
 
@@ -220,6 +221,13 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_knn_candidates_i8.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i32, i64, vp, vp, sz, vp]
     lib.dewi_rescore_candidates_f32.restype = i32
     lib.dewi_rescore_candidates_f32.argtypes = [vp, i64, i32, vp, i32, vp, i32, i64, vp]
+    lib.dewi_knn_i8_filtered_workspace_bytes.restype = sz
+    lib.dewi_knn_i8_filtered_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_knn_candidates_i8_filtered.restype = i32
+    lib.dewi_knn_candidates_i8_filtered.argtypes = [vp, vp, i64, i32, vp, i64, vp, i32, vp, vp, i32, i64, vp, vp, sz, vp]
+    lib.dewi_knn_candidates_i8_query_filtered.restype = i32
+    lib.dewi_knn_candidates_i8_query_filtered.argtypes = [vp, vp, i64, i32, vp, i64, c.POINTER(i64), vp, i32, vp, vp, i32, i64, vp,
+                                                          vp, sz, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

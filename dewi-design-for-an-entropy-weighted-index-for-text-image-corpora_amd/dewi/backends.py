@@ -733,7 +733,8 @@ class ExactIndex(BaseIndex):
         if not self._int8_shadow:
             raise ValueError("approx=True needs an index built with int8_shadow=True")
         if filter is not None:
-            raise ValueError("approx=True does not take a filter: filtered searches run on the fp32 rows (approx=False)")
+            raise ValueError("approx=True does not take a filter: filtered searches run on the fp32 rows (approx=False); "
+                             "the int8 route over an allow-list is search_approx_filtered")
         if similarity != "ip":
             raise ValueError("approx=True does not take a similarity transform")
         return True
@@ -798,6 +799,38 @@ class ExactIndex(BaseIndex):
                                        similarity=similarity, filter=self._prepared(filter))
         return self._corpus.search(q, int(k), float(eta), float(entropy_pref), candidates=candidates,
                                    similarity=similarity)
+
+    # ---------------------------------------------------------------- approximate search over an allow-list (additive)
+    def search_approx_filtered(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                               candidates: Optional[int] = None, *, filter, rescore: bool = True) -> SearchResult:
+        """``search(filter=...)`` on the int8 route (an index built with ``int8_shadow=True``): see
+        ``search_approx_filtered_batch``."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        rows, scores = self.search_approx_filtered_batch(q[:1], k, eta, entropy_pref, candidates, filter=filter, rescore=rescore)
+        keep = rows[0] >= 0
+        return self.results_for(rows[:1][:, keep], scores[:1][:, keep])[0]
+
+    def search_approx_filtered_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                                     candidates: Optional[int] = None, *, filter,
+                                     rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k]) over the rows of ``filter`` — whatever
+        ``search_batch(filter=)`` accepts, a ``dedup_filter(...)`` and per-query filters included — with the candidate cut
+        (``min(2k, |A|)``, or ``candidates`` up to 1024) taken by the INT8 scores of the listed rows: a quarter of the bytes
+        the exact filtered search reads.  ``rescore=True`` re-scores the cut from the fp32 rows; ``False`` blends the int8
+        scores.  Approximate in the way ``search_batch(approx=True)`` is.  ``ValueError``: no int8 shadow, a stale filter,
+        ``k`` above ``|A|``; an empty filter gives [B, 0], an empty list of per-query filters pads its row with -1 / NaN."""
+        if not self._int8_shadow:
+            raise ValueError("search_approx_filtered needs an index built with int8_shadow=True")
+        if filter is None:
+            raise ValueError("search_approx_filtered needs a filter (search(approx=True) is the unfiltered route)")
+        self._ensure_built()
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        return self._corpus.search_approx_filtered(q, int(k), float(eta), float(entropy_pref), filter=self._prepared(filter),
+                                                   candidates=candidates, rescore=bool(rescore))
 
     # ---------------------------------------------------------------- diverse search (additive)
     def search_diverse(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,

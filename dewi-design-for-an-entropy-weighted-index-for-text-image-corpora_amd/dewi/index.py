@@ -168,6 +168,36 @@ class DewiIndex(BaseIndex):
             rows, scores = self._backend.search_batch(q, k, eta, entropy_pref, **self._approx_kwargs(approx, rescore))
         return self._backend.results_for(rows, scores)
 
+    def search_approx_filtered(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
+                               entropy_pref: Optional[float] = None, candidates: Optional[int] = None, *, filter,
+                               rescore: bool = True) -> List[Tuple[str, float, Payload]]:
+        """``search(filter=...)`` with the candidate cut taken by the int8 scores of the allowed rows
+        (``ExactIndex.search_approx_filtered_batch``; an index made with ``int8_shadow=True``)."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.shape != (self.dim,):
+            raise ValueError(f"Expected query shape ({self.dim},), got {q.shape}")
+        return self.search_approx_filtered_batch(q.reshape(1, -1), k, eta, entropy_pref, candidates, filter=filter,
+                                                 rescore=rescore)[0]
+
+    def search_approx_filtered_batch(self, queries: np.ndarray, k: int = 10, eta: Optional[float] = None,
+                                     entropy_pref: Optional[float] = None, candidates: Optional[int] = None, *, filter,
+                                     rescore: bool = True) -> List[List[Tuple[str, float, Payload]]]:
+        """One call for B queries ([B, dim]); each result list equals ``search_approx_filtered`` of that row (per-query
+        filters give ``[]`` for a query whose list is empty)."""
+        eta, entropy_pref = self._defaults(eta, entropy_pref)
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        if not getattr(self._backend, "_int8_shadow", False):          # (argument errors before any build)
+            raise ValueError("search_approx_filtered needs an index built with int8_shadow=True")
+        if not self._built:
+            self.build()
+        rows, scores = self._backend.search_approx_filtered_batch(q, k, eta, entropy_pref, candidates, filter=filter,
+                                                                  rescore=rescore)
+        n_real = (rows >= 0).sum(axis=1)
+        res = self._backend.results_for(np.where(rows < 0, 0, rows), scores)
+        return [r[:int(m)] for r, m in zip(res, n_real)]
+
     def search_diverse_approx(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
                               entropy_pref: Optional[float] = None, mmr_lambda: float = 0.5, candidates: Optional[int] = None,
                               max_sim: Optional[float] = None, rescore: bool = True) -> List[Tuple[str, float, Payload]]:

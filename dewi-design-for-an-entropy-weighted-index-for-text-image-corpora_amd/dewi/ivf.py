@@ -45,7 +45,18 @@ class _IvfState:
 
 
 class IVFIndex(ExactIndex):
-    """IVF-Flat over an ``ExactIndex`` corpus (fp32 only).
+    """IVF-Flat over an ``ExactIndex`` corpus (fp32 rows; ``int8_codes=True`` keeps an int8 copy for approximate probes).
+
+    ``int8_codes=True`` (cosine, ``dim % 16 == 0`` up to 4096: checked here): ``build`` keeps the int8 copy of the rows
+    (``DeviceCorpus.enable_int8_shadow``, +25 % memory) and ``search`` / ``search_batch`` / ``search_device`` take
+    ``approx``: step 3 then picks each query's cut by the int8 scores of its probed rows — a quarter of the bytes —,
+    re-scores it from the fp32 rows (``rescore=False``: not) and blends as ever, so query j's answer is
+    ``ExactIndex.search_approx_filtered`` on the rows of its cells.  ``approx=None`` takes that route iff the index has
+    codes, ``similarity == "ip"``, there is no ``filter``, the cut is at most 1024 and the batch at most
+    ``APPROX_AUTO_MAX_BATCH``; ``approx=False`` is the fp32 probe, bit for bit.  The int8 probe is SLOWER than the fp32 probe
+    wherever the probe is short (fixed cost: profiles/r14/int8_lists/).  ``remove`` / ``upsert*`` mark the copy stale (the
+    next approximate search re-quantises); ``load(path, int8_codes=True)`` re-quantises, nothing changes on disk.
+    ``int8_shadow=True`` (``ExactIndex``'s unfiltered int8 route) is refused.
 
     ``nlist=None``: ``min(4096, max(1, round(sqrt(N))))`` at build; ``nprobe=None``: ``max(1, nlist // 64)``.  Training:
     ``train_iters`` rounds of k-means from ``nlist`` distinct rows drawn with ``np.random.RandomState(train_seed)``, at most
@@ -81,8 +92,14 @@ class IVFIndex(ExactIndex):
         if max_train_rows is not None and int(max_train_rows) < 1:
             raise ValueError(f"max_train_rows must be at least 1, got {max_train_rows}")
         if kwargs.get("int8_shadow"):
-            raise ValueError("IVFIndex does not take int8_shadow: the int8 route scans every row (not in this build)")
+            raise ValueError("IVFIndex does not take int8_shadow (the unfiltered int8 route scans every row): "
+                             "int8_codes=True keeps the int8 copy for the probes")
+        int8_codes = bool(kwargs.pop("int8_codes", False))
+        if int8_codes:
+            from ._engine import check_int8_shape
+            check_int8_shape(space, False, dim)
         super().__init__(dim, space, **kwargs)
+        self._int8_codes = int8_codes
         self.nlist = None if nlist is None else int(nlist)
         self.nprobe = None if nprobe is None else int(nprobe)
         self.train_iters = int(train_iters)
@@ -132,6 +149,8 @@ class IVFIndex(ExactIndex):
             st.centroids, st.assign = centroids, assign
             st.coarse = DeviceCorpus(centroids, zeros, zeros.clone(), self.space)
             st.corpus_id = corpus.corpus_id
+            if self._int8_codes:
+                corpus.enable_int8_shadow()       # the int8 copy the approximate probes scan (remove / upsert* mark it stale)
         self._ivf = st
 
     def _make_lists(self, st: _IvfState, assign, n: int) -> None:
@@ -329,15 +348,78 @@ class IVFIndex(ExactIndex):
                     nat.ptr(out_ids[q0:q0 + nq]), nat.ptr(out_scores[q0:q0 + nq]), nat.ptr(ws), ws.numel(), nat.stream_ptr())
             nat.check(rc)
 
+    #: largest batch ``approx=None`` sends through the int8 probe (``None``: every batch).  Measured at 1 M x 768, nlist 1024,
+    #: k = 10 (profiles/r14/int8_lists/): 32 queries lose at nprobe 1 / 4 / 16 (0.51 / 0.53 / 0.80 ms against 0.29 / 0.39 /
+    #: 0.71 ms on the fp32 rows) and gain 3 % at nprobe 64; batches of 2 .. 31 have not been measured.  One query gains only
+    #: where the probe is long (nprobe 64, 109 k rows: 0.146 against 0.162 ms) and loses 0.024 ms of fixed cost below.
+    APPROX_AUTO_MAX_BATCH = 1
+
+    def _use_approx_probe(self, approx: Optional[bool], similarity: str, filter, k: int, candidates: Optional[int],
+                          n_queries: int = 1) -> bool:
+        """Whether a search scans the int8 codes of the probed cells.  ``True``: it must (``ValueError`` without codes, with a
+        ``filter`` or with a similarity transform); ``None``: where the index has codes and the route serves the call (no
+        filter, no transform, a cut of at most 1024, at most ``APPROX_AUTO_MAX_BATCH`` queries); ``False``: never."""
+        from . import _native as nat
+        if approx is None:
+            cap = self.APPROX_AUTO_MAX_BATCH
+            if not self._int8_codes or filter is not None or similarity != "ip" or (cap is not None and int(n_queries) > cap):
+                return False
+            return (2 * int(k) if candidates is None else int(candidates)) <= nat.I8_MAX_CANDIDATES
+        if not approx:
+            return False
+        if not self._int8_codes:
+            raise ValueError("approx=True needs an IVFIndex built with int8_codes=True (int8_shadow=True is ExactIndex's "
+                             "unfiltered route, which an IVFIndex does not have)")
+        if filter is not None:
+            raise ValueError("approx=True does not take a filter: a user filter together with an IVF probe is not supported")
+        if similarity != "ip":
+            raise ValueError("approx=True does not take a similarity transform")
+        return True
+
+    def _search_groups_i8(self, q_dev, n_union, n_allowed, stride: int, k: int, c: int, rescore: bool, eta: float, pref: float,
+                          out_ids, out_scores) -> None:
+        """Step 3 on the int8 codes: per group the records of the c best rows by int8 score
+        (``dewi_knn_candidates_i8_query_filtered``; a group of one: ``dewi_knn_candidates_i8_filtered``), re-scored from the
+        fp32 rows unless ``rescore`` is off, then ``dewi_merge_rerank``.  Every query holds at least c rows."""
+        import torch
+        from . import _native as nat
+        from ._engine import library_size, merge_rerank_device
+        corpus, lib = self._corpus, self._corpus._lib
+        codes, scales = corpus._int8()
+        b = int(q_dev.shape[0])
+        for g, q0 in enumerate(range(0, b, PROBE_GROUP)):
+            nq = min(PROBE_GROUP, b - q0)
+            buf = self._probe_buf[g * stride:]
+            need = library_size(lib.dewi_knn_i8_filtered_workspace_bytes, n_union[g], self.dim, nq, c)
+            if self._ivf_ws is None or self._ivf_ws.numel() < need or self._ivf_ws.device != corpus.device:
+                self._ivf_ws = torch.empty(need, dtype=torch.uint8, device=corpus.device)
+            ws = self._ivf_ws
+            recs = torch.empty((nq, c, 4), dtype=torch.int32, device=corpus.device)
+            q_g = q_dev[q0:q0 + nq]
+            if nq == 1:
+                rc = lib.dewi_knn_candidates_i8_filtered(
+                    nat.ptr(codes), nat.ptr(scales), corpus.n_rows, self.dim, nat.ptr(buf), n_union[g], nat.ptr(q_g), 1,
+                    nat.ptr(corpus.dewi32), nat.ptr(corpus.ent32), c, 0, nat.ptr(recs), nat.ptr(ws), ws.numel(), nat.stream_ptr())
+            else:
+                counts = (ctypes.c_int64 * nq)(*n_allowed[q0:q0 + nq])
+                rc = lib.dewi_knn_candidates_i8_query_filtered(
+                    nat.ptr(codes), nat.ptr(scales), corpus.n_rows, self.dim, nat.ptr(buf), n_union[g], counts, nat.ptr(q_g), nq,
+                    nat.ptr(corpus.dewi32), nat.ptr(corpus.ent32), c, 0, nat.ptr(recs), nat.ptr(ws), ws.numel(), nat.stream_ptr())
+            nat.check(rc)
+            if rescore:
+                corpus.rescore_candidates_device(q_g, recs, id_offset=0)
+            merge_rerank_device(recs.view(1, nq, c, 4), c, k, eta, pref, out_ids[q0:q0 + nq], out_scores[q0:q0 + nq])
+
     def search_device(self, q_dev, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, candidates: Optional[int] = None,
-                      similarity: str = "ip", nprobe: Optional[int] = None):
+                      similarity: str = "ip", nprobe: Optional[int] = None, approx: Optional[bool] = None, rescore: bool = True):
         """The three steps for fp32 queries [B, dim] on the corpus's device -> (ids int64 [B, k], scores fp32 [B, k]) device
         tensors.  Synchronises the current stream once (the probe's row counts come back to the host to plan the scan); the
         search itself is left enqueued.  A query whose cells hold fewer than k rows fills the rest of its row with id -1 /
-        score NaN.  One caller at a time (shared buffers)."""
+        score NaN.  One caller at a time (shared buffers).  ``approx`` / ``rescore``: see ``search_batch``."""
         import torch
         from . import _native as nat
-        from ._engine import check_search_args, cut_size, default_outputs, empty_result
+        from ._engine import approx_cut, check_search_args, cut_size, default_outputs, empty_result
+        use_i8 = self._use_approx_probe(approx, similarity, None, k, candidates, int(q_dev.shape[0]))
         self._ensure_built()
         corpus, st = self._corpus, self._ivf
         if corpus.is_bf16:
@@ -349,11 +431,38 @@ class IVFIndex(ExactIndex):
         if candidates is not None and int(candidates) < k:
             raise ValueError(f"candidates = {candidates} must be at least k = {k}")
         c = cut_size(k, candidates)
+        if use_i8 and c > nat.I8_MAX_CANDIDATES:
+            approx_cut(k, candidates, c)             # raises: the int8 route re-ranks at most 1024 candidates
         sim, eta, pref = nat.SIM_CODES[similarity], float(eta), float(entropy_pref)
         out_ids, out_scores = default_outputs(b, k, corpus.device)
         probe_ids, _ = st.coarse.search_device(q_dev, npb, 0.0, 0.0, candidates=npb)
         n_union, n_allowed, stride = self._prepare_probe(probe_ids, b, npb)
         short = [j for j in range(b) if n_allowed[j] < c]
+        if use_i8:
+            if short:
+                out_ids.fill_(-1)
+                out_scores.fill_(float("nan"))
+                shared = [j for j in range(b) if n_allowed[j] >= c]
+                if shared:
+                    idx = torch.tensor(shared, dtype=torch.int64, device=corpus.device)
+                    pid_s, q_s = probe_ids[idx].contiguous(), q_dev[idx].contiguous()
+                    o_ids, o_sc = default_outputs(len(shared), k, corpus.device)
+                    u_s, a_s, stride = self._prepare_probe(pid_s, len(shared), npb)
+                    self._search_groups_i8(q_s, u_s, a_s, stride, k, c, rescore, eta, pref, o_ids, o_sc)
+                    out_ids.index_copy_(0, idx, o_ids)
+                    out_scores.index_copy_(0, idx, o_sc)
+                for j in short:                      # one list each, cut and k limited to |F_j|
+                    if n_allowed[j] == 0:
+                        continue
+                    kk, cj = min(k, n_allowed[j]), min(c, n_allowed[j])
+                    u_1, a_1, stride = self._prepare_probe(probe_ids[j:j + 1], 1, npb)
+                    o_ids, o_sc = default_outputs(1, kk, corpus.device)
+                    self._search_groups_i8(q_dev[j:j + 1], u_1, a_1, stride, kk, cj, rescore, eta, pref, o_ids, o_sc)
+                    out_ids[j, :kk] = o_ids[0]
+                    out_scores[j, :kk] = o_sc[0]
+            else:
+                self._search_groups_i8(q_dev, n_union, n_allowed, stride, k, c, rescore, eta, pref, out_ids, out_scores)
+            return out_ids, out_scores
         if not short:
             self._search_groups(q_dev, n_union, n_allowed, stride, k, c, candidates, sim, eta, pref, out_ids, out_scores)
             return out_ids, out_scores
@@ -389,12 +498,18 @@ class IVFIndex(ExactIndex):
         row holds ``|F_j|`` results and is padded with id -1 / score NaN.
 
         ``filter=`` together with IVF is not supported: passing one runs the parent's EXACT filtered search over the whole
-        allow-list (``nprobe`` is then ignored).  ``approx`` / ``rescore`` are ``ExactIndex``'s int8 route, which an
-        ``IVFIndex`` does not have: ``approx=True`` raises ``ValueError``."""
+        allow-list (``nprobe`` is then ignored).
+
+        ``approx`` (an index made with ``int8_codes=True``): step 3 takes the cut of every query by the INT8 scores of its
+        probed rows (a quarter of the bytes), re-scores it from the fp32 rows (``rescore=True``; ``False`` blends the int8
+        scores as they are) and finishes with the same blend — query j's answer is ``search_approx_filtered`` on the rows of
+        its cells.  ``None`` (default): taken iff the index has codes, ``similarity == "ip"``, there is no ``filter``, the
+        cut is at most 1024 and the batch at most ``APPROX_AUTO_MAX_BATCH``; ``False``: the fp32 probe, bit for bit;
+        ``True`` without codes, with a ``filter`` or a transform raises ``ValueError``."""
         if nprobe is not None and int(nprobe) < 1:
             raise ValueError(f"nprobe must be at least 1, got {nprobe}")
-        if approx:
-            raise ValueError("approx=True needs an index built with int8_shadow=True (IVFIndex has no int8 route)")
+        use_i8 = self._use_approx_probe(approx, similarity, filter, k, candidates,      # (argument errors before any build)
+                                        np.shape(queries)[0] if np.ndim(queries) == 2 else 1)
         if filter is not None:
             return super().search_batch(queries, k, eta, entropy_pref, candidates, similarity, filter=filter)
         self._ensure_built()
@@ -405,7 +520,8 @@ class IVFIndex(ExactIndex):
         corpus = self._corpus
         with corpus._lock, torch.cuda.device(corpus.device):
             q_dev = corpus.stage_queries(q)
-            ids, scores = self.search_device(q_dev, k, eta, entropy_pref, candidates, similarity, nprobe)
+            ids, scores = self.search_device(q_dev, k, eta, entropy_pref, candidates, similarity, nprobe, approx=use_i8,
+                                             rescore=bool(rescore))
             return ids.cpu().numpy(), scores.cpu().numpy()
 
     def search(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,

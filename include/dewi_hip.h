@@ -562,6 +562,29 @@ int dewi_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows, int dim,
  * above the limit, 2^32 rows or more: DEWI_ERR_UNSUPPORTED; a short workspace: DEWI_ERR_WORKSPACE.  n_candidates > n_rows is
  * not an error (padding).  Steps 3-5 of the search are dewi_merge_rerank(d_out, 1, n_queries, c, c, k, ...) on the records; a
  * diverse search is dewi_diverse_rerank on the same records with the fp32 rows.
+ *
+ * INT8 copy, filtered: the same scan over the rows of ONE allow-list, or of one list PER QUERY.
+ *   d_filter is the buffer dewi_filter_prepare wrote (one list), or dewi_query_filter_prepare / one group of
+ *   dewi_ivf_probe_prepare (per-query lists), prepared with elem_type 0 for the same n_rows and dim (dim % 16 == 0: the fp32
+ *   rows are whole 16-byte units, the buffer has ONE bucket).  A probe buffer's list is not ascending across cell segments:
+ *   nothing relies on a sorted list.
+ * dewi_knn_i8_filtered_workspace_bytes(n_scan, ...): n_scan = n_allowed / n_union; 0 for a shape the route does not take;
+ *   needs no device.  (Today what dewi_knn_i8_workspace_bytes answers for n_scan rows; a symbol of its own so it can diverge.)
+ * Records: query j's records are exactly what dewi_knn_candidates_i8 returns for a corpus that holds only the rows of its
+ *   list — ids GLOBAL (rows of the whole corpus) with id_offset added, order (ord(sim) desc, id asc), NaN first, -0 as +0,
+ *   the payload pair attached.
+ * dewi_knn_candidates_i8_filtered: one list for every query.  c_local = min(n_candidates, n_allowed), padding (id = -1,
+ *   sim = -inf) behind it.  n_allowed == 0: DEWI_OK, nothing launched, nothing written (dewi_knn_rerank_filtered's rule).
+ *   n_allowed outside [0, n_rows]: DEWI_ERR_INVALID_ARG.
+ * dewi_knn_candidates_i8_query_filtered: n_union = |U|, n_allowed = HOST array [n_queries] of |F_j| (what
+ *   dewi_query_filter_prepare / the probe read-back returned).  n_queries <= 65535; n_union outside [0, n_rows], an
+ *   n_allowed[j] outside [0, n_union], or an n_allowed[j] < n_candidates: DEWI_ERR_INVALID_ARG — a query whose list is shorter
+ *   than the cut is searched on a filter of its own list (the caller's split, as dewi_knn_rerank_query_filtered).
+ * Both: shape limits, alignment, the id range (id_offset + n_rows must fit int32) and the error codes of
+ *   dewi_knn_candidates_i8; every argument error before any device work; asynchronous on `stream`, nothing allocated, nothing
+ *   synchronised.  Passes are four queries, then singles; a pass of four starts at a multiple of 4 and therefore reads ONE
+ *   query word.  The workspace's contents on entry are undefined: every key the select reads is written earlier in the same
+ *   call (list slots no row reached and dense slots of a query whose bit is clear hold the empty key).
  * ------------------------------------------------------------------------------------------ */
 #define DEWI_I8_MAX_CANDIDATES 1024
 #define DEWI_I8_MAX_DIM 4096
@@ -574,6 +597,16 @@ int dewi_knn_candidates_i8(const int8_t* d_codes, const float* d_scales, int64_t
                            dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, void* stream);
 int dewi_rescore_candidates_f32(const float* d_E, int64_t n_rows, int dim, const float* d_Q, int n_queries,
                                 dewi_candidate* d_cand, int n_candidates, int64_t id_offset, void* stream);
+size_t dewi_knn_i8_filtered_workspace_bytes(int64_t n_scan, int dim, int n_queries, int n_candidates);
+int dewi_knn_candidates_i8_filtered(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const void* d_filter,
+                                    int64_t n_allowed, const float* d_Q, int n_queries, const float* d_dewi32,
+                                    const float* d_ent32, int n_candidates, int64_t id_offset, dewi_candidate* d_out,
+                                    void* d_workspace, size_t workspace_bytes, void* stream);
+int dewi_knn_candidates_i8_query_filtered(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim,
+                                          const void* d_filter, int64_t n_union, const int64_t* n_allowed /* HOST */,
+                                          const float* d_Q, int n_queries, const float* d_dewi32, const float* d_ent32,
+                                          int n_candidates, int64_t id_offset, dewi_candidate* d_out, void* d_workspace,
+                                          size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * In-place mutation of a built corpus (ABI 6, additive; the reference has no counterpart: its indexes only append and
