@@ -1105,6 +1105,63 @@ int dewi_ivf_probe_prepare(int elem_type, int64_t n_rows, int dim, const void* d
   return DEWI_OK;
 }
 
+// ---- IVF: the probe under a user filter (additive to ABI 6) -------------------------------------------------------------
+static dewi::IvfProbeFilteredLayout ivf_probe_filtered_layout(int64_t n_rows, int n_buckets, int n_queries, int group) {
+  dewi::IvfProbeFilteredLayout L;
+  L.probe = ivf_probe_layout(n_rows, n_buckets, n_queries, group);
+  const size_t groups = static_cast<size_t>(L.probe.n_groups);
+  L.blk_stride = (n_rows + 255) / 256 + 1;   // (kIvfThreads list positions per block, and the sum)
+  L.uheader_off = L.probe.total_words;
+  L.ucounts_off = L.uheader_off + groups * static_cast<size_t>(dewi::kFilterHeaderWords);
+  L.blk_off = L.ucounts_off + groups + static_cast<size_t>(n_queries);
+  L.tmp_off = L.blk_off + groups * static_cast<size_t>(L.blk_stride);
+  L.total_words = L.tmp_off + groups * 2 * static_cast<size_t>(n_rows);
+  return L;
+}
+
+size_t dewi_ivf_probe_filtered_group_bytes(int64_t n_rows, int dim, int elem_type, int group) {
+  return dewi_ivf_probe_group_bytes(n_rows, dim, elem_type, group);   // the groups' buffers are those of the unfiltered probe
+}
+
+size_t dewi_ivf_probe_filtered_bytes(int64_t n_rows, int dim, int elem_type, int n_queries, int group) {
+  if (!ivf_shape_ok(n_rows, dim, elem_type) || group <= 0 || group > 32 || n_queries <= 0 || n_queries > 65535) return 0;
+  return 4 * ivf_probe_filtered_layout(n_rows, filter_buckets(dim, elem_type), n_queries, group).total_words;
+}
+
+int dewi_ivf_probe_prepare_filtered(int elem_type, int64_t n_rows, int dim, const void* d_lists, int n_cells,
+                                    const int64_t* d_probe_ids, int n_queries, int nprobe, int group, const uint8_t* d_allow,
+                                    int allow_per_query, void* d_out, size_t out_bytes, int64_t* out_n_union,
+                                    int64_t* out_n_allowed, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!d_lists || !d_probe_ids || !d_allow || !d_out || !out_n_union || !out_n_allowed)
+    return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (int rc = check_fp32_only(elem_type, "IVF")) return rc;
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
+  if (n_cells <= 0 || n_cells > dewi::kIvfMaxCells || n_cells > n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_cells %d outside [1, min(%d, n_rows)]", n_cells, dewi::kIvfMaxCells);
+  if (n_queries <= 0 || n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
+  if (nprobe <= 0 || nprobe > n_cells) return fail(DEWI_ERR_INVALID_ARG, "nprobe %d outside [1, n_cells = %d]", nprobe, n_cells);
+  if (group <= 0 || group > 32) return fail(DEWI_ERR_INVALID_ARG, "group %d outside [1, 32]", group);
+  if (allow_per_query != 0 && allow_per_query != 1)
+    return fail(DEWI_ERR_INVALID_ARG, "allow_per_query %d is neither 0 nor 1", allow_per_query);
+  const size_t need = dewi_ivf_probe_filtered_bytes(n_rows, dim, elem_type, n_queries, group);
+  if (out_bytes < need) return fail(DEWI_ERR_WORKSPACE, "probe buffer %zu B < required %zu B", out_bytes, need);
+  const int g = filter_buckets(dim, elem_type);
+  const dewi::IvfProbeFilteredLayout L = ivf_probe_filtered_layout(n_rows, g, n_queries, group);
+  uint32_t* out = static_cast<uint32_t*>(d_out);
+  hipError_t e = dewi::launch_ivf_probe_prepare_filtered(static_cast<const uint32_t*>(d_lists), n_rows, n_cells, g, d_probe_ids,
+                                                         n_queries, nprobe, group, d_allow, allow_per_query, out, L, stream);
+  if (e != hipSuccess) return hip_fail(e, "ivf_probe_prepare_filtered launch");
+  const int n_groups = L.probe.n_groups;
+  std::vector<uint32_t> counts(static_cast<size_t>(n_groups) + static_cast<size_t>(n_queries));
+  e = hipMemcpyAsync(counts.data(), out + L.probe.counts_off, sizeof(uint32_t) * counts.size(), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hip_fail(e, "filtered probe count read-back");
+  for (int i = 0; i < n_groups; ++i) out_n_union[i] = static_cast<int64_t>(counts[i]);
+  for (int j = 0; j < n_queries; ++j) out_n_allowed[j] = static_cast<int64_t>(counts[n_groups + j]);
+  return DEWI_OK;
+}
+
 // ---- range search (additive to ABI 6) ---------------------------------------------------------------------------------
 // Workspace: the dense keys [n_queries][n_scan] from offset 0 (where run_scan puts them), the selection's chunk counts
 // [n_queries][range_chunks(n_scan)], then the prepared queries of the generic row kernel.  The first two depend on n_scan and

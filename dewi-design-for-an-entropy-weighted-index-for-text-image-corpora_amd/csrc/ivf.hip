@@ -1,5 +1,6 @@
 // Inverted-file (IVF-Flat) support for gfx950: the k-means cells of a corpus as row lists (dewi_ivf_lists_build), and the
-// expansion of "these cells" into the prepared filter the LIST / QMASK row kernels walk (dewi_ivf_probe_prepare).
+// expansion of "these cells" into the prepared filter the LIST / QMASK row kernels walk (dewi_ivf_probe_prepare), also with the
+// rows a user filter does not allow dropped on the way (dewi_ivf_probe_prepare_filtered: part (c), described where it starts).
 //
 // (a) Cell lists.  assign[n_rows] (the cell of every row) -> a counting sort by (cell, row mod G, row), G the bucket count of a
 // prepared filter (scan_common.hpp).  Buffer (u32 words, IvfListsLayout in launch.hpp):
@@ -197,6 +198,28 @@ __global__ __launch_bounds__(1024) void ivf_plan(const uint32_t* __restrict__ li
   if (t < group && q0 + t < n_queries) counts[n_groups + q0 + t] = fj[t];
 }
 
+// The row and the cell bits at position p of a group's list (p < seg[n_seg]): the segment that holds p is the last i with
+// seg[i] <= p (empty segments share their start with the next one).  false if the lists are not what (a) built.
+__device__ __forceinline__ bool ivf_locate(const uint32_t* __restrict__ lists, int64_t n_rows, int n_cells, int n_buckets,
+                                           const uint32_t* __restrict__ seg, const uint32_t* __restrict__ bits, int64_t p,
+                                           uint32_t* row, uint32_t* m) {
+  const int64_t n_seg = static_cast<int64_t>(n_cells) * n_buckets;
+  int64_t lo = 0, hi = n_seg;   // first i in [0, n_seg] with seg[i] > p
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (seg[mid] > p) hi = mid;
+    else lo = mid + 1;
+  }
+  const int64_t i = lo - 1;
+  if (i < 0) return false;
+  const int b = static_cast<int>(i / n_cells), cell = static_cast<int>(i % n_cells);
+  const int64_t src = static_cast<int64_t>(lists[static_cast<int64_t>(cell) * n_buckets + b]) + (p - seg[i]);
+  if (src >= n_rows) return false;
+  *row = lists[n_seg + 1 + src];
+  *m = bits[cell];
+  return true;
+}
+
 __global__ __launch_bounds__(kIvfThreads) void ivf_copy(const uint32_t* __restrict__ lists, int64_t n_rows, int n_cells, int n_buckets,
                                                         const uint32_t* __restrict__ cellbits, const uint32_t* __restrict__ seg_all,
                                                         uint32_t* __restrict__ out, int64_t group_words) {
@@ -204,26 +227,16 @@ __global__ __launch_bounds__(kIvfThreads) void ivf_copy(const uint32_t* __restri
   const int64_t n_seg = static_cast<int64_t>(n_cells) * n_buckets;
   const uint32_t* __restrict__ seg = seg_all + static_cast<int64_t>(grp) * (n_seg + 1);
   const uint32_t* __restrict__ bits = cellbits + static_cast<int64_t>(grp) * n_cells;
-  const uint32_t* __restrict__ src_rows = lists + n_seg + 1;
   uint32_t* __restrict__ dst_rows = out + static_cast<int64_t>(grp) * group_words + kFilterHeaderWords;
   uint32_t* __restrict__ dst_words = dst_rows + n_rows;
   int64_t n_union = seg[n_seg];
   if (n_union > n_rows) n_union = n_rows;   // (cells are disjoint: cannot happen with lists this library built)
   for (int64_t p = static_cast<int64_t>(blockIdx.x) * kIvfThreads + threadIdx.x; p < n_union;
        p += static_cast<int64_t>(gridDim.x) * kIvfThreads) {
-    // the segment that holds p: the last i with seg[i] <= p (empty segments share their start with the next one)
-    int64_t lo = 0, hi = n_seg;   // first i in [0, n_seg] with seg[i] > p
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (seg[mid] > p) hi = mid;
-      else lo = mid + 1;
-    }
-    const int64_t i = lo - 1;
-    const int b = static_cast<int>(i / n_cells), cell = static_cast<int>(i % n_cells);
-    const int64_t src = static_cast<int64_t>(lists[static_cast<int64_t>(cell) * n_buckets + b]) + (p - seg[i]);
-    if (src < n_rows) {
-      dst_rows[p] = src_rows[src];
-      dst_words[p] = bits[cell];
+    uint32_t row, m;
+    if (ivf_locate(lists, n_rows, n_cells, n_buckets, seg, bits, p, &row, &m)) {
+      dst_rows[p] = row;
+      dst_words[p] = m;
     }
   }
 }
@@ -250,6 +263,187 @@ hipError_t launch_ivf_probe_prepare(const uint32_t* d_lists, int64_t n_rows, int
   if (blocks > 512) blocks = 512;
   hipLaunchKernelGGL(ivf_copy, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(L.n_groups)), dim3(kIvfThreads), 0, stream,
                      d_lists, n_rows, n_cells, n_buckets, cellbits, seg, d_out, static_cast<int64_t>(L.group_words));
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// (c) probe expansion under a user filter
+//
+// The list of (b) with every row the user does not allow dropped, in the same order.  mark and plan run as in (b), but the plan's
+// header and counts go to scratch: they describe the UNFILTERED list U0, whose positions the rest walks in blocks of
+// kIvfThreads.  Three launches, the ordered compaction of filter.hip over list positions instead of corpus rows:
+//   ivf_filter_count    position p -> its row and cell bits (the search of ivf_copy), w = bits & allow(row): the mask bytes are
+//                       gathered for probed rows only.  (row, w) go to scratch, the kept positions of the block to blk[block],
+//                       and per query bit the popcount of a ballot to |F_j| (integer adds: order-free)
+//   ivf_filter_scan     one workgroup per group: exclusive scan of the used blocks' counts; |U|, the header words that no
+//                       position owns (buckets that start at |U0|, words G .. 15)
+//   ivf_filter_scatter  position p -> blk[block] + its rank among the block's kept positions (ballots); the position at which an
+//                       unfiltered bucket starts writes where the filtered one does
+// Work: O(n_cells * G) per group + O(|U0|).  No kernel reads a count another block of the same launch writes.
+
+struct IvfFilterArgs {
+  int64_t n_rows, blk_stride;       // blk_stride: words of one group's block counts (ceil(n_rows / kIvfThreads) + 1)
+  int n_cells, n_buckets, n_queries, group;
+  const uint32_t* cellbits;         // [n_groups][n_cells]
+  const uint32_t* seg;              // [n_groups][n_cells * n_buckets + 1]
+  const uint32_t* uheader;          // [n_groups][kFilterHeaderWords]: the header of U0
+  uint32_t* blk;                    // [n_groups][blk_stride]
+  uint32_t* tmp;                    // [n_groups][2 * n_rows]: rows, then words, by position of U0
+  uint32_t* counts;                 // [n_groups] |U|, [n_queries] |F_j|
+  uint32_t* out;
+  int64_t group_words;
+};
+
+__device__ __forceinline__ int64_t ivf_unfiltered_size(const IvfFilterArgs& A, int grp) {
+  const int64_t n_seg = static_cast<int64_t>(A.n_cells) * A.n_buckets;
+  const int64_t u0 = A.seg[static_cast<int64_t>(grp) * (n_seg + 1) + n_seg];
+  return u0 > A.n_rows ? A.n_rows : u0;
+}
+
+__global__ __launch_bounds__(kIvfThreads) void ivf_filter_count(IvfFilterArgs A, const uint32_t* __restrict__ lists,
+                                                                const uint8_t* __restrict__ allow, int per_query) {
+  __shared__ uint32_t kept_sh, fj[32];
+  const int grp = blockIdx.y, t = threadIdx.x, lane = t & (kWave - 1);
+  const int64_t n_seg = static_cast<int64_t>(A.n_cells) * A.n_buckets;
+  const uint32_t* __restrict__ seg = A.seg + static_cast<int64_t>(grp) * (n_seg + 1);
+  const uint32_t* __restrict__ bits = A.cellbits + static_cast<int64_t>(grp) * A.n_cells;
+  uint32_t* __restrict__ tmp_rows = A.tmp + static_cast<int64_t>(grp) * 2 * A.n_rows;
+  uint32_t* __restrict__ tmp_words = tmp_rows + A.n_rows;
+  uint32_t* __restrict__ blk = A.blk + static_cast<int64_t>(grp) * A.blk_stride;
+  const int q0 = grp * A.group;
+  const int64_t u0 = ivf_unfiltered_size(A, grp);
+  const int64_t n_blk = (u0 + kIvfThreads - 1) / kIvfThreads;
+  for (int64_t bi = blockIdx.x; bi < n_blk; bi += gridDim.x) {   // (n_blk is the same for every thread of the workgroup)
+    if (t < 32) fj[t] = 0u;
+    if (t == 0) kept_sh = 0u;
+    __syncthreads();
+    const int64_t p = bi * kIvfThreads + t;
+    uint32_t row = 0u, m = 0u, w = 0u;
+    if (p < u0 && ivf_locate(lists, A.n_rows, A.n_cells, A.n_buckets, seg, bits, p, &row, &m) && row < A.n_rows) {
+      if (!per_query) {
+        w = allow[row] != 0 ? m : 0u;
+      } else {
+        while (m != 0u) {   // (at most `group` bits, each of a query below n_queries: ivf_mark set no other)
+          const int i = __ffs(m) - 1;
+          m &= m - 1u;
+          if (allow[static_cast<int64_t>(q0 + i) * A.n_rows + row] != 0) w |= 1u << i;
+        }
+      }
+    }
+    if (p < u0) {
+      tmp_rows[p] = row;
+      tmp_words[p] = w;
+    }
+    const unsigned long long any = __ballot(w != 0u);
+    if (any != 0ull) {   // (wave-uniform)
+      if (lane == 0) atomicAdd(&kept_sh, static_cast<uint32_t>(__popcll(any)));
+      for (int i = 0; i < A.group; ++i) {
+        const unsigned long long mi = __ballot(((w >> i) & 1u) != 0u);
+        if (lane == 0 && mi != 0ull) atomicAdd(&fj[i], static_cast<uint32_t>(__popcll(mi)));
+      }
+    }
+    __syncthreads();
+    if (t == 0) blk[bi] = kept_sh;
+    if (t < A.group && q0 + t < A.n_queries && fj[t] != 0u) atomicAdd(&A.counts[gridDim.y + q0 + t], fj[t]);
+    __syncthreads();   // fj and kept_sh are zeroed by the next round
+  }
+}
+
+__global__ __launch_bounds__(1024) void ivf_filter_scan(IvfFilterArgs A) {
+  const int grp = blockIdx.x, t = threadIdx.x;
+  const int64_t u0 = ivf_unfiltered_size(A, grp);
+  const int64_t n_blk = (u0 + kIvfThreads - 1) / kIvfThreads;
+  const uint32_t* __restrict__ uheader = A.uheader + static_cast<int64_t>(grp) * kFilterHeaderWords;
+  uint32_t* __restrict__ header = A.out + static_cast<int64_t>(grp) * A.group_words;
+  const uint32_t n_union = block_scan_1024(A.blk + static_cast<int64_t>(grp) * A.blk_stride, n_blk, nullptr, 1, true);
+  if (t < A.n_buckets && uheader[t] >= u0) header[t] = n_union;   // an empty tail of buckets: no position of U0 stands there
+  if (t >= A.n_buckets && t <= kFilterMaxBuckets) header[t] = n_union;
+  if (t == kFilterMaxBuckets + 1) header[t] = static_cast<uint32_t>(A.n_buckets);
+  if (t > kFilterMaxBuckets + 1 && t < kFilterHeaderWords) header[t] = 0u;
+  if (t == 0) A.counts[grp] = n_union;
+}
+
+__global__ __launch_bounds__(kIvfThreads) void ivf_filter_scatter(IvfFilterArgs A) {
+  __shared__ uint32_t part[kIvfThreads / kWave];
+  const int grp = blockIdx.y, t = threadIdx.x, lane = t & (kWave - 1), wv = t >> 6;
+  const uint32_t* __restrict__ tmp_rows = A.tmp + static_cast<int64_t>(grp) * 2 * A.n_rows;
+  const uint32_t* __restrict__ tmp_words = tmp_rows + A.n_rows;
+  const uint32_t* __restrict__ blk = A.blk + static_cast<int64_t>(grp) * A.blk_stride;
+  const uint32_t* __restrict__ uheader = A.uheader + static_cast<int64_t>(grp) * kFilterHeaderWords;
+  uint32_t* __restrict__ header = A.out + static_cast<int64_t>(grp) * A.group_words;
+  uint32_t* __restrict__ dst_rows = header + kFilterHeaderWords;
+  uint32_t* __restrict__ dst_words = dst_rows + A.n_rows;
+  const int64_t u0 = ivf_unfiltered_size(A, grp);
+  const int64_t n_blk = (u0 + kIvfThreads - 1) / kIvfThreads;
+  for (int64_t bi = blockIdx.x; bi < n_blk; bi += gridDim.x) {
+    const int64_t p = bi * kIvfThreads + t;
+    const uint32_t w = p < u0 ? tmp_words[p] : 0u;
+    const unsigned long long keep = __ballot(w != 0u);
+    if (lane == 0) part[wv] = static_cast<uint32_t>(__popcll(keep));
+    __syncthreads();
+    uint32_t before = 0;
+    for (int j = 0; j < kIvfThreads / kWave; ++j) before += j < wv ? part[j] : 0u;
+    const int64_t at = static_cast<int64_t>(blk[bi]) + before + __popcll(keep & ((1ull << lane) - 1ull));
+    if (p < u0) {
+      for (int b = 0; b < A.n_buckets; ++b)
+        if (static_cast<int64_t>(uheader[b]) == p) header[b] = static_cast<uint32_t>(at);
+      if (w != 0u && at < A.n_rows) {
+        dst_rows[at] = tmp_rows[p];
+        dst_words[at] = w;
+      }
+    }
+    __syncthreads();   // part[] is rewritten by the next round
+  }
+}
+
+hipError_t launch_ivf_probe_prepare_filtered(const uint32_t* d_lists, int64_t n_rows, int n_cells, int n_buckets,
+                                             const int64_t* d_probe_ids, int n_queries, int nprobe, int group,
+                                             const uint8_t* d_allow, int allow_per_query, uint32_t* d_out,
+                                             const IvfProbeFilteredLayout& L, hipStream_t stream) {
+  const IvfProbeLayout& P = L.probe;
+  uint32_t* counts = d_out + P.counts_off;
+  uint32_t* cellbits = d_out + P.bits_off;
+  uint32_t* seg = d_out + P.seg_off;
+  // the counts (|F_j| is summed by atomic adds) and the cell words are neighbours: one memset
+  hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint32_t) * (P.bits_off - P.counts_off + static_cast<size_t>(P.n_groups) * n_cells),
+                                stream);
+  if (e != hipSuccess) return e;
+  const int64_t pairs = static_cast<int64_t>(n_queries) * nprobe;
+  hipLaunchKernelGGL(ivf_mark, dim3(static_cast<unsigned>((pairs + kIvfThreads - 1) / kIvfThreads)), dim3(kIvfThreads), 0, stream,
+                     d_probe_ids, n_queries, nprobe, group, n_cells, cellbits);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  // the plan of the unfiltered list: its header and its counts go to scratch
+  hipLaunchKernelGGL(ivf_plan, dim3(static_cast<unsigned>(P.n_groups)), dim3(1024), 0, stream, d_lists, n_cells, n_buckets, n_queries,
+                     group, cellbits, seg, d_out + L.uheader_off, static_cast<int64_t>(kFilterHeaderWords), d_out + L.ucounts_off);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  IvfFilterArgs A;
+  A.n_rows = n_rows;
+  A.blk_stride = L.blk_stride;
+  A.n_cells = n_cells;
+  A.n_buckets = n_buckets;
+  A.n_queries = n_queries;
+  A.group = group;
+  A.cellbits = cellbits;
+  A.seg = seg;
+  A.uheader = d_out + L.uheader_off;
+  A.blk = d_out + L.blk_off;
+  A.tmp = d_out + L.tmp_off;
+  A.counts = counts;
+  A.out = d_out;
+  A.group_words = static_cast<int64_t>(P.group_words);
+  // as ivf_copy: a fixed grid that strides over the blocks of |U0| positions, 512 workgroups = 128 K positions per round
+  int64_t blocks = (n_rows + kIvfThreads - 1) / kIvfThreads;
+  if (blocks > 512) blocks = 512;
+  const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(P.n_groups));
+  hipLaunchKernelGGL(ivf_filter_count, grid, dim3(kIvfThreads), 0, stream, A, d_lists, d_allow, allow_per_query);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ivf_filter_scan, dim3(static_cast<unsigned>(P.n_groups)), dim3(1024), 0, stream, A);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ivf_filter_scatter, grid, dim3(kIvfThreads), 0, stream, A);
   return hipGetLastError();
 }
 

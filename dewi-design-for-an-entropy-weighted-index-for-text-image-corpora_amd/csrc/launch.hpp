@@ -178,6 +178,19 @@ struct IvfProbeLayout {
 hipError_t launch_ivf_probe_prepare(const uint32_t* d_lists, int64_t n_rows, int n_cells, int n_buckets, const int64_t* d_probe_ids,
                                     int n_queries, int nprobe, int group, uint32_t* d_out, const IvfProbeLayout& L,
                                     hipStream_t stream);
+// The probe under a user filter: the probe buffer, then the scratch of the compaction — the header and counts of the
+// unfiltered list ([n_groups][kFilterHeaderWords], [n_groups + n_queries]), one count per block of 256 list positions
+// ([n_groups][blk_stride]) and the unfiltered (row, word) pairs ([n_groups][2 * n_rows]) (abi.cpp ivf_probe_filtered_layout).
+struct IvfProbeFilteredLayout {
+  IvfProbeLayout probe;
+  int64_t blk_stride;
+  size_t uheader_off, ucounts_off, blk_off, tmp_off, total_words;
+};
+// d_allow: bytes, nonzero = allowed; [n_rows] for every query, or (allow_per_query) [n_queries][n_rows].
+hipError_t launch_ivf_probe_prepare_filtered(const uint32_t* d_lists, int64_t n_rows, int n_cells, int n_buckets,
+                                             const int64_t* d_probe_ids, int n_queries, int nprobe, int group,
+                                             const uint8_t* d_allow, int allow_per_query, uint32_t* d_out,
+                                             const IvfProbeFilteredLayout& L, hipStream_t stream);
 
 // ---- knn_scan_any_f32.hip / knn_scan_any_bf16.hip: plan.kind == kScanAnyLong / kScanAnyShort (raw queries)
 hipError_t launch_scan_any_f32(const ScanPlan& plan, const float* d_E, int64_t n_rows, int dim, const float* d_q_raw, int q0,

@@ -156,19 +156,35 @@ def plan_remove(n_rows: int, rows) -> Tuple[np.ndarray, np.ndarray, int]:
     return src, dst, n_keep
 
 
+FILTER_HEADER_WORDS = 16       # kFilterHeaderWords (csrc/launch.hpp): a prepared filter lists its rows from this u32 word on
+
+
 class DeviceFilter:
     """A prepared allow-list of corpus rows (``DeviceCorpus.make_filter``): the device buffer the filtered row kernels walk
     (``dewi_filter_prepare``: the allowed rows, sorted, grouped by the residue of their offset inside a 16-byte unit), the
     number of allowed rows and the identity of the corpus it was prepared for.  Prepare once, search many times; a filter
     used with another corpus — an index rebuilt since — raises ``ValueError`` instead of answering from stale rows."""
 
-    __slots__ = ("buf", "n_allowed", "corpus_id", "n_rows")
+    __slots__ = ("buf", "n_allowed", "corpus_id", "n_rows", "_mask")
 
     def __init__(self, buf, n_allowed: int, corpus_id: int, n_rows: int):
         self.buf = buf
         self.n_allowed = int(n_allowed)
         self.corpus_id = int(corpus_id)
         self.n_rows = int(n_rows)
+        self._mask = None
+
+    def byte_mask(self):
+        """The allow-list as device bytes [n_rows] (1 = allowed), what ``dewi_ivf_probe_prepare_filtered`` gathers from: built
+        from the listed rows at the first call (zeros, ones scattered at the rows from word 16 of the buffer) and kept."""
+        if self._mask is None:
+            torch = _torch()
+            with torch.cuda.device(self.buf.device):
+                rows = self.buf.view(torch.int32)[FILTER_HEADER_WORDS: FILTER_HEADER_WORDS + self.n_allowed]
+                mask = torch.zeros(self.n_rows, dtype=torch.uint8, device=self.buf.device)
+                mask[rows.to(torch.int64) & 0xFFFFFFFF] = 1
+            self._mask = mask
+        return self._mask
 
     def __len__(self) -> int:
         return self.n_allowed

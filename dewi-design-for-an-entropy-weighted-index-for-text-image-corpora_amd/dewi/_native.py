@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "dewi_knn_rerank_query_filtered",
     "dewi_ivf_buckets", "dewi_ivf_lists_bytes", "dewi_ivf_lists_build", "dewi_ivf_probe_group_bytes", "dewi_ivf_probe_bytes",
     "dewi_ivf_probe_prepare",
+    "dewi_ivf_probe_filtered_group_bytes", "dewi_ivf_probe_filtered_bytes", "dewi_ivf_probe_prepare_filtered",
     "dewi_knn_range_workspace_bytes", "dewi_knn_range_count", "dewi_knn_range_collect",
     "dewi_knn_range_shadow_supported", "dewi_knn_range_shadow_workspace_bytes", "dewi_knn_range_shadow_count",
     "dewi_knn_range_shadow_collect",
@@ -179,6 +180,13 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_ivf_probe_bytes.argtypes = [i64, i32, i32, i32, i32]
     lib.dewi_ivf_probe_prepare.restype = i32
     lib.dewi_ivf_probe_prepare.argtypes = [i32, i64, i32, vp, i32, vp, i32, i32, i32, vp, sz, c.POINTER(i64), c.POINTER(i64), vp]
+    lib.dewi_ivf_probe_filtered_group_bytes.restype = sz
+    lib.dewi_ivf_probe_filtered_group_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_ivf_probe_filtered_bytes.restype = sz
+    lib.dewi_ivf_probe_filtered_bytes.argtypes = [i64, i32, i32, i32, i32]
+    lib.dewi_ivf_probe_prepare_filtered.restype = i32
+    lib.dewi_ivf_probe_prepare_filtered.argtypes = [i32, i64, i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, sz, c.POINTER(i64),
+                                                    c.POINTER(i64), vp]
     lib.dewi_knn_range_workspace_bytes.restype = sz
     lib.dewi_knn_range_workspace_bytes.argtypes = [i64, i32, i32, i32]
     lib.dewi_knn_range_count.restype = i32

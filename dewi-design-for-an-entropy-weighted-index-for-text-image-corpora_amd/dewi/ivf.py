@@ -12,6 +12,9 @@ nearest centroid and sorts the rows into per-cell lists (``dewi_ivf_lists_build`
 
 So query j's answer is, bit for bit, ``ExactIndex.search(q_j, k, ..., filter=<rows of its probed cells>)``: the reference's
 search on those rows only.  ``nprobe >= nlist`` probes every row and returns the exact result.
+
+``search_probe_filtered*`` run the same three steps under a user filter: step 2 is ``dewi_ivf_probe_prepare_filtered``, which
+drops the probed rows the filter does not allow on the device, and query j's answer is the search on what is left.
 """
 from __future__ import annotations
 
@@ -69,7 +72,16 @@ class IVFIndex(ExactIndex):
     probed cells only is not part of this build.
 
     ``duplicate_groups`` / ``dedup_filter`` are inherited as well and exact.  ``search(..., filter=dedup_filter(...))`` on
-    this class is what any user filter is here: the parent's exact filtered search over the whole allow-list, not a probe.
+    this class is what any user filter is there: the parent's exact filtered search over the whole allow-list, not a probe.
+
+    A user filter TOGETHER with the probe is ``search_probe_filtered`` / ``search_probe_filtered_batch`` /
+    ``search_probe_filtered_device``: ``filter=`` is whatever ``search(filter=)`` takes (a mask, doc ids, rows, a prepared
+    ``DeviceFilter``, ``dedup_filter(...)``, per-query masks or ``DeviceQueryFilters``), and step 2 becomes
+    ``dewi_ivf_probe_prepare_filtered``: the probed cells are expanded and the rows the user does not allow are dropped on
+    the device, at a cost proportional to the probed rows.  Query j's answer is the exact search on (rows of its cells) ∩
+    (its allow-list); ``widen=True`` doubles ``nprobe`` for the queries that a selective filter leaves below the cut;
+    ``approx=True`` scans the int8 codes (``int8_codes=True``).  ``search`` / ``search_batch`` do not route there by
+    themselves (measurements: profiles/r15/ivf_filtered/).
 
     ``search_diverse`` / ``search_diverse_batch`` are ``ExactIndex``'s too, in their EXACT form: the candidate pool is the
     exact cut over every row, not over the probed cells, and there is no ``nprobe`` argument.  A diverse search over an IVF
@@ -489,6 +501,197 @@ class IVFIndex(ExactIndex):
             out_scores[j, :kk] = o_sc[0]
         return out_ids, out_scores
 
+    # ---------------------------------------------------------------- probe under a user filter
+    def _check_probe_filtered(self, k, candidates: Optional[int], similarity: str, filter, nprobe: Optional[int],
+                              approx: bool) -> None:
+        """The argument errors of ``search_probe_filtered*`` that need no device (raised before anything is built)."""
+        from . import _native as nat
+        if filter is None:
+            raise ValueError("search_probe_filtered needs a filter (search / search_batch are the unfiltered probe)")
+        if nprobe is not None and int(nprobe) < 1:
+            raise ValueError(f"nprobe must be at least 1, got {nprobe}")
+        if approx:
+            if not self._int8_codes:
+                raise ValueError("approx=True needs an IVFIndex built with int8_codes=True")
+            if similarity != "ip":
+                raise ValueError("approx=True does not take a similarity transform")
+            cut = 2 * int(k) if candidates is None else int(candidates)
+            if cut > nat.I8_MAX_CANDIDATES:
+                raise ValueError(f"approx=True re-ranks at most {nat.I8_MAX_CANDIDATES} candidates, got a cut of {cut}")
+
+    def _allow_of(self, filter, b: int):
+        """``filter`` as the stage reads it -> (device bytes, per-query flag); a stale filter raises ``ValueError``."""
+        from ._engine import DeviceQueryFilters
+        f = self._prepared(filter)
+        if isinstance(f, DeviceQueryFilters):
+            self._corpus.check_query_filters(f, b)
+            return f.masks, 1
+        self._corpus.check_filter(f)
+        return f.byte_mask(), 0
+
+    def _prepare_probe_filtered(self, probe_ids, b: int, nprobe: int, allow, per_query: int):
+        """``dewi_ivf_probe_prepare_filtered`` into the index's probe buffer -> (|U| per group, |F_j| per query, bytes per
+        group): ``_prepare_probe`` with the rows ``allow`` does not hold dropped on the device."""
+        import torch
+        from . import _native as nat
+        lib, st, corpus = nat.load_library(), self._ivf, self._corpus
+        need = int(lib.dewi_ivf_probe_filtered_bytes(corpus.n_rows, self.dim, 0, b, PROBE_GROUP))
+        stride = int(lib.dewi_ivf_probe_filtered_group_bytes(corpus.n_rows, self.dim, 0, PROBE_GROUP))
+        if need == 0 or stride == 0:
+            raise nat.NativeLibraryError(f"dewi_ivf_probe_filtered_bytes returned 0 for {b} queries")
+        if self._probe_buf is None or self._probe_buf.numel() < need or self._probe_buf.device != corpus.device:
+            self._probe_buf = torch.empty(need, dtype=torch.uint8, device=corpus.device)
+        n_groups = (b + PROBE_GROUP - 1) // PROBE_GROUP
+        n_union = (ctypes.c_int64 * n_groups)()
+        n_allowed = (ctypes.c_int64 * b)()
+        nat.check(lib.dewi_ivf_probe_prepare_filtered(
+            0, corpus.n_rows, self.dim, nat.ptr(st.lists), st.nlist, nat.ptr(probe_ids), b, nprobe, PROBE_GROUP, nat.ptr(allow),
+            per_query, nat.ptr(self._probe_buf), self._probe_buf.numel(), n_union, n_allowed, nat.stream_ptr()))
+        return list(n_union), list(n_allowed), stride
+
+    def search_probe_filtered_device(self, q_dev, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                                     candidates: Optional[int] = None, similarity: str = "ip", *, filter,
+                                     nprobe: Optional[int] = None, widen: bool = False, approx: bool = False,
+                                     rescore: bool = True, return_nprobe: bool = False):
+        """``search_device`` where query j searches the rows of its ``nprobe`` nearest cells that ``filter`` allows: the three
+        steps, with ``dewi_ivf_probe_prepare_filtered`` as step 2 -> (ids int64 [B, k], scores fp32 [B, k]) device tensors, and
+        with ``return_nprobe`` the ``nprobe`` every query ended at (int64 [B], on the device).  ``filter``: a ``DeviceFilter``,
+        ``DeviceQueryFilters`` or anything ``search_batch(filter=)`` prepares on the fly.  The rules of ``search_device``: groups
+        of 8 share a pass, a query with ``|F_j|`` below the cut is searched on its own list with cut ``|F_j|``, ``|F_j| < k`` pads
+        with id -1 / score NaN.  Synchronises the stream once per prepared buffer.  See ``search_probe_filtered_batch``."""
+        import torch
+        from . import _native as nat
+        from ._engine import check_search_args, cut_size, default_outputs, empty_result
+        approx = bool(approx)
+        self._check_probe_filtered(k, candidates, similarity, filter, nprobe, approx)
+        self._ensure_built()
+        corpus, st = self._corpus, self._ivf
+        if corpus.is_bf16:
+            raise NotImplementedError("IVFIndex serves fp32 corpora (bf16: not in this build)")
+        npb = self._resolve_nprobe(nprobe, st.nlist)
+        b, k = check_search_args(q_dev.shape, self.dim, k, candidates, similarity)
+        allow, per_query = self._allow_of(filter, b)
+        used = [npb] * b                             # the nprobe every query ended at
+
+        def result(ids, scores):
+            if not return_nprobe:
+                return ids, scores
+            return ids, scores, torch.tensor(used, dtype=torch.int64, device=corpus.device)
+
+        if k <= 0:
+            return result(*empty_result(b, corpus.device))
+        if candidates is not None and int(candidates) < k:
+            raise ValueError(f"candidates = {candidates} must be at least k = {k}")
+        c = cut_size(k, candidates)
+        sim, eta, pref = nat.SIM_CODES[similarity], float(eta), float(entropy_pref)
+        out_ids, out_scores = default_outputs(b, k, corpus.device)
+
+        def groups(q, n_union, n_allowed, stride, kk, cc, o_ids, o_sc):
+            if approx:
+                self._search_groups_i8(q, n_union, n_allowed, stride, kk, cc, rescore, eta, pref, o_ids, o_sc)
+            else:
+                self._search_groups(q, n_union, n_allowed, stride, kk, cc, candidates, sim, eta, pref, o_ids, o_sc)
+
+        pending = list(range(b))
+        while pending:
+            # the coarse step runs for the whole batch (nlist rows: cheap), so that a query's cells at a given nprobe never
+            # depend on which other queries are still pending
+            probe_all, _ = st.coarse.search_device(q_dev, npb, 0.0, 0.0, candidates=npb)
+            n_p = len(pending)
+            if n_p == b:
+                pid, q_p, allow_p = probe_all, q_dev, allow
+            else:
+                at = torch.tensor(pending, dtype=torch.int64, device=corpus.device)
+                pid, q_p = probe_all[at].contiguous(), q_dev[at].contiguous()
+                allow_p = allow[at].contiguous() if per_query else allow
+            for j in pending:
+                used[j] = npb
+            n_union, n_allowed, stride = self._prepare_probe_filtered(pid, n_p, npb, allow_p, per_query)
+            ready = [i for i in range(n_p) if n_allowed[i] >= c]
+            if len(ready) == b:                      # the usual case: every list reaches the cut at the first probe
+                groups(q_dev, n_union, n_allowed, stride, k, c, out_ids, out_scores)
+                return result(out_ids, out_scores)
+            if n_p == b:                             # somebody is short: rows are written one by one, the rest is padding
+                out_ids.fill_(-1)
+                out_scores.fill_(float("nan"))
+            again = [i for i in range(n_p) if n_allowed[i] < c] if widen and npb < st.nlist else []
+            short = [i for i in range(n_p) if 0 < n_allowed[i] < c and i not in again]
+            if ready:
+                o_ids, o_sc = default_outputs(len(ready), k, corpus.device)
+                if len(ready) == n_p:
+                    groups(q_p, n_union, n_allowed, stride, k, c, o_ids, o_sc)
+                else:                                # the lists that reach the cut, prepared again as a batch of their own
+                    sub = torch.tensor(ready, dtype=torch.int64, device=corpus.device)
+                    pid_s, q_s = pid[sub].contiguous(), q_p[sub].contiguous()
+                    allow_s = allow_p[sub].contiguous() if per_query else allow_p
+                    u_s, a_s, stride = self._prepare_probe_filtered(pid_s, len(ready), npb, allow_s, per_query)
+                    groups(q_s, u_s, a_s, stride, k, c, o_ids, o_sc)
+                dst = torch.tensor([pending[i] for i in ready], dtype=torch.int64, device=corpus.device)
+                out_ids.index_copy_(0, dst, o_ids)
+                out_scores.index_copy_(0, dst, o_sc)
+            for i in short:                          # one list each, cut and k limited to |F_j|
+                j, kk = pending[i], min(k, n_allowed[i])
+                allow_1 = allow_p[i:i + 1] if per_query else allow_p
+                u_1, a_1, stride = self._prepare_probe_filtered(pid[i:i + 1], 1, npb, allow_1, per_query)
+                o_ids, o_sc = default_outputs(1, kk, corpus.device)
+                groups(q_p[i:i + 1], u_1, a_1, stride, kk, min(c, n_allowed[i]) if approx else c, o_ids, o_sc)
+                out_ids[j, :kk] = o_ids[0]
+                out_scores[j, :kk] = o_sc[0]
+            pending = [pending[i] for i in again]
+            npb = min(2 * npb, st.nlist)
+        return result(out_ids, out_scores)
+
+    def search_probe_filtered_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                                    candidates: Optional[int] = None, similarity: str = "ip", *, filter,
+                                    nprobe: Optional[int] = None, widen: bool = False, approx: bool = False,
+                                    rescore: bool = True, return_nprobe: bool = False):
+        """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k][, nprobe_used int64 [B]]): the probe of
+        ``search_batch`` UNDER a user filter.  Query j's answer is, bit for bit, ``ExactIndex.search_batch(q_j, k', ...,
+        filter=<rows of its probed cells that its allow-list holds>)``; the cells are expanded and filtered on the device
+        (``dewi_ivf_probe_prepare_filtered``: work proportional to the probed rows, not to N).
+
+        ``filter`` (required; ``None`` raises ``ValueError``): whatever ``ExactIndex.search_batch(filter=)`` takes — a bool
+        mask, doc ids, rows, a prepared ``DeviceFilter``, ``dedup_filter(...)``, or per query a bool [B, N] mask /
+        ``DeviceQueryFilters``.  A stale filter raises ``ValueError``.  Short lists do not raise: ``|F_j| < k`` pads the row
+        with id -1 / score NaN, ``|F_j| = 0`` is an all-padded row.
+
+        ``widen=True``: a query whose ``|F_j|`` is below the cut is probed again with ``nprobe`` doubled (capped at ``nlist``)
+        until it reaches the cut or ``nprobe == nlist`` (there the answer is the exact filtered search); its answer is the
+        rule above at its final ``nprobe_j``, which ``return_nprobe=True`` returns.  Only the short queries are re-run.
+
+        ``approx=True`` (an index with ``int8_codes=True``, ``similarity="ip"``, a cut of at most 1024; else ``ValueError``):
+        the cut is taken by the int8 scores — query j's answer is ``search_approx_filtered`` on the same rows; ``rescore``
+        as there.  ``approx=False`` is the default: nothing about this combination has been measured to choose by."""
+        self._check_probe_filtered(k, candidates, similarity, filter, nprobe, bool(approx))
+        self._ensure_built()
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        import torch
+        corpus = self._corpus
+        with corpus._lock, torch.cuda.device(corpus.device):
+            q_dev = corpus.stage_queries(q)
+            out = self.search_probe_filtered_device(q_dev, k, eta, entropy_pref, candidates, similarity, filter=filter,
+                                                    nprobe=nprobe, widen=widen, approx=approx, rescore=bool(rescore),
+                                                    return_nprobe=return_nprobe)
+            return tuple(t.cpu().numpy() for t in out)
+
+    def search_probe_filtered(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                              candidates: Optional[int] = None, similarity: str = "ip", *, filter,
+                              nprobe: Optional[int] = None, widen: bool = False, approx: bool = False, rescore: bool = True,
+                              return_nprobe: bool = False):
+        """``search_probe_filtered_batch`` for one query -> ``SearchResult`` (fewer than k results when the probed cells hold
+        fewer than k allowed rows), with ``return_nprobe`` the pair (``SearchResult``, nprobe used)."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        out = self.search_probe_filtered_batch(q[:1], k, eta, entropy_pref, candidates, similarity, filter=filter,
+                                               nprobe=nprobe, widen=widen, approx=approx, rescore=rescore,
+                                               return_nprobe=return_nprobe)
+        keep = out[0][0] >= 0
+        result = self.results_for(out[0][:1][:, keep], out[1][:1][:, keep])[0]
+        return (result, int(out[2][0])) if return_nprobe else result
+
     def search_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
                      candidates: Optional[int] = None, similarity: str = "ip", *, approx: Optional[bool] = None,
                      rescore: bool = True, filter=None, nprobe: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
@@ -497,8 +700,8 @@ class IVFIndex(ExactIndex):
         ``candidates``, blend, top-k).  An approximate index does not raise when the probe is short: with ``|F_j| < k`` the
         row holds ``|F_j|`` results and is padded with id -1 / score NaN.
 
-        ``filter=`` together with IVF is not supported: passing one runs the parent's EXACT filtered search over the whole
-        allow-list (``nprobe`` is then ignored).
+        ``filter=`` here runs the parent's EXACT filtered search over the whole allow-list (``nprobe`` is then ignored);
+        the probe under a filter is ``search_probe_filtered_batch``.
 
         ``approx`` (an index made with ``int8_codes=True``): step 3 takes the cut of every query by the INT8 scores of its
         probed rows (a quarter of the bytes), re-scores it from the fp32 rows (``rescore=True``; ``False`` blends the int8

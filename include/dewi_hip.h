@@ -277,6 +277,36 @@ int dewi_ivf_probe_prepare(int elem_type, int64_t n_rows, int dim, const void* d
                            int64_t* out_n_allowed, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * IVF probe under a user filter (additive to ABI 6): dewi_ivf_probe_prepare with every row the user does not allow dropped
+ * on the device, so that a filtered approximate search is the same filtered entry points over (probed cells ∩ allow-list).
+ * fp32 corpora (elem_type 0); a bf16 corpus returns DEWI_ERR_UNSUPPORTED.
+ *
+ * dewi_ivf_probe_filtered_bytes: size of the buffer for n_queries queries in groups of `group` (1..32) consecutive queries
+ * (0 for a bad shape; needs no device; at least dewi_ivf_probe_bytes: the scratch of the compaction lies behind the probe
+ * buffer); dewi_ivf_probe_filtered_group_bytes: the distance between the buffers of consecutive groups inside it (at least
+ * dewi_ivf_probe_group_bytes).
+ * dewi_ivf_probe_prepare_filtered: d_lists, d_probe_ids, n_cells, nprobe, group as dewi_ivf_probe_prepare takes them.
+ * d_allow (DEVICE bytes, nonzero = allowed): allow_per_query == 0: ONE mask [n_rows] for every query; allow_per_query == 1:
+ * [n_queries][n_rows], row j the list of query j.  For group g, at d_out + g * dewi_ivf_probe_filtered_group_bytes(...), a
+ * buffer in the layout dewi_knn_rerank_query_filtered reads (16-word header, rows from word 16, one u32 of query bits per list
+ * position at 16 + n_rows); a group of one query is a prepared filter for dewi_knn_rerank_filtered.  With bits[cell] = the OR of
+ * 1 << i over the group's queries i that name the cell with a valid id (ids outside [0, n_cells) and repeated ids are IGNORED)
+ * and allow(row) = all bits if the shared mask allows the row, else 0 (per query: bit i set iff query q0 + i allows it), a row
+ * is listed iff w = bits[cell(row)] & allow(row) != 0, and its word is w.  The listed rows keep the order of the unfiltered
+ * probe: bucket row % G, then cell ascending, then row ascending.  header[b] = start of bucket b (b < G), header[G..8] = |U|,
+ * header[9] = G, header[10..15] = 0.  Returns |U_g| in out_n_union[g] (HOST, one per group) and in out_n_allowed[j] (HOST,
+ * n_queries) the number of listed rows whose word holds query j's bit.  It SYNCHRONISES `stream` once.  Integer work only: the
+ * same inputs give the same header, rows[:|U|] and words[:|U|], whatever the buffer held on entry; nothing is written beyond
+ * out_bytes.  Work: O(n_cells * G) per group + O(rows of the probed cells); mask bytes are read for probed rows only.
+ * ------------------------------------------------------------------------------------------ */
+size_t dewi_ivf_probe_filtered_group_bytes(int64_t n_rows, int dim, int elem_type, int group);
+size_t dewi_ivf_probe_filtered_bytes(int64_t n_rows, int dim, int elem_type, int n_queries, int group);
+int dewi_ivf_probe_prepare_filtered(int elem_type, int64_t n_rows, int dim, const void* d_lists, int n_cells,
+                                    const int64_t* d_probe_ids, int n_queries, int nprobe, int group, const uint8_t* d_allow,
+                                    int allow_per_query, void* d_out, size_t out_bytes, int64_t* out_n_union,
+                                    int64_t* out_n_allowed, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Range search (additive to ABI 6): every row at least as similar to the query as a threshold, however many that is — steps
  * 1-2 of the search above (query preparation, sim[i] for every scanned row, with exactly the arithmetic the one-query search
  * of this shape uses for the row), then the test  sim[i] >= threshold  in fp32 instead of the cut of step 3: NO cut, no k.
