@@ -862,12 +862,14 @@ static int check_rerank_rule(int sim_transform, int n_candidates) {
   return DEWI_OK;
 }
 
-// The two filtered searches from the device on: the row kernels of this dim planned on the n_scan listed rows (grid, lists or
-// dense keys, keys per query; no matrix-core pass), then select + re-rank over the keys they left in the workspace (local ids,
-// no candidate records).  d_qwords: see run_scan (n_scan doubles as its n_union: the stride of the query-word planes, read
-// only with d_qwords, so the one-filter caller's value is ignored).  `what` names the select launch in the error message.
+// The filtered searches from the device on: the row kernels of this dim planned on the n_scan listed rows (grid, lists or
+// dense keys, keys per query; no matrix-core pass), then select + re-rank over the keys they left in the workspace (the keys
+// carry GLOBAL rows), or — O.d_out_cand — the select alone: n_out >= c candidate records per query, O.id_offset added, padding
+// behind c (c <= kMaxSortCandidates there: the caller's check).  d_qwords: see run_scan (n_scan doubles as its n_union: the
+// stride of the query-word planes, read only with d_qwords, so the one-filter caller's value is ignored).  `what` names the
+// select launch in the error message.
 static int scan_select_filtered(const Batch& B, const SelectOut& O, int64_t n_scan, int c, const uint32_t* d_filter,
-                                const uint32_t* d_qwords, void* d_ws, size_t ws_bytes, const char* what) {
+                                const uint32_t* d_qwords, void* d_ws, size_t ws_bytes, const char* what, int n_out = 0) {
   DeviceInfo dev;
   int rc = ensure_device(dev);
   if (rc) return rc;
@@ -885,9 +887,11 @@ static int scan_select_filtered(const Batch& B, const SelectOut& O, int64_t n_sc
                                          g1 + static_cast<size_t>(B.n_queries) * L.p2, O.d_out_ids, O.d_out_scores, nullptr, c,
                                          B.stream);
   } else {
-    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, L.plan.slots == 1 ? L.plan.n_lists : 0, B.n_queries, c, O.k, O.rp,
-                                   O.d_dewi32, O.d_ent32, 0, O.d_out_ids, O.d_out_scores, nullptr, nullptr, dewi::SegmentLayout{},
-                                   B.stream);
+    // (records: n_out per query; lists shorter than that are not "n_out sorted keys each": the unsorted route, as batch_select)
+    const int n_select = O.d_out_cand ? n_out : c;
+    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, (L.plan.slots == 1 && n_select == c) ? L.plan.n_lists : 0,
+                                   B.n_queries, n_select, O.k, O.rp, O.d_dewi32, O.d_ent32, O.id_offset, O.d_out_ids, O.d_out_scores,
+                                   O.d_out_cand, nullptr, dewi::SegmentLayout{}, B.stream);
   }
   return launched(e, what);
 }
@@ -918,6 +922,33 @@ int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int
   const SelectOut O{k, make_rerank(eta, entropy_pref, sim_transform, space), d_dewi32, d_ent32, 0, d_out_ids, d_out_scores, nullptr};
   return scan_select_filtered(B, O, n_allowed, c, static_cast<const uint32_t*>(d_filter), nullptr, d_workspace, workspace_bytes,
                               "select launch (filtered)");
+}
+
+int dewi_knn_candidates_filtered(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_allowed,
+                                 const float* d_Q, int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates,
+                                 int space, int64_t id_offset, dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes,
+                                 void* stream_) {
+  const Batch B{d_E, elem_type, n_rows, dim, d_Q, n_queries, space, static_cast<hipStream_t>(stream_)};
+  int rc = check_common(B);
+  if (rc) return rc;
+  rc = check_fp32_only(elem_type, "filtered search");
+  if (rc) return rc;
+  if (!d_filter) return fail(DEWI_ERR_INVALID_ARG, "null filter pointer");
+  if (n_allowed < 0 || n_allowed > n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+  if (n_candidates <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_candidates must be positive (got %d)", n_candidates);
+  if (n_candidates > dewi::kMaxSortCandidates)   // (the select of larger cuts writes final results only)
+    return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds the %d filtered candidate records take", n_candidates,
+                dewi::kMaxSortCandidates);
+  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
+  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
+                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
+  if (n_allowed == 0) return DEWI_OK;            // nothing launched, nothing written (dewi_knn_rerank_filtered's rule)
+  const int c_local = n_candidates < n_allowed ? n_candidates : static_cast<int>(n_allowed);
+  const SelectOut O{0, make_rerank(0.0, 0.0), d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out};
+  return scan_select_filtered(B, O, n_allowed, c_local, static_cast<const uint32_t*>(d_filter), nullptr, d_workspace,
+                              workspace_bytes, "select launch (filtered records)", n_candidates);
 }
 
 // ---- per-query filters (additive to ABI 6) ----------------------------------------------------------------------------
@@ -1467,6 +1498,34 @@ int dewi_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows, int dim,
                                               static_cast<float>(1.0 - mmr_lambda), static_cast<float>(max_sim), id_offset,
                                               d_out_ids, d_out_scores, d_out_mmr, static_cast<hipStream_t>(stream)),
                   "diverse_rerank launch");
+}
+
+// The collapse keeps a query's pool in LDS: no workspace for any shape (and 0 for a bad one).  Needs no device.
+size_t dewi_collapse_workspace_bytes(int n_queries, int n_candidates) {
+  (void)n_queries; (void)n_candidates;
+  return 0;
+}
+
+int dewi_collapse_rerank(const dewi_candidate* d_cand, int n_queries, int n_candidates, const int32_t* d_labels, int64_t n_rows,
+                         int64_t id_offset, int k, int per_group, double eta, double entropy_pref, int64_t* d_out_ids,
+                         float* d_out_scores, int32_t* d_out_hits, int32_t* d_out_counts, void* d_workspace,
+                         size_t workspace_bytes, void* stream) {
+  if (!d_cand || !d_labels || !d_out_ids || !d_out_scores) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (n_queries <= 0 || n_candidates <= 0)
+    return fail(DEWI_ERR_INVALID_ARG, "non-positive size (%d queries, %d candidates)", n_queries, n_candidates);
+  if (n_rows <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_rows must be positive (got %lld)", static_cast<long long>(n_rows));
+  if (per_group <= 0) return fail(DEWI_ERR_INVALID_ARG, "per_group must be positive (got %d)", per_group);
+  if (k <= 0) return DEWI_OK;
+  if (k > n_candidates) return fail(DEWI_ERR_K_OUT_OF_BOUNDS, "k %d exceeds candidate count %d", k, n_candidates);
+  if (n_candidates > DEWI_COLLAPSE_MAX_CANDIDATES)
+    return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds the %d a collapsed re-rank takes", n_candidates,
+                DEWI_COLLAPSE_MAX_CANDIDATES);
+  if (const size_t need = dewi_collapse_workspace_bytes(n_queries, n_candidates))
+    if (int rc = check_workspace(d_workspace, workspace_bytes, need)) return rc;
+  return launched(dewi::launch_collapse_rerank(d_cand, n_queries, n_candidates, d_labels, n_rows, id_offset, k, per_group,
+                                               make_rerank(eta, entropy_pref), d_out_ids, d_out_scores, d_out_hits,
+                                               d_out_counts, static_cast<hipStream_t>(stream)),
+                  "collapse_rerank launch");
 }
 
 // ---- approximate search over an int8 copy of the corpus (additive to ABI 6; knn_scan_i8.hip) ---------------------------------

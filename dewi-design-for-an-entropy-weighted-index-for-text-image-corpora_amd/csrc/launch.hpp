@@ -430,6 +430,15 @@ hipError_t launch_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows,
                                  float max_sim, int64_t id_offset, int64_t* d_out_ids, float* d_out_scores, float* d_out_mmr,
                                  hipStream_t stream);
 
+// ---- collapse.hip: at most per_group results per label, one workgroup per query (no workspace)
+constexpr int kCollapseMaxCandidates = DEWI_COLLAPSE_MAX_CANDIDATES;
+static_assert(kCollapseMaxCandidates == kMaxSortCandidates, "a collapsed pool is what one workgroup sorts in LDS");
+// d_labels: int32 [n_rows]; d_out_hits / d_out_counts may be NULL.  1 <= k <= n_candidates <= kCollapseMaxCandidates.
+hipError_t launch_collapse_rerank(const dewi_candidate* d_cand, int n_queries, int n_candidates, const int32_t* d_labels,
+                                  int64_t n_rows, int64_t id_offset, int k, int per_group, const RerankParams& rp,
+                                  int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_hits, int32_t* d_out_counts,
+                                  hipStream_t stream);
+
 // ---- knn_scan_i8.hip: the approximate route over an int8 copy of the corpus (include/dewi_hip.h, "INT8 copy") ----
 constexpr int kI8MaxCandidates = DEWI_I8_MAX_CANDIDATES;
 constexpr int kI8MaxDim = DEWI_I8_MAX_DIM;

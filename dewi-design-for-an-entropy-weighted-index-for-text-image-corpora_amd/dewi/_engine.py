@@ -224,6 +224,87 @@ class DeviceQueryFilters:
                 f"of {self.n_rows} rows each, union {self.n_union})")
 
 
+class DeviceGroups:
+    """Prepared group labels of a corpus (``DeviceCorpus.make_groups``) for ``search_collapsed*``: ``labels`` is the device
+    int32 tensor [N] ``dewi_collapse_rerank`` gathers from (negative: ungrouped, a group of its own), ``n_groups`` the number of
+    groups (every ungrouped row counting as one).  Stale-checked like ``DeviceFilter``: labels used with another corpus — a
+    rebuild, ``remove``, ``upsert*`` — raise ``ValueError`` instead of folding the wrong rows."""
+
+    __slots__ = ("labels", "n_groups", "corpus_id", "n_rows")
+
+    def __init__(self, labels, n_groups: int, corpus_id: int, n_rows: int):
+        self.labels = labels
+        self.n_groups = int(n_groups)
+        self.corpus_id = int(corpus_id)
+        self.n_rows = int(n_rows)
+
+    def __len__(self) -> int:
+        return self.n_groups
+
+    def __repr__(self) -> str:
+        return f"DeviceGroups({self.n_groups} groups over {self.n_rows} rows)"
+
+
+def group_labels(groups, n_rows: int, row_of=None) -> Tuple[np.ndarray, int]:
+    """What ``make_groups`` takes -> ``(labels int32 [n_rows], n_groups)``.  Host logic only (NumPy).
+
+    ``groups``: an object with a ``labels`` array (``DuplicateGroups``); an integer array [N] in row order (negative:
+    ungrouped); a sequence of N hashables, factorised in order of first appearance (``None``: ungrouped); or a mapping
+    ``doc_id -> hashable`` with ``row_of`` the index's ``doc_id -> row`` (documents not named are ungrouped, ``None`` values too;
+    an unknown doc id raises ``KeyError``).  ``ValueError``: a wrong length, integer labels outside int32.  ``n_groups``
+    counts every distinct non-negative label and every ungrouped row."""
+    n = int(n_rows)
+    if hasattr(groups, "labels") and not isinstance(groups, dict):
+        groups = groups.labels
+    if hasattr(groups, "is_cuda"):
+        groups = groups.detach().cpu().numpy()
+
+    def factorise(pairs) -> np.ndarray:
+        out = np.full(n, -1, dtype=np.int64)
+        codes: Dict[object, int] = {}
+        for row, value in pairs:
+            if value is not None:
+                out[row] = codes.setdefault(value, len(codes))
+        return out
+
+    if hasattr(groups, "keys") and hasattr(groups, "__getitem__") and not isinstance(groups, np.ndarray):
+        if row_of is None:
+            raise ValueError("a doc_id -> group mapping needs an index (ExactIndex.make_groups)")
+        missing = [d for d in groups.keys() if d not in row_of]
+        if missing:
+            raise KeyError(f"unknown doc ids: {sorted(missing, key=str)[:5]}")
+        lab = factorise((row_of[d], groups[d]) for d in groups.keys())
+    else:
+        arr = groups if isinstance(groups, np.ndarray) else None
+        if arr is None:
+            items = list(groups)
+            if len(items) != n:
+                raise ValueError(f"group labels must have length {n}, got {len(items)}")
+            if items and all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) for x in items):
+                arr = np.asarray(items, dtype=np.int64)
+            else:
+                lab = factorise(enumerate(items))
+        if arr is not None:
+            if arr.shape != (n,):
+                raise ValueError(f"group labels must have shape ({n},), got {tuple(arr.shape)}")
+            if not np.issubdtype(arr.dtype, np.integer):
+                return group_labels(arr.tolist(), n, row_of)        # an object / string array: a sequence of hashables
+            lab = arr.astype(np.int64) if arr.dtype != np.uint64 else arr
+            if n and (int(lab.max()) > 0x7FFFFFFF or int(lab.min()) < -0x80000000):
+                raise ValueError("group labels must fit int32")
+    lab = np.asarray(lab)
+    grouped = lab[lab >= 0]
+    n_groups = int(np.unique(grouped).size) + int(lab.size - grouped.size)
+    return np.ascontiguousarray(lab.astype(np.int32)), n_groups
+
+
+def collapse_pool(k: int, candidates: Optional[int], n: int, approx: bool = False) -> int:
+    """The pool of a collapsed search: ``candidates`` (default ``4k``), at most the ``n`` rows there are to choose from and at
+    most what one re-rank takes (``COLLAPSE_MAX_CANDIDATES``; ``I8_MAX_CANDIDATES`` on the int8 route).  Host logic only."""
+    cap = min(nat.COLLAPSE_MAX_CANDIDATES, nat.I8_MAX_CANDIDATES) if approx else nat.COLLAPSE_MAX_CANDIDATES
+    return min(cut_size(k, 4 * int(k) if candidates is None else int(candidates), n), cap)
+
+
 #: smallest range batch that goes through the bf16 shadow (DeviceCorpus.range_shadow_min_batch): the smallest MEASURED batch at
 #: which the shadow route wins at 1 M x 768 — 8 queries 0.40 ms against 1.27 ms dense (profiles/r08/range_shadow/); smaller
 #: batches have not been measured
@@ -1544,6 +1625,162 @@ class DeviceCorpus:
             q = self.stage_queries(queries)
             ids_d, sc_d = self.search_diverse_approx_device(q, k, eta, entropy_pref, mmr_lambda, candidates, max_sim, rescore)
             return ids_d.cpu().numpy(), sc_d.cpu().numpy()
+
+    # ------------------------------------------------------------------ collapsed search (at most m results per group)
+    def make_groups(self, groups) -> DeviceGroups:
+        """Prepare group labels for ``search_collapsed*``: whatever ``group_labels`` takes without an index — a
+        ``DuplicateGroups``, an integer array [N] (negative: ungrouped) or a sequence of N hashables (``None``: ungrouped).
+        The result is bound to the corpus as it stands (stale-checked like a ``DeviceFilter``)."""
+        torch = _torch()
+        lab, n_groups = group_labels(groups, self.n_rows)
+        with torch.cuda.device(self.device):
+            dev = torch.from_numpy(lab).to(self.device)
+        return DeviceGroups(dev, n_groups, self.corpus_id, self.n_rows)
+
+    def check_groups(self, groups: DeviceGroups) -> None:
+        if not isinstance(groups, DeviceGroups):
+            raise TypeError(f"expected DeviceGroups (make_groups), got {type(groups).__name__}")
+        if groups.corpus_id != self.corpus_id:
+            raise ValueError("these group labels were prepared for another corpus (the index was rebuilt or changed since): "
+                             "prepare them again with make_groups")
+
+    def candidates_filtered_device(self, q_dev, n_candidates: int, filter: DeviceFilter, out=None):
+        """``candidates_device`` over the rows of ``filter`` only (``dewi_knn_candidates_filtered``; fp32 corpora, at most
+        2048 records per query): int32 view [B, n_candidates, 4], ids rows of the whole corpus plus ``id_offset``, padding
+        behind ``min(n_candidates, |A|)``.  An empty filter writes nothing: ``out`` is returned filled with padding."""
+        torch = _torch()
+        self.check_filter(filter)
+        b, c = int(q_dev.shape[0]), int(n_candidates)
+        if out is None:
+            out = torch.empty((b, c, 4), dtype=torch.int32, device=self.device)
+        n_a = filter.n_allowed
+        if n_a == 0:
+            # the padding record (sim -inf, dewi 0, ent 0, id -1) as int32 words
+            out.copy_(torch.tensor([-0x800000, 0, 0, -1], dtype=torch.int32, device=self.device).expand(b, c, 4))
+            return out
+        ws = self._cached_workspace(("filtered", b, n_a, min(c, n_a)), self._lib.dewi_knn_filtered_workspace_bytes, n_a, self.dim,
+                                    b, c)
+        nat.check(self._lib.dewi_knn_candidates_filtered(
+            nat.ptr(self.emb), self._elem, self.n_rows, self.dim, nat.ptr(filter.buf), n_a, nat.ptr(q_dev), b,
+            nat.ptr(self.dewi32), nat.ptr(self.ent32), c, nat.SPACE_CODES[self.space], self.id_offset, nat.ptr(out), nat.ptr(ws),
+            ws.numel(), nat.stream_ptr()))
+        return out
+
+    def collapse_rerank_device(self, recs, k: int, eta: float, entropy_pref: float, groups: DeviceGroups, per_group: int = 1,
+                               out_ids=None, out_scores=None, out_hits=None, out_counts=None):
+        """``dewi_collapse_rerank`` on candidate records of this corpus ([B, c, 4] int32 view, ids including ``id_offset``):
+        ``(ids, scores, hits, counts)`` device tensors, no sync.  Outputs the caller does not pass are prefilled with
+        -1 / NaN / 0 (positions from each query's count on are not written)."""
+        torch = _torch()
+        self.check_groups(groups)
+        b, c = int(recs.shape[0]), int(recs.shape[1])
+        if out_ids is None:
+            out_ids = torch.full((b, k), -1, dtype=torch.int64, device=self.device)
+        if out_scores is None:
+            out_scores = torch.full((b, k), float("nan"), dtype=torch.float32, device=self.device)
+        if out_hits is None:
+            out_hits = torch.zeros((b, k), dtype=torch.int32, device=self.device)
+        if out_counts is None:
+            out_counts = torch.zeros(b, dtype=torch.int32, device=self.device)
+        nat.check(self._lib.dewi_collapse_rerank(
+            nat.ptr(recs), b, c, nat.ptr(groups.labels), self.n_rows, self.id_offset, int(k), int(per_group), float(eta),
+            float(entropy_pref), nat.ptr(out_ids), nat.ptr(out_scores), nat.ptr(out_hits), nat.ptr(out_counts), None, 0,
+            nat.stream_ptr()))
+        return out_ids, out_scores, out_hits, out_counts
+
+    def search_collapsed_device(self, q_dev, k: int, eta: float, entropy_pref: float, groups: DeviceGroups, per_group: int = 1,
+                                candidates: Optional[int] = None, filter: Optional[DeviceFilter] = None, approx: bool = False,
+                                rescore: bool = True, out_ids=None, out_scores=None, out_hits=None):
+        """Enqueue one COLLAPSED search on the current stream: the k best documents of every query with at most ``per_group``
+        of them from one group of ``groups`` (``make_groups``).  Returns device tensors ``(ids, scores, hits, counts)`` — ids
+        [B, k] as the candidate records carry them (``id_offset`` included), adjusted scores, ``hits`` [B, k] the number of
+        documents of the pool in the result's group (1 for an ungrouped one: what "+37 similar" shows) and ``counts`` [B] the
+        number of results —, no sync.
+
+        The pool is the search's own candidate cut: the ``candidates`` most similar rows of every query (default ``4k``, at
+        most N — or the rows ``filter`` allows — and ``COLLAPSE_MAX_CANDIDATES`` = 2048), from ``candidates_device``, with
+        ``filter`` (one ``DeviceFilter``; fp32 corpora) from ``candidates_filtered_device``, with ``approx=True`` (the int8
+        shadow; pools up to 1024) from the int8 records, re-scored from the fp32 rows unless ``rescore=False``.
+        ``dewi_collapse_rerank`` then walks the pool in the search's order and keeps a document unless ``per_group``
+        documents of its group came before it.  The outputs are prefilled with -1 / NaN / 0: a query whose pool holds fewer
+        than k groups' worth of documents has a short row.  Cosine and l2, fp32 and bf16 (no ``filter`` on bf16).  Per-query
+        filters: ``NotImplementedError``.  ``k <= 0`` or an empty filter: [B, 0].  NOT thread-safe on one instance."""
+        torch = _torch()
+        self.check_groups(groups)
+        if isinstance(filter, DeviceQueryFilters):
+            raise NotImplementedError("a collapsed search takes one allow-list for the batch (per-query filters: not in this build)")
+        if filter is not None:
+            self.check_filter(filter)
+            if self.is_bf16:
+                raise NotImplementedError("filtered search serves fp32 corpora (bf16: not in this build)")
+        b, k = check_search_args(q_dev.shape, self.dim, k, None, "ip")
+        if int(per_group) <= 0:
+            raise ValueError(f"per_group must be positive, got {per_group}")
+        if approx:
+            self._int8()
+        n_avail = self.n_rows if filter is None else filter.n_allowed
+        if k <= 0 or n_avail == 0:
+            ids, sc = empty_result(b, self.device)
+            return ids, sc, torch.zeros((b, 0), dtype=torch.int32, device=self.device), torch.zeros(b, dtype=torch.int32, device=self.device)
+        c = collapse_pool(k, candidates, n_avail, approx)
+        if k > c:
+            raise ValueError(f"k = {k} exceeds the pool of {c} candidates")
+        if approx:
+            recs = self.candidates_i8_device(q_dev, c) if filter is None else self.candidates_i8_filtered_device(q_dev, c, filter)
+            if rescore:
+                self.rescore_candidates_device(q_dev, recs)
+        elif filter is None:
+            recs = self.candidates_device(q_dev, c)
+        else:
+            recs = self.candidates_filtered_device(q_dev, c, filter)
+        if out_ids is not None:
+            out_ids.fill_(-1)
+        if out_scores is not None:
+            out_scores.fill_(float("nan"))
+        if out_hits is not None:
+            out_hits.fill_(0)
+        return self.collapse_rerank_device(recs, k, eta, entropy_pref, groups, per_group, out_ids, out_scores, out_hits)
+
+    def search_collapsed(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, *, groups: DeviceGroups,
+                         per_group: int = 1, candidates: Optional[int] = None, filter: Optional[DeviceFilter] = None,
+                         approx: bool = False, rescore: bool = True, widen: bool = False, return_pool: bool = False):
+        """Blocking twin of ``search_collapsed_device``: ``(ids int64 [B, k], scores fp32 [B, k], hits int32 [B, k])`` on the
+        host — ids global, as the candidate records carry them; the tail of a short row holds -1 / NaN / 0.
+
+        ``widen=True``: after a round each query's number of results is read back (one synchronisation per round); a query
+        with fewer than k results whose pool was smaller than ``min(2048, N or |A|)`` is run again with four times the pool
+        (capped there) and its row replaced, until no such query is left.  A query's final answer is by definition what
+        ``search_collapsed(candidates=<its final pool>, widen=False)`` returns.  ``return_pool=True`` appends each query's
+        final pool size (int64 [B]).  A query still short at the cap stays short (id -1): for groups larger than the cap,
+        fold them corpus-wide with ``dedup_filter`` (or a filter of one row per group) instead.  Serialised by the per-corpus
+        lock."""
+        torch = _torch()
+        with self._lock, torch.cuda.device(self.device):
+            q = self.stage_queries(queries)
+            ids_d, sc_d, hits_d, cnt_d = self.search_collapsed_device(q, k, eta, entropy_pref, groups, per_group, candidates, filter,
+                                                                      approx, rescore)
+            b, kk = int(ids_d.shape[0]), int(ids_d.shape[1])
+            pool = np.zeros(b, dtype=np.int64)
+            if kk > 0:
+                n_avail = self.n_rows if filter is None else filter.n_allowed
+                c = collapse_pool(kk, candidates, n_avail, approx)
+                pool[:] = c
+                limit = collapse_pool(kk, n_avail, n_avail, approx)          # the largest pool a round can take
+                active = np.arange(b)
+                while widen and c < limit:
+                    counts = cnt_d.cpu().numpy()                            # the round's one synchronisation
+                    active = active[counts < kk]
+                    if active.size == 0:
+                        break
+                    c = min(4 * c, limit)
+                    idx = torch.from_numpy(active).to(self.device)
+                    out = self.search_collapsed_device(q[idx].contiguous(), kk, eta, entropy_pref, groups, per_group, c, filter,
+                                                       approx, rescore)
+                    ids_d[idx], sc_d[idx], hits_d[idx] = out[0], out[1], out[2]
+                    cnt_d = out[3]
+                    pool[active] = c
+            res = (ids_d.cpu().numpy(), sc_d.cpu().numpy(), hits_d.cpu().numpy())
+        return res + (pool,) if return_pool else res
 
 
 class Int8Corpus(DeviceCorpus):

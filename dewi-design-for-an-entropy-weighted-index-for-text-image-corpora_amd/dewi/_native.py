@@ -38,6 +38,8 @@ RANGE_MAX_QUERIES = 32
 RANGE_SHADOW_MAX_QUERIES = 2048
 #: largest candidate pool of a diverse (MMR) re-rank (include/dewi_hip.h DEWI_DIVERSE_MAX_CANDIDATES)
 DIVERSE_MAX_CANDIDATES = 1024
+#: largest candidate pool of a collapsed re-rank (include/dewi_hip.h DEWI_COLLAPSE_MAX_CANDIDATES)
+COLLAPSE_MAX_CANDIDATES = 2048
 #: largest candidate cut and widest row of the int8 route (include/dewi_hip.h DEWI_I8_MAX_CANDIDATES / DEWI_I8_MAX_DIM)
 I8_MAX_CANDIDATES = 1024
 I8_MAX_DIM = 4096
@@ -66,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "dewi_quantize_rows_i8", "dewi_prepare_queries_i8", "dewi_knn_i8_workspace_bytes", "dewi_knn_candidates_i8",
     "dewi_rescore_candidates_f32",
     "dewi_knn_i8_filtered_workspace_bytes", "dewi_knn_candidates_i8_filtered", "dewi_knn_candidates_i8_query_filtered",
+    "dewi_collapse_workspace_bytes", "dewi_collapse_rerank", "dewi_knn_candidates_filtered",
 )
 
 
@@ -236,6 +239,12 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_knn_candidates_i8_query_filtered.restype = i32
     lib.dewi_knn_candidates_i8_query_filtered.argtypes = [vp, vp, i64, i32, vp, i64, c.POINTER(i64), vp, i32, vp, vp, i32, i64, vp,
                                                           vp, sz, vp]
+    lib.dewi_collapse_workspace_bytes.restype = sz
+    lib.dewi_collapse_workspace_bytes.argtypes = [i32, i32]
+    lib.dewi_collapse_rerank.restype = i32
+    lib.dewi_collapse_rerank.argtypes = [vp, i32, i32, vp, i64, i64, i32, i32, f64, f64, vp, vp, vp, vp, vp, sz, vp]
+    lib.dewi_knn_candidates_filtered.restype = i32
+    lib.dewi_knn_candidates_filtered.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, vp, vp, i32, i32, i64, vp, vp, sz, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

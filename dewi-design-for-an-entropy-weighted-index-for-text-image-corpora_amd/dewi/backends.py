@@ -891,6 +891,84 @@ class ExactIndex(BaseIndex):
         return self._corpus.search_diverse_approx(q, int(k), float(eta), float(entropy_pref), float(mmr_lambda), candidates,
                                                   max_sim, bool(rescore))
 
+    # ---------------------------------------------------------------- collapsed search (additive)
+    def make_groups(self, groups):
+        """Prepare group labels for ``search_collapsed`` / ``search_collapsed_batch`` (additive).  ``groups`` is one of: a
+        ``DuplicateGroups`` (its ``labels``); an integer array [N] in row order, negative meaning ungrouped; a sequence of N
+        hashables in row order (source site, album, author, ...; ``None``: ungrouped), factorised on the host; a mapping
+        ``doc_id -> hashable`` (documents not named are ungrouped; an unknown doc id raises ``KeyError``).  A wrong length or
+        integer labels outside int32 raise ``ValueError``.  The result is a ``DeviceGroups`` bound to the index as it is built
+        now: after a rebuild, ``remove`` or ``upsert*`` it raises ``ValueError`` instead of folding the wrong rows."""
+        from ._engine import DeviceGroups, group_labels
+        self._ensure_built()
+        if isinstance(groups, DeviceGroups):
+            self._corpus.check_groups(groups)
+            return groups
+        is_mapping = hasattr(groups, "keys") and not hasattr(groups, "dtype")
+        lab, _ = group_labels(groups, len(self._doc_ids), self._row_map() if is_mapping else None)
+        return self._corpus.make_groups(lab)
+
+    def search_collapsed(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, *, groups,
+                         per_group: int = 1, candidates: Optional[int] = None, filter=None, approx: bool = False,
+                         rescore: bool = True, widen: bool = False, return_hits: bool = False):
+        """``search`` with at most ``per_group`` results from one group (additive; the reference has no such method; search
+        engines call it field collapsing): the k best documents of the query's pool — its ``candidates`` most similar
+        documents, default ``4k``, at most 2048 — in ``search`` order, a document being dropped when ``per_group`` documents of
+        its group rank before it.  ``groups``: anything ``make_groups`` takes, or a prepared ``DeviceGroups``.  Unlike
+        ``dedup_filter`` the member that stands for a group is the best one FOR THIS QUERY, and a group need not be geometric.
+
+        ``filter``: whatever ``search(filter=)`` takes for ONE allow-list (a mask, doc ids, rows, a prepared filter,
+        ``dedup_filter(...)``); per-query filters raise ``NotImplementedError``.  ``approx=True`` (an index with the int8
+        shadow) takes the pool by the int8 scores (at most 1024), re-scored from the fp32 rows unless ``rescore=False``.
+        ``widen=True`` runs a query again with four times the pool while it has fewer than k results and the pool can still
+        grow (cap 2048, N, or the filter's rows); a query still short at the cap returns fewer than k results — for groups
+        larger than the cap fold them corpus-wide with ``dedup_filter`` instead.
+
+        Returns ``(doc_id, adjusted score, Payload)`` tuples like ``search``; with ``return_hits=True`` ``(results, hits)``,
+        ``hits[i]`` the number of documents of the pool in result i's group (1 for an ungrouped document): "+37 similar"."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        rows, scores, hits = self.search_collapsed_batch(q[:1], k, eta, entropy_pref, groups=groups, per_group=per_group,
+                                                         candidates=candidates, filter=filter, approx=approx, rescore=rescore,
+                                                         widen=widen, return_hits=True)
+        keep = rows[0] >= 0             # (fewer than k results: the tail is padded with id -1)
+        res = self.results_for(rows[:1][:, keep], scores[:1][:, keep])[0]
+        return (res, hits[0][keep].tolist()) if return_hits else res
+
+    def search_collapsed_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, *, groups,
+                               per_group: int = 1, candidates: Optional[int] = None, filter=None, approx: bool = False,
+                               rescore: bool = True, widen: bool = False, return_hits: bool = False, return_pool: bool = False):
+        """[B, dim] queries -> ``(row indices int64 [B, k], adjusted scores fp32 [B, k])``, with ``return_hits=True`` also
+        ``hits`` int32 [B, k], with ``return_pool=True`` also each query's final pool size int64 [B]; a query with fewer than
+        k results pads its row with -1 / NaN / 0.  See ``search_collapsed``."""
+        from ._engine import DeviceQueryFilters
+        if int(per_group) <= 0:
+            raise ValueError(f"per_group must be positive, got {per_group}")
+        if isinstance(filter, DeviceQueryFilters) or (filter is not None and len(getattr(filter, "shape", ())) == 2):
+            raise NotImplementedError("a collapsed search takes one allow-list for the batch (per-query filters: not in this build)")
+        self._ensure_built()
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        corpus = self._corpus
+        if approx and not corpus.has_int8_shadow:
+            raise ValueError("approx=True needs an index built with its int8 copy (int8_shadow=True)")
+        if filter is not None and corpus.is_bf16:
+            raise NotImplementedError("filtered search serves fp32 corpora (bf16: not in this build)")
+        out = corpus.search_collapsed(q, int(k), float(eta), float(entropy_pref), groups=self.make_groups(groups),
+                                      per_group=int(per_group), candidates=candidates, filter=self._prepared(filter),
+                                      approx=bool(approx), rescore=bool(rescore), widen=bool(widen), return_pool=True)
+        rows, scores, hits, pool = out
+        if corpus.id_offset:
+            rows = np.where(rows >= 0, rows - corpus.id_offset, rows)
+        res = (rows, scores)
+        if return_hits:
+            res += (hits,)
+        if return_pool:
+            res += (pool,)
+        return res
+
     # ---------------------------------------------------------------- range search (additive)
     def range_search(self, query: np.ndarray, threshold: float, eta: float = 0.5, entropy_pref: float = 0.0, filter=None,
                      max_results: Optional[int] = None) -> SearchResult:

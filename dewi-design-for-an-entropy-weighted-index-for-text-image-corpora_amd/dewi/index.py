@@ -5,7 +5,7 @@ the query, fills in the default ``eta`` / ``entropy_pref`` and delegates to a ba
 this build every backend choice resolves to the HIP ``ExactIndex`` (ANN graph libraries
 are out of scope), with the reference's own warning when an ANN backend was asked for.
 Additions: ``add_batch``, ``search_batch``, ``range_search``, ``range_search_batch``, ``near_duplicates``, ``duplicate_groups``,
-``dedup_filter`` and the in-place ``remove`` / ``upsert`` / ``upsert_batch`` / ``upsert_batch_columns`` / ``rows_of`` / ``reserve``.
+``dedup_filter``, ``make_groups`` / ``search_collapsed`` / ``search_collapsed_batch`` and the in-place ``remove`` / ``upsert`` / ``upsert_batch`` / ``upsert_batch_columns`` / ``rows_of`` / ``reserve``.
 """
 from __future__ import annotations
 
@@ -253,6 +253,48 @@ class DewiIndex(BaseIndex):
         n_real = (rows >= 0).sum(axis=1)           # fewer than k eligible documents: the tail is padded with id -1
         res = self._backend.results_for(np.where(rows < 0, 0, rows), scores)
         return [r[:int(m)] for r, m in zip(res, n_real)]
+
+    def make_groups(self, groups):
+        """Prepare group labels for ``search_collapsed`` / ``search_collapsed_batch`` (``ExactIndex.make_groups``)."""
+        if not self._built:
+            self.build()
+        return self._backend.make_groups(groups)
+
+    def search_collapsed(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
+                         entropy_pref: Optional[float] = None, *, groups, per_group: int = 1, candidates: Optional[int] = None,
+                         filter=None, approx: bool = False, rescore: bool = True, widen: bool = False,
+                         return_hits: bool = False):
+        """``search`` with at most ``per_group`` results from one group of ``groups`` (additive;
+        ``ExactIndex.search_collapsed``): possibly fewer than k results; with ``return_hits=True`` ``(results, hits)``."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.shape != (self.dim,):
+            raise ValueError(f"Expected query shape ({self.dim},), got {q.shape}")
+        out = self.search_collapsed_batch(q.reshape(1, -1), k, eta, entropy_pref, groups=groups, per_group=per_group,
+                                          candidates=candidates, filter=filter, approx=approx, rescore=rescore, widen=widen,
+                                          return_hits=return_hits)
+        return (out[0][0], out[1][0]) if return_hits else out[0]
+
+    def search_collapsed_batch(self, queries: np.ndarray, k: int = 10, eta: Optional[float] = None,
+                               entropy_pref: Optional[float] = None, *, groups, per_group: int = 1,
+                               candidates: Optional[int] = None, filter=None, approx: bool = False, rescore: bool = True,
+                               widen: bool = False, return_hits: bool = False):
+        """One call for B queries ([B, dim]); each result list equals ``search_collapsed`` of that row.  With
+        ``return_hits=True``: ``(results, hits)``, ``hits[j]`` the list of group sizes in the pool for query j's results."""
+        eta, entropy_pref = self._defaults(eta, entropy_pref)
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        if not self._built:
+            self.build()
+        rows, scores, hits = self._backend.search_collapsed_batch(q, k, eta, entropy_pref, groups=groups, per_group=per_group,
+                                                                  candidates=candidates, filter=filter, approx=approx,
+                                                                  rescore=rescore, widen=widen, return_hits=True)
+        n_real = (rows >= 0).sum(axis=1)           # fewer than k results: the tail is padded with id -1
+        res = self._backend.results_for(np.where(rows < 0, 0, rows), scores)
+        res = [r[:int(m)] for r, m in zip(res, n_real)]
+        if return_hits:
+            return res, [h[:int(m)].tolist() for h, m in zip(hits, n_real)]
+        return res
 
     def range_search(self, query: np.ndarray, threshold: float, eta: Optional[float] = None,
                      entropy_pref: Optional[float] = None, filter=None,

@@ -85,6 +85,8 @@ class IVFIndex(ExactIndex):
 
     ``search_diverse`` / ``search_diverse_batch`` are ``ExactIndex``'s too, in their EXACT form: the candidate pool is the
     exact cut over every row, not over the probed cells, and there is no ``nprobe`` argument.  A diverse search over an IVF
+    probe is not part of this build.  ``search_collapsed`` / ``search_collapsed_batch`` are inherited in the same EXACT form
+    (the pool is the exact cut over every row, or over every row of ``filter``; no ``nprobe``): a collapsed search over a
     probe is not part of this build.
 
     ``remove`` / ``upsert`` / ``upsert_batch`` / ``upsert_batch_columns`` maintain the cells instead of retraining: the

@@ -203,6 +203,15 @@ int dewi_knn_rerank_candidates(const void* d_E, int elem_type, int64_t n_rows, i
  * sim_transform as dewi_knn_rerank_candidates (DEWI_SIM_RAW unless n_candidates > 0).  Batches run the row kernels'
  * 4- and 8-query passes over the list — never a matrix-core pass, so nothing is refused.  elem_type 0 (fp32) only:
  * a bf16 corpus returns DEWI_ERR_UNSUPPORTED.  Asynchronous on `stream`.
+ * dewi_knn_candidates_filtered (additive): steps 1-3 of dewi_knn_rerank_filtered — one allow-list for every query, the row
+ * kernels' 1-, 4- and 8-query passes over the list, never a matrix-core pass — emitted as candidate records in exactly
+ * dewi_knn_candidates' layout and order (d_out [n_queries][n_candidates]): ids are GLOBAL rows plus id_offset, the payload
+ * pair is attached, c_local = min(n_candidates, n_allowed), padding (id -1, sim -inf) lies behind c_local — what
+ * dewi_knn_candidates_i8_filtered states for the codes.  Workspace: dewi_knn_filtered_workspace_bytes for (n_allowed, dim,
+ * n_queries, n_candidates).  1 <= n_candidates <= 2048: above that DEWI_ERR_UNSUPPORTED (the select of larger cuts has no
+ * record output); id_offset + n_rows must fit int32 (DEWI_ERR_UNSUPPORTED); fp32 corpora only.  n_allowed == 0: DEWI_OK,
+ * nothing launched, nothing written; n_allowed outside [0, n_rows]: DEWI_ERR_INVALID_ARG.  Every argument error before any
+ * device work; the workspace's contents on entry are undefined.  Asynchronous on `stream`.
  * ------------------------------------------------------------------------------------------ */
 size_t dewi_filter_bytes(int64_t n_rows, int dim, int elem_type);
 int dewi_filter_prepare(int elem_type, int64_t n_rows, int dim, const uint8_t* d_mask, void* d_filter, size_t filter_bytes,
@@ -212,6 +221,10 @@ int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int
                              const float* d_Q, int n_queries, const float* d_dewi32, const float* d_ent32, int k, int n_candidates,
                              int sim_transform, double eta, double entropy_pref, int space, int64_t* d_out_ids,
                              float* d_out_scores, void* d_workspace, size_t workspace_bytes, void* stream);
+int dewi_knn_candidates_filtered(const void* d_E, int elem_type, int64_t n_rows, int dim, const void* d_filter, int64_t n_allowed,
+                                 const float* d_Q, int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates,
+                                 int space, int64_t id_offset, dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes,
+                                 void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-query filters (additive to ABI 6): one batch in which query j has its own allow-list F_j.  Query j's ids and scores
@@ -548,6 +561,58 @@ int dewi_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows, int dim,
                         int n_candidates, int k, double eta, double entropy_pref, double mmr_lambda, double max_sim,
                         int64_t id_offset, int64_t* d_out_ids, float* d_out_scores, float* d_out_mmr, void* d_workspace,
                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Collapsed search (additive to ABI 6; the reference has no such method; search engines call it field collapsing): the k
+ * best candidates of a query with at most `per_group` of them from the same group.  A group is whatever the caller labels
+ * alike: a near-duplicate cluster, a source site, an album, an author, a crawl batch.  Integer work plus the fp32 blend.
+ *
+ * Contract per query (tests/collapse_model.py restates it in NumPy):
+ *   - Input.  `n_candidates` = c records in dewi_knn_candidates' layout and order: sorted by (ord(sim) desc, id asc), padding
+ *     at the tail (d_cand [n_queries][c]).
+ *   - Valid records.  A record is valid iff id >= 0 and id - id_offset lies in [0, n_rows).  This is dewi_diverse_rerank's
+ *     rule.  Every other record is padding, and d_labels is never indexed with it.  Candidate rank t is the position among the
+ *     valid records, t = 0 .. n_sel - 1.
+ *   - Labels.  label_t = d_labels[id_t - id_offset], where d_labels is device int32 [n_rows].  Any int32 value is a group.  A
+ *     negative label means "ungrouped": such a record is a group of its own and is never folded.
+ *   - Blend.  adj_t is the blend of step 4 of the search with DEWI_SIM_RAW.  Products are rounded once.  The ent term is added
+ *     only if entropy_pref != 0.
+ *   - Walk order.  S = (ord(adj_t) desc, t asc), with NaN counting as the largest value and -0 == +0.  This is exactly step
+ *     5's selection order.
+ *   - Keep rule.  The record at position p of S is kept iff its label is negative or fewer than `per_group` records before p
+ *     in S carry the same label.  "Before p" counts every earlier record, kept or not.  The two readings are equivalent,
+ *     because the first `per_group` members of a group in S are the ones kept.
+ *   - Selected set.  The first kk = min(k, number kept) kept records in S.
+ *   - Output.
+ *       - The selected records are written in S order, with those whose adj is NaN moved behind the numbers in their own
+ *         order.  dewi_merge_rerank and dewi_diverse_rerank emit the same way.
+ *       - d_out_ids [n_queries][k] holds the id as in the record.
+ *       - d_out_scores [n_queries][k] holds adj, with -0 written as +0.
+ *       - d_out_hits [n_queries][k], if given, holds the number of valid records of this query's pool that carry the result's
+ *         label.  It is 1 for a negative label.
+ *       - d_out_counts[q], if given, holds kk.
+ *       - Positions kk .. k-1 of ids, scores and hits are not written, as everywhere in this ABI.
+ *   - Identity 1.  If per_group >= n_sel, or all labels are negative, or all labels are distinct, then ids and scores equal
+ *     dewi_merge_rerank on (d_cand, 1, n_queries, c, c, k, ...) bit for bit, NaN records included (for records dewi_merge_rerank
+ *     takes as valid too: every id >= 0 inside the rows).
+ *   - Identity 2.  per_group = 1 with every label equal returns exactly the one best record.
+ *   - Errors, all reported before any device work.  Null d_cand, d_labels, ids or scores: DEWI_ERR_INVALID_ARG.
+ *     n_queries <= 0, n_candidates <= 0, n_rows <= 0 or per_group <= 0: DEWI_ERR_INVALID_ARG.  k > n_candidates:
+ *     DEWI_ERR_K_OUT_OF_BOUNDS.  n_candidates > DEWI_COLLAPSE_MAX_CANDIDATES: DEWI_ERR_UNSUPPORTED.  A workspace below
+ *     dewi_collapse_workspace_bytes: DEWI_ERR_WORKSPACE.  k <= 0 writes nothing and returns DEWI_OK.
+ *   - Calling.  Asynchronous on `stream`.  No allocation, no synchronisation, no atomics.  The same inputs give the same bytes.
+ *
+ * One workgroup per query keeps the pool in LDS (256 threads up to 256 records, 1024 above: at most two records per thread):
+ * up to 256 valid records a rank sort and, for the rank inside the group, a counting pass over the labels in S order; above,
+ * the bitonic network twice — for S, then for (label, position in S) keys, whose runs are the groups —; the kept records
+ * compacted by ballots.  dewi_collapse_workspace_bytes is 0 for every shape and needs no device; d_workspace may be NULL.
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_COLLAPSE_MAX_CANDIDATES 2048      /* what one workgroup sorts in LDS: launch.hpp kMaxSortCandidates */
+size_t dewi_collapse_workspace_bytes(int n_queries, int n_candidates);
+int dewi_collapse_rerank(const dewi_candidate* d_cand, int n_queries, int n_candidates, const int32_t* d_labels, int64_t n_rows,
+                         int64_t id_offset, int k, int per_group, double eta, double entropy_pref, int64_t* d_out_ids,
+                         float* d_out_scores, int32_t* d_out_hits /* may be NULL */, int32_t* d_out_counts /* may be NULL */,
+                         void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Approximate search over an INT8 copy of the corpus (additive to ABI 6; the reference has no counterpart).  One byte per
