@@ -1750,6 +1750,17 @@ int dewi_robust_fit_f32(const float* d_S, int64_t n, int64_t ld, int n_signals, 
                   "robust_fit launch");
 }
 
+int dewi_robust_fit_fast_plan(int64_t n, int n_signals, int64_t* out, int n_out) {
+  if (!out) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (n <= 0 || n_signals <= 0) return fail(DEWI_ERR_INVALID_ARG, "bad shape n=%lld n_signals=%d", static_cast<long long>(n), n_signals);
+  if (n > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n exceeds 2^32-1");
+  if (n_out < 1) return fail(DEWI_ERR_INVALID_ARG, "n_out %d: room for at least one word", n_out);
+  int64_t plan[dewi::kFitFastPlanWords];
+  dewi::robust_fit_fast_plan(n, n_signals, plan);
+  for (int i = 0; i < n_out && i < dewi::kFitFastPlanWords; ++i) out[i] = plan[i];
+  return DEWI_OK;
+}
+
 // ---- sharded robust fit: the select of dewi_robust_fit_f32 split at its histogram boundaries ----
 static int check_fit_step(int n_signals, int phase, int pass, void* d_workspace, size_t workspace_bytes) {
   if (n_signals <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_signals %d", n_signals);

@@ -486,6 +486,10 @@ size_t robust_fit_workspace_bytes(int n_signals);
 constexpr int64_t kFitFastCap = 1024 * 1024;   // keys the compact buffer of a column holds (4 MiB)
 size_t robust_fit_fast_bytes(int n_signals);
 bool robust_fit_fast_supported(int64_t n, int n_signals);
+size_t robust_fit_fast_offset(int n_signals);                 // robust_stats.hip: where that region starts in the workspace
+int64_t robust_fit_fast_slices(int64_t n, int n_signals);     // workgroups per column of a phase (grid.x)
+constexpr int kFitFastPlanWords = 11;                         // dewi_robust_fit_fast_plan (include/dewi_hip.h)
+void robust_fit_fast_plan(int64_t n, int n_signals, int64_t (&out)[kFitFastPlanWords]);
 hipError_t launch_robust_fit_fast(const float* d_S, int64_t n, int64_t ld, int n_signals, float* d_med, float* d_mad,
                                   void* d_fast_ws, hipStream_t stream);
 void robust_fit_region(int n_signals, int phase, int pass, int which, size_t* offset_bytes, size_t* count_u32);

@@ -48,7 +48,7 @@ constexpr int kPer = 2048 / kT;        // histogram bins a thread owns in a pick
 constexpr int kCopies = kT >= 1024 ? 4 : 2;   // copies 0 and 1 double as the two refinement histograms
 constexpr int64_t kSmallN = 64 * 1024; // at or below: one workgroup per column selects exactly, no bracket
 
-struct Counters {                      // per (phase, column); zeroed by the launcher
+struct Counters {                      // per (phase, column); zeroed by the launcher; documented in include/dewi_hip.h
   uint32_t lt, eqlo, eqhi, nan, overflow, ticket, fallback, pad;
   uint32_t bucket[kBuckets];           // keys collected per bucket
   uint32_t stamp[8];                   // diagnostics (DEWI_FIT_STAMPS): 10 ns ticks of the last workgroup's steps
@@ -630,6 +630,29 @@ bool robust_fit_fast_supported(int64_t n, int n_signals) {
   return n_signals >= 1 && n_signals <= 1024 && 2 * per_bucket <= kFitFastCap / fastfit::kBuckets;
 }
 
+int64_t robust_fit_fast_slices(int64_t n, int n_signals) {
+  if (n <= fastfit::kSmallN) return 1;
+  int64_t slices = (256 * (1024 / fastfit::kT)) / n_signals;    // 1024 threads per CU over all columns
+  const int64_t by_size = n / 4096;                             // at least 4 K elements per workgroup
+  if (slices > by_size) slices = by_size;
+  return slices < 1 ? 1 : slices;
+}
+
+// What a test needs to read the Counters of a call and to model the kernel's bracket (dewi_robust_fit_fast_plan).
+void robust_fit_fast_plan(int64_t n, int n_signals, int64_t (&out)[kFitFastPlanWords]) {
+  out[0] = robust_fit_fast_supported(n, n_signals) ? 1 : 0;
+  out[1] = robust_fit_fast_slices(n, n_signals);
+  out[2] = static_cast<int64_t>(robust_fit_fast_offset(n_signals));   // the Counters lead the two-launch path's region
+  out[3] = static_cast<int64_t>(sizeof(fastfit::Counters));
+  out[4] = fastfit::kSmallN;
+  out[5] = fastfit::kSample;
+  out[6] = fastfit::kDelta;
+  out[7] = fastfit::kBuckets;
+  out[8] = fastfit::kBucketLds;
+  out[9] = kFitFastCap / fastfit::kBuckets;
+  out[10] = fastfit::kRegKeys * fastfit::kT;
+}
+
 hipError_t launch_robust_fit_fast(const float* d_S, int64_t n, int64_t ld, int n_signals, float* d_med, float* d_mad,
                                   void* d_fast_ws, hipStream_t stream) {
   char* p = static_cast<char*>(d_fast_ws);
@@ -637,13 +660,7 @@ hipError_t launch_robust_fit_fast(const float* d_S, int64_t n, int64_t ld, int n
   uint32_t* compact = reinterpret_cast<uint32_t*>(p + fast_counters_bytes(n_signals));
   hipError_t e = hipMemsetAsync(ctr, 0, sizeof(fastfit::Counters) * 2 * n_signals, stream);
   if (e != hipSuccess) return e;
-  int64_t slices = 1;
-  if (n > fastfit::kSmallN) {
-    slices = (256 * (1024 / fastfit::kT)) / n_signals;    // 1024 threads per CU over all columns
-    const int64_t by_size = n / 4096;                     // at least 4 K elements per workgroup
-    if (slices > by_size) slices = by_size;
-    if (slices < 1) slices = 1;
-  }
+  const int64_t slices = robust_fit_fast_slices(n, n_signals);
   const int64_t bucket_cap = kFitFastCap / fastfit::kBuckets;
   const dim3 grid(static_cast<unsigned>(slices), static_cast<unsigned>(n_signals));
   hipLaunchKernelGGL(fastfit::fit_fast_kernel<false>, grid, dim3(fastfit::kT), 0, stream, d_S, n, ld,

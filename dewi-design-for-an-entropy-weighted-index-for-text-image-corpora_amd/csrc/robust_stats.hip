@@ -59,6 +59,8 @@ size_t robust_fit_workspace_bytes(int n_signals) {
   return hist_path_bytes(n_signals) + robust_fit_fast_bytes(n_signals);
 }
 
+size_t robust_fit_fast_offset(int n_signals) { return hist_path_bytes(n_signals); }
+
 template <int PASS>
 __device__ __forceinline__ bool digit_of(uint32_t key, uint32_t prefix, uint32_t& digit) {
   if constexpr (PASS == 0) {
@@ -291,7 +293,7 @@ hipError_t launch_fit_finish(int64_t n_total, int n_signals, int phase, void* d_
 hipError_t launch_robust_fit(const float* d_S, int64_t n, int64_t ld, int n_signals, float* d_med, float* d_mad,
                              void* d_ws, hipStream_t stream) {
   if (robust_fit_fast_supported(n, n_signals))   // one device, columns the compact buffers hold: two launches
-    return launch_robust_fit_fast(d_S, n, ld, n_signals, d_med, d_mad, static_cast<char*>(d_ws) + hist_path_bytes(n_signals),
+    return launch_robust_fit_fast(d_S, n, ld, n_signals, d_med, d_mad, static_cast<char*>(d_ws) + robust_fit_fast_offset(n_signals),
                                   stream);
   hipError_t e = launch_fit_begin(d_ws, n_signals, stream);
   if (e != hipSuccess) return e;

@@ -69,7 +69,11 @@ EXPORTED_SYMBOLS = (
     "dewi_rescore_candidates_f32",
     "dewi_knn_i8_filtered_workspace_bytes", "dewi_knn_candidates_i8_filtered", "dewi_knn_candidates_i8_query_filtered",
     "dewi_collapse_workspace_bytes", "dewi_collapse_rerank", "dewi_knn_candidates_filtered",
+    "dewi_robust_fit_fast_plan",
 )
+#: the words dewi_robust_fit_fast_plan fills, in order (include/dewi_hip.h)
+FIT_FAST_PLAN_WORDS = ("supported", "slices", "counters_offset", "counters_bytes", "small_n", "sample", "delta", "buckets",
+                       "bucket_lds", "bucket_cap", "reg_keys")
 
 
 class NativeLibraryError(RuntimeError):
@@ -245,6 +249,8 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_collapse_rerank.argtypes = [vp, i32, i32, vp, i64, i64, i32, i32, f64, f64, vp, vp, vp, vp, vp, sz, vp]
     lib.dewi_knn_candidates_filtered.restype = i32
     lib.dewi_knn_candidates_filtered.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, vp, vp, i32, i32, i64, vp, vp, sz, vp]
+    lib.dewi_robust_fit_fast_plan.restype = i32
+    lib.dewi_robust_fit_fast_plan.argtypes = [i64, i32, c.POINTER(i64), i32]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:
@@ -295,6 +301,13 @@ def check(rc: int) -> None:
     if rc == ERR_UNSUPPORTED:
         raise NotImplementedError(msg)
     raise NativeLibraryError(f"dewi_hip error {rc}: {msg}")
+
+
+def fit_fast_plan(n: int, n_signals: int) -> dict:
+    """``dewi_robust_fit_fast_plan`` as a dict keyed by ``FIT_FAST_PLAN_WORDS`` (host only: needs no GPU)."""
+    out = (ctypes.c_int64 * len(FIT_FAST_PLAN_WORDS))()
+    check(load_library(require_gpu=False).dewi_robust_fit_fast_plan(n, n_signals, out, len(out)))
+    return dict(zip(FIT_FAST_PLAN_WORDS, (int(v) for v in out)))
 
 
 def is_device_tensor(x) -> bool:

@@ -752,6 +752,27 @@ size_t dewi_robust_fit_workspace_bytes(int n_signals);
 int dewi_robust_fit_f32(const float* d_S, int64_t n, int64_t ld, int n_signals, float* d_med, float* d_mad,
                         void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Diagnostics of the two-launch path of dewi_robust_fit_f32 (csrc/robust_fit_fast.hip), for tests and probes: host only,
+ * launches nothing.  Fills the first min(n_out, 11) int64 words of `out`, in this order:
+ *    0  1 if dewi_robust_fit_f32 serves (n, n_signals) through the two-launch path, else 0 (the histogram path)
+ *    1  slices: workgroups per column and phase (1 while n <= word 4: one workgroup selects over the whole column)
+ *    2  byte offset of the counters inside a workspace of dewi_robust_fit_workspace_bytes(n_signals)
+ *    3  bytes of one counter record (128)
+ *    4  kSmallN: columns up to this length take no bracket
+ *    5  kSample: sampled keys per column      6  kDelta: the bracket's half-width in sample ranks
+ *    7  kBuckets: buckets of the bracket      8  kBucketLds: keys per bucket a workgroup stages
+ *    9  keys a column's bucket buffer holds  10  keys of a bucket the last workgroup selects among in registers
+ * The counters are records [2 phases: median, MAD][n_signals] of 32 uint32 words, as the last call left them:
+ *    lt eqlo eqhi nan   keys below the bracket's lower key, equal to it, equal to its upper key; NaNs
+ *    overflow           (workgroup, bucket) pairs whose keys did not fit the staging or the bucket buffer
+ *    ticket             workgroups that have published (== slices after a call; 0 while n <= kSmallN)
+ *    fallback           1: the bracket missed or a buffer overflowed, the whole column was selected over instead
+ *    pad
+ *    bucket[16]         keys collected per bucket (after an overflow: of the workgroups that published theirs)
+ *    stamp[8]           timing diagnostics, zero in a normal build
+ * n <= 0 or n_signals <= 0, a null `out`, n_out < 1: DEWI_ERR_INVALID_ARG; n above 2^32-1: DEWI_ERR_UNSUPPORTED. */
+int dewi_robust_fit_fast_plan(int64_t n, int n_signals, int64_t* out, int n_out);
+
 /* ------------------------------------------------------------------------------------------
  * A6 over doc-id shards ("fit_stats shards too").  The same exact select, split at
  * its histogram boundaries so that the rows of a column may live on several GPUs:

@@ -1,5 +1,5 @@
 """Times dewi_robust_fit_f32 at 7 x 1M and reports which columns took the whole-column fallback
-(Counters.pad of csrc/robust_fit_fast.hip)."""
+(Counters.fallback of csrc/robust_fit_fast.hip; the counters lie where dewi_robust_fit_fast_plan says)."""
 import sys
 from pathlib import Path
 import numpy as np
@@ -24,9 +24,9 @@ for a, b in ev:
     a.record(); fit(); b.record()
 torch.cuda.synchronize()
 print("fit ms", np.mean([a.elapsed_time(b) for a, b in ev]))
-fast_bytes = ((128 * 2 * ns + 255) // 256) * 256 + 4 * ns * 1024 * 1024 + 256
-hist_bytes = wsb - fast_bytes
-ctr = ws[hist_bytes: hist_bytes + 128 * 2 * ns].view(torch.int32).view(2, ns, 32).cpu().numpy()
+plan = nat.fit_fast_plan(n, ns)
+off, rec = plan["counters_offset"], plan["counters_bytes"]
+ctr = ws[off: off + rec * 2 * ns].view(torch.int32).view(2, ns, rec // 4).cpu().numpy()
 print("counters [phase][col]: lt eqlo eqhi nan overflow ticket fallback pad | 16 bucket counts | stamps (10 ns): bracket stream publish tail")
 np.set_printoptions(linewidth=250)
 print(ctr[:, :, :8]); print(ctr[:, :, 8:24].sum(axis=2)); print(ctr[:, :, 24:28])

@@ -333,6 +333,14 @@ CASES = [
     ("fit finish", lambda lib: lib.dewi_robust_fit_finish(10, 7, 0, P, FIT, None, None), INVALID, "bad arguments"),
     ("fit finish order: the workspace before the output", lambda lib: lib.dewi_robust_fit_finish(10, 7, 0, None, 1 << 20, None, None),
      WORKSPACE, "workspace 1048576 B < required 30051072 B"),
+    ("fit plan null", lambda lib: lib.dewi_robust_fit_fast_plan(10, 7, None, 11), INVALID, "null pointer"),
+    ("fit plan shape", lambda lib: lib.dewi_robust_fit_fast_plan(0, 7, CNT, 4), INVALID, "bad shape n=0 n_signals=7"),
+    ("fit plan n_signals", lambda lib: lib.dewi_robust_fit_fast_plan(10, 0, CNT, 4), INVALID, "bad shape n=10 n_signals=0"),
+    ("fit plan rows", lambda lib: lib.dewi_robust_fit_fast_plan(BIG, 7, CNT, 4), UNSUPPORTED, "n exceeds 2^32-1"),
+    ("fit plan n_out", lambda lib: lib.dewi_robust_fit_fast_plan(10, 7, CNT, 0), INVALID, "n_out 0: room for at least one word"),
+    ("fit plan ok", lambda lib: lib.dewi_robust_fit_fast_plan(10, 7, CNT, 4), OK, None),
+    ("fit plan order: the shape before n_out", lambda lib: lib.dewi_robust_fit_fast_plan(-1, 7, CNT, 0), INVALID,
+     "bad shape n=-1 n_signals=7"),
     # ---- score
     ("score null stats", score(med=None), INVALID, "null pointer"),
     ("score null signals", score(S=None), INVALID, "null pointer"),
