@@ -1528,6 +1528,59 @@ int dewi_collapse_rerank(const dewi_candidate* d_cand, int n_queries, int n_cand
                   "collapse_rerank launch");
 }
 
+// ---- subset selection over the whole corpus (additive to ABI 6; select_subset.hip) --------------------------------------------
+// the checks the three calls share, in one order: shape, 2^31, elem_type, the workspace
+static int check_select_state(int64_t n_rows, int dim, int elem_type, const void* d_ws, size_t ws_bytes) {
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
+  if (n_rows > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld: a subset selection takes fewer than 2^31 rows", static_cast<long long>(n_rows));
+  if (int rc = check_elem_type(elem_type)) return rc;
+  return check_workspace(d_ws, ws_bytes, dewi::subset_layout(n_rows).total);
+}
+
+size_t dewi_select_workspace_bytes(int64_t n_rows, int dim, int elem_type) {
+  if (n_rows <= 0 || n_rows > 0x7FFFFFFFll || dim <= 0 || (elem_type != 0 && elem_type != 1)) return 0;
+  return dewi::subset_layout(n_rows).total;
+}
+
+int dewi_select_begin(int64_t n_rows, int dim, int elem_type, const uint8_t* d_mask, void* d_workspace, size_t workspace_bytes,
+                      void* stream) {
+  if (int rc = check_select_state(n_rows, dim, elem_type, d_workspace, workspace_bytes)) return rc;
+  return launched(dewi::launch_subset_begin(dewi::subset_layout(n_rows), n_rows, d_mask, static_cast<char*>(d_workspace),
+                                            static_cast<hipStream_t>(stream)),
+                  "select_begin launch");
+}
+
+int dewi_select_seed(const void* d_E, int elem_type, int64_t n_rows, int dim, const int64_t* d_seed_rows, int n_seeds,
+                     double max_sim, void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (!d_E || (!d_seed_rows && n_seeds > 0)) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (n_seeds < 0) return fail(DEWI_ERR_INVALID_ARG, "n_seeds must not be negative (got %d)", n_seeds);
+  if (max_sim != max_sim) return fail(DEWI_ERR_INVALID_ARG, "max_sim is NaN");
+  if (int rc = check_select_state(n_rows, dim, elem_type, d_workspace, workspace_bytes)) return rc;
+  if (n_seeds == 0) return DEWI_OK;
+  return launched(dewi::launch_subset_seed(dewi::subset_layout(n_rows), d_E, elem_type, n_rows, dim, d_seed_rows, n_seeds,
+                                           static_cast<float>(max_sim), static_cast<char*>(d_workspace),
+                                           static_cast<hipStream_t>(stream)),
+                  "select_seed launch");
+}
+
+int dewi_select_run(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel, int64_t budget,
+                    double mmr_lambda, double max_sim, int64_t id_offset, int64_t* d_out_rows, float* d_out_gain,
+                    int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner, void* d_workspace, size_t workspace_bytes,
+                    void* stream) {
+  if (!d_E || !d_rel || !d_out_rows || !d_out_gain || !d_n_picked) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (!(mmr_lambda >= 0.0 && mmr_lambda <= 1.0)) return fail(DEWI_ERR_INVALID_ARG, "mmr_lambda %g outside [0, 1]", mmr_lambda);
+  if (max_sim != max_sim) return fail(DEWI_ERR_INVALID_ARG, "max_sim is NaN");
+  if (int rc = check_select_state(n_rows, dim, elem_type, d_workspace, workspace_bytes)) return rc;
+  if (budget <= 0) return DEWI_OK;
+  return launched(dewi::launch_subset_run(dewi::subset_layout(n_rows), d_E, elem_type, n_rows, dim, d_rel,
+                                          budget < n_rows ? budget : n_rows, static_cast<float>(mmr_lambda),
+                                          static_cast<float>(1.0 - mmr_lambda), static_cast<float>(max_sim), id_offset, d_out_rows,
+                                          d_out_gain, d_n_picked, d_out_pen, d_out_owner, static_cast<char*>(d_workspace),
+                                          static_cast<hipStream_t>(stream)),
+                  "select_run launch");
+}
+
 // ---- approximate search over an int8 copy of the corpus (additive to ABI 6; knn_scan_i8.hip) ---------------------------------
 // the shape checks the int8 entry points share, in one order: rows, 2^32, dim, the unit (16 codes; the re-scoring: 4 floats)
 static int check_i8_shape(int64_t n_rows, int dim, int unit) {

@@ -430,6 +430,29 @@ hipError_t launch_diverse_rerank(const void* d_E, int elem_type, int64_t n_rows,
                                  float max_sim, int64_t id_offset, int64_t* d_out_ids, float* d_out_scores, float* d_out_mmr,
                                  hipStream_t stream);
 
+// ---- select_subset.hip: greedy subset selection over the whole corpus, one launch per pick (include/dewi_hip.h) ----
+constexpr int kSubsetGrid = 256;       // most workgroups of a pass = keys per ping-pong array: one per compute unit of an MI355X,
+                                       // whatever the device (the workspace layout needs no device)
+constexpr int kSubsetThreads = 1024;   // 16 waves per workgroup
+struct SubsetLayout {                  // byte offsets inside the caller's workspace
+  size_t keys;                         // uint64 [2][kSubsetGrid]: the workgroups' best keys, ping-pong by launch parity
+  size_t header;                       // the pick counter
+  size_t pen;                          // float [n_rows]: largest similarity to the selection (NaN: none yet)
+  size_t owner;                        // int32 [n_rows]: the selected row that gave it (-1: none)
+  size_t struck;                       // uint8 [n_rows]: 1 = struck out for ever
+  size_t total;
+};
+SubsetLayout subset_layout(int64_t n_rows);
+hipError_t launch_subset_begin(const SubsetLayout& L, int64_t n_rows, const uint8_t* d_mask, char* ws, hipStream_t stream);
+// d_seed_rows: local rows; one pass per seed
+hipError_t launch_subset_seed(const SubsetLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                              const int64_t* d_seed_rows, int n_seeds, float max_sim, char* ws, hipStream_t stream);
+// n_launches pick launches behind one pass that forms the keys of the state as it stands; d_out_pen / d_out_owner may be NULL
+hipError_t launch_subset_run(const SubsetLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel,
+                             int64_t n_launches, float lam, float one_minus_lam, float max_sim, int64_t id_offset,
+                             int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner,
+                             char* ws, hipStream_t stream);
+
 // ---- collapse.hip: at most per_group results per label, one workgroup per query (no workspace)
 constexpr int kCollapseMaxCandidates = DEWI_COLLAPSE_MAX_CANDIDATES;
 static_assert(kCollapseMaxCandidates == kMaxSortCandidates, "a collapsed pool is what one workgroup sorts in LDS");

@@ -1,0 +1,461 @@
+// Subset selection for gfx950 (MI355X): greedy DEWI-weighted coverage of the WHOLE corpus.
+//
+// The contract is the comment of dewi_select_run in include/dewi_hip.h (tests/select_model.py restates it in NumPy): greedy
+// maximal marginal relevance with the pool = all n_rows rows and the relevance = an fp32 column.  One launch per pick;
+// everything workgroups tell each other crosses a kernel boundary (no in-launch flag, ticket or fence, no dependence on
+// the dispatch order):
+//
+//   launch j   1. every workgroup reduces the G keys (G: the grid, up to kSubsetGrid = 256) the previous launch left in key
+//                 array j & 1: the pick s.
+//                 An empty best key: the workgroup stores an empty key into ITS slot of the other array and returns, so
+//                 every launch still queued behind finds nothing to pick either.  Workgroup 0 writes the outputs.
+//              2. every wave loads row s into registers, unit -> lane as for the corpus rows below.
+//              3. a wave takes R consecutive rows per step.  The step's struck-out bytes are ONE load (lane r holds row
+//                 r's), fetched one step ahead; a ballot makes the live mask wave-uniform and only the live rows are
+//                 loaded: with max_sim set, later passes read less than the corpus.  pen and rel of the step are one load
+//                 each, behind the row loads, handed out by readlane.  For a live row: g, pen / owner (stored where they
+//                 change), the strike-out by max_sim, m, the key.
+//              4. the keys of a wave's rows are wave-uniform (g comes off the DPP crossbar into every lane): a running
+//                 maximum per wave, workgroup max in LDS, thread 0 stores the key into array (j + 1) & 1.
+//
+// g(i, s) has ONE summation order whatever the load path, n_rows, the budget, the step, the grid or the alignment of d_E:
+//   - the row is cut into units of 16 bytes' worth of elements (4 fp32 / 8 bf16; the last unit of a row that is not whole
+//     units is filled up with zeros);
+//   - unit u belongs to lane u % 64; a lane walks its units in ascending order and, inside a unit, the elements in ascending
+//     order, with  acc = fma(a_i, b_i, acc)  from acc = +0 (bf16: widened to fp32, the product is exact);
+//   - the 64 partial sums are added as a balanced pairwise tree: lanes 2p and 2p + 1, then neighbouring pairs, ... (the DPP
+//     sequence of wave_sum_f32; fp32 addition commutes, so the tree is the whole definition).
+// Loads: 16-byte nontemporal loads where rows are whole units and d_E is 16-byte aligned, element loads otherwise; nothing
+// outside the rows is touched.  Rows of up to 512 units keep the picked row in registers (UPL units per lane); wider rows
+// re-read it from memory (it stays in the caches) one unit at a time.
+//
+// Roofline: HBM.  Algorithmic bytes per pick = live rows * (row bytes + 1 B struck-out byte + 4 B rel + 4 B pen read, + 4 B pen
+// and 4 B owner written where they change).  Measured: DESIGN.md 4.1u, profiles/r17/select/.
+#include <stdlib.h>
+
+#include "scan_common.hpp"
+
+namespace dewi {
+
+namespace {
+
+constexpr int kSubWaves = kSubsetThreads / kWave;
+
+struct SubsetHeader {
+  int64_t n_picked;   // picks written so far (every run of the state continues here)
+};
+
+// m and the key of a row that is not struck out; *strike: pen has reached max_sim (the caller strikes the row out).
+__device__ __forceinline__ uint64_t subset_key(float pen, float rel, uint32_t row, float lam, float one_minus_lam, float max_sim,
+                                               bool cut_on, bool* strike) {
+  const bool has_pen = pen == pen;
+  *strike = cut_on && has_pen && pen >= max_sim;
+  if (*strike || rel != rel) return kKeyEmpty;
+  float m = __fmul_rn(lam, rel);
+  if (has_pen) m = __fsub_rn(m, __fmul_rn(one_minus_lam, pen));
+  return make_key(m, row);
+}
+
+// the largest key of the workgroup, in every thread (one barrier in front: `slots` may still be read from the last use)
+__device__ __forceinline__ uint64_t block_max_key(uint64_t key, uint64_t (&slots)[kSubWaves]) {
+  const int tid = static_cast<int>(threadIdx.x);
+  const uint64_t w = wave_max_u64(key);
+  __syncthreads();
+  if ((tid & (kWave - 1)) == 0) slots[tid / kWave] = w;
+  __syncthreads();
+  uint64_t best = kKeyEmpty;
+#pragma unroll
+  for (int i = 0; i < kSubWaves; ++i) best = slots[i] > best ? slots[i] : best;
+  return best;
+}
+
+// ---- begin: every region of the state made defined
+__global__ void __launch_bounds__(kSubsetThreads) subset_begin_kernel(int64_t n_rows, const uint8_t* __restrict__ mask,
+                                                                      uint64_t* __restrict__ keys, SubsetHeader* __restrict__ hdr,
+                                                                      float* __restrict__ pen, int32_t* __restrict__ owner,
+                                                                      uint8_t* __restrict__ struck) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kSubsetThreads + threadIdx.x;
+  const int64_t nt = static_cast<int64_t>(gridDim.x) * kSubsetThreads;
+  if (t < 2 * kSubsetGrid) keys[t] = kKeyEmpty;
+  if (t == 0) hdr->n_picked = 0;
+  for (int64_t i = t; i < n_rows; i += nt) {
+    pen[i] = __builtin_nanf("");
+    owner[i] = -1;
+    struck[i] = mask && mask[i] == 0 ? 1 : 0;
+  }
+}
+
+// ---- the keys of the state as it stands (the first launch of a run: no pick is applied, no row is read)
+__global__ void __launch_bounds__(kSubsetThreads) subset_keys_kernel(int64_t n_rows, const float* __restrict__ rel, float lam,
+                                                                     float one_minus_lam, float max_sim,
+                                                                     const float* __restrict__ pen, uint8_t* __restrict__ struck,
+                                                                     uint64_t* __restrict__ keys_out,
+                                                                     const SubsetHeader* __restrict__ hdr,
+                                                                     int64_t* __restrict__ n_picked_out) {
+  __shared__ uint64_t slots[kSubWaves];
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kSubsetThreads + threadIdx.x;
+  const int64_t nt = static_cast<int64_t>(gridDim.x) * kSubsetThreads;
+  const bool cut_on = max_sim != __builtin_inff();
+  uint64_t best = kKeyEmpty;
+  for (int64_t i = t; i < n_rows; i += nt) {
+    if (struck[i]) continue;
+    bool strike;
+    const uint64_t key = subset_key(pen[i], rel[i], static_cast<uint32_t>(i), lam, one_minus_lam, max_sim, cut_on, &strike);
+    if (strike) struck[i] = 1;
+    best = key > best ? key : best;
+  }
+  best = block_max_key(best, slots);
+  if (threadIdx.x == 0) {
+    keys_out[blockIdx.x] = best;
+    if (blockIdx.x == 0) *n_picked_out = hdr->n_picked;
+  }
+}
+
+// ---- the state's pen / owner columns for the caller (either may be NULL)
+__global__ void __launch_bounds__(kSubsetThreads) subset_export_kernel(int64_t n_rows, const float* __restrict__ pen,
+                                                                       const int32_t* __restrict__ owner, int64_t id_offset,
+                                                                       float* __restrict__ out_pen, int64_t* __restrict__ out_owner) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kSubsetThreads + threadIdx.x;
+  const int64_t nt = static_cast<int64_t>(gridDim.x) * kSubsetThreads;
+  for (int64_t i = t; i < n_rows; i += nt) {
+    if (out_pen) out_pen[i] = pen[i];
+    if (out_owner) out_owner[i] = owner[i] < 0 ? -1 : static_cast<int64_t>(owner[i]) + id_offset;
+  }
+}
+
+// ---- one unit of a row -------------------------------------------------------------------------
+template <int ELEM>
+struct SubElem;
+template <>
+struct SubElem<0> {
+  static constexpr int kCols = 4, kBytes = 4;
+};
+template <>
+struct SubElem<1> {
+  static constexpr int kCols = 8, kBytes = 2;
+};
+
+// unit `unit` of the row at `row` (its first byte); VEC: whole units, 16-byte aligned; otherwise element loads of the columns
+// below `dim`, zeros behind them
+template <int ELEM, bool VEC, bool NT>
+__device__ __forceinline__ u32x4 subset_load_unit(const char* row, int unit, int dim) {
+  if constexpr (VEC) {
+    return load_u4<NT>(reinterpret_cast<const u32x4*>(row) + unit);
+  } else if constexpr (ELEM == 0) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(row);
+    uint32_t w[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w[e] = unit * 4 + e < dim ? p[unit * 4 + e] : 0u;
+    return u32x4{w[0], w[1], w[2], w[3]};
+  } else {
+    const uint16_t* p = reinterpret_cast<const uint16_t*>(row);
+    uint32_t w[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const uint32_t lo = unit * 8 + 2 * e < dim ? p[unit * 8 + 2 * e] : 0u;
+      const uint32_t hi = unit * 8 + 2 * e + 1 < dim ? p[unit * 8 + 2 * e + 1] : 0u;
+      w[e] = lo | (hi << 16);
+    }
+    return u32x4{w[0], w[1], w[2], w[3]};
+  }
+}
+
+// the picked row's values that face one unit
+template <int ELEM>
+struct SubFrag {
+  float f[SubElem<ELEM>::kCols];
+  __device__ __forceinline__ void set(u32x4 v) {
+    if constexpr (ELEM == 0) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) f[e] = __uint_as_float(v[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint32_t w = v[e];
+        f[2 * e] = __uint_as_float(w << 16);
+        f[2 * e + 1] = __uint_as_float(w & 0xFFFF0000u);
+      }
+    }
+  }
+  __device__ __forceinline__ float dot(u32x4 v, float acc) const {
+    SubFrag<ELEM> o;
+    o.set(v);
+#pragma unroll
+    for (int e = 0; e < SubElem<ELEM>::kCols; ++e) acc = __builtin_fmaf(o.f[e], f[e], acc);
+    return acc;
+  }
+};
+
+// rows a wave loads before it reduces: about 12 KiB in flight per wave, 16 waves per workgroup (what the registers of a
+// 1024-thread workgroup allow next to the picked row: 128 per lane)
+constexpr int subset_rows(int upl) { return upl == 1 ? 12 : (upl == 2 ? 6 : (upl == 3 ? 4 : (upl == 4 ? 3 : (upl == 6 ? 2 : 1)))); }
+// workgroups of every pass of a state: one per compute unit of an MI355X, but never more waves than give each at least four
+// steps of work (a small corpus still makes every wave loop); a function of the shape alone, the same for every call
+int subset_grid(int64_t n_rows, int dim, int elem_type) {
+  const int cols = elem_type == 0 ? 4 : 8;
+  const int per_lane = ((dim + cols - 1) / cols + kWave - 1) / kWave;
+  const int upl = per_lane <= 4 ? per_lane : (per_lane <= 6 ? 6 : (per_lane <= 8 ? 8 : 0));
+  const int64_t groups = (n_rows + subset_rows(upl) - 1) / subset_rows(upl);
+  const int64_t blocks = (groups + 4 * kSubWaves - 1) / (4 * kSubWaves);
+  return static_cast<int>(blocks < 1 ? 1 : (blocks > kSubsetGrid ? kSubsetGrid : blocks));
+}
+
+// UPL: 16-byte units per lane held in registers (rows of up to 64 * UPL units); 0: any width, the picked row re-read.
+// d_seeds != NULL: the pick is d_seeds[seed_idx] (a local row; outside [0, n_rows): nothing happens); no keys, no outputs.
+template <int ELEM, bool VEC, int UPL>
+__global__ void __launch_bounds__(kSubsetThreads) subset_apply_kernel(
+    const char* __restrict__ E, int64_t n_rows, int dim, const float* __restrict__ rel, float lam, float one_minus_lam,
+    float max_sim, int64_t id_offset, const uint64_t* __restrict__ keys_in, uint64_t* __restrict__ keys_out,
+    SubsetHeader* __restrict__ hdr, float* __restrict__ pen, int32_t* __restrict__ owner, uint8_t* __restrict__ struck,
+    int64_t* __restrict__ out_rows, float* __restrict__ out_gain, int64_t* __restrict__ n_picked_out,
+    const int64_t* __restrict__ d_seeds, int seed_idx) {
+  constexpr int kCols = SubElem<ELEM>::kCols;
+  constexpr int R = subset_rows(UPL);
+  constexpr int UU = UPL > 0 ? UPL : 1;
+  __shared__ uint64_t slots[kSubWaves];
+  const int tid = static_cast<int>(threadIdx.x);
+  const int lane = tid & (kWave - 1);
+  const bool seeding = d_seeds != nullptr;
+  const bool cut_on = max_sim != __builtin_inff();
+
+  // ---- 1. the pick
+  int64_t s;
+  if (seeding) {
+    s = d_seeds[seed_idx];
+    if (s < 0 || s >= n_rows) return;
+  } else {
+    const uint64_t best = block_max_key(tid < static_cast<int>(gridDim.x) ? keys_in[tid] : kKeyEmpty, slots);   // (gridDim.x <= kSubsetGrid <= threads)
+    if (best == kKeyEmpty) {                       // nothing eligible: the launches behind this one find the same
+      if (tid == 0) keys_out[blockIdx.x] = kKeyEmpty;
+      return;
+    }
+    s = static_cast<int64_t>(key_row(best));
+    if (blockIdx.x == 0 && tid == 0) {
+      const int64_t at = hdr->n_picked;
+      out_rows[at] = s + id_offset;
+      out_gain[at] = key_score(best);              // m as it stood at the pick (-0 as +0)
+      hdr->n_picked = at + 1;
+      *n_picked_out = at + 1;
+    }
+  }
+  // row s is struck out for ever; the wave that owns it skips it by its number, so this store races with nobody's decision
+  if (blockIdx.x == 0 && tid == 0) struck[s] = 1;
+
+  // ---- 2. the picked row
+  const int units = (dim + kCols - 1) / kCols;
+  const int64_t row_bytes = static_cast<int64_t>(dim) * SubElem<ELEM>::kBytes;
+  const char* srow = E + s * row_bytes;
+  [[maybe_unused]] bool act[UU];
+  [[maybe_unused]] SubFrag<ELEM> qf[UU];
+  if constexpr (UPL > 0) {
+#pragma unroll
+    for (int u = 0; u < UPL; ++u) {
+      act[u] = lane + 64 * u < units;
+      u32x4 v = u32x4{0u, 0u, 0u, 0u};
+      if (act[u]) v = subset_load_unit<ELEM, VEC, false>(srow, lane + 64 * u, dim);
+      qf[u].set(v);
+    }
+  }
+
+  // ---- 3. the scan
+  const int wave_in_block = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t gwave = static_cast<int64_t>(blockIdx.x) * kSubWaves + wave_in_block;
+  const int64_t n_waves = static_cast<int64_t>(gridDim.x) * kSubWaves;
+  const int64_t n_groups = (n_rows + R - 1) / R;
+  // A step's state travels in ONE load per column: lane r holds what belongs to row g * R + r.
+  // bit r: that row exists, is not the pick and is not struck out (wave-uniform: a ballot)
+  auto live_of = [&](int64_t g) -> uint32_t {
+    const int64_t row = g * R + lane;
+    bool ok = false;
+    if (g < n_groups && lane < R && row < n_rows && row != s) ok = struck[row] == 0;
+    return static_cast<uint32_t>(__ballot(ok));
+  };
+  uint64_t best = kKeyEmpty;
+  uint32_t live = live_of(gwave);
+  for (int64_t g = gwave; g < n_groups; g += n_waves) {
+    [[maybe_unused]] u32x4 v[R][UU];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if ((live >> r) & 1u) {
+        const int64_t row = g * R + r;
+        if constexpr (UPL > 0) {
+          const char* p = E + row * row_bytes;
+#pragma unroll
+          for (int u = 0; u < UPL; ++u) {
+            v[r][u] = u32x4{0u, 0u, 0u, 0u};
+            if (act[u]) v[r][u] = subset_load_unit<ELEM, VEC, true>(p, lane + 64 * u, dim);
+          }
+        }
+      }
+    }
+    float pen_v = 0.f, rel_v = 0.f;                     // behind the rows: the rows' requests go out first
+    if (lane < R && ((live >> lane) & 1u)) {
+      pen_v = pen[g * R + lane];
+      if (!seeding) rel_v = rel[g * R + lane];
+    }
+    const uint32_t live_next = live_of(g + n_waves);   // the next step's struck-out bytes travel with this step's rows
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if ((live >> r) & 1u) {
+        const int64_t row = g * R + r;
+        float acc = 0.f;
+        if constexpr (UPL > 0) {
+#pragma unroll
+          for (int u = 0; u < UPL; ++u)
+            if (act[u]) acc = qf[u].dot(v[r][u], acc);
+        } else {
+          const char* p = E + row * row_bytes;
+          for (int u = lane; u < units; u += kWave) {
+            SubFrag<ELEM> q;
+            q.set(subset_load_unit<ELEM, VEC, false>(srow, u, dim));
+            acc = q.dot(subset_load_unit<ELEM, VEC, true>(p, u, dim), acc);
+          }
+        }
+        const float gval = wave_sum_f32(acc);
+        const float pen_old = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pen_v), r));
+        const float rel_row = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rel_v), r));
+        const bool g_num = gval == gval;
+        const bool takes = g_num && (!(pen_old == pen_old) || gval > pen_old);
+        const float pen_new = fmaxf(pen_old, gval);    // fmaxf ignores a NaN operand
+        if (lane == 0 && takes) {
+          owner[row] = static_cast<int32_t>(s);
+          pen[row] = pen_new;
+        }
+        bool strike;
+        const uint64_t key = subset_key(pen_new, rel_row, static_cast<uint32_t>(row), lam, one_minus_lam, max_sim, cut_on, &strike);
+        if (lane == 0 && strike) struck[row] = 1;
+        if (!seeding) best = key > best ? key : best;
+      }
+    }
+    live = live_next;
+  }
+
+  // ---- 4. the workgroup's key for the next launch
+  if (seeding) return;
+  __syncthreads();
+  if (lane == 0) slots[tid / kWave] = best;            // `best` is wave-uniform
+  __syncthreads();
+  if (tid == 0) {
+    uint64_t b = kKeyEmpty;
+#pragma unroll
+    for (int i = 0; i < kSubWaves; ++i) b = slots[i] > b ? slots[i] : b;
+    keys_out[blockIdx.x] = b;
+  }
+}
+
+struct SubsetPtrs {
+  uint64_t* keys;
+  SubsetHeader* hdr;
+  float* pen;
+  int32_t* owner;
+  uint8_t* struck;
+};
+SubsetPtrs subset_carve(const SubsetLayout& L, char* ws) {
+  return SubsetPtrs{reinterpret_cast<uint64_t*>(ws + L.keys), reinterpret_cast<SubsetHeader*>(ws + L.header),
+                    reinterpret_cast<float*>(ws + L.pen), reinterpret_cast<int32_t*>(ws + L.owner),
+                    reinterpret_cast<uint8_t*>(ws + L.struck)};
+}
+
+int subset_small_grid(int64_t n_rows) {
+  const int64_t b = (n_rows + kSubsetThreads - 1) / kSubsetThreads;
+  return static_cast<int>(b < 1 ? 1 : (b > kSubsetGrid ? kSubsetGrid : b));
+}
+
+template <int ELEM, bool VEC>
+hipError_t subset_apply_upl(int upl, const char* E, int64_t n_rows, int dim, const float* rel, float lam, float one_minus_lam,
+                            float max_sim, int64_t id_offset, const uint64_t* keys_in, uint64_t* keys_out, const SubsetPtrs& P,
+                            int64_t* out_rows, float* out_gain, int64_t* n_picked, const int64_t* d_seeds, int seed_idx,
+                            hipStream_t stream) {
+#define DEWI_SUBSET_LAUNCH(UPL)                                                                                                \
+  hipLaunchKernelGGL((subset_apply_kernel<ELEM, VEC, UPL>), dim3(grid), dim3(kSubsetThreads), 0, stream, E, n_rows, dim,        \
+                     rel, lam, one_minus_lam, max_sim, id_offset, keys_in, keys_out, P.hdr, P.pen, P.owner, P.struck, out_rows,   \
+                     out_gain, n_picked, d_seeds, seed_idx);                                                                    \
+  break;
+  const int grid = subset_grid(n_rows, dim, ELEM);
+  switch (upl) {
+    case 1: DEWI_SUBSET_LAUNCH(1)
+    case 2: DEWI_SUBSET_LAUNCH(2)
+    case 3: DEWI_SUBSET_LAUNCH(3)
+    case 4: DEWI_SUBSET_LAUNCH(4)
+    case 6: DEWI_SUBSET_LAUNCH(6)
+    case 8: DEWI_SUBSET_LAUNCH(8)
+    default: DEWI_SUBSET_LAUNCH(0)
+  }
+#undef DEWI_SUBSET_LAUNCH
+  return hipGetLastError();
+}
+
+hipError_t subset_apply(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* rel, float lam, float one_minus_lam,
+                        float max_sim, int64_t id_offset, const uint64_t* keys_in, uint64_t* keys_out, const SubsetPtrs& P,
+                        int64_t* out_rows, float* out_gain, int64_t* n_picked, const int64_t* d_seeds, int seed_idx,
+                        hipStream_t stream) {
+  const int cols = elem_type == 0 ? 4 : 8;
+  const int units = (dim + cols - 1) / cols;
+  const int per_lane = (units + kWave - 1) / kWave;
+  const int upl = per_lane <= 4 ? per_lane : (per_lane <= 6 ? 6 : (per_lane <= 8 ? 8 : 0));
+  const bool vec = dim % cols == 0 && reinterpret_cast<uintptr_t>(d_E) % 16 == 0;
+  const char* E = static_cast<const char*>(d_E);
+#define DEWI_SUBSET_APPLY(ELEM, VEC)                                                                                          \
+  return subset_apply_upl<ELEM, VEC>(upl, E, n_rows, dim, rel, lam, one_minus_lam, max_sim, id_offset, keys_in, keys_out, P,   \
+                                     out_rows, out_gain, n_picked, d_seeds, seed_idx, stream)
+  if (elem_type == 0) {
+    if (vec) DEWI_SUBSET_APPLY(0, true);
+    DEWI_SUBSET_APPLY(0, false);
+  }
+  if (vec) DEWI_SUBSET_APPLY(1, true);
+  DEWI_SUBSET_APPLY(1, false);
+#undef DEWI_SUBSET_APPLY
+}
+
+}  // namespace
+
+SubsetLayout subset_layout(int64_t n_rows) {
+  SubsetLayout L;
+  const size_t n = (static_cast<size_t>(n_rows) + 63) / 64 * 64;
+  L.keys = 0;
+  L.header = 2 * kSubsetGrid * sizeof(uint64_t);
+  L.pen = L.header + 256;
+  L.owner = L.pen + 4 * n;
+  L.struck = L.owner + 4 * n;
+  L.total = L.struck + n;
+  return L;
+}
+
+hipError_t launch_subset_begin(const SubsetLayout& L, int64_t n_rows, const uint8_t* d_mask, char* ws, hipStream_t stream) {
+  const SubsetPtrs P = subset_carve(L, ws);
+  hipLaunchKernelGGL(subset_begin_kernel, dim3(subset_small_grid(n_rows)), dim3(kSubsetThreads), 0, stream, n_rows, d_mask, P.keys,
+                     P.hdr, P.pen, P.owner, P.struck);
+  return hipGetLastError();
+}
+
+hipError_t launch_subset_seed(const SubsetLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                              const int64_t* d_seed_rows, int n_seeds, float max_sim, char* ws, hipStream_t stream) {
+  const SubsetPtrs P = subset_carve(L, ws);
+  for (int j = 0; j < n_seeds; ++j) {
+    const hipError_t e = subset_apply(d_E, elem_type, n_rows, dim, nullptr, 0.f, 0.f, max_sim, 0, P.keys, P.keys, P, nullptr,
+                                      nullptr, nullptr, d_seed_rows, j, stream);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_subset_run(const SubsetLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel,
+                             int64_t n_launches, float lam, float one_minus_lam, float max_sim, int64_t id_offset,
+                             int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner,
+                             char* ws, hipStream_t stream) {
+  const SubsetPtrs P = subset_carve(L, ws);
+  hipLaunchKernelGGL(subset_keys_kernel, dim3(subset_grid(n_rows, dim, elem_type)), dim3(kSubsetThreads), 0, stream, n_rows, d_rel, lam, one_minus_lam,
+                     max_sim, P.pen, P.struck, P.keys, P.hdr, d_n_picked);
+  hipError_t e = hipGetLastError();
+  for (int64_t j = 0; j < n_launches && e == hipSuccess; ++j)
+    e = subset_apply(d_E, elem_type, n_rows, dim, d_rel, lam, one_minus_lam, max_sim, id_offset, P.keys + (j & 1) * kSubsetGrid,
+                     P.keys + ((j + 1) & 1) * kSubsetGrid, P, d_out_rows, d_out_gain, d_n_picked, nullptr, 0, stream);
+  if (e == hipSuccess && (d_out_pen || d_out_owner)) {
+    hipLaunchKernelGGL(subset_export_kernel, dim3(subset_small_grid(n_rows)), dim3(kSubsetThreads), 0, stream, n_rows, P.pen,
+                       P.owner, id_offset, d_out_pen, d_out_owner);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
+}  // namespace dewi

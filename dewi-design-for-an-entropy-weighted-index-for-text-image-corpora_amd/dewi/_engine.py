@@ -1626,6 +1626,75 @@ class DeviceCorpus:
             ids_d, sc_d = self.search_diverse_approx_device(q, k, eta, entropy_pref, mmr_lambda, candidates, max_sim, rescore)
             return ids_d.cpu().numpy(), sc_d.cpu().numpy()
 
+    # ------------------------------------------------------------------ subset selection (greedy coverage of the whole corpus)
+    def select_subset_device(self, budget: int, mmr_lambda: float = 0.5, max_sim: Optional[float] = None, relevance=None,
+                             mask=None, seeds=None, return_coverage: bool = False):
+        """Enqueue one SUBSET SELECTION on the current stream: the ``budget`` most informative rows that do not repeat each
+        other (``dewi_select_begin`` / ``_seed`` / ``_run``, include/dewi_hip.h).  Greedy maximal marginal relevance over
+        ALL rows: each pick is the row with the largest ``mmr_lambda * relevance - (1 - mmr_lambda) * (largest inner product
+        with a row already picked)``; a row at least ``max_sim`` similar to a picked row is struck out (``None``: no such
+        cut).  One pass over the rows still in play per pick.
+
+        ``relevance``: fp32 [N] on this device (default: the ``dewi32`` column; a NaN entry makes its row unpickable);
+        ``mask``: bool / uint8 [N] on this device, 0 = not pickable; ``seeds``: LOCAL rows (a sequence or an int64 device
+        tensor) applied as picks before the first choice — they penalise, are not returned and do not count.
+
+        Returns device tensors, no host synchronisation: ``(rows int64 [min(budget, N)] — global, prefilled with -1 —,
+        gain fp32 — the marginal value at the pick, prefilled with NaN —, n_picked int64 [1])``, in pick order; with
+        ``return_coverage`` also ``(pen fp32 [N], owner int64 [N])``: every row's largest similarity to the selection (NaN:
+        none; frozen once the row was struck out) and the global row that gave it (-1: none).  Cosine / inner-product rows
+        (``space="l2"``: ``NotImplementedError``), fp32 and bf16.  NOT thread-safe on one instance (shared workspace)."""
+        torch = _torch()
+        n = self.n_rows
+        if self.space == "l2":
+            raise NotImplementedError("subset selection penalises the inner product of unit rows: space='l2' is not in this build")
+        lam = float(mmr_lambda)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"mmr_lambda must lie in [0, 1], got {mmr_lambda}")
+        cut = float("inf") if max_sim is None else float(max_sim)
+        if cut != cut:
+            raise ValueError("max_sim must not be NaN")
+        b = min(int(budget), n)
+        if b < 0:
+            raise ValueError(f"budget must not be negative, got {budget}")
+        if return_coverage and b == 0:
+            raise ValueError("return_coverage needs a budget of at least 1 (a run of no picks writes nothing)")
+        rel = self.dewi32 if relevance is None else relevance
+        if tuple(rel.shape) != (n,) or rel.dtype != torch.float32 or rel.device != self.device:
+            raise ValueError(f"relevance must be a float32 tensor of shape ({n},) on {self.device}")
+        rel = rel.contiguous()
+        m8 = None
+        if mask is not None:
+            if tuple(mask.shape) != (n,) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != self.device:
+                raise ValueError(f"mask must be a bool or uint8 tensor of shape ({n},) on {self.device}")
+            m8 = mask.contiguous().view(torch.uint8)
+        seed_rows = None
+        if seeds is not None:
+            seed_rows = (seeds if isinstance(seeds, torch.Tensor) else torch.as_tensor(np.asarray(seeds, np.int64).reshape(-1)))
+            seed_rows = seed_rows.to(device=self.device, dtype=torch.int64).contiguous()
+        rows = torch.full((b,), -1, dtype=torch.int64, device=self.device)
+        gain = torch.full((b,), float("nan"), dtype=torch.float32, device=self.device)
+        n_picked = torch.zeros(1, dtype=torch.int64, device=self.device)
+        pen = owner = None
+        if return_coverage:
+            pen = torch.empty(n, dtype=torch.float32, device=self.device)
+            owner = torch.empty(n, dtype=torch.int64, device=self.device)
+        ws = self._cached_workspace(("select", n), self._lib.dewi_select_workspace_bytes, n, self.dim, self._elem)
+        stream = nat.stream_ptr()
+        nat.check(self._lib.dewi_select_begin(n, self.dim, self._elem, nat.ptr(m8) if m8 is not None else None, nat.ptr(ws),
+                                              ws.numel(), stream))
+        if seed_rows is not None and seed_rows.numel():
+            nat.check(self._lib.dewi_select_seed(nat.ptr(self.emb), self._elem, n, self.dim, nat.ptr(seed_rows),
+                                                 int(seed_rows.numel()), cut, nat.ptr(ws), ws.numel(), stream))
+        if b > 0:
+            nat.check(self._lib.dewi_select_run(
+                nat.ptr(self.emb), self._elem, n, self.dim, nat.ptr(rel), b, lam, cut, self.id_offset, nat.ptr(rows),
+                nat.ptr(gain), nat.ptr(n_picked), nat.ptr(pen) if pen is not None else None,
+                nat.ptr(owner) if owner is not None else None, nat.ptr(ws), ws.numel(), stream))
+        if return_coverage:
+            return rows, gain, n_picked, pen, owner
+        return rows, gain, n_picked
+
     # ------------------------------------------------------------------ collapsed search (at most m results per group)
     def make_groups(self, groups) -> DeviceGroups:
         """Prepare group labels for ``search_collapsed*``: whatever ``group_labels`` takes without an index — a

@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = (
     "dewi_knn_i8_filtered_workspace_bytes", "dewi_knn_candidates_i8_filtered", "dewi_knn_candidates_i8_query_filtered",
     "dewi_collapse_workspace_bytes", "dewi_collapse_rerank", "dewi_knn_candidates_filtered",
     "dewi_robust_fit_fast_plan",
+    "dewi_select_workspace_bytes", "dewi_select_begin", "dewi_select_seed", "dewi_select_run",
 )
 #: the words dewi_robust_fit_fast_plan fills, in order (include/dewi_hip.h)
 FIT_FAST_PLAN_WORDS = ("supported", "slices", "counters_offset", "counters_bytes", "small_n", "sample", "delta", "buckets",
@@ -247,6 +248,14 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_collapse_workspace_bytes.argtypes = [i32, i32]
     lib.dewi_collapse_rerank.restype = i32
     lib.dewi_collapse_rerank.argtypes = [vp, i32, i32, vp, i64, i64, i32, i32, f64, f64, vp, vp, vp, vp, vp, sz, vp]
+    lib.dewi_select_workspace_bytes.restype = sz
+    lib.dewi_select_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.dewi_select_begin.restype = i32
+    lib.dewi_select_begin.argtypes = [i64, i32, i32, vp, vp, sz, vp]
+    lib.dewi_select_seed.restype = i32
+    lib.dewi_select_seed.argtypes = [vp, i32, i64, i32, vp, i32, f64, vp, sz, vp]
+    lib.dewi_select_run.restype = i32
+    lib.dewi_select_run.argtypes = [vp, i32, i64, i32, vp, i64, f64, f64, i64, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.dewi_knn_candidates_filtered.restype = i32
     lib.dewi_knn_candidates_filtered.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, vp, vp, i32, i32, i64, vp, vp, sz, vp]
     lib.dewi_robust_fit_fast_plan.restype = i32

@@ -864,6 +864,64 @@ class ExactIndex(BaseIndex):
             raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
         return self._corpus.search_diverse(q, int(k), float(eta), float(entropy_pref), float(mmr_lambda), candidates, max_sim)
 
+    # ---------------------------------------------------------------- subset selection (additive)
+    def select_subset(self, budget: int, mmr_lambda: float = 0.5, max_sim: Optional[float] = None, relevance=None,
+                      filter=None, seeds: Optional[Sequence[str]] = None, return_gain: bool = False,
+                      return_coverage: bool = False):
+        """The ``budget`` most informative documents that do not repeat each other (additive; the reference measures such a
+        selection — ``metrics.cluster_coverage`` — but cannot make one): greedy maximal marginal relevance over the WHOLE
+        corpus.  Each pick is the document with the largest ``mmr_lambda * relevance - (1 - mmr_lambda) * (largest similarity
+        to a document already picked)``; a document at least ``max_sim`` similar to a picked one is struck out, so the answer
+        may be shorter than ``budget`` (a budget above N returns at most N).  ``relevance``: N values, an array or a CUDA
+        tensor (default: the ``dewi`` column as built; NaN: never picked).  ``filter``: what ``search(filter=)`` takes for one
+        list — only its documents can be picked (and only they are penalised).  ``seeds``: doc ids already chosen elsewhere:
+        they penalise, are not returned and do not count.
+
+        Returns the doc ids IN PICK ORDER; with ``return_gain`` also their marginal values at the pick (fp32 array); with
+        ``return_coverage`` also, per document of the index, the nearest selected doc id (``None``: none) and its similarity
+        (NaN: none; for a struck-out document as it stood when it was struck out).  ``make_filter(doc_ids=
+        index.select_subset(...))`` is the allow-list of the subset.  One corpus pass per pick: thousands of picks over a
+        million documents take seconds.  Cosine indexes (``space="l2"``: ``NotImplementedError``)."""
+        if self.space == "l2":
+            raise NotImplementedError("subset selection penalises the inner product of unit rows: space='l2' is not in this build")
+        self._ensure_built()
+        import torch
+        from ._engine import DeviceFilter, DeviceQueryFilters
+        corpus = self._corpus
+        n = len(self._doc_ids)
+        with corpus._lock, torch.cuda.device(corpus.device):
+            mask = None
+            if isinstance(filter, DeviceQueryFilters):
+                raise ValueError("select_subset takes one allow-list, not per-query filters")
+            if isinstance(filter, DeviceFilter):
+                corpus.check_filter(filter)
+                mask = filter.byte_mask()
+            elif filter is not None:
+                m = self.filter_mask(**filter_kwargs(filter))
+                mask = (m if hasattr(m, "is_cuda") else torch.from_numpy(np.ascontiguousarray(m))).to(corpus.device)
+            rel = None
+            if relevance is not None:
+                r = relevance if hasattr(relevance, "is_cuda") else torch.from_numpy(
+                    np.ascontiguousarray(np.asarray(relevance, dtype=np.float32)))
+                if tuple(r.shape) != (n,):
+                    raise ValueError(f"relevance must have shape ({n},), got {tuple(r.shape)}")
+                rel = r.to(device=corpus.device, dtype=torch.float32)
+            seed_rows = None
+            if seeds is not None:
+                seed_rows = self.rows_of([seeds] if isinstance(seeds, str) else list(seeds))
+            out = corpus.select_subset_device(int(budget), float(mmr_lambda), max_sim, rel, mask, seed_rows,
+                                              return_coverage=bool(return_coverage))
+            kk = int(out[2].item())
+            rows = out[0][:kk].cpu().numpy() - corpus.id_offset
+            result = [[self._doc_ids[r] for r in rows.tolist()]]
+            if return_gain:
+                result.append(out[1][:kk].cpu().numpy())
+            if return_coverage:
+                owner = out[4].cpu().numpy()
+                result.append([self._doc_ids[o - corpus.id_offset] if o >= 0 else None for o in owner.tolist()])
+                result.append(out[3].cpu().numpy())
+        return result[0] if len(result) == 1 else tuple(result)
+
     def search_diverse_approx(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
                               mmr_lambda: float = 0.5, candidates: Optional[int] = None, max_sim: Optional[float] = None,
                               rescore: bool = True) -> SearchResult:

@@ -254,6 +254,16 @@ class DewiIndex(BaseIndex):
         res = self._backend.results_for(np.where(rows < 0, 0, rows), scores)
         return [r[:int(m)] for r, m in zip(res, n_real)]
 
+    def select_subset(self, budget: int, mmr_lambda: float = 0.5, max_sim: Optional[float] = None, relevance=None,
+                      filter=None, seeds=None, return_gain: bool = False, return_coverage: bool = False):
+        """The ``budget`` most informative documents that do not repeat each other (additive; ``ExactIndex.select_subset``):
+        greedy DEWI-weighted coverage of the whole corpus, doc ids in pick order."""
+        if self.space == "l2":
+            raise NotImplementedError("subset selection penalises the inner product of unit rows: space='l2' is not in this build")
+        if not self._built:
+            self.build()
+        return self._backend.select_subset(budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain, return_coverage)
+
     def make_groups(self, groups):
         """Prepare group labels for ``search_collapsed`` / ``search_collapsed_batch`` (``ExactIndex.make_groups``)."""
         if not self._built:

@@ -615,6 +615,77 @@ int dewi_collapse_rerank(const dewi_candidate* d_cand, int n_queries, int n_cand
                          void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Subset selection (additive to ABI 6; the reference measures such a selection — metrics.cluster_coverage, duplicate_rate —
+ * but cannot make one): "the B most informative rows that do not repeat each other".  It is dewi_diverse_rerank's rule,
+ * greedy maximal marginal relevance, with the pool = ALL n_rows rows and the relevance = an fp32 column (the corpus' dewi32
+ * column, or any other).  tests/select_model.py restates the contract in NumPy.
+ *
+ * State per row i (it lives in the caller's workspace between the calls below):
+ *   - pen_i: initially "no number" (NaN);  owner_i: initially -1;  a struck-out bit, initially clear.
+ *   - A row is STRUCK OUT, for ever, when it is picked or applied as a seed, when the mask of dewi_select_begin excludes it,
+ *     and when its pen has reached max_sim (below).
+ * g(i, s) is the fp32 inner product of stored rows i and s (d_E, elem_type 0 fp32 / 1 bf16 widened to fp32, the products
+ * exact), no re-normalisation.  ONE summation order, symmetric in (i, s):
+ *   - the row is cut into units of 16 bytes' worth of elements (4 fp32 / 8 bf16); the last unit of a row that is not whole
+ *     units is filled up with zeros;
+ *   - unit u belongs to lane u % 64 of 64; a lane walks its units in ascending order and, inside a unit, the elements in
+ *     ascending order, with acc = fma(a, b, acc) from acc = +0;
+ *   - the 64 sums are added as a balanced pairwise tree: lanes 2p and 2p + 1, then neighbouring pairs of those, and so on.
+ *   It does not depend on n_rows, the budget, the step, the launch shape or the alignment of d_E.
+ * Applying a pick (or seed) s: row s becomes struck out; for every OTHER row i that is not struck out, in this order:
+ *   - if g(i, s) is a number and (pen_i is no number or g > pen_i): owner_i = s;
+ *   - pen_i = fmaxf(pen_i, g(i, s)) — NaN is ignored, so a NaN row never penalises anybody and is never penalised;
+ *   - if pen_i is a number and pen_i >= fp32(max_sim): row i is struck out (its pen and owner are frozen as they stand).
+ *     max_sim = +inf (any max_sim that rounds to +inf in fp32) disables this rule.
+ * Marginal value: m_i = fp32(lambda) * rel_i while pen_i is no number, otherwise fp32(lambda) * rel_i - fp32(1 - lambda) * pen_i:
+ *   two products, each rounded once, and one subtraction; no contraction.
+ * Eligibility: row i is INELIGIBLE when it is struck out, or rel_i is NaN (new here: dewi_diverse_rerank ranks a NaN score
+ *   first; a corpus-wide selection must not start with the rows whose dewi is missing).  A row with a NaN rel is still
+ *   penalised and owned like any other row — rel belongs to the run, not to the state.
+ * Picking: dewi_select_run first strikes out every row whose pen is a number >= fp32(max_sim) (the rule above, for a state
+ *   whose seeds were applied under another max_sim); then, pick by pick: the eligible row first in (ord(m_i) desc, row asc),
+ *   NaN the largest value and -0 == +0 as in step 5 of the search; apply it; stop after `budget` picks or when nothing is
+ *   eligible.
+ * Outputs, in pick order.  The state counts its picks from dewi_select_begin on; call the count before this run p0 and
+ *   after it kk.
+ *   - d_out_rows [p0 + budget] int64: positions p0 .. kk-1 receive row + id_offset.
+ *   - d_out_gain [p0 + budget] fp32: m as it stood at the pick, -0 written as +0 (a NaN m: some NaN).
+ *   - d_n_picked: one int64, receives kk (also when nothing was picked).
+ *   - d_out_pen [n_rows] fp32 (may be NULL): pen_i as the state holds it after the run — each row's largest similarity to
+ *     the selection, frozen for a row at the moment it was struck out; NaN: none.
+ *   - d_out_owner [n_rows] int64 (may be NULL): owner_i + id_offset, the selected row that gave pen_i; -1: none.
+ *   Positions kk .. p0 + budget - 1 of rows / gain are NOT written, as everywhere in this ABI.
+ * Resume: a run of b1 followed by a run of b2 on the same state (same d_rel, lambda, max_sim) equals one run of b1 + b2 bit
+ *   for bit; the second run writes from position p0 = b1' on (the picks the first made).
+ * Seeds: dewi_select_seed applies the LOCAL rows d_seed_rows[0 .. n_seeds) as picks, in order, before a run: they update
+ *   pen and owner, are struck out, are not output and do not count.  A seed outside [0, n_rows) is skipped; a seed the mask
+ *   excludes, or an all-NaN row, is applied like any other (the latter changes nobody's pen).
+ * Two consequences: lambda = 1 with max_sim = +inf is the top-`budget` of rel in (value desc, row asc), NaN rel left out;
+ * lambda = 0 after one seed is farthest-first traversal (the greedy k-centre).
+ *
+ * One launch per pick, each one HBM-bound pass over the rows that are not struck out (their struck-out byte is read first:
+ * a struck-out row's bytes are never loaded) — live rows * (row bytes + 9 B of state, + 8 B where pen and owner change); a
+ * launch finds its pick by reducing the (at most 256) workgroup keys the launch before it left.  Any dim, any element-aligned d_E
+ * (16-byte nontemporal loads where rows are whole units and d_E is 16-byte aligned, element loads otherwise; nothing
+ * outside the rows is touched).  n_rows < 2^31.  The run enqueues min(budget, n_rows) pick launches.
+ * Workspace: dewi_select_workspace_bytes(n_rows, dim, elem_type) bytes (0 for a bad shape; needs no device), 256-byte aligned.
+ * dewi_select_begin defines every region the later calls read; nothing is assumed about its bytes before.
+ * Asynchronous on `stream`; no allocation, no synchronisation.  Argument errors are reported before any device work: null
+ * pointers, a bad shape, an unknown elem_type, mmr_lambda outside [0, 1] or NaN, a NaN max_sim, negative n_seeds:
+ * DEWI_ERR_INVALID_ARG; n_rows >= 2^31: DEWI_ERR_UNSUPPORTED; a short workspace: DEWI_ERR_WORKSPACE.  budget <= 0 (and
+ * n_seeds == 0) writes nothing and returns DEWI_OK.
+ * ------------------------------------------------------------------------------------------ */
+size_t dewi_select_workspace_bytes(int64_t n_rows, int dim, int elem_type);
+int dewi_select_begin(int64_t n_rows, int dim, int elem_type, const uint8_t* d_mask /* [n_rows], 0 = excluded; NULL: all rows */,
+                      void* d_workspace, size_t workspace_bytes, void* stream);
+int dewi_select_seed(const void* d_E, int elem_type, int64_t n_rows, int dim, const int64_t* d_seed_rows, int n_seeds,
+                     double max_sim, void* d_workspace, size_t workspace_bytes, void* stream);
+int dewi_select_run(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel, int64_t budget,
+                    double mmr_lambda, double max_sim, int64_t id_offset, int64_t* d_out_rows, float* d_out_gain,
+                    int64_t* d_n_picked, float* d_out_pen /* may be NULL */, int64_t* d_out_owner /* may be NULL */,
+                    void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Approximate search over an INT8 copy of the corpus (additive to ABI 6; the reference has no counterpart).  One byte per
  * element instead of four: a symmetric per-row scalar quantisation, integer inner products, and — optionally — the candidate
  * cut re-scored from the fp32 rows.  Unlike the bf16 shadow this route is NOT exact: no error band of a useful width is
