@@ -1581,6 +1581,58 @@ int dewi_select_run(const void* d_E, int elem_type, int64_t n_rows, int dim, con
                   "select_run launch");
 }
 
+// ---- the blocked form of the subset selection: up to `block` picks per corpus pass ------------------------------------------
+// shape, 2^31, elem_type as check_select_state, then the block, then the (larger) workspace
+static int check_select_blocked(int64_t n_rows, int dim, int elem_type, int block, const void* d_ws, size_t ws_bytes) {
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
+  if (n_rows > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld: a subset selection takes fewer than 2^31 rows", static_cast<long long>(n_rows));
+  if (int rc = check_elem_type(elem_type)) return rc;
+  if (block < 1 || block > dewi::subset_block_max(dim, elem_type))
+    return fail(DEWI_ERR_INVALID_ARG, "block %d outside [1, %d] (dewi_select_block_max of dim %d)", block,
+                dewi::subset_block_max(dim, elem_type), dim);
+  return check_workspace(d_ws, ws_bytes, dewi::subset_blocked_layout(n_rows).total);
+}
+
+int dewi_select_block_max(int dim, int elem_type) { return dewi::subset_block_max(dim, elem_type); }
+
+size_t dewi_select_blocked_workspace_bytes(int64_t n_rows, int dim, int elem_type, int block) {
+  if (n_rows <= 0 || n_rows > 0x7FFFFFFFll || dim <= 0 || (elem_type != 0 && elem_type != 1)) return 0;
+  if (block < 1 || block > dewi::subset_block_max(dim, elem_type)) return 0;
+  return dewi::subset_blocked_layout(n_rows).total;
+}
+
+int dewi_select_seed_blocked(const void* d_E, int elem_type, int64_t n_rows, int dim, const int64_t* d_seed_rows, int n_seeds,
+                             double max_sim, void* d_workspace, size_t workspace_bytes, void* stream, int block) {
+  if (!d_E || (!d_seed_rows && n_seeds > 0)) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (n_seeds < 0) return fail(DEWI_ERR_INVALID_ARG, "n_seeds must not be negative (got %d)", n_seeds);
+  if (max_sim != max_sim) return fail(DEWI_ERR_INVALID_ARG, "max_sim is NaN");
+  if (int rc = check_select_blocked(n_rows, dim, elem_type, block, d_workspace, workspace_bytes)) return rc;
+  if (n_seeds == 0) return DEWI_OK;
+  return launched(dewi::launch_subset_seed_blocked(dewi::subset_blocked_layout(n_rows), d_E, elem_type, n_rows, dim, d_seed_rows,
+                                                   n_seeds, static_cast<float>(max_sim), block, static_cast<char*>(d_workspace),
+                                                   static_cast<hipStream_t>(stream)),
+                  "select_seed_blocked launch");
+}
+
+int dewi_select_run_blocked(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel, int64_t budget,
+                            double mmr_lambda, double max_sim, int64_t id_offset, int64_t* d_out_rows, float* d_out_gain,
+                            int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner, void* d_workspace, size_t workspace_bytes,
+                            void* stream, int block, int n_rounds, int64_t* d_stats) {
+  if (!d_E || !d_rel || !d_out_rows || !d_out_gain || !d_n_picked) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (!(mmr_lambda >= 0.0 && mmr_lambda <= 1.0)) return fail(DEWI_ERR_INVALID_ARG, "mmr_lambda %g outside [0, 1]", mmr_lambda);
+  if (max_sim != max_sim) return fail(DEWI_ERR_INVALID_ARG, "max_sim is NaN");
+  if (n_rounds < 0) return fail(DEWI_ERR_INVALID_ARG, "n_rounds must not be negative (got %d)", n_rounds);
+  if (int rc = check_select_blocked(n_rows, dim, elem_type, block, d_workspace, workspace_bytes)) return rc;
+  if (budget <= 0) return DEWI_OK;
+  return launched(dewi::launch_subset_run_blocked(dewi::subset_blocked_layout(n_rows), d_E, elem_type, n_rows, dim, d_rel,
+                                                  budget < n_rows ? budget : n_rows, static_cast<float>(mmr_lambda),
+                                                  static_cast<float>(1.0 - mmr_lambda), static_cast<float>(max_sim), id_offset,
+                                                  d_out_rows, d_out_gain, d_n_picked, d_out_pen, d_out_owner, block, n_rounds,
+                                                  d_stats, static_cast<char*>(d_workspace), static_cast<hipStream_t>(stream)),
+                  "select_run_blocked launch");
+}
+
 // ---- approximate search over an int8 copy of the corpus (additive to ABI 6; knn_scan_i8.hip) ---------------------------------
 // the shape checks the int8 entry points share, in one order: rows, 2^32, dim, the unit (16 codes; the re-scoring: 4 floats)
 static int check_i8_shape(int64_t n_rows, int dim, int unit) {

@@ -453,6 +453,29 @@ hipError_t launch_subset_run(const SubsetLayout& L, const void* d_E, int elem_ty
                              int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner,
                              char* ws, hipStream_t stream);
 
+// ---- select_subset.hip, the blocked form: up to `block` picks per corpus pass (include/dewi_hip.h, "BLOCKED form") ----
+constexpr int kSubsetMaxBlock = DEWI_SELECT_MAX_BLOCK;   // most picks of a pass, and the most members of a round's set S
+constexpr int kSubsetTopT = 16;                          // keys a workgroup of the key pass hands on; one more is its bound
+constexpr size_t kSubsetBlockLds = 128 * 1024;           // LDS the picks' rows of one apply pass may take (of 160 KiB)
+struct SubsetBlockedLayout {
+  SubsetLayout state;                  // the one-pick form's regions, at the same offsets
+  size_t lists;                        // uint64 [kSubsetGrid][kSubsetTopT + 1]: each workgroup's best keys, descending
+  size_t unsafe;                       // uint32 [kSubsetGrid]: each workgroup's live eligible rows whose pen is NaN
+  size_t picks;                        // int64 [kSubsetMaxBlock]: the round's picks (local rows), in pick order
+  size_t ctl;                          // int64 [2]: how many picks the list holds; the pick count at which the run ends
+  size_t total;
+};
+int subset_block_max(int dim, int elem_type);
+SubsetBlockedLayout subset_blocked_layout(int64_t n_rows);
+hipError_t launch_subset_seed_blocked(const SubsetBlockedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                                      const int64_t* d_seed_rows, int n_seeds, float max_sim, int block, char* ws,
+                                      hipStream_t stream);
+hipError_t launch_subset_run_blocked(const SubsetBlockedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                                     const float* d_rel, int64_t budget, float lam, float one_minus_lam, float max_sim,
+                                     int64_t id_offset, int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked,
+                                     float* d_out_pen, int64_t* d_out_owner, int block, int n_rounds, int64_t* d_stats, char* ws,
+                                     hipStream_t stream);
+
 // ---- collapse.hip: at most per_group results per label, one workgroup per query (no workspace)
 constexpr int kCollapseMaxCandidates = DEWI_COLLAPSE_MAX_CANDIDATES;
 static_assert(kCollapseMaxCandidates == kMaxSortCandidates, "a collapsed pool is what one workgroup sorts in LDS");

@@ -407,6 +407,377 @@ hipError_t subset_apply(const void* d_E, int elem_type, int64_t n_rows, int dim,
 #undef DEWI_SUBSET_APPLY
 }
 
+// =====================================================================================================================
+// The blocked form: up to `block` picks per corpus pass, bit for bit the one-pick form (include/dewi_hip.h, "BLOCKED
+// form"; tests/select_blocked_model.py restates the round rule).  A round is three launches, and again
+// everything workgroups tell each other crosses a kernel boundary:
+//   key pass    no row is read: every workgroup forms the keys of its rows from pen / rel / struck and leaves its best
+//               kSubsetTopT keys, descending, the next one as its BOUND, and its count of unsafe rows (eligible, pen NaN).
+//   round       one workgroup: S = the best kSubsetMaxBlock keys of all lists, tau = the largest key outside S (the next
+//               candidate or a workgroup's bound); the greedy inside S, g against each new pick in the contract's order;
+//               it writes the outputs, the counter and the pick list.  It writes no row state.
+//   apply pass  the picks' rows staged in LDS once per workgroup; every live row is loaded once; g against pick j lands in
+//               lane j, and the picks are taken in order for a row at once: a running maximum over the lanes and three
+//               ballots (own row: struck out; owner / pen; the strike-out by max_sim freezes the row).
+// =====================================================================================================================
+struct SubsetCtl {
+  int64_t n_list;    // picks the list holds for the next apply pass (0: the launches behind are no-ops)
+  int64_t run_end;   // the pick count at which this run ends: p0 + budget
+};
+static_assert(kSubsetGrid * kSubsetTopT % kSubsetThreads == 0, "the round kernel holds the candidates in registers");
+static_assert(kSubsetMaxBlock <= kWave, "the round kernel reduces the members' keys in one wave");
+
+// opening (budget > 0): the first launch of a run — the run's end, the counters; otherwise a pass behind a round that made
+// no pick returns at once: the lists still describe the state.
+__global__ void __launch_bounds__(kSubsetThreads) subset_top_kernel(
+    int64_t n_rows, const float* __restrict__ rel, float lam, float one_minus_lam, float max_sim, const float* __restrict__ pen,
+    uint8_t* __restrict__ struck, uint64_t* __restrict__ lists, uint32_t* __restrict__ unsafe,
+    const SubsetHeader* __restrict__ hdr, SubsetCtl* __restrict__ ctl, int64_t budget, int64_t* __restrict__ n_picked_out,
+    int64_t* __restrict__ stats) {
+  __shared__ uint64_t slots[kSubWaves];
+  const int tid = static_cast<int>(threadIdx.x);
+  if (budget > 0) {
+    if (blockIdx.x == 0 && tid == 0) {
+      ctl->run_end = hdr->n_picked + budget;
+      *n_picked_out = hdr->n_picked;
+      if (stats) stats[0] = stats[1] = stats[2] = 0;
+    }
+  } else if (ctl->n_list == 0) {
+    return;
+  }
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kSubsetThreads + tid;
+  const int64_t nt = static_cast<int64_t>(gridDim.x) * kSubsetThreads;
+  const bool cut_on = max_sim != __builtin_inff();
+  uint64_t prev = ~0ull;              // keys are unique (they carry the row): the k-th best is the best below the (k-1)-th
+                                      // (a NaN m on row 0 IS ~0: the first round takes every key)
+  uint32_t n_unsafe = 0;
+  for (int k = 0; k <= kSubsetTopT; ++k) {
+    uint64_t best = kKeyEmpty;
+    if (prev != kKeyEmpty) {
+      for (int64_t i = t; i < n_rows; i += nt) {
+        if (struck[i]) continue;
+        const float p = pen[i], r = rel[i];
+        bool strike;
+        const uint64_t key = subset_key(p, r, static_cast<uint32_t>(i), lam, one_minus_lam, max_sim, cut_on, &strike);
+        if (k == 0) {
+          if (strike) struck[i] = 1;
+          else if (r == r && !(p == p)) ++n_unsafe;
+        }
+        if ((k == 0 || key < prev) && key > best) best = key;
+      }
+    }
+    best = block_max_key(best, slots);
+    if (tid == 0) lists[blockIdx.x * (kSubsetTopT + 1) + k] = best;
+    prev = best;
+  }
+  n_unsafe = wave_sum_u32(n_unsafe);
+  __syncthreads();
+  if ((tid & (kWave - 1)) == 0) slots[tid / kWave] = n_unsafe;
+  __syncthreads();
+  if (tid == 0) {
+    uint64_t total = 0;
+#pragma unroll
+    for (int i = 0; i < kSubWaves; ++i) total += slots[i];
+    unsafe[blockIdx.x] = total > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(total);
+  }
+}
+
+// g(a, b) by one wave in the contract's order, any width: unit u on lane u % 64, ascending
+template <int ELEM, bool VEC>
+__device__ __forceinline__ float subset_wave_dot(const char* a, const char* b, int units, int dim, int lane) {
+  float acc = 0.f;
+  for (int u = lane; u < units; u += kWave) {
+    SubFrag<ELEM> q;
+    q.set(subset_load_unit<ELEM, VEC, false>(b, u, dim));
+    acc = q.dot(subset_load_unit<ELEM, VEC, false>(a, u, dim), acc);
+  }
+  return wave_sum_f32(acc);
+}
+
+// block == 0: no pick, only `finished` (the launch that closes a run)
+template <int ELEM, bool VEC>
+__global__ void __launch_bounds__(kSubsetThreads) subset_round_kernel(
+    const char* __restrict__ E, int64_t n_rows, int dim, const float* __restrict__ rel, float lam, float one_minus_lam,
+    float max_sim, int64_t id_offset, int n_lists, const uint64_t* __restrict__ lists, const uint32_t* __restrict__ unsafe,
+    SubsetHeader* __restrict__ hdr, SubsetCtl* __restrict__ ctl, const float* __restrict__ pen, int64_t* __restrict__ picks,
+    int64_t* __restrict__ out_rows, float* __restrict__ out_gain, int64_t* __restrict__ n_picked_out,
+    int64_t* __restrict__ stats, int block) {
+  constexpr int kPer = kSubsetGrid * kSubsetTopT / kSubsetThreads;
+  __shared__ uint64_t slots[kSubWaves];
+  __shared__ uint64_t s_key[kSubsetMaxBlock];     // the members' up-to-date keys (empty: picked or struck out)
+  __shared__ float s_pen[kSubsetMaxBlock];
+  __shared__ float s_rel[kSubsetMaxBlock];
+  const int tid = static_cast<int>(threadIdx.x);
+  const int lane = tid & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool cut_on = max_sim != __builtin_inff();
+  const int units = (dim + SubElem<ELEM>::kCols - 1) / SubElem<ELEM>::kCols;
+  const int64_t row_bytes = static_cast<int64_t>(dim) * SubElem<ELEM>::kBytes;
+  if (ctl->run_end - hdr->n_picked <= 0) {        // the budget is reached: this launch and those behind it are no-ops
+    if (tid == 0) {
+      ctl->n_list = 0;
+      if (stats) stats[2] = 1;
+    }
+    return;
+  }
+
+  // ---- S and tau
+  uint64_t cand[kPer];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    const int idx = tid + k * kSubsetThreads;
+    cand[k] = idx < n_lists * kSubsetTopT ? lists[(idx / kSubsetTopT) * (kSubsetTopT + 1) + idx % kSubsetTopT] : kKeyEmpty;
+  }
+  uint64_t tau = block_max_key(tid < n_lists ? lists[tid * (kSubsetTopT + 1) + kSubsetTopT] : kKeyEmpty, slots);
+  const bool any_unsafe = block_max_key(tid < n_lists && unsafe[tid] != 0 ? 1ull : 0ull, slots) != 0;
+  int n_s = 0;
+  for (int e = 0; e <= kSubsetMaxBlock; ++e) {
+    uint64_t mine = kKeyEmpty;
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) mine = cand[k] > mine ? cand[k] : mine;
+    const uint64_t best = block_max_key(mine, slots);
+    if (best == kKeyEmpty) break;
+    if (e == kSubsetMaxBlock) {              // the best candidate that is not a member
+      tau = best > tau ? best : tau;
+      break;
+    }
+#pragma unroll
+    for (int k = 0; k < kPer; ++k)
+      if (cand[k] == best) cand[k] = kKeyEmpty;
+    if (tid == 0) s_key[e] = best;
+    n_s = e + 1;
+  }
+  __syncthreads();
+  if (tid < n_s) {
+    const uint32_t row = key_row(s_key[tid]);
+    s_pen[tid] = pen[row];
+    s_rel[tid] = rel[row];
+  }
+  __syncthreads();
+
+  // ---- the greedy inside S
+  const int64_t at0 = hdr->n_picked;
+  const int64_t room = ctl->run_end - at0;
+  int max_take = room < block ? static_cast<int>(room < 0 ? 0 : room) : block;
+  if (any_unsafe && max_take > 1) max_take = 1;
+  int count = 0;
+  while (count < max_take) {
+    const uint64_t best = wave_max_u64(lane < n_s ? s_key[lane] : kKeyEmpty);
+    if (best == kKeyEmpty || best <= tau) break;     // (the same in every wave: the keys change only between the barriers)
+    __syncthreads();
+    const uint32_t s = key_row(best);
+    if (tid == 0) {
+      picks[count] = static_cast<int64_t>(s);
+      out_rows[at0 + count] = static_cast<int64_t>(s) + id_offset;
+      out_gain[at0 + count] = key_score(best);
+    }
+    const char* srow = E + static_cast<int64_t>(s) * row_bytes;
+    for (int i = wave; i < n_s; i += kSubWaves) {
+      const uint64_t ki = s_key[i];
+      if (ki == kKeyEmpty) continue;
+      const uint32_t row = key_row(ki);
+      if (row == s) {
+        if (lane == 0) s_key[i] = kKeyEmpty;
+        continue;
+      }
+      const float gval = subset_wave_dot<ELEM, VEC>(E + static_cast<int64_t>(row) * row_bytes, srow, units, dim, lane);
+      const float pen_new = fmaxf(s_pen[i], gval);
+      bool strike;
+      const uint64_t key = subset_key(pen_new, s_rel[i], row, lam, one_minus_lam, max_sim, cut_on, &strike);
+      if (lane == 0) {
+        s_pen[i] = pen_new;
+        s_key[i] = key;
+      }
+    }
+    __syncthreads();
+    ++count;
+  }
+  if (tid == 0) {
+    ctl->n_list = count;
+    if (count > 0) {
+      hdr->n_picked = at0 + count;
+      *n_picked_out = at0 + count;
+    }
+    if (stats) {
+      if (count > 0) {
+        stats[0] += 1;
+        stats[1] += 1;
+      }
+      stats[2] = (room - count <= 0 || (count == 0 && n_s == 0)) ? 1 : 0;
+    }
+  }
+}
+
+// running maximum over the lanes in ascending order (inclusive), -inf the neutral element: shifts inside the rows of 16
+// lanes, then the rows' totals handed on (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3)
+__device__ __forceinline__ float wave_scan_max_f32(float v) {
+  const int none = __float_as_int(-__builtin_inff());
+#define DEWI_STEP(CTRL, MASK) v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(none, __float_as_int(v), CTRL, MASK, 0xF, false)));
+  DEWI_STEP(0x111, 0xF)    // row_shr:1
+  DEWI_STEP(0x112, 0xF)    // row_shr:2
+  DEWI_STEP(0x114, 0xF)    // row_shr:4
+  DEWI_STEP(0x118, 0xF)    // row_shr:8
+  DEWI_STEP(0x142, 0xA)
+  DEWI_STEP(0x143, 0xC)
+#undef DEWI_STEP
+  return v;
+}
+// lane j receives lane j - 1's value, lane 0 `first` (wave_shr:1)
+__device__ __forceinline__ float wave_shift_up_f32(float v, float first) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(first), __float_as_int(v), 0x138, 0xF, 0xF, false));
+}
+
+// list[0 .. n): the picks (local rows; outside [0, n_rows): skipped), n = ctl->n_list (ctl != NULL) or n_host, at most `block`.
+// Dynamic LDS: block * units * 16 bytes, the picks' rows.
+template <int ELEM, bool VEC, int UPL>
+__global__ void __launch_bounds__(kSubsetThreads) subset_apply_blocked_kernel(
+    const char* __restrict__ E, int64_t n_rows, int dim, float max_sim, const int64_t* __restrict__ list,
+    const SubsetCtl* __restrict__ ctl, int n_host, int block, float* __restrict__ pen, int32_t* __restrict__ owner,
+    uint8_t* __restrict__ struck) {
+  constexpr int kCols = SubElem<ELEM>::kCols;
+  constexpr int R = subset_rows(UPL);
+  constexpr int UU = UPL > 0 ? UPL : 1;
+  extern __shared__ u32x4 q_lds[];                   // [picks][units]
+  __shared__ int32_t s_rows[kSubsetMaxBlock];
+  __shared__ int s_n;
+  const int tid = static_cast<int>(threadIdx.x);
+  const int lane = tid & (kWave - 1);
+  const bool cut_on = max_sim != __builtin_inff();
+  int n_list = ctl ? static_cast<int>(ctl->n_list) : n_host;
+  n_list = n_list < block ? n_list : block;
+  n_list = n_list < kSubsetMaxBlock ? n_list : kSubsetMaxBlock;
+  if (n_list <= 0) return;
+
+  // ---- 1. the picks that exist, in order, and their rows
+  if (tid == 0) {
+    int c = 0;
+    for (int j = 0; j < n_list; ++j) {
+      const int64_t s = list[j];
+      if (s >= 0 && s < n_rows) s_rows[c++] = static_cast<int32_t>(s);
+    }
+    s_n = c;
+  }
+  __syncthreads();
+  const int np = s_n;
+  if (np == 0) return;
+  const int units = (dim + kCols - 1) / kCols;
+  const int64_t row_bytes = static_cast<int64_t>(dim) * SubElem<ELEM>::kBytes;
+  for (int idx = tid; idx < np * units; idx += kSubsetThreads) {
+    const int j = idx / units;
+    q_lds[idx] = subset_load_unit<ELEM, VEC, false>(E + static_cast<int64_t>(s_rows[j]) * row_bytes, idx - j * units, dim);
+  }
+  __syncthreads();
+  [[maybe_unused]] bool act[UU];
+  if constexpr (UPL > 0) {
+#pragma unroll
+    for (int u = 0; u < UPL; ++u) act[u] = lane + 64 * u < units;
+  }
+  const bool has_pick = lane < np;                       // lane j speaks for pick j (np <= 64)
+  const int32_t s_lane = has_pick ? s_rows[lane] : -1;
+
+  // ---- 2. the scan: the steps of subset_apply_kernel, every live row against all picks
+  const int wave_in_block = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t gwave = static_cast<int64_t>(blockIdx.x) * kSubWaves + wave_in_block;
+  const int64_t n_waves = static_cast<int64_t>(gridDim.x) * kSubWaves;
+  const int64_t n_groups = (n_rows + R - 1) / R;
+  auto live_of = [&](int64_t g) -> uint32_t {
+    const int64_t row = g * R + lane;
+    bool ok = false;
+    if (g < n_groups && lane < R && row < n_rows) ok = struck[row] == 0;
+    return static_cast<uint32_t>(__ballot(ok));
+  };
+  uint32_t live = live_of(gwave);
+  for (int64_t g = gwave; g < n_groups; g += n_waves) {
+    [[maybe_unused]] u32x4 v[R][UU];
+    if constexpr (UPL > 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if ((live >> r) & 1u) {
+          const char* p = E + (g * R + r) * row_bytes;
+#pragma unroll
+          for (int u = 0; u < UPL; ++u) {
+            v[r][u] = u32x4{0u, 0u, 0u, 0u};
+            if (act[u]) v[r][u] = subset_load_unit<ELEM, VEC, true>(p, lane + 64 * u, dim);
+          }
+        }
+      }
+    }
+    float pen_v = 0.f;
+    if (lane < R && ((live >> lane) & 1u)) pen_v = pen[g * R + lane];
+    const uint32_t live_next = live_of(g + n_waves);
+    // lane j of gl[r] receives g(row r, pick j): the sums come off the DPP tree as scalars, one select each
+    float gl[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) gl[r] = 0.f;
+    uint32_t todo = live;                // a row leaves once a g has reached max_sim: it is frozen at that pick or before it
+    for (int j = 0; j < np && todo != 0u; ++j) {
+      [[maybe_unused]] SubFrag<ELEM> qf[UU];
+      if constexpr (UPL > 0) {
+#pragma unroll
+        for (int u = 0; u < UPL; ++u) {
+          u32x4 q = u32x4{0u, 0u, 0u, 0u};
+          if (act[u]) q = q_lds[j * units + lane + 64 * u];
+          qf[u].set(q);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if ((todo >> r) & 1u) {
+          float acc = 0.f;
+          if constexpr (UPL > 0) {
+#pragma unroll
+            for (int u = 0; u < UPL; ++u)
+              if (act[u]) acc = qf[u].dot(v[r][u], acc);
+          } else {
+            const char* p = E + (g * R + r) * row_bytes;   // a wide row stays in the caches between the picks
+            for (int u = lane; u < units; u += kWave) {
+              SubFrag<ELEM> q;
+              q.set(q_lds[j * units + u]);
+              acc = q.dot(subset_load_unit<ELEM, VEC, false>(p, u, dim), acc);
+            }
+          }
+          const float gval = wave_sum_f32(acc);
+          gl[r] = lane == j ? gval : gl[r];
+          if (cut_on && gval >= max_sim) todo &= ~(1u << r);
+        }
+      }
+    }
+    // The picks in order, for a row at once: lane j looks at pick j.  "No number" travels as -inf through the running
+    // maximum (no g is infinite: the premise of the blocked form).
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if ((live >> r) & 1u) {
+        const int64_t row = g * R + r;
+        const float pen_old = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pen_v), r));
+        const float none = -__builtin_inff();
+        const float gv = gl[r];
+        const bool num = has_pick && gv == gv;
+        const float run = wave_scan_max_f32(num ? gv : none);          // max of g(., picks 0 .. j)
+        const float p0 = pen_old == pen_old ? pen_old : none;
+        const float before = fmaxf(wave_shift_up_f32(run, none), p0);  // pen as pick j finds it
+        const float after = fmaxf(run, p0);                            // pen as pick j leaves it
+        const uint64_t self_m = __ballot(has_pick && static_cast<int64_t>(s_lane) == row);
+        const uint64_t cut_m = __ballot(has_pick && cut_on && after != none && after >= max_sim);
+        const int j_self = self_m ? __builtin_ctzll(self_m) : 64;      // the row is this pick: struck out, nothing applied from here on
+        const int j_cut = cut_m ? __builtin_ctzll(cut_m) : 64;         // this pick takes pen to max_sim: applied, then frozen
+        const int n_applied = j_self < j_cut + 1 ? j_self : j_cut + 1;
+        const uint64_t takes_m = __ballot(num && lane < n_applied && gv > before);
+        if (takes_m != 0) {
+          const int last = __builtin_amdgcn_readfirstlane(63 - __builtin_clzll(takes_m));
+          const float pen_new = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gv), last));
+          const int32_t owner_new = __builtin_amdgcn_readlane(s_lane, last);
+          if (lane == 0) {
+            owner[row] = owner_new;
+            pen[row] = pen_new;
+          }
+        }
+        if ((self_m | cut_m) != 0 && lane == 0) struck[row] = 1;
+      }
+    }
+    live = live_next;
+  }
+}
+
 }  // namespace
 
 SubsetLayout subset_layout(int64_t n_rows) {
@@ -450,6 +821,156 @@ hipError_t launch_subset_run(const SubsetLayout& L, const void* d_E, int elem_ty
   for (int64_t j = 0; j < n_launches && e == hipSuccess; ++j)
     e = subset_apply(d_E, elem_type, n_rows, dim, d_rel, lam, one_minus_lam, max_sim, id_offset, P.keys + (j & 1) * kSubsetGrid,
                      P.keys + ((j + 1) & 1) * kSubsetGrid, P, d_out_rows, d_out_gain, d_n_picked, nullptr, 0, stream);
+  if (e == hipSuccess && (d_out_pen || d_out_owner)) {
+    hipLaunchKernelGGL(subset_export_kernel, dim3(subset_small_grid(n_rows)), dim3(kSubsetThreads), 0, stream, n_rows, P.pen,
+                       P.owner, id_offset, d_out_pen, d_out_owner);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
+// ---- the blocked form ----------------------------------------------------------------------------------------------
+namespace {
+
+struct SubsetBlockedPtrs {
+  uint64_t* lists;
+  uint32_t* unsafe;
+  int64_t* picks;
+  SubsetCtl* ctl;
+};
+SubsetBlockedPtrs subset_blocked_carve(const SubsetBlockedLayout& L, char* ws) {
+  return SubsetBlockedPtrs{reinterpret_cast<uint64_t*>(ws + L.lists), reinterpret_cast<uint32_t*>(ws + L.unsafe),
+                           reinterpret_cast<int64_t*>(ws + L.picks), reinterpret_cast<SubsetCtl*>(ws + L.ctl)};
+}
+
+template <int ELEM, bool VEC, int UPL>
+hipError_t subset_apply_blocked_one(const char* E, int64_t n_rows, int dim, float max_sim, const int64_t* list, const SubsetCtl* ctl,
+                                    int n_host, int block, const SubsetPtrs& P, hipStream_t stream) {
+  static PerDeviceOnce attr_once;   // one per instantiation
+  const hipError_t ea = attr_once.run([] {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&subset_apply_blocked_kernel<ELEM, VEC, UPL>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kSubsetBlockLds));
+  });
+  if (ea != hipSuccess) return ea;
+  const int units = (dim + SubElem<ELEM>::kCols - 1) / SubElem<ELEM>::kCols;
+  const size_t lds = static_cast<size_t>(block) * units * 16;
+  if (lds > kSubsetBlockLds) return hipErrorInvalidValue;      // (block <= subset_block_max: the entry points check it)
+  hipLaunchKernelGGL((subset_apply_blocked_kernel<ELEM, VEC, UPL>), dim3(subset_grid(n_rows, dim, ELEM)), dim3(kSubsetThreads), lds,
+                     stream, E, n_rows, dim, max_sim, list, ctl, n_host, block, P.pen, P.owner, P.struck);
+  return hipGetLastError();
+}
+
+template <int ELEM, bool VEC>
+hipError_t subset_apply_blocked_upl(int upl, const char* E, int64_t n_rows, int dim, float max_sim, const int64_t* list,
+                                    const SubsetCtl* ctl, int n_host, int block, const SubsetPtrs& P, hipStream_t stream) {
+#define DEWI_SUBSET_LAUNCH(UPL) \
+  return subset_apply_blocked_one<ELEM, VEC, UPL>(E, n_rows, dim, max_sim, list, ctl, n_host, block, P, stream);
+  switch (upl) {
+    case 1: DEWI_SUBSET_LAUNCH(1)
+    case 2: DEWI_SUBSET_LAUNCH(2)
+    case 3: DEWI_SUBSET_LAUNCH(3)
+    case 4: DEWI_SUBSET_LAUNCH(4)
+    case 6: DEWI_SUBSET_LAUNCH(6)
+    case 8: DEWI_SUBSET_LAUNCH(8)
+    default: DEWI_SUBSET_LAUNCH(0)
+  }
+#undef DEWI_SUBSET_LAUNCH
+}
+
+bool subset_vec(const void* d_E, int elem_type, int dim) {
+  return dim % (elem_type == 0 ? 4 : 8) == 0 && reinterpret_cast<uintptr_t>(d_E) % 16 == 0;
+}
+
+hipError_t subset_apply_blocked(const void* d_E, int elem_type, int64_t n_rows, int dim, float max_sim, const int64_t* list,
+                                const SubsetCtl* ctl, int n_host, int block, const SubsetPtrs& P, hipStream_t stream) {
+  const int cols = elem_type == 0 ? 4 : 8;
+  const int per_lane = ((dim + cols - 1) / cols + kWave - 1) / kWave;
+  const int upl = per_lane <= 4 ? per_lane : (per_lane <= 6 ? 6 : (per_lane <= 8 ? 8 : 0));
+  const bool vec = subset_vec(d_E, elem_type, dim);
+  const char* E = static_cast<const char*>(d_E);
+#define DEWI_SUBSET_APPLY(ELEM, VEC) \
+  return subset_apply_blocked_upl<ELEM, VEC>(upl, E, n_rows, dim, max_sim, list, ctl, n_host, block, P, stream)
+  if (elem_type == 0) {
+    if (vec) DEWI_SUBSET_APPLY(0, true);
+    DEWI_SUBSET_APPLY(0, false);
+  }
+  if (vec) DEWI_SUBSET_APPLY(1, true);
+  DEWI_SUBSET_APPLY(1, false);
+#undef DEWI_SUBSET_APPLY
+}
+
+}  // namespace
+
+int subset_block_max(int dim, int elem_type) {
+  if (dim <= 0 || (elem_type != 0 && elem_type != 1)) return 0;
+  const int cols = elem_type == 0 ? 4 : 8;
+  const size_t row_lds = (static_cast<size_t>(dim) + cols - 1) / cols * 16;
+  const size_t fit = kSubsetBlockLds / row_lds;
+  return static_cast<int>(fit < static_cast<size_t>(kSubsetMaxBlock) ? fit : kSubsetMaxBlock);
+}
+
+SubsetBlockedLayout subset_blocked_layout(int64_t n_rows) {
+  SubsetBlockedLayout L;
+  L.state = subset_layout(n_rows);
+  L.lists = (L.state.total + 255) / 256 * 256;
+  L.unsafe = L.lists + static_cast<size_t>(kSubsetGrid) * (kSubsetTopT + 1) * sizeof(uint64_t);
+  L.picks = L.unsafe + kSubsetGrid * sizeof(uint32_t);
+  L.ctl = L.picks + kSubsetMaxBlock * sizeof(int64_t);
+  L.total = L.ctl + 256;
+  return L;
+}
+
+hipError_t launch_subset_seed_blocked(const SubsetBlockedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                                      const int64_t* d_seed_rows, int n_seeds, float max_sim, int block, char* ws,
+                                      hipStream_t stream) {
+  const SubsetPtrs P = subset_carve(L.state, ws);
+  for (int at = 0; at < n_seeds; at += block) {
+    const int n = n_seeds - at < block ? n_seeds - at : block;
+    const hipError_t e = subset_apply_blocked(d_E, elem_type, n_rows, dim, max_sim, d_seed_rows + at, nullptr, n, block, P, stream);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_subset_run_blocked(const SubsetBlockedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                                     const float* d_rel, int64_t budget, float lam, float one_minus_lam, float max_sim,
+                                     int64_t id_offset, int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked,
+                                     float* d_out_pen, int64_t* d_out_owner, int block, int n_rounds, int64_t* d_stats, char* ws,
+                                     hipStream_t stream) {
+  const SubsetPtrs P = subset_carve(L.state, ws);
+  const SubsetBlockedPtrs B = subset_blocked_carve(L, ws);
+  const int grid = subset_grid(n_rows, dim, elem_type);
+  const char* E = static_cast<const char*>(d_E);
+  const bool vec = subset_vec(d_E, elem_type, dim);
+  auto top = [&](int64_t opening_budget) {
+    hipLaunchKernelGGL(subset_top_kernel, dim3(grid), dim3(kSubsetThreads), 0, stream, n_rows, d_rel, lam, one_minus_lam, max_sim,
+                       P.pen, P.struck, B.lists, B.unsafe, P.hdr, B.ctl, opening_budget, d_n_picked, d_stats);
+    return hipGetLastError();
+  };
+  auto round = [&](int take) {
+#define DEWI_SUBSET_ROUND(ELEM, VEC)                                                                                          \
+  hipLaunchKernelGGL((subset_round_kernel<ELEM, VEC>), dim3(1), dim3(kSubsetThreads), 0, stream, E, n_rows, dim, d_rel, lam,   \
+                     one_minus_lam, max_sim, id_offset, grid, B.lists, B.unsafe, P.hdr, B.ctl, P.pen, B.picks, d_out_rows,      \
+                     d_out_gain, d_n_picked, d_stats, take)
+    if (elem_type == 0 && vec) {
+      DEWI_SUBSET_ROUND(0, true);
+    } else if (elem_type == 0) {
+      DEWI_SUBSET_ROUND(0, false);
+    } else if (vec) {
+      DEWI_SUBSET_ROUND(1, true);
+    } else {
+      DEWI_SUBSET_ROUND(1, false);
+    }
+#undef DEWI_SUBSET_ROUND
+    return hipGetLastError();
+  };
+  hipError_t e = top(budget);
+  for (int j = 0; j < n_rounds && e == hipSuccess; ++j) {
+    e = round(block);
+    if (e == hipSuccess) e = subset_apply_blocked(d_E, elem_type, n_rows, dim, max_sim, B.picks, B.ctl, 0, block, P, stream);
+    if (e == hipSuccess) e = top(0);
+  }
+  if (e == hipSuccess && d_stats) e = round(0);      // `finished` for the state as the last pass left it
   if (e == hipSuccess && (d_out_pen || d_out_owner)) {
     hipLaunchKernelGGL(subset_export_kernel, dim3(subset_small_grid(n_rows)), dim3(kSubsetThreads), 0, stream, n_rows, P.pen,
                        P.owner, id_offset, d_out_pen, d_out_owner);

@@ -1628,7 +1628,8 @@ class DeviceCorpus:
 
     # ------------------------------------------------------------------ subset selection (greedy coverage of the whole corpus)
     def select_subset_device(self, budget: int, mmr_lambda: float = 0.5, max_sim: Optional[float] = None, relevance=None,
-                             mask=None, seeds=None, return_coverage: bool = False):
+                             mask=None, seeds=None, return_coverage: bool = False, picks_per_pass: Optional[int] = None,
+                             return_stats: bool = False):
         """Enqueue one SUBSET SELECTION on the current stream: the ``budget`` most informative rows that do not repeat each
         other (``dewi_select_begin`` / ``_seed`` / ``_run``, include/dewi_hip.h).  Greedy maximal marginal relevance over
         ALL rows: each pick is the row with the largest ``mmr_lambda * relevance - (1 - mmr_lambda) * (largest inner product
@@ -1643,7 +1644,14 @@ class DeviceCorpus:
         gain fp32 — the marginal value at the pick, prefilled with NaN —, n_picked int64 [1])``, in pick order; with
         ``return_coverage`` also ``(pen fp32 [N], owner int64 [N])``: every row's largest similarity to the selection (NaN:
         none; frozen once the row was struck out) and the global row that gave it (-1: none).  Cosine / inner-product rows
-        (``space="l2"``: ``NotImplementedError``), fp32 and bf16.  NOT thread-safe on one instance (shared workspace)."""
+        (``space="l2"``: ``NotImplementedError``), fp32 and bf16.  NOT thread-safe on one instance (shared workspace).
+
+        ``picks_per_pass``: ``None`` or 1 is the form above.  An integer above 1 takes the BLOCKED form (``dewi_select_seed_blocked``
+        / ``dewi_select_run_blocked``): the same selection bit for bit, with up to that many picks (clipped to
+        ``dewi_select_block_max`` of the row shape; 0 there: the one-pick form) applied by one corpus pass.  It enqueues about
+        ``1.25 * budget / block + 2`` rounds, reads the run's counters back and repeats with the remaining budget until the
+        run is finished: ONE HOST SYNCHRONISATION PER CHUNK, unlike the one-pick form.  ``return_stats`` appends a dict
+        ``{"rounds", "passes", "picks_per_pass"}`` to the result (one-pick form: one round and one pass per pick)."""
         torch = _torch()
         n = self.n_rows
         if self.space == "l2":
@@ -1679,8 +1687,44 @@ class DeviceCorpus:
         if return_coverage:
             pen = torch.empty(n, dtype=torch.float32, device=self.device)
             owner = torch.empty(n, dtype=torch.int64, device=self.device)
-        ws = self._cached_workspace(("select", n), self._lib.dewi_select_workspace_bytes, n, self.dim, self._elem)
+        block = 1
+        if picks_per_pass is not None:
+            block = int(picks_per_pass)
+            if block < 1:
+                raise ValueError(f"picks_per_pass must be at least 1, got {picks_per_pass}")
+            if block > 1:
+                block = min(block, int(self._lib.dewi_select_block_max(self.dim, self._elem))) or 1
         stream = nat.stream_ptr()
+        if block > 1:
+            # one workspace for both forms: the blocked layout is the one-pick layout plus regions behind it, so an entry that
+            # a one-pick call sized is dropped here once and the larger one serves every later call of either form
+            size = (self._lib.dewi_select_blocked_workspace_bytes, n, self.dim, self._elem, block)
+            hit = self._ws.get(("select", n))
+            if hit is not None and hit[0].numel() < library_size(*size):
+                del self._ws[("select", n)]
+            ws = self._cached_workspace(("select", n), *size)
+            nat.check(self._lib.dewi_select_begin(n, self.dim, self._elem, nat.ptr(m8) if m8 is not None else None, nat.ptr(ws),
+                                                  ws.numel(), stream))
+            if seed_rows is not None and seed_rows.numel():
+                nat.check(self._lib.dewi_select_seed_blocked(nat.ptr(self.emb), self._elem, n, self.dim, nat.ptr(seed_rows),
+                                                             int(seed_rows.numel()), cut, nat.ptr(ws), ws.numel(), stream, block))
+            stats_d = torch.zeros(3, dtype=torch.int64, device=self.device)
+            rounds = passes = done = 0
+            while done < b:
+                left = b - done
+                nat.check(self._lib.dewi_select_run_blocked(
+                    nat.ptr(self.emb), self._elem, n, self.dim, nat.ptr(rel), left, lam, cut, self.id_offset, nat.ptr(rows),
+                    nat.ptr(gain), nat.ptr(n_picked), nat.ptr(pen) if pen is not None else None,
+                    nat.ptr(owner) if owner is not None else None, nat.ptr(ws), ws.numel(), stream, block,
+                    int(1.25 * left / block) + 2, nat.ptr(stats_d)))
+                st = stats_d.tolist()             # (the synchronisation of the chunk)
+                rounds, passes = rounds + st[0], passes + st[1]
+                if st[2]:
+                    break
+                done = int(n_picked.item())
+            out = (rows, gain, n_picked) + ((pen, owner) if return_coverage else ())
+            return out + ({"rounds": rounds, "passes": passes, "picks_per_pass": block},) if return_stats else out
+        ws = self._cached_workspace(("select", n), self._lib.dewi_select_workspace_bytes, n, self.dim, self._elem)
         nat.check(self._lib.dewi_select_begin(n, self.dim, self._elem, nat.ptr(m8) if m8 is not None else None, nat.ptr(ws),
                                               ws.numel(), stream))
         if seed_rows is not None and seed_rows.numel():
@@ -1691,9 +1735,10 @@ class DeviceCorpus:
                 nat.ptr(self.emb), self._elem, n, self.dim, nat.ptr(rel), b, lam, cut, self.id_offset, nat.ptr(rows),
                 nat.ptr(gain), nat.ptr(n_picked), nat.ptr(pen) if pen is not None else None,
                 nat.ptr(owner) if owner is not None else None, nat.ptr(ws), ws.numel(), stream))
-        if return_coverage:
-            return rows, gain, n_picked, pen, owner
-        return rows, gain, n_picked
+        out = (rows, gain, n_picked) + ((pen, owner) if return_coverage else ())
+        if return_stats:       # (no read-back: the counters of the one-pick form are its launches)
+            return out + ({"rounds": b, "passes": b, "picks_per_pass": 1},)
+        return out
 
     # ------------------------------------------------------------------ collapsed search (at most m results per group)
     def make_groups(self, groups) -> DeviceGroups:

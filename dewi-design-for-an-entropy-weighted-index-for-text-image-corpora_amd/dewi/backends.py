@@ -881,7 +881,22 @@ class ExactIndex(BaseIndex):
         ``return_coverage`` also, per document of the index, the nearest selected doc id (``None``: none) and its similarity
         (NaN: none; for a struck-out document as it stood when it was struck out).  ``make_filter(doc_ids=
         index.select_subset(...))`` is the allow-list of the subset.  One corpus pass per pick: thousands of picks over a
-        million documents take seconds.  Cosine indexes (``space="l2"``: ``NotImplementedError``)."""
+        million documents take seconds; ``select_subset_blocked`` gives the same answer with many picks per pass.
+        Cosine indexes (``space="l2"``: ``NotImplementedError``)."""
+        return self._select_subset(budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain, return_coverage, None)
+
+    def select_subset_blocked(self, budget: int, mmr_lambda: float = 0.5, max_sim: Optional[float] = None, relevance=None,
+                              filter=None, seeds: Optional[Sequence[str]] = None, return_gain: bool = False,
+                              return_coverage: bool = False, picks_per_pass: Optional[int] = 32):
+        """``select_subset`` in the BLOCKED form: the same answer bit for bit — an exact batched greedy, not a lazy or
+        stochastic one — with up to ``picks_per_pass`` picks applied by one corpus pass (clipped to what the row shape
+        takes; ``None`` / 1: the one-pick form; ``DeviceCorpus.select_subset_device``).  For budgets of a real fraction of
+        the corpus and for many ``seeds``.  One host synchronisation per chunk of rounds.  A method of its own: the parameter
+        list of ``select_subset`` is fixed."""
+        return self._select_subset(budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain, return_coverage,
+                                   picks_per_pass)
+
+    def _select_subset(self, budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain, return_coverage, picks_per_pass):
         if self.space == "l2":
             raise NotImplementedError("subset selection penalises the inner product of unit rows: space='l2' is not in this build")
         self._ensure_built()
@@ -910,7 +925,7 @@ class ExactIndex(BaseIndex):
             if seeds is not None:
                 seed_rows = self.rows_of([seeds] if isinstance(seeds, str) else list(seeds))
             out = corpus.select_subset_device(int(budget), float(mmr_lambda), max_sim, rel, mask, seed_rows,
-                                              return_coverage=bool(return_coverage))
+                                              return_coverage=bool(return_coverage), picks_per_pass=picks_per_pass)
             kk = int(out[2].item())
             rows = out[0][:kk].cpu().numpy() - corpus.id_offset
             result = [[self._doc_ids[r] for r in rows.tolist()]]

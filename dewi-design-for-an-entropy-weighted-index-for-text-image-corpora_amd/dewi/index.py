@@ -264,6 +264,18 @@ class DewiIndex(BaseIndex):
             self.build()
         return self._backend.select_subset(budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain, return_coverage)
 
+    def select_subset_blocked(self, budget: int, mmr_lambda: float = 0.5, max_sim: Optional[float] = None, relevance=None,
+                              filter=None, seeds=None, return_gain: bool = False, return_coverage: bool = False,
+                              picks_per_pass: Optional[int] = 32):
+        """``select_subset`` with up to ``picks_per_pass`` picks per corpus pass, the same answer bit for bit (additive;
+        ``ExactIndex.select_subset_blocked``)."""
+        if self.space == "l2":
+            raise NotImplementedError("subset selection penalises the inner product of unit rows: space='l2' is not in this build")
+        if not self._built:
+            self.build()
+        return self._backend.select_subset_blocked(budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain,
+                                                   return_coverage, picks_per_pass)
+
     def make_groups(self, groups):
         """Prepare group labels for ``search_collapsed`` / ``search_collapsed_batch`` (``ExactIndex.make_groups``)."""
         if not self._built:

@@ -686,6 +686,59 @@ int dewi_select_run(const void* d_E, int elem_type, int64_t n_rows, int dim, con
                     void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Subset selection, the BLOCKED form (additive to ABI 6): the same greedy selection with up to `block` picks per corpus
+ * pass instead of one.  It is exact, not lazy or stochastic.
+ *
+ * Contract: for every input in which no g(i, s) is +-inf, the state and every output after a blocked call equal those of
+ * the one-pick call with the same arguments bit for bit, whatever `block` and `n_rounds`; a blocked run that stops
+ * unfinished, followed by another run of either form with the remaining budget, equals one run.  Premise for raw callers:
+ * rows whose inner products overflow to +-inf (the index stores normalised rows: not reachable through the Python API)
+ * leave the blocked run's result unspecified; the one-pick run keeps its contract.
+ *
+ * Why it is exact.  m_i = fp32(lambda) * rel_i - fp32(1 - lambda) * pen_i; once pen_i is a number it only grows, rounding
+ * is monotone and fp32(1 - lambda) >= 0, so the key ord(m_i) << 32 | ~row never rises from one pick to the next.  A ROUND
+ * takes a set S of eligible rows with the largest start-of-round keys; tau is the largest start-of-round key of an eligible
+ * row outside S.  Inside the round only the members of S are updated, against the round's own picks; while the best
+ * up-to-date key in S is above tau that member is the global argmax (every row outside S sits at or below its stale key).
+ * The round ends when the best key falls to tau or below, S is exhausted, `block` picks were made or the budget is
+ * reached; ONE corpus pass then applies all of the round's picks to every live row, in pick order.
+ * The exception: a live eligible row whose pen is still NaN is UNSAFE (its first number may be negative: m rises).  While
+ * any unsafe row exists a round takes only its first pick, which is always exact.  Every row is unsafe before the first
+ * pick of an unseeded run; rows that are NaN with everybody stay unsafe for ever (exclude them with the mask).
+ *
+ * dewi_select_block_max(dim, elem_type): the largest `block` the blocked kernels take for this row shape — the picks' rows
+ *   of a pass are kept in LDS —, at most DEWI_SELECT_MAX_BLOCK; 0: none (a bad shape, or one row exceeds the LDS budget): use
+ *   the one-pick form.  Any dim and any element-aligned d_E is taken (whole 16-byte units and an aligned base are loaded
+ *   with 16-byte loads, as in the one-pick form).
+ * dewi_select_blocked_workspace_bytes(n_rows, dim, elem_type, block): the per-row state occupies the same bytes as in
+ *   dewi_select_workspace_bytes' layout, the blocked form's regions lie behind it: dewi_select_begin / _seed / _run work
+ *   on this workspace unchanged, and blocked and one-pick calls can alternate on one state.  0 for a bad shape or a block
+ *   outside [1, block_max].  The blocked calls need nothing of their regions defined on entry.
+ * dewi_select_seed_blocked: dewi_select_seed with up to `block` seeds per corpus pass; the final state is dewi_select_seed's
+ *   bit for bit (out-of-range seeds skipped, a repeated or masked seed applied like any other, a row struck out by seed j
+ *   frozen before seed j + 1).
+ * dewi_select_run_blocked: dewi_select_run's arguments, outputs, p0 / kk, id_offset, d_out_pen / d_out_owner and unwritten
+ *   tail.  It enqueues the opening pass (keys of the state as it stands, no row read) and n_rounds rounds, each of: the round
+ *   kernel (one workgroup), one apply pass, one key pass; no allocation, no synchronisation.  A round that finds the budget
+ *   reached or nothing eligible is a no-op and so are the launches queued behind it.
+ *   d_stats (int64 [3], may be NULL) receives [rounds that made at least one pick, corpus passes that applied picks,
+ *   finished]; finished = the budget was reached or nothing eligible is left.  An unfinished run is continued by another run
+ *   with the remaining budget (d_n_picked tells how many were made).
+ * Errors as for dewi_select_seed / dewi_select_run, and block < 1 or block > dewi_select_block_max(dim, elem_type) or
+ * n_rounds < 0: DEWI_ERR_INVALID_ARG; all reported before any device work.
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_SELECT_MAX_BLOCK 64
+int dewi_select_block_max(int dim, int elem_type);
+size_t dewi_select_blocked_workspace_bytes(int64_t n_rows, int dim, int elem_type, int block);
+int dewi_select_seed_blocked(const void* d_E, int elem_type, int64_t n_rows, int dim, const int64_t* d_seed_rows, int n_seeds,
+                             double max_sim, void* d_workspace, size_t workspace_bytes, void* stream, int block);
+int dewi_select_run_blocked(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel, int64_t budget,
+                            double mmr_lambda, double max_sim, int64_t id_offset, int64_t* d_out_rows, float* d_out_gain,
+                            int64_t* d_n_picked, float* d_out_pen /* may be NULL */, int64_t* d_out_owner /* may be NULL */,
+                            void* d_workspace, size_t workspace_bytes, void* stream, int block, int n_rounds,
+                            int64_t* d_stats /* [3], may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  * Approximate search over an INT8 copy of the corpus (additive to ABI 6; the reference has no counterpart).  One byte per
  * element instead of four: a symmetric per-row scalar quantisation, integer inner products, and — optionally — the candidate
  * cut re-scored from the fp32 rows.  Unlike the bf16 shadow this route is NOT exact: no error band of a useful width is
