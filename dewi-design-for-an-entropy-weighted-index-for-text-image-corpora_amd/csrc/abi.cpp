@@ -1633,6 +1633,87 @@ int dewi_select_run_blocked(const void* d_E, int elem_type, int64_t n_rows, int 
                   "select_run_blocked launch");
 }
 
+// ---- subset selection with group quotas: at most q_g picks per group (additive to ABI 6) ---------------------------------------
+// shape, 2^31, elem_type as check_select_state, then n_groups, then the block (the blocked run only), then the grouped workspace
+static int check_select_grouped(int64_t n_rows, int dim, int elem_type, int64_t n_groups, bool blocked, int block, const void* d_ws,
+                                size_t ws_bytes) {
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
+  if (n_rows > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld: a subset selection takes fewer than 2^31 rows", static_cast<long long>(n_rows));
+  if (int rc = check_elem_type(elem_type)) return rc;
+  if (n_groups < 1 || n_groups > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_INVALID_ARG, "n_groups %lld outside [1, 2^31-1]", static_cast<long long>(n_groups));
+  if (blocked && (block < 1 || block > dewi::subset_block_max(dim, elem_type)))
+    return fail(DEWI_ERR_INVALID_ARG, "block %d outside [1, %d] (dewi_select_block_max of dim %d)", block,
+                dewi::subset_block_max(dim, elem_type), dim);
+  return check_workspace(d_ws, ws_bytes, dewi::subset_grouped_layout(n_rows, n_groups).total);
+}
+// the group arguments of a run: labels, then n_groups' range (before it is narrowed to int), then per_group
+static int check_select_groups(const int32_t* d_labels, int64_t n_groups, const int32_t* d_quota, int per_group) {
+  if (!d_labels) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (n_groups < 1 || n_groups > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_INVALID_ARG, "n_groups %lld outside [1, 2^31-1]", static_cast<long long>(n_groups));
+  if (!d_quota && per_group < 1) return fail(DEWI_ERR_INVALID_ARG, "per_group must be at least 1 (got %d)", per_group);
+  return DEWI_OK;
+}
+
+size_t dewi_select_grouped_workspace_bytes(int64_t n_rows, int dim, int elem_type, int64_t n_groups, int block) {
+  if (n_rows <= 0 || n_rows > 0x7FFFFFFFll || dim <= 0 || (elem_type != 0 && elem_type != 1)) return 0;
+  if (n_groups < 1 || n_groups > 0x7FFFFFFFll) return 0;
+  if (block != 0 && (block < 1 || block > dewi::subset_block_max(dim, elem_type))) return 0;
+  return dewi::subset_grouped_layout(n_rows, n_groups).total;
+}
+
+int dewi_select_groups_begin(int64_t n_rows, int dim, int elem_type, int64_t n_groups, void* d_workspace, size_t workspace_bytes,
+                             void* stream) {
+  if (int rc = check_select_grouped(n_rows, dim, elem_type, n_groups, false, 0, d_workspace, workspace_bytes)) return rc;
+  return launched(dewi::launch_subset_groups_begin(dewi::subset_grouped_layout(n_rows, n_groups), n_groups,
+                                                   static_cast<char*>(d_workspace), static_cast<hipStream_t>(stream)),
+                  "select_groups_begin launch");
+}
+
+int dewi_select_run_grouped(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel, int64_t budget,
+                            double mmr_lambda, double max_sim, int64_t id_offset, int64_t* d_out_rows, float* d_out_gain,
+                            int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner, void* d_workspace, size_t workspace_bytes,
+                            void* stream, const int32_t* d_labels, int64_t n_groups, const int32_t* d_quota, int per_group,
+                            int32_t* d_out_group_counts) {
+  if (!d_E || !d_rel || !d_out_rows || !d_out_gain || !d_n_picked) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (int rc = check_select_groups(d_labels, n_groups, d_quota, per_group)) return rc;
+  if (!(mmr_lambda >= 0.0 && mmr_lambda <= 1.0)) return fail(DEWI_ERR_INVALID_ARG, "mmr_lambda %g outside [0, 1]", mmr_lambda);
+  if (max_sim != max_sim) return fail(DEWI_ERR_INVALID_ARG, "max_sim is NaN");
+  if (int rc = check_select_grouped(n_rows, dim, elem_type, n_groups, false, 0, d_workspace, workspace_bytes)) return rc;
+  if (budget <= 0) return DEWI_OK;
+  const dewi::SubsetGroups Q{d_labels, static_cast<int32_t>(n_groups), d_quota, per_group, d_out_group_counts};
+  return launched(dewi::launch_subset_run_grouped(dewi::subset_grouped_layout(n_rows, n_groups), d_E, elem_type, n_rows, dim, d_rel,
+                                                  budget < n_rows ? budget : n_rows, static_cast<float>(mmr_lambda),
+                                                  static_cast<float>(1.0 - mmr_lambda), static_cast<float>(max_sim), id_offset,
+                                                  d_out_rows, d_out_gain, d_n_picked, d_out_pen, d_out_owner, Q,
+                                                  static_cast<char*>(d_workspace), static_cast<hipStream_t>(stream)),
+                  "select_run_grouped launch");
+}
+
+int dewi_select_run_blocked_grouped(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel, int64_t budget,
+                                    double mmr_lambda, double max_sim, int64_t id_offset, int64_t* d_out_rows, float* d_out_gain,
+                                    int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner, void* d_workspace,
+                                    size_t workspace_bytes, void* stream, int block, int n_rounds, int64_t* d_stats,
+                                    const int32_t* d_labels, int64_t n_groups, const int32_t* d_quota, int per_group,
+                                    int32_t* d_out_group_counts) {
+  if (!d_E || !d_rel || !d_out_rows || !d_out_gain || !d_n_picked) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (int rc = check_select_groups(d_labels, n_groups, d_quota, per_group)) return rc;
+  if (!(mmr_lambda >= 0.0 && mmr_lambda <= 1.0)) return fail(DEWI_ERR_INVALID_ARG, "mmr_lambda %g outside [0, 1]", mmr_lambda);
+  if (max_sim != max_sim) return fail(DEWI_ERR_INVALID_ARG, "max_sim is NaN");
+  if (n_rounds < 0) return fail(DEWI_ERR_INVALID_ARG, "n_rounds must not be negative (got %d)", n_rounds);
+  if (int rc = check_select_grouped(n_rows, dim, elem_type, n_groups, true, block, d_workspace, workspace_bytes)) return rc;
+  if (budget <= 0) return DEWI_OK;
+  const dewi::SubsetGroups Q{d_labels, static_cast<int32_t>(n_groups), d_quota, per_group, d_out_group_counts};
+  return launched(dewi::launch_subset_run_blocked_grouped(
+                      dewi::subset_grouped_layout(n_rows, n_groups), d_E, elem_type, n_rows, dim, d_rel,
+                      budget < n_rows ? budget : n_rows, static_cast<float>(mmr_lambda), static_cast<float>(1.0 - mmr_lambda),
+                      static_cast<float>(max_sim), id_offset, d_out_rows, d_out_gain, d_n_picked, d_out_pen, d_out_owner, block,
+                      n_rounds, d_stats, Q, static_cast<char*>(d_workspace), static_cast<hipStream_t>(stream)),
+                  "select_run_blocked_grouped launch");
+}
+
 // ---- approximate search over an int8 copy of the corpus (additive to ABI 6; knn_scan_i8.hip) ---------------------------------
 // the shape checks the int8 entry points share, in one order: rows, 2^32, dim, the unit (16 codes; the re-scoring: 4 floats)
 static int check_i8_shape(int64_t n_rows, int dim, int unit) {

@@ -476,6 +476,35 @@ hipError_t launch_subset_run_blocked(const SubsetBlockedLayout& L, const void* d
                                      float* d_out_pen, int64_t* d_out_owner, int block, int n_rounds, int64_t* d_stats, char* ws,
                                      hipStream_t stream);
 
+// ---- select_subset.hip, group quotas: at most q_g picks per group (include/dewi_hip.h, "GROUP QUOTAS") ----
+// ONE layout for both grouped forms (the grouped run calls take no `block`, and either continues the other): the blocked
+// layout — so every ungrouped call works on it unchanged — with the group regions behind it.
+struct SubsetGroupedLayout {
+  SubsetBlockedLayout blocked;         // the one-pick and the blocked form's regions, at the same offsets
+  size_t rec;                          // {int32 group, uint32 count} [2]: the count a one-pick launch changed, ping-pong by parity
+  size_t fills;                        // int32 [kSubsetMaxBlock]: per pick of the round's list the group it fills (-1: none)
+  size_t counts;                       // uint32 [n_groups]: picks made in each group
+  size_t total;
+};
+struct SubsetGroups {                  // the caller's group arguments
+  const int32_t* d_labels;             // [n_rows]
+  int32_t n_groups;
+  const int32_t* d_quota;              // [n_groups] or NULL: per_group everywhere
+  int32_t per_group;
+  int32_t* d_out_counts;               // [n_groups] or NULL
+};
+SubsetGroupedLayout subset_grouped_layout(int64_t n_rows, int64_t n_groups);
+hipError_t launch_subset_groups_begin(const SubsetGroupedLayout& L, int64_t n_groups, char* ws, hipStream_t stream);
+hipError_t launch_subset_run_grouped(const SubsetGroupedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                                     const float* d_rel, int64_t n_launches, float lam, float one_minus_lam, float max_sim,
+                                     int64_t id_offset, int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked,
+                                     float* d_out_pen, int64_t* d_out_owner, const SubsetGroups& Q, char* ws, hipStream_t stream);
+hipError_t launch_subset_run_blocked_grouped(const SubsetGroupedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                                             const float* d_rel, int64_t budget, float lam, float one_minus_lam, float max_sim,
+                                             int64_t id_offset, int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked,
+                                             float* d_out_pen, int64_t* d_out_owner, int block, int n_rounds, int64_t* d_stats,
+                                             const SubsetGroups& Q, char* ws, hipStream_t stream);
+
 // ---- collapse.hip: at most per_group results per label, one workgroup per query (no workspace)
 constexpr int kCollapseMaxCandidates = DEWI_COLLAPSE_MAX_CANDIDATES;
 static_assert(kCollapseMaxCandidates == kMaxSortCandidates, "a collapsed pool is what one workgroup sorts in LDS");

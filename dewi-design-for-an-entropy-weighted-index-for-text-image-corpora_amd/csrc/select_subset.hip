@@ -29,6 +29,14 @@
 // outside the rows is touched.  Rows of up to 512 units keep the picked row in registers (UPL units per lane); wider rows
 // re-read it from memory (it stays in the caches) one unit at a time.
 //
+// Group quotas (include/dewi_hip.h, "GROUP QUOTAS"): GROUPED instantiations of the same kernels — a trailing
+// parameter pack, empty for the ungrouped launches, whose code is what it was.  One-pick form: launch j must know whether its
+// pick fills its group, that is the group's count BEFORE the launch, while workgroup 0 raises it: the raise travels as a
+// record {group, new count} in slot (j + 1) & 1 of a two-slot array; launch j + 1 reads slot j & 1 (its pick's group is the
+// record's: the record's count; otherwise counts[group]) and its workgroup 0 stores the record into `counts` — an address no
+// workgroup of that launch reads.  A pass whose pick fills a group reads the live rows' labels and strikes the group out behind
+// the update; no other pass but the opening key pass reads labels.
+//
 // Roofline: HBM.  Algorithmic bytes per pick = live rows * (row bytes + 1 B struck-out byte + 4 B rel + 4 B pen read, + 4 B pen
 // and 4 B owner written where they change).  Measured: DESIGN.md 4.1u, profiles/r17/select/.
 #include <stdlib.h>
@@ -69,6 +77,48 @@ __device__ __forceinline__ uint64_t block_max_key(uint64_t key, uint64_t (&slots
   return best;
 }
 
+// ---- group quotas (include/dewi_hip.h, "GROUP QUOTAS"): what the grouped instantiations take on top
+struct SubsetGroupArgs {
+  const int32_t* labels;   // [n_rows]; grouped: 0 <= label < n_groups
+  const int32_t* quota;    // [n_groups], or NULL: per_group for every group
+  uint32_t* counts;        // [n_groups], in the workspace
+  int32_t n_groups;
+  int32_t per_group;
+};
+// the change one pick launch of the one-pick form made to the counts, applied to `counts` by the launch behind it (ping-pong
+// by launch parity like the key arrays: no launch reads an address it writes); g < 0: none
+struct SubsetGroupRec {
+  int32_t g;
+  uint32_t count;
+};
+// What a GROUPED launch passes behind the kernel's own arguments.  The kernels below take it as a parameter pack `G... grp`:
+// empty for the ungrouped launches — their signatures and their code stay what they were —, one SubsetGroupCall for the
+// grouped ones; `if constexpr (GROUPED)` fences everything that touches it.
+struct SubsetGroupCall {
+  SubsetGroupArgs ga;
+  const SubsetGroupRec* rec_in;    // one-pick form: the record the launch before left (key pass: unused)
+  SubsetGroupRec* rec_out;         // one-pick form: this launch's record (key pass: both records, cleared)
+  int32_t* fills;                  // blocked form: per pick of the round's list the group it fills (-1: none)
+};
+struct SubsetNoGroups {};
+__device__ __forceinline__ SubsetNoGroups subset_group_of() { return SubsetNoGroups{}; }
+__device__ __forceinline__ const SubsetGroupCall& subset_group_of(const SubsetGroupCall& g) { return g; }
+#define DEWI_SUBSET_GROUP_PACK                                  \
+  constexpr bool GROUPED = sizeof...(G) != 0;                   \
+  static_assert(sizeof...(G) <= 1, "one SubsetGroupCall");      \
+  [[maybe_unused]] const auto& gq = subset_group_of(grp...);
+
+__device__ __forceinline__ bool subset_grouped(int32_t label, int32_t n_groups) {
+  return static_cast<uint32_t>(label) < static_cast<uint32_t>(n_groups);
+}
+__device__ __forceinline__ int32_t subset_quota(const SubsetGroupArgs& ga, int32_t g) { return ga.quota ? ga.quota[g] : ga.per_group; }
+// a grouped row whose group is full (the counts are current: no record is pending)
+__device__ __forceinline__ bool subset_group_full(const SubsetGroupArgs& ga, int64_t row) {
+  const int32_t g = ga.labels[row];
+  if (!subset_grouped(g, ga.n_groups)) return false;
+  return static_cast<int64_t>(ga.counts[g]) >= static_cast<int64_t>(subset_quota(ga, g));
+}
+
 // ---- begin: every region of the state made defined
 __global__ void __launch_bounds__(kSubsetThreads) subset_begin_kernel(int64_t n_rows, const uint8_t* __restrict__ mask,
                                                                       uint64_t* __restrict__ keys, SubsetHeader* __restrict__ hdr,
@@ -86,12 +136,16 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_begin_kernel(int64_t n_
 }
 
 // ---- the keys of the state as it stands (the first launch of a run: no pick is applied, no row is read)
+// GROUPED: the rows of full groups are struck out as well, and both records are cleared (the closing launch of the run
+// before applied the last one)
+template <class... G>
 __global__ void __launch_bounds__(kSubsetThreads) subset_keys_kernel(int64_t n_rows, const float* __restrict__ rel, float lam,
                                                                      float one_minus_lam, float max_sim,
                                                                      const float* __restrict__ pen, uint8_t* __restrict__ struck,
                                                                      uint64_t* __restrict__ keys_out,
                                                                      const SubsetHeader* __restrict__ hdr,
-                                                                     int64_t* __restrict__ n_picked_out) {
+                                                                     int64_t* __restrict__ n_picked_out, G... grp) {
+  DEWI_SUBSET_GROUP_PACK
   __shared__ uint64_t slots[kSubWaves];
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kSubsetThreads + threadIdx.x;
   const int64_t nt = static_cast<int64_t>(gridDim.x) * kSubsetThreads;
@@ -100,14 +154,50 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_keys_kernel(int64_t n_r
   for (int64_t i = t; i < n_rows; i += nt) {
     if (struck[i]) continue;
     bool strike;
-    const uint64_t key = subset_key(pen[i], rel[i], static_cast<uint32_t>(i), lam, one_minus_lam, max_sim, cut_on, &strike);
+    uint64_t key = subset_key(pen[i], rel[i], static_cast<uint32_t>(i), lam, one_minus_lam, max_sim, cut_on, &strike);
     if (strike) struck[i] = 1;
+    if constexpr (GROUPED) {
+      if (!strike && subset_group_full(gq.ga, i)) {
+        struck[i] = 1;
+        key = kKeyEmpty;
+      }
+    }
     best = key > best ? key : best;
   }
   best = block_max_key(best, slots);
   if (threadIdx.x == 0) {
     keys_out[blockIdx.x] = best;
     if (blockIdx.x == 0) *n_picked_out = hdr->n_picked;
+    if constexpr (GROUPED) {
+      if (blockIdx.x == 0) gq.rec_out[0] = gq.rec_out[1] = SubsetGroupRec{-1, 0u};
+    }
+  }
+}
+
+// ---- group quotas: the counts zeroed, the records cleared (dewi_select_groups_begin)
+__global__ void __launch_bounds__(kSubsetThreads) subset_groups_begin_kernel(int64_t n_groups, uint32_t* __restrict__ counts,
+                                                                             SubsetGroupRec* __restrict__ rec,
+                                                                             int32_t* __restrict__ fills) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kSubsetThreads + threadIdx.x;
+  const int64_t nt = static_cast<int64_t>(gridDim.x) * kSubsetThreads;
+  if (t < 2) rec[t] = SubsetGroupRec{-1, 0u};
+  if (t < kSubsetMaxBlock) fills[t] = -1;
+  for (int64_t g = t; g < n_groups; g += nt) counts[g] = 0u;
+}
+// ---- the launch that closes a grouped run: the last record applied (one-pick form; rec NULL: none), the counts for the caller
+__global__ void __launch_bounds__(kSubsetThreads) subset_groups_close_kernel(int64_t n_groups, uint32_t* __restrict__ counts,
+                                                                             const SubsetGroupRec* __restrict__ rec,
+                                                                             int32_t* __restrict__ out_counts) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kSubsetThreads + threadIdx.x;
+  const int64_t nt = static_cast<int64_t>(gridDim.x) * kSubsetThreads;
+  const SubsetGroupRec last = rec ? *rec : SubsetGroupRec{-1, 0u};
+  for (int64_t g = t; g < n_groups; g += nt) {
+    uint32_t c = counts[g];
+    if (last.g >= 0 && g == last.g) {
+      c = last.count;
+      counts[g] = c;
+    }
+    if (out_counts) out_counts[g] = static_cast<int32_t>(c);
   }
 }
 
@@ -202,24 +292,28 @@ int subset_grid(int64_t n_rows, int dim, int elem_type) {
 
 // UPL: 16-byte units per lane held in registers (rows of up to 64 * UPL units); 0: any width, the picked row re-read.
 // d_seeds != NULL: the pick is d_seeds[seed_idx] (a local row; outside [0, n_rows): nothing happens); no keys, no outputs.
-template <int ELEM, bool VEC, int UPL>
+// GROUPED (never seeding): the pick raises its group's count — through rec_out, see SubsetGroupRec —, and a pick that FILLS its
+// group strikes out the group's live rows behind their update; only such a pass reads labels (4 B per live row).
+template <int ELEM, bool VEC, int UPL, class... G>
 __global__ void __launch_bounds__(kSubsetThreads) subset_apply_kernel(
     const char* __restrict__ E, int64_t n_rows, int dim, const float* __restrict__ rel, float lam, float one_minus_lam,
     float max_sim, int64_t id_offset, const uint64_t* __restrict__ keys_in, uint64_t* __restrict__ keys_out,
     SubsetHeader* __restrict__ hdr, float* __restrict__ pen, int32_t* __restrict__ owner, uint8_t* __restrict__ struck,
     int64_t* __restrict__ out_rows, float* __restrict__ out_gain, int64_t* __restrict__ n_picked_out,
-    const int64_t* __restrict__ d_seeds, int seed_idx) {
+    const int64_t* __restrict__ d_seeds, int seed_idx, G... grp) {
+  DEWI_SUBSET_GROUP_PACK
   constexpr int kCols = SubElem<ELEM>::kCols;
   constexpr int R = subset_rows(UPL);
   constexpr int UU = UPL > 0 ? UPL : 1;
   __shared__ uint64_t slots[kSubWaves];
   const int tid = static_cast<int>(threadIdx.x);
   const int lane = tid & (kWave - 1);
-  const bool seeding = d_seeds != nullptr;
+  const bool seeding = !GROUPED && d_seeds != nullptr;
   const bool cut_on = max_sim != __builtin_inff();
 
   // ---- 1. the pick
   int64_t s;
+  [[maybe_unused]] int32_t fill_g = -1;              // GROUPED: the group this pick fills (workgroup-uniform; -1: none)
   if (seeding) {
     s = d_seeds[seed_idx];
     if (s < 0 || s >= n_rows) return;
@@ -227,9 +321,32 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_apply_kernel(
     const uint64_t best = block_max_key(tid < static_cast<int>(gridDim.x) ? keys_in[tid] : kKeyEmpty, slots);   // (gridDim.x <= kSubsetGrid <= threads)
     if (best == kKeyEmpty) {                       // nothing eligible: the launches behind this one find the same
       if (tid == 0) keys_out[blockIdx.x] = kKeyEmpty;
+      if constexpr (GROUPED) {
+        if (blockIdx.x == 0 && tid == 0) {           // the record is handed on as "none"; applying it twice is harmless
+          const SubsetGroupRec prev = *gq.rec_in;
+          if (prev.g >= 0) gq.ga.counts[prev.g] = prev.count;
+          *gq.rec_out = SubsetGroupRec{-1, 0u};
+        }
+      }
       return;
     }
     s = static_cast<int64_t>(key_row(best));
+    if constexpr (GROUPED) {
+      // c_g as it stood before this pass: the launch before may have changed it (its record), and workgroup 0 of THIS
+      // launch writes counts[prev.g] — which nobody reads here: prev.g == gs takes the record's value
+      const SubsetGroupRec prev = *gq.rec_in;
+      const int32_t gs = gq.ga.labels[s];
+      SubsetGroupRec now{-1, 0u};
+      if (subset_grouped(gs, gq.ga.n_groups)) {
+        const uint32_t before = prev.g == gs ? prev.count : gq.ga.counts[gs];
+        now = SubsetGroupRec{gs, before + 1u};
+        if (static_cast<int64_t>(before) + 1 >= static_cast<int64_t>(subset_quota(gq.ga, gs))) fill_g = gs;
+      }
+      if (blockIdx.x == 0 && tid == 0) {
+        if (prev.g >= 0) gq.ga.counts[prev.g] = prev.count;
+        *gq.rec_out = now;
+      }
+    }
     if (blockIdx.x == 0 && tid == 0) {
       const int64_t at = hdr->n_picked;
       out_rows[at] = s + id_offset;
@@ -289,9 +406,13 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_apply_kernel(
       }
     }
     float pen_v = 0.f, rel_v = 0.f;                     // behind the rows: the rows' requests go out first
+    [[maybe_unused]] int32_t lab_v = -1;
     if (lane < R && ((live >> lane) & 1u)) {
       pen_v = pen[g * R + lane];
       if (!seeding) rel_v = rel[g * R + lane];
+      if constexpr (GROUPED) {
+        if (fill_g >= 0) lab_v = gq.ga.labels[g * R + lane];
+      }
     }
     const uint32_t live_next = live_of(g + n_waves);   // the next step's struck-out bytes travel with this step's rows
 #pragma unroll
@@ -322,8 +443,14 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_apply_kernel(
           pen[row] = pen_new;
         }
         bool strike;
-        const uint64_t key = subset_key(pen_new, rel_row, static_cast<uint32_t>(row), lam, one_minus_lam, max_sim, cut_on, &strike);
+        uint64_t key = subset_key(pen_new, rel_row, static_cast<uint32_t>(row), lam, one_minus_lam, max_sim, cut_on, &strike);
         if (lane == 0 && strike) struck[row] = 1;
+        if constexpr (GROUPED) {
+          if (fill_g >= 0 && __builtin_amdgcn_readlane(lab_v, r) == fill_g) {     // updated by the pick that fills its group, then frozen
+            key = kKeyEmpty;
+            if (lane == 0) struck[row] = 1;
+          }
+        }
         if (!seeding) best = key > best ? key : best;
       }
     }
@@ -365,11 +492,16 @@ template <int ELEM, bool VEC>
 hipError_t subset_apply_upl(int upl, const char* E, int64_t n_rows, int dim, const float* rel, float lam, float one_minus_lam,
                             float max_sim, int64_t id_offset, const uint64_t* keys_in, uint64_t* keys_out, const SubsetPtrs& P,
                             int64_t* out_rows, float* out_gain, int64_t* n_picked, const int64_t* d_seeds, int seed_idx,
-                            hipStream_t stream) {
+                            const SubsetGroupCall* G, hipStream_t stream) {
 #define DEWI_SUBSET_LAUNCH(UPL)                                                                                                \
-  hipLaunchKernelGGL((subset_apply_kernel<ELEM, VEC, UPL>), dim3(grid), dim3(kSubsetThreads), 0, stream, E, n_rows, dim,        \
-                     rel, lam, one_minus_lam, max_sim, id_offset, keys_in, keys_out, P.hdr, P.pen, P.owner, P.struck, out_rows,   \
-                     out_gain, n_picked, d_seeds, seed_idx);                                                                    \
+  if (G)                                                                                                                       \
+    hipLaunchKernelGGL((subset_apply_kernel<ELEM, VEC, UPL, SubsetGroupCall>), dim3(grid), dim3(kSubsetThreads), 0, stream, E,  \
+                       n_rows, dim, rel, lam, one_minus_lam, max_sim, id_offset, keys_in, keys_out, P.hdr, P.pen, P.owner,      \
+                       P.struck, out_rows, out_gain, n_picked, d_seeds, seed_idx, *G);                                          \
+  else                                                                                                                         \
+    hipLaunchKernelGGL((subset_apply_kernel<ELEM, VEC, UPL>), dim3(grid), dim3(kSubsetThreads), 0, stream, E, n_rows, dim,      \
+                       rel, lam, one_minus_lam, max_sim, id_offset, keys_in, keys_out, P.hdr, P.pen, P.owner, P.struck,         \
+                       out_rows, out_gain, n_picked, d_seeds, seed_idx);                                                        \
   break;
   const int grid = subset_grid(n_rows, dim, ELEM);
   switch (upl) {
@@ -388,7 +520,7 @@ hipError_t subset_apply_upl(int upl, const char* E, int64_t n_rows, int dim, con
 hipError_t subset_apply(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* rel, float lam, float one_minus_lam,
                         float max_sim, int64_t id_offset, const uint64_t* keys_in, uint64_t* keys_out, const SubsetPtrs& P,
                         int64_t* out_rows, float* out_gain, int64_t* n_picked, const int64_t* d_seeds, int seed_idx,
-                        hipStream_t stream) {
+                        const SubsetGroupCall* G, hipStream_t stream) {
   const int cols = elem_type == 0 ? 4 : 8;
   const int units = (dim + cols - 1) / cols;
   const int per_lane = (units + kWave - 1) / kWave;
@@ -397,7 +529,7 @@ hipError_t subset_apply(const void* d_E, int elem_type, int64_t n_rows, int dim,
   const char* E = static_cast<const char*>(d_E);
 #define DEWI_SUBSET_APPLY(ELEM, VEC)                                                                                          \
   return subset_apply_upl<ELEM, VEC>(upl, E, n_rows, dim, rel, lam, one_minus_lam, max_sim, id_offset, keys_in, keys_out, P,   \
-                                     out_rows, out_gain, n_picked, d_seeds, seed_idx, stream)
+                                     out_rows, out_gain, n_picked, d_seeds, seed_idx, G, stream)
   if (elem_type == 0) {
     if (vec) DEWI_SUBSET_APPLY(0, true);
     DEWI_SUBSET_APPLY(0, false);
@@ -429,11 +561,15 @@ static_assert(kSubsetMaxBlock <= kWave, "the round kernel reduces the members' k
 
 // opening (budget > 0): the first launch of a run — the run's end, the counters; otherwise a pass behind a round that made
 // no pick returns at once: the lists still describe the state.
+// GROUPED: the opening pass strikes out the rows of full groups as well (the only key pass that reads labels: behind a
+// round the apply pass has struck them out).
+template <class... G>
 __global__ void __launch_bounds__(kSubsetThreads) subset_top_kernel(
     int64_t n_rows, const float* __restrict__ rel, float lam, float one_minus_lam, float max_sim, const float* __restrict__ pen,
     uint8_t* __restrict__ struck, uint64_t* __restrict__ lists, uint32_t* __restrict__ unsafe,
     const SubsetHeader* __restrict__ hdr, SubsetCtl* __restrict__ ctl, int64_t budget, int64_t* __restrict__ n_picked_out,
-    int64_t* __restrict__ stats) {
+    int64_t* __restrict__ stats, G... grp) {
+  DEWI_SUBSET_GROUP_PACK
   __shared__ uint64_t slots[kSubWaves];
   const int tid = static_cast<int>(threadIdx.x);
   if (budget > 0) {
@@ -458,10 +594,18 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_top_kernel(
         if (struck[i]) continue;
         const float p = pen[i], r = rel[i];
         bool strike;
-        const uint64_t key = subset_key(p, r, static_cast<uint32_t>(i), lam, one_minus_lam, max_sim, cut_on, &strike);
+        uint64_t key = subset_key(p, r, static_cast<uint32_t>(i), lam, one_minus_lam, max_sim, cut_on, &strike);
         if (k == 0) {
+          [[maybe_unused]] bool full = false;
+          if constexpr (GROUPED) {
+            if (budget > 0 && !strike && subset_group_full(gq.ga, i)) {
+              full = true;
+              struck[i] = 1;
+              key = kKeyEmpty;
+            }
+          }
           if (strike) struck[i] = 1;
-          else if (r == r && !(p == p)) ++n_unsafe;
+          else if (!full && r == r && !(p == p)) ++n_unsafe;
         }
         if ((k == 0 || key < prev) && key > best) best = key;
       }
@@ -495,18 +639,25 @@ __device__ __forceinline__ float subset_wave_dot(const char* a, const char* b, i
 }
 
 // block == 0: no pick, only `finished` (the launch that closes a run)
-template <int ELEM, bool VEC>
+// GROUPED: the workgroup keeps the members' labels and their groups' counts; a pick raises its group's count (in `counts`
+// too: this is the only workgroup of the launch), and one that fills the group empties the group's other members at once and
+// is marked in `fills` for the apply pass.
+template <int ELEM, bool VEC, class... G>
 __global__ void __launch_bounds__(kSubsetThreads) subset_round_kernel(
     const char* __restrict__ E, int64_t n_rows, int dim, const float* __restrict__ rel, float lam, float one_minus_lam,
     float max_sim, int64_t id_offset, int n_lists, const uint64_t* __restrict__ lists, const uint32_t* __restrict__ unsafe,
     SubsetHeader* __restrict__ hdr, SubsetCtl* __restrict__ ctl, const float* __restrict__ pen, int64_t* __restrict__ picks,
     int64_t* __restrict__ out_rows, float* __restrict__ out_gain, int64_t* __restrict__ n_picked_out,
-    int64_t* __restrict__ stats, int block) {
+    int64_t* __restrict__ stats, int block, G... grp) {
+  DEWI_SUBSET_GROUP_PACK
   constexpr int kPer = kSubsetGrid * kSubsetTopT / kSubsetThreads;
   __shared__ uint64_t slots[kSubWaves];
   __shared__ uint64_t s_key[kSubsetMaxBlock];     // the members' up-to-date keys (empty: picked or struck out)
   __shared__ float s_pen[kSubsetMaxBlock];
   __shared__ float s_rel[kSubsetMaxBlock];
+  [[maybe_unused]] __shared__ int32_t s_lab[GROUPED ? kSubsetMaxBlock : 1];     // the member's group (-1: ungrouped)
+  [[maybe_unused]] __shared__ uint32_t s_cnt[GROUPED ? kSubsetMaxBlock : 1];    // its count, kept current while the member is live
+  [[maybe_unused]] __shared__ int32_t s_quota[GROUPED ? kSubsetMaxBlock : 1];
   const int tid = static_cast<int>(threadIdx.x);
   const int lane = tid & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -552,6 +703,13 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_round_kernel(
     const uint32_t row = key_row(s_key[tid]);
     s_pen[tid] = pen[row];
     s_rel[tid] = rel[row];
+    if constexpr (GROUPED) {
+      const int32_t lab = gq.ga.labels[row];
+      const bool grouped = subset_grouped(lab, gq.ga.n_groups);
+      s_lab[tid] = grouped ? lab : -1;
+      s_cnt[tid] = grouped ? gq.ga.counts[lab] : 0u;
+      s_quota[tid] = grouped ? subset_quota(gq.ga, lab) : 0;
+    }
   }
   __syncthreads();
 
@@ -564,12 +722,26 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_round_kernel(
   while (count < max_take) {
     const uint64_t best = wave_max_u64(lane < n_s ? s_key[lane] : kKeyEmpty);
     if (best == kKeyEmpty || best <= tau) break;     // (the same in every wave: the keys change only between the barriers)
+    [[maybe_unused]] int32_t g_pick = -1;            // GROUPED: the pick's group, its new count, whether that fills it
+    [[maybe_unused]] uint32_t cnt_new = 0u;
+    [[maybe_unused]] bool fills_g = false;
+    if constexpr (GROUPED) {
+      // the picked member (keys are unique); nobody writes ITS count in this turn: it is picked, not updated
+      const int at = __builtin_ctzll(__ballot(lane < n_s && s_key[lane < n_s ? lane : 0] == best));
+      g_pick = s_lab[at];
+      cnt_new = s_cnt[at] + 1u;
+      fills_g = g_pick >= 0 && static_cast<int64_t>(cnt_new) >= static_cast<int64_t>(s_quota[at]);
+    }
     __syncthreads();
     const uint32_t s = key_row(best);
     if (tid == 0) {
       picks[count] = static_cast<int64_t>(s);
       out_rows[at0 + count] = static_cast<int64_t>(s) + id_offset;
       out_gain[at0 + count] = key_score(best);
+      if constexpr (GROUPED) {
+        gq.fills[count] = fills_g ? g_pick : -1;
+        if (g_pick >= 0) gq.ga.counts[g_pick] = cnt_new;
+      }
     }
     const char* srow = E + static_cast<int64_t>(s) * row_bytes;
     for (int i = wave; i < n_s; i += kSubWaves) {
@@ -583,7 +755,13 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_round_kernel(
       const float gval = subset_wave_dot<ELEM, VEC>(E + static_cast<int64_t>(row) * row_bytes, srow, units, dim, lane);
       const float pen_new = fmaxf(s_pen[i], gval);
       bool strike;
-      const uint64_t key = subset_key(pen_new, s_rel[i], row, lam, one_minus_lam, max_sim, cut_on, &strike);
+      uint64_t key = subset_key(pen_new, s_rel[i], row, lam, one_minus_lam, max_sim, cut_on, &strike);
+      if constexpr (GROUPED) {
+        if (g_pick >= 0 && s_lab[i] == g_pick) {
+          if (fills_g) key = kKeyEmpty;
+          if (lane == 0) s_cnt[i] = cnt_new;
+        }
+      }
       if (lane == 0) {
         s_pen[i] = pen_new;
         s_key[i] = key;
@@ -629,17 +807,23 @@ __device__ __forceinline__ float wave_shift_up_f32(float v, float first) {
 
 // list[0 .. n): the picks (local rows; outside [0, n_rows): skipped), n = ctl->n_list (ctl != NULL) or n_host, at most `block`.
 // Dynamic LDS: block * units * 16 bytes, the picks' rows.
-template <int ELEM, bool VEC, int UPL>
+// GROUPED: fills[j] is the group pick j fills (-1: none) — a third freeze point per row, beside its own pick and max_sim:
+// the first pick of the list that fills the row's group is applied, then the row is frozen.  Labels are read only by a pass
+// whose list fills a group.
+template <int ELEM, bool VEC, int UPL, class... G>
 __global__ void __launch_bounds__(kSubsetThreads) subset_apply_blocked_kernel(
     const char* __restrict__ E, int64_t n_rows, int dim, float max_sim, const int64_t* __restrict__ list,
     const SubsetCtl* __restrict__ ctl, int n_host, int block, float* __restrict__ pen, int32_t* __restrict__ owner,
-    uint8_t* __restrict__ struck) {
+    uint8_t* __restrict__ struck, G... grp) {
+  DEWI_SUBSET_GROUP_PACK
   constexpr int kCols = SubElem<ELEM>::kCols;
   constexpr int R = subset_rows(UPL);
   constexpr int UU = UPL > 0 ? UPL : 1;
   extern __shared__ u32x4 q_lds[];                   // [picks][units]
   __shared__ int32_t s_rows[kSubsetMaxBlock];
   __shared__ int s_n;
+  [[maybe_unused]] __shared__ int32_t s_fill[GROUPED ? kSubsetMaxBlock : 1];
+  [[maybe_unused]] __shared__ int s_any_fill;
   const int tid = static_cast<int>(threadIdx.x);
   const int lane = tid & (kWave - 1);
   const bool cut_on = max_sim != __builtin_inff();
@@ -651,11 +835,19 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_apply_blocked_kernel(
   // ---- 1. the picks that exist, in order, and their rows
   if (tid == 0) {
     int c = 0;
+    [[maybe_unused]] int any_fill = 0;
     for (int j = 0; j < n_list; ++j) {
       const int64_t s = list[j];
-      if (s >= 0 && s < n_rows) s_rows[c++] = static_cast<int32_t>(s);
+      if (s >= 0 && s < n_rows) {
+        if constexpr (GROUPED) {
+          s_fill[c] = gq.fills[j];
+          any_fill |= gq.fills[j] >= 0;
+        }
+        s_rows[c++] = static_cast<int32_t>(s);
+      }
     }
     s_n = c;
+    if constexpr (GROUPED) s_any_fill = any_fill;
   }
   __syncthreads();
   const int np = s_n;
@@ -674,6 +866,12 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_apply_blocked_kernel(
   }
   const bool has_pick = lane < np;                       // lane j speaks for pick j (np <= 64)
   const int32_t s_lane = has_pick ? s_rows[lane] : -1;
+  [[maybe_unused]] int32_t fill_lane = -1;               // GROUPED: the group pick `lane` fills
+  [[maybe_unused]] bool any_fill = false;
+  if constexpr (GROUPED) {
+    fill_lane = has_pick ? s_fill[lane] : -1;
+    any_fill = s_any_fill != 0;
+  }
 
   // ---- 2. the scan: the steps of subset_apply_kernel, every live row against all picks
   const int wave_in_block = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -704,6 +902,10 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_apply_blocked_kernel(
     }
     float pen_v = 0.f;
     if (lane < R && ((live >> lane) & 1u)) pen_v = pen[g * R + lane];
+    [[maybe_unused]] int32_t lab_v = -1;
+    if constexpr (GROUPED) {
+      if (any_fill && lane < R && ((live >> lane) & 1u)) lab_v = gq.ga.labels[g * R + lane];
+    }
     const uint32_t live_next = live_of(g + n_waves);
     // lane j of gl[r] receives g(row r, pick j): the sums come off the DPP tree as scalars, one select each
     float gl[R];
@@ -760,7 +962,16 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_apply_blocked_kernel(
         const uint64_t cut_m = __ballot(has_pick && cut_on && after != none && after >= max_sim);
         const int j_self = self_m ? __builtin_ctzll(self_m) : 64;      // the row is this pick: struck out, nothing applied from here on
         const int j_cut = cut_m ? __builtin_ctzll(cut_m) : 64;         // this pick takes pen to max_sim: applied, then frozen
-        const int n_applied = j_self < j_cut + 1 ? j_self : j_cut + 1;
+        int n_applied = j_self < j_cut + 1 ? j_self : j_cut + 1;
+        [[maybe_unused]] uint64_t fill_m = 0;            // GROUPED: this pick fills the row's group: applied, then frozen
+        if constexpr (GROUPED) {
+          if (any_fill) {
+            const int32_t lab = __builtin_amdgcn_readlane(lab_v, r);
+            fill_m = __ballot(has_pick && fill_lane >= 0 && fill_lane == lab);
+            const int j_fill = fill_m ? __builtin_ctzll(fill_m) : 64;
+            n_applied = n_applied < j_fill + 1 ? n_applied : j_fill + 1;
+          }
+        }
         const uint64_t takes_m = __ballot(num && lane < n_applied && gv > before);
         if (takes_m != 0) {
           const int last = __builtin_amdgcn_readfirstlane(63 - __builtin_clzll(takes_m));
@@ -771,7 +982,11 @@ __global__ void __launch_bounds__(kSubsetThreads) subset_apply_blocked_kernel(
             pen[row] = pen_new;
           }
         }
-        if ((self_m | cut_m) != 0 && lane == 0) struck[row] = 1;
+        if constexpr (GROUPED) {
+          if ((self_m | cut_m | fill_m) != 0 && lane == 0) struck[row] = 1;
+        } else {
+          if ((self_m | cut_m) != 0 && lane == 0) struck[row] = 1;
+        }
       }
     }
     live = live_next;
@@ -804,23 +1019,63 @@ hipError_t launch_subset_seed(const SubsetLayout& L, const void* d_E, int elem_t
   const SubsetPtrs P = subset_carve(L, ws);
   for (int j = 0; j < n_seeds; ++j) {
     const hipError_t e = subset_apply(d_E, elem_type, n_rows, dim, nullptr, 0.f, 0.f, max_sim, 0, P.keys, P.keys, P, nullptr,
-                                      nullptr, nullptr, d_seed_rows, j, stream);
+                                      nullptr, nullptr, d_seed_rows, j, nullptr, stream);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-hipError_t launch_subset_run(const SubsetLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel,
-                             int64_t n_launches, float lam, float one_minus_lam, float max_sim, int64_t id_offset,
-                             int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner,
-                             char* ws, hipStream_t stream) {
+SubsetGroupedLayout subset_grouped_layout(int64_t n_rows, int64_t n_groups) {
+  SubsetGroupedLayout L;
+  L.blocked = subset_blocked_layout(n_rows);
+  L.rec = (L.blocked.total + 255) / 256 * 256;
+  L.fills = L.rec + 256;
+  L.counts = L.fills + 256;
+  static_assert(kSubsetMaxBlock * sizeof(int32_t) <= 256, "the fill list has 256 bytes");
+  L.total = L.counts + (static_cast<size_t>(n_groups) * sizeof(uint32_t) + 255) / 256 * 256;
+  return L;
+}
+
+namespace {
+SubsetGroupArgs subset_group_args(const SubsetGroupedLayout& L, const SubsetGroups& Q, char* ws) {
+  return SubsetGroupArgs{Q.d_labels, Q.d_quota, reinterpret_cast<uint32_t*>(ws + L.counts), Q.n_groups, Q.per_group};
+}
+hipError_t subset_groups_close(const SubsetGroupedLayout& L, const SubsetGroups& Q, const SubsetGroupRec* last, char* ws,
+                               hipStream_t stream) {
+  hipLaunchKernelGGL(subset_groups_close_kernel, dim3(subset_small_grid(Q.n_groups)), dim3(kSubsetThreads), 0, stream,
+                     static_cast<int64_t>(Q.n_groups), reinterpret_cast<uint32_t*>(ws + L.counts), last, Q.d_out_counts);
+  return hipGetLastError();
+}
+
+// G / Q: NULL (the ungrouped run, the kernels it always launched) or the grouped layout and the caller's group arguments
+hipError_t subset_run(const SubsetLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel,
+                      int64_t n_launches, float lam, float one_minus_lam, float max_sim, int64_t id_offset, int64_t* d_out_rows,
+                      float* d_out_gain, int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner, const SubsetGroupedLayout* G,
+                      const SubsetGroups* Q, char* ws, hipStream_t stream) {
   const SubsetPtrs P = subset_carve(L, ws);
-  hipLaunchKernelGGL(subset_keys_kernel, dim3(subset_grid(n_rows, dim, elem_type)), dim3(kSubsetThreads), 0, stream, n_rows, d_rel, lam, one_minus_lam,
-                     max_sim, P.pen, P.struck, P.keys, P.hdr, d_n_picked);
+  SubsetGroupCall call{};
+  SubsetGroupRec* rec = nullptr;
+  if (G) {
+    call.ga = subset_group_args(*G, *Q, ws);
+    rec = reinterpret_cast<SubsetGroupRec*>(ws + G->rec);
+    call.rec_out = rec;
+    hipLaunchKernelGGL(subset_keys_kernel<SubsetGroupCall>, dim3(subset_grid(n_rows, dim, elem_type)), dim3(kSubsetThreads), 0, stream,
+                       n_rows, d_rel, lam, one_minus_lam, max_sim, P.pen, P.struck, P.keys, P.hdr, d_n_picked, call);
+  } else {
+    hipLaunchKernelGGL(subset_keys_kernel<>, dim3(subset_grid(n_rows, dim, elem_type)), dim3(kSubsetThreads), 0, stream, n_rows, d_rel, lam, one_minus_lam,
+                       max_sim, P.pen, P.struck, P.keys, P.hdr, d_n_picked);
+  }
   hipError_t e = hipGetLastError();
-  for (int64_t j = 0; j < n_launches && e == hipSuccess; ++j)
+  for (int64_t j = 0; j < n_launches && e == hipSuccess; ++j) {
+    if (G) {
+      call.rec_in = rec + (j & 1);
+      call.rec_out = rec + ((j + 1) & 1);
+    }
     e = subset_apply(d_E, elem_type, n_rows, dim, d_rel, lam, one_minus_lam, max_sim, id_offset, P.keys + (j & 1) * kSubsetGrid,
-                     P.keys + ((j + 1) & 1) * kSubsetGrid, P, d_out_rows, d_out_gain, d_n_picked, nullptr, 0, stream);
+                     P.keys + ((j + 1) & 1) * kSubsetGrid, P, d_out_rows, d_out_gain, d_n_picked, nullptr, 0, G ? &call : nullptr,
+                     stream);
+  }
+  if (e == hipSuccess && G) e = subset_groups_close(*G, *Q, rec + (n_launches & 1), ws, stream);
   if (e == hipSuccess && (d_out_pen || d_out_owner)) {
     hipLaunchKernelGGL(subset_export_kernel, dim3(subset_small_grid(n_rows)), dim3(kSubsetThreads), 0, stream, n_rows, P.pen,
                        P.owner, id_offset, d_out_pen, d_out_owner);
@@ -828,6 +1083,31 @@ hipError_t launch_subset_run(const SubsetLayout& L, const void* d_E, int elem_ty
   }
   return e;
 }
+}  // namespace
+
+hipError_t launch_subset_run(const SubsetLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel,
+                             int64_t n_launches, float lam, float one_minus_lam, float max_sim, int64_t id_offset,
+                             int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner,
+                             char* ws, hipStream_t stream) {
+  return subset_run(L, d_E, elem_type, n_rows, dim, d_rel, n_launches, lam, one_minus_lam, max_sim, id_offset, d_out_rows,
+                    d_out_gain, d_n_picked, d_out_pen, d_out_owner, nullptr, nullptr, ws, stream);
+}
+
+hipError_t launch_subset_groups_begin(const SubsetGroupedLayout& L, int64_t n_groups, char* ws, hipStream_t stream) {
+  hipLaunchKernelGGL(subset_groups_begin_kernel, dim3(subset_small_grid(n_groups)), dim3(kSubsetThreads), 0, stream, n_groups,
+                     reinterpret_cast<uint32_t*>(ws + L.counts), reinterpret_cast<SubsetGroupRec*>(ws + L.rec),
+                     reinterpret_cast<int32_t*>(ws + L.fills));
+  return hipGetLastError();
+}
+
+hipError_t launch_subset_run_grouped(const SubsetGroupedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                                     const float* d_rel, int64_t n_launches, float lam, float one_minus_lam, float max_sim,
+                                     int64_t id_offset, int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked,
+                                     float* d_out_pen, int64_t* d_out_owner, const SubsetGroups& Q, char* ws, hipStream_t stream) {
+  return subset_run(L.blocked.state, d_E, elem_type, n_rows, dim, d_rel, n_launches, lam, one_minus_lam, max_sim, id_offset,
+                    d_out_rows, d_out_gain, d_n_picked, d_out_pen, d_out_owner, &L, &Q, ws, stream);
+}
+
 
 // ---- the blocked form ----------------------------------------------------------------------------------------------
 namespace {
@@ -845,9 +1125,12 @@ SubsetBlockedPtrs subset_blocked_carve(const SubsetBlockedLayout& L, char* ws) {
 
 template <int ELEM, bool VEC, int UPL>
 hipError_t subset_apply_blocked_one(const char* E, int64_t n_rows, int dim, float max_sim, const int64_t* list, const SubsetCtl* ctl,
-                                    int n_host, int block, const SubsetPtrs& P, hipStream_t stream) {
-  static PerDeviceOnce attr_once;   // one per instantiation
-  const hipError_t ea = attr_once.run([] {
+                                    int n_host, int block, const SubsetPtrs& P, const SubsetGroupCall* G, hipStream_t stream) {
+  static PerDeviceOnce attr_once, attr_once_grouped;   // one per instantiation
+  const hipError_t ea = G ? attr_once_grouped.run([] {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&subset_apply_blocked_kernel<ELEM, VEC, UPL, SubsetGroupCall>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kSubsetBlockLds));
+  }) : attr_once.run([] {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&subset_apply_blocked_kernel<ELEM, VEC, UPL>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kSubsetBlockLds));
   });
@@ -855,16 +1138,22 @@ hipError_t subset_apply_blocked_one(const char* E, int64_t n_rows, int dim, floa
   const int units = (dim + SubElem<ELEM>::kCols - 1) / SubElem<ELEM>::kCols;
   const size_t lds = static_cast<size_t>(block) * units * 16;
   if (lds > kSubsetBlockLds) return hipErrorInvalidValue;      // (block <= subset_block_max: the entry points check it)
-  hipLaunchKernelGGL((subset_apply_blocked_kernel<ELEM, VEC, UPL>), dim3(subset_grid(n_rows, dim, ELEM)), dim3(kSubsetThreads), lds,
-                     stream, E, n_rows, dim, max_sim, list, ctl, n_host, block, P.pen, P.owner, P.struck);
+  if (G)
+    hipLaunchKernelGGL((subset_apply_blocked_kernel<ELEM, VEC, UPL, SubsetGroupCall>), dim3(subset_grid(n_rows, dim, ELEM)),
+                       dim3(kSubsetThreads), lds, stream, E, n_rows, dim, max_sim, list, ctl, n_host, block, P.pen, P.owner, P.struck,
+                       *G);
+  else
+    hipLaunchKernelGGL((subset_apply_blocked_kernel<ELEM, VEC, UPL>), dim3(subset_grid(n_rows, dim, ELEM)), dim3(kSubsetThreads), lds,
+                       stream, E, n_rows, dim, max_sim, list, ctl, n_host, block, P.pen, P.owner, P.struck);
   return hipGetLastError();
 }
 
 template <int ELEM, bool VEC>
 hipError_t subset_apply_blocked_upl(int upl, const char* E, int64_t n_rows, int dim, float max_sim, const int64_t* list,
-                                    const SubsetCtl* ctl, int n_host, int block, const SubsetPtrs& P, hipStream_t stream) {
+                                    const SubsetCtl* ctl, int n_host, int block, const SubsetPtrs& P, const SubsetGroupCall* G,
+                                    hipStream_t stream) {
 #define DEWI_SUBSET_LAUNCH(UPL) \
-  return subset_apply_blocked_one<ELEM, VEC, UPL>(E, n_rows, dim, max_sim, list, ctl, n_host, block, P, stream);
+  return subset_apply_blocked_one<ELEM, VEC, UPL>(E, n_rows, dim, max_sim, list, ctl, n_host, block, P, G, stream);
   switch (upl) {
     case 1: DEWI_SUBSET_LAUNCH(1)
     case 2: DEWI_SUBSET_LAUNCH(2)
@@ -882,14 +1171,15 @@ bool subset_vec(const void* d_E, int elem_type, int dim) {
 }
 
 hipError_t subset_apply_blocked(const void* d_E, int elem_type, int64_t n_rows, int dim, float max_sim, const int64_t* list,
-                                const SubsetCtl* ctl, int n_host, int block, const SubsetPtrs& P, hipStream_t stream) {
+                                const SubsetCtl* ctl, int n_host, int block, const SubsetPtrs& P, const SubsetGroupCall* G,
+                                hipStream_t stream) {      // G: NULL, the ungrouped pass
   const int cols = elem_type == 0 ? 4 : 8;
   const int per_lane = ((dim + cols - 1) / cols + kWave - 1) / kWave;
   const int upl = per_lane <= 4 ? per_lane : (per_lane <= 6 ? 6 : (per_lane <= 8 ? 8 : 0));
   const bool vec = subset_vec(d_E, elem_type, dim);
   const char* E = static_cast<const char*>(d_E);
 #define DEWI_SUBSET_APPLY(ELEM, VEC) \
-  return subset_apply_blocked_upl<ELEM, VEC>(upl, E, n_rows, dim, max_sim, list, ctl, n_host, block, P, stream)
+  return subset_apply_blocked_upl<ELEM, VEC>(upl, E, n_rows, dim, max_sim, list, ctl, n_host, block, P, G, stream)
   if (elem_type == 0) {
     if (vec) DEWI_SUBSET_APPLY(0, true);
     DEWI_SUBSET_APPLY(0, false);
@@ -926,32 +1216,49 @@ hipError_t launch_subset_seed_blocked(const SubsetBlockedLayout& L, const void* 
   const SubsetPtrs P = subset_carve(L.state, ws);
   for (int at = 0; at < n_seeds; at += block) {
     const int n = n_seeds - at < block ? n_seeds - at : block;
-    const hipError_t e = subset_apply_blocked(d_E, elem_type, n_rows, dim, max_sim, d_seed_rows + at, nullptr, n, block, P, stream);
+    const hipError_t e = subset_apply_blocked(d_E, elem_type, n_rows, dim, max_sim, d_seed_rows + at, nullptr, n, block, P, nullptr, stream);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-hipError_t launch_subset_run_blocked(const SubsetBlockedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
-                                     const float* d_rel, int64_t budget, float lam, float one_minus_lam, float max_sim,
-                                     int64_t id_offset, int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked,
-                                     float* d_out_pen, int64_t* d_out_owner, int block, int n_rounds, int64_t* d_stats, char* ws,
-                                     hipStream_t stream) {
+namespace {
+// G / Q: NULL (the ungrouped run, the kernels it always launched) or the grouped layout and the caller's group arguments
+hipError_t subset_run_blocked(const SubsetBlockedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                              const float* d_rel, int64_t budget, float lam, float one_minus_lam, float max_sim, int64_t id_offset,
+                              int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked, float* d_out_pen, int64_t* d_out_owner,
+                              int block, int n_rounds, int64_t* d_stats, const SubsetGroupedLayout* G, const SubsetGroups* Q, char* ws,
+                              hipStream_t stream) {
   const SubsetPtrs P = subset_carve(L.state, ws);
   const SubsetBlockedPtrs B = subset_blocked_carve(L, ws);
+  SubsetGroupCall call{};
+  if (G) {
+    call.ga = subset_group_args(*G, *Q, ws);
+    call.fills = reinterpret_cast<int32_t*>(ws + G->fills);
+  }
   const int grid = subset_grid(n_rows, dim, elem_type);
   const char* E = static_cast<const char*>(d_E);
   const bool vec = subset_vec(d_E, elem_type, dim);
   auto top = [&](int64_t opening_budget) {
-    hipLaunchKernelGGL(subset_top_kernel, dim3(grid), dim3(kSubsetThreads), 0, stream, n_rows, d_rel, lam, one_minus_lam, max_sim,
-                       P.pen, P.struck, B.lists, B.unsafe, P.hdr, B.ctl, opening_budget, d_n_picked, d_stats);
+    if (G)
+      hipLaunchKernelGGL(subset_top_kernel<SubsetGroupCall>, dim3(grid), dim3(kSubsetThreads), 0, stream, n_rows, d_rel, lam,
+                         one_minus_lam, max_sim, P.pen, P.struck, B.lists, B.unsafe, P.hdr, B.ctl, opening_budget, d_n_picked, d_stats,
+                         call);
+    else
+      hipLaunchKernelGGL(subset_top_kernel<>, dim3(grid), dim3(kSubsetThreads), 0, stream, n_rows, d_rel, lam, one_minus_lam, max_sim,
+                         P.pen, P.struck, B.lists, B.unsafe, P.hdr, B.ctl, opening_budget, d_n_picked, d_stats);
     return hipGetLastError();
   };
   auto round = [&](int take) {
 #define DEWI_SUBSET_ROUND(ELEM, VEC)                                                                                          \
-  hipLaunchKernelGGL((subset_round_kernel<ELEM, VEC>), dim3(1), dim3(kSubsetThreads), 0, stream, E, n_rows, dim, d_rel, lam,   \
-                     one_minus_lam, max_sim, id_offset, grid, B.lists, B.unsafe, P.hdr, B.ctl, P.pen, B.picks, d_out_rows,      \
-                     d_out_gain, d_n_picked, d_stats, take)
+  if (G)                                                                                                                       \
+    hipLaunchKernelGGL((subset_round_kernel<ELEM, VEC, SubsetGroupCall>), dim3(1), dim3(kSubsetThreads), 0, stream, E, n_rows, \
+                       dim, d_rel, lam, one_minus_lam, max_sim, id_offset, grid, B.lists, B.unsafe, P.hdr, B.ctl, P.pen, B.picks, \
+                       d_out_rows, d_out_gain, d_n_picked, d_stats, take, call);                                                 \
+  else                                                                                                                         \
+    hipLaunchKernelGGL((subset_round_kernel<ELEM, VEC>), dim3(1), dim3(kSubsetThreads), 0, stream, E, n_rows, dim, d_rel, lam, \
+                       one_minus_lam, max_sim, id_offset, grid, B.lists, B.unsafe, P.hdr, B.ctl, P.pen, B.picks, d_out_rows,    \
+                       d_out_gain, d_n_picked, d_stats, take)
     if (elem_type == 0 && vec) {
       DEWI_SUBSET_ROUND(0, true);
     } else if (elem_type == 0) {
@@ -967,16 +1274,37 @@ hipError_t launch_subset_run_blocked(const SubsetBlockedLayout& L, const void* d
   hipError_t e = top(budget);
   for (int j = 0; j < n_rounds && e == hipSuccess; ++j) {
     e = round(block);
-    if (e == hipSuccess) e = subset_apply_blocked(d_E, elem_type, n_rows, dim, max_sim, B.picks, B.ctl, 0, block, P, stream);
+    if (e == hipSuccess)
+      e = subset_apply_blocked(d_E, elem_type, n_rows, dim, max_sim, B.picks, B.ctl, 0, block, P, G ? &call : nullptr, stream);
     if (e == hipSuccess) e = top(0);
   }
   if (e == hipSuccess && d_stats) e = round(0);      // `finished` for the state as the last pass left it
+  if (e == hipSuccess && G && Q->d_out_counts) e = subset_groups_close(*G, *Q, nullptr, ws, stream);
   if (e == hipSuccess && (d_out_pen || d_out_owner)) {
     hipLaunchKernelGGL(subset_export_kernel, dim3(subset_small_grid(n_rows)), dim3(kSubsetThreads), 0, stream, n_rows, P.pen,
                        P.owner, id_offset, d_out_pen, d_out_owner);
     e = hipGetLastError();
   }
   return e;
+}
+}  // namespace
+
+hipError_t launch_subset_run_blocked(const SubsetBlockedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                                     const float* d_rel, int64_t budget, float lam, float one_minus_lam, float max_sim,
+                                     int64_t id_offset, int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked,
+                                     float* d_out_pen, int64_t* d_out_owner, int block, int n_rounds, int64_t* d_stats, char* ws,
+                                     hipStream_t stream) {
+  return subset_run_blocked(L, d_E, elem_type, n_rows, dim, d_rel, budget, lam, one_minus_lam, max_sim, id_offset, d_out_rows,
+                            d_out_gain, d_n_picked, d_out_pen, d_out_owner, block, n_rounds, d_stats, nullptr, nullptr, ws, stream);
+}
+
+hipError_t launch_subset_run_blocked_grouped(const SubsetGroupedLayout& L, const void* d_E, int elem_type, int64_t n_rows, int dim,
+                                             const float* d_rel, int64_t budget, float lam, float one_minus_lam, float max_sim,
+                                             int64_t id_offset, int64_t* d_out_rows, float* d_out_gain, int64_t* d_n_picked,
+                                             float* d_out_pen, int64_t* d_out_owner, int block, int n_rounds, int64_t* d_stats,
+                                             const SubsetGroups& Q, char* ws, hipStream_t stream) {
+  return subset_run_blocked(L.blocked, d_E, elem_type, n_rows, dim, d_rel, budget, lam, one_minus_lam, max_sim, id_offset, d_out_rows,
+                            d_out_gain, d_n_picked, d_out_pen, d_out_owner, block, n_rounds, d_stats, &L, &Q, ws, stream);
 }
 
 }  // namespace dewi

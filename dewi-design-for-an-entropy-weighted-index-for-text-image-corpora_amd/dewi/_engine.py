@@ -298,6 +298,63 @@ def group_labels(groups, n_rows: int, row_of=None) -> Tuple[np.ndarray, int]:
     return np.ascontiguousarray(lab.astype(np.int32)), n_groups
 
 
+def dense_group_labels(groups, n_rows: int, row_of=None) -> Tuple[np.ndarray, Dict[object, int]]:
+    """What ``make_groups`` takes (or a ``DeviceGroups``) -> ``(labels int32 [n_rows], {group value: dense label})`` for the
+    group quotas of ``select_subset_grouped``: the labels are DENSE, ``0 .. G-1``, ungrouped rows -1 — ``DuplicateGroups``
+    labels and user integers can be sparse up to 2^31, and ``DeviceGroups.n_groups`` counts ungrouped rows, neither of which
+    sizes a count per group.  Integer labels are numbered in ascending order of their value, hashables in order of first
+    appearance by row; the map is keyed by the caller's own values (Python ints for integer labels).  Host logic only (NumPy);
+    the errors are ``group_labels``'."""
+    n = int(n_rows)
+    if hasattr(groups, "labels") and not isinstance(groups, dict):
+        groups = groups.labels
+    if hasattr(groups, "is_cuda"):
+        groups = groups.detach().cpu().numpy()
+    values = arr = None
+    if hasattr(groups, "keys") and hasattr(groups, "__getitem__") and not isinstance(groups, np.ndarray):
+        group_labels(groups, n, row_of)                      # its checks: an index, unknown doc ids
+        values = [None] * n
+        for d in groups.keys():
+            values[row_of[d]] = groups[d]
+    elif isinstance(groups, np.ndarray) and np.issubdtype(groups.dtype, np.integer):
+        arr = groups
+    else:
+        values = groups.tolist() if isinstance(groups, np.ndarray) else list(groups)
+        if values and all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) for x in values):
+            arr, values = np.asarray(values, dtype=np.int64), None
+    if arr is not None:
+        lab = group_labels(arr, n)[0].astype(np.int64)       # its checks: the shape, int32
+        uniq = np.unique(lab[lab >= 0])
+        dense = np.where(lab >= 0, np.searchsorted(uniq, lab), -1).astype(np.int32)
+        return np.ascontiguousarray(dense), {int(v): i for i, v in enumerate(uniq.tolist())}
+    if len(values) != n:
+        raise ValueError(f"group labels must have length {n}, got {len(values)}")
+    dense = np.full(n, -1, dtype=np.int32)
+    codes: Dict[object, int] = {}
+    for row, value in enumerate(values):
+        if value is not None:
+            dense[row] = codes.setdefault(value, len(codes))
+    return dense, codes
+
+
+def grouped_quotas(codes: Dict[object, int], per_group: int, quotas=None, seed_labels=()) -> Optional[np.ndarray]:
+    """The quota array of ``select_subset_grouped`` (int32 [G]) or ``None`` when ``per_group`` serves every group: ``quotas``
+    maps a group value to its quota (an unknown value: ``KeyError``) and overrides ``per_group``; every dense label in
+    ``seed_labels`` — the groups of the seeds that count — lowers its group's quota by one.  Host logic only."""
+    if int(per_group) <= 0:
+        raise ValueError(f"per_group must be at least 1, got {per_group}")
+    seed_labels = [int(g) for g in seed_labels if int(g) >= 0]
+    if not quotas and not seed_labels:
+        return None
+    q = np.full(len(codes), int(per_group), dtype=np.int64)
+    for value, quota in (quotas or {}).items():
+        if value not in codes:
+            raise KeyError(f"quotas names an unknown group: {value!r}")
+        q[codes[value]] = int(quota)
+    np.subtract.at(q, seed_labels, 1)
+    return np.clip(q, -0x80000000, 0x7FFFFFFF).astype(np.int32)
+
+
 def collapse_pool(k: int, candidates: Optional[int], n: int, approx: bool = False) -> int:
     """The pool of a collapsed search: ``candidates`` (default ``4k``), at most the ``n`` rows there are to choose from and at
     most what one re-rank takes (``COLLAPSE_MAX_CANDIDATES``; ``I8_MAX_CANDIDATES`` on the int8 route).  Host logic only."""
@@ -1629,7 +1686,8 @@ class DeviceCorpus:
     # ------------------------------------------------------------------ subset selection (greedy coverage of the whole corpus)
     def select_subset_device(self, budget: int, mmr_lambda: float = 0.5, max_sim: Optional[float] = None, relevance=None,
                              mask=None, seeds=None, return_coverage: bool = False, picks_per_pass: Optional[int] = None,
-                             return_stats: bool = False):
+                             return_stats: bool = False, *, group_labels=None, n_groups: int = 0, per_group: int = 1,
+                             group_quota=None, return_group_counts: bool = False):
         """Enqueue one SUBSET SELECTION on the current stream: the ``budget`` most informative rows that do not repeat each
         other (``dewi_select_begin`` / ``_seed`` / ``_run``, include/dewi_hip.h).  Greedy maximal marginal relevance over
         ALL rows: each pick is the row with the largest ``mmr_lambda * relevance - (1 - mmr_lambda) * (largest inner product
@@ -1651,7 +1709,14 @@ class DeviceCorpus:
         ``dewi_select_block_max`` of the row shape; 0 there: the one-pick form) applied by one corpus pass.  It enqueues about
         ``1.25 * budget / block + 2`` rounds, reads the run's counters back and repeats with the remaining budget until the
         run is finished: ONE HOST SYNCHRONISATION PER CHUNK, unlike the one-pick form.  ``return_stats`` appends a dict
-        ``{"rounds", "passes", "picks_per_pass"}`` to the result (one-pick form: one round and one pass per pick)."""
+        ``{"rounds", "passes", "picks_per_pass"}`` to the result (one-pick form: one round and one pass per pick).
+
+        ``group_labels`` (keyword-only, with the arguments behind it): GROUP QUOTAS — at most ``per_group`` picks from one
+        group (``dewi_select_groups_begin`` / ``dewi_select_run_grouped`` / ``dewi_select_run_blocked_grouped``).  An int32
+        tensor [N] on this device, DENSE: row i is grouped when ``0 <= label < n_groups``, anything else is free of any quota
+        (``dense_group_labels`` makes such labels).  ``group_quota``: an int32 tensor [n_groups] on this device, one quota per
+        group, instead of ``per_group`` (<= 0: nothing is picked from that group).  Seeds do not count against a quota.
+        ``return_group_counts`` appends the picks made per group (int32 [n_groups], behind the coverage, before the stats)."""
         torch = _torch()
         n = self.n_rows
         if self.space == "l2":
@@ -1695,16 +1760,48 @@ class DeviceCorpus:
             if block > 1:
                 block = min(block, int(self._lib.dewi_select_block_max(self.dim, self._elem))) or 1
         stream = nat.stream_ptr()
-        if block > 1:
-            # one workspace for both forms: the blocked layout is the one-pick layout plus regions behind it, so an entry that
-            # a one-pick call sized is dropped here once and the larger one serves every later call of either form
-            size = (self._lib.dewi_select_blocked_workspace_bytes, n, self.dim, self._elem, block)
+        grp, counts = (), None
+        if group_labels is not None:
+            g = int(n_groups)
+            if g < 1:
+                raise ValueError(f"n_groups must be at least 1, got {n_groups}")
+            if tuple(group_labels.shape) != (n,) or group_labels.dtype != torch.int32 or group_labels.device != self.device:
+                raise ValueError(f"group_labels must be an int32 tensor of shape ({n},) on {self.device}")
+            if group_quota is None and int(per_group) < 1:
+                raise ValueError(f"per_group must be at least 1, got {per_group}")
+            if group_quota is not None and (tuple(group_quota.shape) != (g,) or group_quota.dtype != torch.int32
+                                            or group_quota.device != self.device):
+                raise ValueError(f"group_quota must be an int32 tensor of shape ({g},) on {self.device}")
+            lab = group_labels.contiguous()
+            quota = None if group_quota is None else group_quota.contiguous()
+            counts = torch.zeros(g, dtype=torch.int32, device=self.device)
+            grp = (nat.ptr(lab), g, nat.ptr(quota) if quota is not None else None, int(per_group) if quota is None else 1,
+                   nat.ptr(counts))
+        elif return_group_counts:
+            raise ValueError("return_group_counts needs group_labels")
+
+        def workspace(size):
+            # one workspace for every form: each layout is the one before it plus regions behind it, so an entry that a smaller
+            # form sized is dropped here once and the larger one serves every later call of any form
             hit = self._ws.get(("select", n))
             if hit is not None and hit[0].numel() < library_size(*size):
                 del self._ws[("select", n)]
             ws = self._cached_workspace(("select", n), *size)
             nat.check(self._lib.dewi_select_begin(n, self.dim, self._elem, nat.ptr(m8) if m8 is not None else None, nat.ptr(ws),
                                                   ws.numel(), stream))
+            if grp:
+                nat.check(self._lib.dewi_select_groups_begin(n, self.dim, self._elem, grp[1], nat.ptr(ws), ws.numel(), stream))
+            return ws
+
+        def finish(out, stats):
+            out = out + ((pen, owner) if return_coverage else ()) + ((counts,) if return_group_counts else ())
+            return out + (stats,) if return_stats else out
+
+        if block > 1:
+            if grp:
+                ws = workspace((self._lib.dewi_select_grouped_workspace_bytes, n, self.dim, self._elem, grp[1], block))
+            else:
+                ws = workspace((self._lib.dewi_select_blocked_workspace_bytes, n, self.dim, self._elem, block))
             if seed_rows is not None and seed_rows.numel():
                 nat.check(self._lib.dewi_select_seed_blocked(nat.ptr(self.emb), self._elem, n, self.dim, nat.ptr(seed_rows),
                                                              int(seed_rows.numel()), cut, nat.ptr(ws), ws.numel(), stream, block))
@@ -1712,33 +1809,33 @@ class DeviceCorpus:
             rounds = passes = done = 0
             while done < b:
                 left = b - done
-                nat.check(self._lib.dewi_select_run_blocked(
+                run = self._lib.dewi_select_run_blocked_grouped if grp else self._lib.dewi_select_run_blocked
+                nat.check(run(
                     nat.ptr(self.emb), self._elem, n, self.dim, nat.ptr(rel), left, lam, cut, self.id_offset, nat.ptr(rows),
                     nat.ptr(gain), nat.ptr(n_picked), nat.ptr(pen) if pen is not None else None,
                     nat.ptr(owner) if owner is not None else None, nat.ptr(ws), ws.numel(), stream, block,
-                    int(1.25 * left / block) + 2, nat.ptr(stats_d)))
+                    int(1.25 * left / block) + 2, nat.ptr(stats_d), *grp))
                 st = stats_d.tolist()             # (the synchronisation of the chunk)
                 rounds, passes = rounds + st[0], passes + st[1]
                 if st[2]:
                     break
                 done = int(n_picked.item())
-            out = (rows, gain, n_picked) + ((pen, owner) if return_coverage else ())
-            return out + ({"rounds": rounds, "passes": passes, "picks_per_pass": block},) if return_stats else out
-        ws = self._cached_workspace(("select", n), self._lib.dewi_select_workspace_bytes, n, self.dim, self._elem)
-        nat.check(self._lib.dewi_select_begin(n, self.dim, self._elem, nat.ptr(m8) if m8 is not None else None, nat.ptr(ws),
-                                              ws.numel(), stream))
+            return finish((rows, gain, n_picked), {"rounds": rounds, "passes": passes, "picks_per_pass": block})
+        if grp:
+            ws = workspace((self._lib.dewi_select_grouped_workspace_bytes, n, self.dim, self._elem, grp[1], 0))
+        else:
+            ws = workspace((self._lib.dewi_select_workspace_bytes, n, self.dim, self._elem))
         if seed_rows is not None and seed_rows.numel():
             nat.check(self._lib.dewi_select_seed(nat.ptr(self.emb), self._elem, n, self.dim, nat.ptr(seed_rows),
                                                  int(seed_rows.numel()), cut, nat.ptr(ws), ws.numel(), stream))
         if b > 0:
-            nat.check(self._lib.dewi_select_run(
+            run = self._lib.dewi_select_run_grouped if grp else self._lib.dewi_select_run
+            nat.check(run(
                 nat.ptr(self.emb), self._elem, n, self.dim, nat.ptr(rel), b, lam, cut, self.id_offset, nat.ptr(rows),
                 nat.ptr(gain), nat.ptr(n_picked), nat.ptr(pen) if pen is not None else None,
-                nat.ptr(owner) if owner is not None else None, nat.ptr(ws), ws.numel(), stream))
-        out = (rows, gain, n_picked) + ((pen, owner) if return_coverage else ())
-        if return_stats:       # (no read-back: the counters of the one-pick form are its launches)
-            return out + ({"rounds": b, "passes": b, "picks_per_pass": 1},)
-        return out
+                nat.ptr(owner) if owner is not None else None, nat.ptr(ws), ws.numel(), stream, *grp))
+        # (no read-back: the counters of the one-pick form are its launches)
+        return finish((rows, gain, n_picked), {"rounds": b, "passes": b, "picks_per_pass": 1})
 
     # ------------------------------------------------------------------ collapsed search (at most m results per group)
     def make_groups(self, groups) -> DeviceGroups:

@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "dewi_robust_fit_fast_plan",
     "dewi_select_workspace_bytes", "dewi_select_begin", "dewi_select_seed", "dewi_select_run",
     "dewi_select_block_max", "dewi_select_blocked_workspace_bytes", "dewi_select_seed_blocked", "dewi_select_run_blocked",
+    "dewi_select_grouped_workspace_bytes", "dewi_select_groups_begin", "dewi_select_run_grouped", "dewi_select_run_blocked_grouped",
 )
 #: the words dewi_robust_fit_fast_plan fills, in order (include/dewi_hip.h)
 FIT_FAST_PLAN_WORDS = ("supported", "slices", "counters_offset", "counters_bytes", "small_n", "sample", "delta", "buckets",
@@ -265,6 +266,14 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_select_seed_blocked.argtypes = [vp, i32, i64, i32, vp, i32, f64, vp, sz, vp, i32]
     lib.dewi_select_run_blocked.restype = i32
     lib.dewi_select_run_blocked.argtypes = [vp, i32, i64, i32, vp, i64, f64, f64, i64, vp, vp, vp, vp, vp, vp, sz, vp, i32, i32, vp]
+    lib.dewi_select_grouped_workspace_bytes.restype = sz
+    lib.dewi_select_grouped_workspace_bytes.argtypes = [i64, i32, i32, i64, i32]
+    lib.dewi_select_groups_begin.restype = i32
+    lib.dewi_select_groups_begin.argtypes = [i64, i32, i32, i64, vp, sz, vp]
+    lib.dewi_select_run_grouped.restype = i32
+    lib.dewi_select_run_grouped.argtypes = lib.dewi_select_run.argtypes + [vp, i64, vp, i32, vp]
+    lib.dewi_select_run_blocked_grouped.restype = i32
+    lib.dewi_select_run_blocked_grouped.argtypes = lib.dewi_select_run_blocked.argtypes + [vp, i64, vp, i32, vp]
     lib.dewi_knn_candidates_filtered.restype = i32
     lib.dewi_knn_candidates_filtered.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, vp, vp, i32, i32, i64, vp, vp, sz, vp]
     lib.dewi_robust_fit_fast_plan.restype = i32

@@ -896,7 +896,34 @@ class ExactIndex(BaseIndex):
         return self._select_subset(budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain, return_coverage,
                                    picks_per_pass)
 
-    def _select_subset(self, budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain, return_coverage, picks_per_pass):
+    def select_subset_grouped(self, budget: int, *, groups, per_group: int = 1, quotas=None, mmr_lambda: float = 0.5,
+                              max_sim: Optional[float] = None, relevance=None, filter=None, seeds: Optional[Sequence[str]] = None,
+                              seeds_count: bool = True, return_gain: bool = False, return_coverage: bool = False,
+                              picks_per_pass: Optional[int] = 32):
+        """``select_subset`` with GROUP QUOTAS: at most ``per_group`` picks from one group — "10 000 documents, at most 50 per
+        site" (additive; the selection side of ``search_collapsed``).  It is the greedy run itself that respects the quota: a
+        group that is full is struck out, so the budget it would have taken goes to other groups and its documents stop
+        penalising nobody they did not penalise already — selecting too many and pruning afterwards is a different subset.
+        ``groups``: anything ``make_groups`` takes, or a prepared ``DeviceGroups`` (stale-checked); ungrouped documents are free
+        of any quota.  ``quotas``: a mapping from group value to that group's quota; it overrides ``per_group`` (<= 0: nothing
+        from that group).  ``seeds_count``: each seed lowers its group's quota by one.  ``picks_per_pass``: ``None`` / 1 takes
+        the one-pick form, otherwise as in ``select_subset_blocked``; the answer is the same bit for bit.  Everything else,
+        and the return values, as ``select_subset``."""
+        if self.space == "l2":
+            raise NotImplementedError("subset selection penalises the inner product of unit rows: space='l2' is not in this build")
+        if int(per_group) <= 0:
+            raise ValueError(f"per_group must be at least 1, got {per_group}")
+        from ._engine import DeviceGroups, dense_group_labels
+        self._ensure_built()
+        if isinstance(groups, DeviceGroups):
+            self._corpus.check_groups(groups)
+        is_mapping = hasattr(groups, "keys") and not hasattr(groups, "dtype")
+        dense, codes = dense_group_labels(groups, len(self._doc_ids), self._row_map() if is_mapping else None)
+        return self._select_subset(budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain, return_coverage,
+                                   picks_per_pass, (dense, codes, int(per_group), quotas, bool(seeds_count)))
+
+    def _select_subset(self, budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain, return_coverage, picks_per_pass,
+                       grouped=None):
         if self.space == "l2":
             raise NotImplementedError("subset selection penalises the inner product of unit rows: space='l2' is not in this build")
         self._ensure_built()
@@ -924,8 +951,19 @@ class ExactIndex(BaseIndex):
             seed_rows = None
             if seeds is not None:
                 seed_rows = self.rows_of([seeds] if isinstance(seeds, str) else list(seeds))
+            group_kw = {}
+            if grouped is not None:
+                from ._engine import grouped_quotas
+                dense, codes, per_group, quotas, seeds_count = grouped
+                in_range = [r for r in np.asarray(seed_rows if seed_rows is not None else [], np.int64).reshape(-1).tolist()
+                            if 0 <= r < n]
+                q = grouped_quotas(codes, per_group, quotas, dense[in_range] if seeds_count else ())
+                if q is not None and q.size == 0:
+                    q = None                       # nobody is grouped: one group that nobody belongs to
+                group_kw = dict(group_labels=torch.from_numpy(dense).to(corpus.device), n_groups=max(len(codes), 1),
+                                per_group=per_group, group_quota=None if q is None else torch.from_numpy(q).to(corpus.device))
             out = corpus.select_subset_device(int(budget), float(mmr_lambda), max_sim, rel, mask, seed_rows,
-                                              return_coverage=bool(return_coverage), picks_per_pass=picks_per_pass)
+                                              return_coverage=bool(return_coverage), picks_per_pass=picks_per_pass, **group_kw)
             kk = int(out[2].item())
             rows = out[0][:kk].cpu().numpy() - corpus.id_offset
             result = [[self._doc_ids[r] for r in rows.tolist()]]

@@ -276,6 +276,20 @@ class DewiIndex(BaseIndex):
         return self._backend.select_subset_blocked(budget, mmr_lambda, max_sim, relevance, filter, seeds, return_gain,
                                                    return_coverage, picks_per_pass)
 
+    def select_subset_grouped(self, budget: int, *, groups, per_group: int = 1, quotas=None, mmr_lambda: float = 0.5,
+                              max_sim: Optional[float] = None, relevance=None, filter=None, seeds=None, seeds_count: bool = True,
+                              return_gain: bool = False, return_coverage: bool = False, picks_per_pass: Optional[int] = 32):
+        """``select_subset`` with at most ``per_group`` picks from one group of ``groups`` (additive;
+        ``ExactIndex.select_subset_grouped``)."""
+        if self.space == "l2":
+            raise NotImplementedError("subset selection penalises the inner product of unit rows: space='l2' is not in this build")
+        if not self._built:
+            self.build()
+        return self._backend.select_subset_grouped(budget, groups=groups, per_group=per_group, quotas=quotas, mmr_lambda=mmr_lambda,
+                                                   max_sim=max_sim, relevance=relevance, filter=filter, seeds=seeds,
+                                                   seeds_count=seeds_count, return_gain=return_gain,
+                                                   return_coverage=return_coverage, picks_per_pass=picks_per_pass)
+
     def make_groups(self, groups):
         """Prepare group labels for ``search_collapsed`` / ``search_collapsed_batch`` (``ExactIndex.make_groups``)."""
         if not self._built:

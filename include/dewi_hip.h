@@ -739,6 +739,75 @@ int dewi_select_run_blocked(const void* d_E, int elem_type, int64_t n_rows, int 
                             int64_t* d_stats /* [3], may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ * Subset selection with GROUP QUOTAS (additive to ABI 6): the two selections above with at most q_g picks from group g — a
+ * site, an album, an author, a k-means cell.  It extends their vocabulary (pen, owner, struck out, g, m, eligibility);
+ * tests/select_grouped_model.py restates it in NumPy.  Selecting too many and pruning on the host is NOT this selection: a
+ * pruned pick has penalised everything near it, and the greedy would have spent the freed budget elsewhere.
+ *
+ * Inputs.  d_labels: int32 [n_rows].  Row i is GROUPED when 0 <= label_i < n_groups; any other value (negative, >= n_groups)
+ *   means ungrouped: free of any quota.  No label indexes out of bounds.  The quota q_g is d_quota[g] (int32 [n_groups]), or
+ *   per_group for every group when d_quota is NULL.
+ * State.  One count c_g per group (uint32), part of the state in the workspace: zeroed by dewi_select_groups_begin, never
+ *   decreased, raised only by the picks of the grouped runs.  dewi_select_seed / _seed_blocked and the ungrouped runs do not
+ *   touch the counts (a caller who wants seeds to count lowers the quotas: the Python layer does).
+ * Full groups.  Group g is FULL when c_g >= q_g; a quota <= 0 is full from the start.  A new cause of striking out: a
+ *   grouped row whose group is full is struck out for ever, its pen and owner frozen as they stand.
+ * A run:  1. the start-of-run strike by max_sim, as dewi_select_run;
+ *         2. every grouped row of a full group is struck out (the counts may come from an earlier run under other quotas);
+ *         3. pick by pick: the choice is dewi_select_run's;
+ *         4. the pick is applied as there — to the live rows of its own group as well;
+ *         5. a grouped pick: c_g += 1;
+ *         6. if g is now full: every row of g that is not yet struck out is struck out;
+ *         7. stop as there: the budget is reached or nothing is eligible.
+ *   A row is therefore updated by the pick that fills its group and then frozen: the order of the max_sim rule.
+ * Outputs: those of dewi_select_run (p0 / kk, id_offset, the unwritten tail), and d_out_group_counts, int32 [n_groups] (may
+ *   be NULL): the counts after the run.
+ * Resume: a run of b1 then a run of b2 with the same arguments equals one run of b1 + b2, bit for bit; a second run under
+ *   smaller quotas begins with step 2.
+ * Equivalences: with every row ungrouped the rows, gains, kk, pen, owner and struck-out bytes equal dewi_select_run's with
+ *   the same other arguments bit for bit; likewise when no quota can bind (q_g >= budget), and with label_i = i and
+ *   per_group = 1.  One group of all rows with quota q makes exactly min(q, eligible picks) picks.
+ * Blocked form: dewi_select_run_blocked_grouped equals dewi_select_run_grouped bit for bit — every output and the whole
+ *   state, counts included —, whatever `block` and `n_rounds` (the blocked form's premise: no g is +-inf); an unfinished run
+ *   is continued by either form.  Why it stays exact: striking out only removes keys, so "a row's key never rises" still holds
+ *   and a round is exact while its best up-to-date key is above tau.  Inside the round the one workgroup keeps the counts and
+ *   the labels of the members of S: a pick that fills its group empties the other members of that group at once.  Rows of
+ *   that group outside S keep their stale keys until the apply pass — that only makes tau conservative.  The first pick of a
+ *   round is always made, as in the ungrouped form.
+ *
+ * dewi_select_grouped_workspace_bytes(n_rows, dim, elem_type, n_groups, block): needs no device; 0 for a bad shape, n_groups
+ *   outside [1, 2^31-1], or a block that is neither 0 (the one-pick form) nor in [1, dewi_select_block_max].  The per-row
+ *   state and the blocked form's regions sit at today's offsets, the group regions behind them, at ONE offset whatever
+ *   `block` (the size does not depend on it): every existing call (dewi_select_begin, _seed, _seed_blocked, _run,
+ *   _run_blocked) works unchanged on a grouped workspace, grouped and plain runs can alternate on one state, and either
+ *   grouped form continues the other.  The two older size functions return what they returned.
+ * dewi_select_groups_begin: after dewi_select_begin; defines every group region — nothing is assumed about their bytes before.
+ * dewi_select_run_grouped / dewi_select_run_blocked_grouped: the arguments of dewi_select_run / dewi_select_run_blocked, then
+ *   the group arguments.  Labels are read only by the opening key pass of a run and by a pass whose pick (a pick of whose
+ *   list) fills a group: 4 B per live row there; a full group's rows are never loaded again.
+ * Errors, before any device work, in this order: a null pointer (d_labels too): DEWI_ERR_INVALID_ARG; n_groups outside
+ *   [1, 2^31-1]: DEWI_ERR_INVALID_ARG; per_group < 1 with a NULL d_quota: DEWI_ERR_INVALID_ARG; then everything
+ *   dewi_select_run / dewi_select_run_blocked refuse, the workspace checked against the grouped size (DEWI_ERR_WORKSPACE).
+ *   budget <= 0 writes nothing and returns DEWI_OK.
+ * ------------------------------------------------------------------------------------------ */
+size_t dewi_select_grouped_workspace_bytes(int64_t n_rows, int dim, int elem_type, int64_t n_groups, int block);
+int dewi_select_groups_begin(int64_t n_rows, int dim, int elem_type, int64_t n_groups, void* d_workspace, size_t workspace_bytes,
+                             void* stream);
+int dewi_select_run_grouped(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel, int64_t budget,
+                            double mmr_lambda, double max_sim, int64_t id_offset, int64_t* d_out_rows, float* d_out_gain,
+                            int64_t* d_n_picked, float* d_out_pen /* may be NULL */, int64_t* d_out_owner /* may be NULL */,
+                            void* d_workspace, size_t workspace_bytes, void* stream, const int32_t* d_labels /* [n_rows] */,
+                            int64_t n_groups, const int32_t* d_quota /* [n_groups], may be NULL */, int per_group,
+                            int32_t* d_out_group_counts /* [n_groups], may be NULL */);
+int dewi_select_run_blocked_grouped(const void* d_E, int elem_type, int64_t n_rows, int dim, const float* d_rel, int64_t budget,
+                                    double mmr_lambda, double max_sim, int64_t id_offset, int64_t* d_out_rows, float* d_out_gain,
+                                    int64_t* d_n_picked, float* d_out_pen /* may be NULL */, int64_t* d_out_owner /* may be NULL */,
+                                    void* d_workspace, size_t workspace_bytes, void* stream, int block, int n_rounds,
+                                    int64_t* d_stats /* [3], may be NULL */, const int32_t* d_labels /* [n_rows] */,
+                                    int64_t n_groups, const int32_t* d_quota /* [n_groups], may be NULL */, int per_group,
+                                    int32_t* d_out_group_counts /* [n_groups], may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  * Approximate search over an INT8 copy of the corpus (additive to ABI 6; the reference has no counterpart).  One byte per
  * element instead of four: a symmetric per-row scalar quantisation, integer inner products, and — optionally — the candidate
  * cut re-scored from the fp32 rows.  Unlike the bf16 shadow this route is NOT exact: no error band of a useful width is
