@@ -1806,6 +1806,85 @@ int dewi_knn_candidates_i8(const int8_t* d_codes, const float* d_scales, int64_t
                   "select launch");
 }
 
+// ---- query batches on the int8 codes: 32 queries per matrix-core pass (additive to ABI 6; knn_mfma_i8.hip) ------
+// the plan of a shape the pass takes; false otherwise (the size function's 0)
+static bool i8_batch_layout(int64_t n_rows, int dim, int n_queries, int n_candidates, dewi::MfmaI8Layout* out) {
+  if (!dewi::mfma_i8_supported(n_rows, dim, n_queries, n_candidates)) return false;
+  const dewi::MfmaI8Layout m = dewi::plan_mfma_i8(n_rows, dim, n_queries, n_candidates);
+  if (!m.fits) return false;
+  *out = m;
+  return true;
+}
+
+size_t dewi_knn_i8_batch_workspace_bytes(int64_t n_rows, int dim, int n_queries, int n_candidates) {
+  dewi::MfmaI8Layout m;
+  return i8_batch_layout(n_rows, dim, n_queries, n_candidates, &m) ? m.total : 0;
+}
+
+int dewi_knn_i8_batch_plan(int64_t n_rows, int dim, int n_queries, int n_candidates, int64_t* out_words) {
+  if (!out_words) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  dewi::MfmaI8Layout m;
+  if (!i8_batch_layout(n_rows, dim, n_queries, n_candidates, &m))
+    return fail(DEWI_ERR_UNSUPPORTED, "the int8 batch pass does not take %lld rows x %d columns, %d queries, %d candidates",
+                static_cast<long long>(n_rows), dim, n_queries, n_candidates);
+  const int64_t words[dewi::kI8BatchPlanWords] = {m.groups, m.n_blocks, m.n_seg, m.seg_cap, m.tile_stride, m.n_sample_tiles,
+                                                  m.sample_blocks, static_cast<int64_t>(m.flags_off), static_cast<int64_t>(m.cnt_off),
+                                                  static_cast<int64_t>(m.cand_off), static_cast<int64_t>(m.repair_off),
+                                                  static_cast<int64_t>(m.total)};
+  for (int i = 0; i < dewi::kI8BatchPlanWords; ++i) out_words[i] = words[i];
+  return DEWI_OK;
+}
+
+int dewi_knn_candidates_i8_batch(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const float* d_Q,
+                                 int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
+                                 dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, void* stream_) {
+  // the checks of dewi_knn_candidates_i8, in its order; then what the pass itself does not take
+  if (!d_codes || !d_scales || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "null codes, scales or query pointer");
+  if (int rc = check_i8_shape(n_rows, dim, 16)) return rc;
+  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
+  if (int rc = check_i8_candidates(n_candidates)) return rc;
+  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
+  if (int rc = check_aligned16(d_codes, "the codes")) return rc;
+  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
+  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
+                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
+  dewi::MfmaI8Layout m;
+  if (!i8_batch_layout(n_rows, dim, n_queries, n_candidates, &m))
+    return fail(DEWI_ERR_UNSUPPORTED, "the int8 batch pass does not take %lld rows x %d columns, %d queries, %d candidates "
+                "(dewi_knn_i8_batch_workspace_bytes is 0: use dewi_knn_candidates_i8)",
+                static_cast<long long>(n_rows), dim, n_queries, n_candidates);
+  if (int rc = check_workspace(d_workspace, workspace_bytes, m.total)) return rc;
+  if (int rc = check_aligned16(d_workspace, "the workspace")) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  char* ws = static_cast<char*>(d_workspace);
+  hipError_t e = dewi::launch_mfma_i8(m, d_codes, d_scales, n_rows, dim, d_Q, n_queries, n_candidates, ws, stream);
+  if (e != hipSuccess) return hip_fail(e, "int8 batch pass launch");
+  // one select per pass of 32 queries (each has its own survivor segments); it raises the flag of a query it refuses
+  const dewi::RerankParams rp = make_rerank(0.0, 0.0);
+  const dewi::SegmentLayout seg{m.n_seg, m.seg_cap, 1, static_cast<int64_t>(32) * m.seg_cap, 32, 8192, 1};
+  uint32_t* flags = reinterpret_cast<uint32_t*>(ws + m.flags_off);
+  for (int g = 0; g < m.groups; ++g) {
+    const int q0 = g * 32;
+    const int nq = n_queries - q0 < 32 ? n_queries - q0 : 32;
+    const uint64_t* recs = reinterpret_cast<const uint64_t*>(ws + m.cand_off) + static_cast<int64_t>(g) * m.n_seg * 32 * m.seg_cap;
+    const uint32_t* counts = reinterpret_cast<const uint32_t*>(ws + m.cnt_off) + static_cast<int64_t>(g) * m.n_seg * 32;
+    e = dewi::launch_select_rerank(recs, 0, 0, nq, n_candidates, 0, rp, d_dewi32, d_ent32, id_offset, nullptr, nullptr,
+                                   d_out + static_cast<int64_t>(q0) * n_candidates, counts, seg, stream,
+                                   dewi::RefineParams{nullptr, nullptr, nullptr, 0, 0.f, 0}, dewi::QueryFlags{flags + q0, 1});
+    if (e != hipSuccess) return hip_fail(e, "select launch");
+  }
+  // the repair: flagged queries once more with the row route's arithmetic; both launches return at once when no flag is set
+  e = dewi::launch_scan_i8_flagged(m, d_codes, d_scales, n_rows, dim, n_queries, n_candidates, ws, stream);
+  if (e != hipSuccess) return hip_fail(e, "int8 repair scan launch");
+  const int sorted = m.repair_slots == 1 ? m.repair_blocks : 0;
+  return launched(dewi::launch_select_rerank(reinterpret_cast<const uint64_t*>(ws + m.repair_off), m.repair_keys_per_query, sorted,
+                                             n_queries, n_candidates, 0, rp, d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out,
+                                             nullptr, dewi::SegmentLayout{}, stream,
+                                             dewi::RefineParams{nullptr, nullptr, nullptr, 0, 0.f, 0}, dewi::QueryFlags{flags, 2}),
+                  "repair select launch");
+}
+
 // ---- the int8 scan over the rows of a prepared filter / of per-query lists (additive to ABI 6) -----------------
 size_t dewi_knn_i8_filtered_workspace_bytes(int64_t n_scan, int dim, int n_queries, int n_candidates) {
   // today what the unfiltered call needs on n_scan rows (keys of every query: lists, or one dense key per list position)

@@ -20,6 +20,7 @@
 //
 // Roofline: HBM.  Algorithmic bytes per pass = n_rows * (dim + 4) + n_queries * dim * 4 (a list of |A| rows: |A| * (dim + 4) +
 // 4 * |A| + n_queries * dim * 4).
+#include "i8_common.hpp"
 #include "scan_any.hpp"
 #include "select_common.hpp"
 
@@ -27,7 +28,6 @@ namespace dewi {
 
 namespace {
 
-constexpr int kUnitCodes = 16;                       // codes per 16-byte unit
 constexpr int kI8MaxU = kI8MaxDim / kUnitCodes / kWave;   // units a lane holds at most (4)
 
 // the rows-in-flight choices launch_long instantiates are scan_any.hpp's
@@ -110,19 +110,7 @@ __device__ __forceinline__ void load_unit_f32(const float* __restrict__ row, int
   }
 }
 
-// 16 codes x 16 codes -> int32 (v_dot4c_i32_i8 four times)
-__device__ __forceinline__ int dot16_i8(u32x4 e, const uint32_t (&q)[4], int acc) {
-  const uint32_t e0 = e.x, e1 = e.y, e2 = e.z, e3 = e.w;   // (scalars first: see dot8_packed in scan_common.hpp)
-  acc = __builtin_amdgcn_sdot4(static_cast<int>(e0), static_cast<int>(q[0]), acc, false);
-  acc = __builtin_amdgcn_sdot4(static_cast<int>(e1), static_cast<int>(q[1]), acc, false);
-  acc = __builtin_amdgcn_sdot4(static_cast<int>(e2), static_cast<int>(q[2]), acc, false);
-  acc = __builtin_amdgcn_sdot4(static_cast<int>(e3), static_cast<int>(q[3]), acc, false);
-  return acc;
-}
-
-__device__ __forceinline__ float score_i8(int d, float scale_row, float scale_q) {
-  return __fmul_rn(__fmul_rn(__int2float_rn(d), scale_row), scale_q);
-}
+// (dot16_i8 and score_i8: i8_common.hpp, shared with the matrix-core batch pass)
 
 // ---------------------------------------------------------------------------------------------
 // dewi_quantize_rows_i8 / dewi_prepare_queries_i8: one wave per vector, lane l holds the units l + 64 u

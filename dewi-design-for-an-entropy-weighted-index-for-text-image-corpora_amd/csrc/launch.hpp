@@ -537,6 +537,47 @@ hipError_t launch_scan_i8_list(const ScanPlan& plan, const int8_t* d_codes, cons
 hipError_t launch_rescore_candidates_f32(const float* d_E, int64_t n_rows, int dim, const float* d_Q, int n_queries,
                                          dewi_candidate* d_cand, int n_candidates, int64_t id_offset, hipStream_t stream);
 
+// ---- knn_mfma_i8.hip: query batches on the int8 codes, 32 queries per matrix-core pass (include/dewi_hip.h, "INT8 batch pass") ----
+#ifndef DEWI_I8_MFMA_MIN_QUERIES
+#define DEWI_I8_MFMA_MIN_QUERIES 2
+#endif
+// batches of at least this many queries take the pass.  1 M x 768 embedding_like, whole re-scored search, pass against row
+// passes: 2 queries 0.222 / 0.278 ms (k = 10) and 0.240 / 1.136 (k = 100), 4 queries 0.224 / 0.331 and 0.244 / 1.459 — the pass
+// won every repetition from 2 queries on at both k (profiles/r20/int8_batch/); one query keeps the row pass (0.150 ms at k = 10)
+constexpr int kI8MfmaMinQueries = DEWI_I8_MFMA_MIN_QUERIES;
+constexpr int kI8MfmaMaxQueries = 1 << 20;   // (the plan's int arithmetic on n_queries stays far from overflow)
+constexpr int kI8MfmaMinRows = 4096;   // 128 tiles.  (What the entry point TAKES; below 262 144 rows a batch of fewer than 8 queries is
+                                       // faster on the row passes — the Python layer's default route knows: DESIGN.md 4.1x)
+constexpr int kI8BatchPlanWords = DEWI_I8_BATCH_PLAN_WORDS;   // dewi_knn_i8_batch_plan (include/dewi_hip.h)
+struct MfmaI8Layout {
+  int groups;              // passes of up to 32 queries
+  int q_pad;               // groups * 32
+  int64_t n_tiles;         // 32-row tiles
+  int64_t tile_stride;     // the sample pass takes every tile_stride-th tile
+  int64_t n_sample_tiles;
+  int sample_blocks;       // workgroups of the sample pass
+  int64_t sample_stride;   // group maxima per query (sample_blocks * 256)
+  int n_blocks;            // workgroups of the full pass = survivor segments per query
+  int n_seg;
+  int seg_cap;             // records per (workgroup, query) segment
+  bool fits;               // a pass's records stay below 2^32
+  int repair_slots;        // the repair's row scan: 1 (c <= 64: a sorted list per workgroup) or 4 (a list per wave)
+  int repair_blocks;
+  int64_t repair_keys_per_query;
+  // bytes: prepared query codes [q_pad][dim], their scales, thresholds, refusal flags [n_queries], survivor counts
+  // [groups][n_seg][32], sample maxima [32][sample_stride], records [groups][n_seg][32][seg_cap]; the repair's keys
+  // [n_queries][repair_keys_per_query] start at cnt_off (the pass's regions from there on are dead by then)
+  size_t qc_off, qs_off, thr_off, flags_off, cnt_off, dense_off, cand_off, repair_off, total;
+};
+bool mfma_i8_supported(int64_t n_rows, int dim, int n_queries, int n_candidates);
+MfmaI8Layout plan_mfma_i8(int64_t n_rows, int dim, int n_queries, int n_candidates);   // needs no device
+// prepares the queries, then per group of 32: sample, thresholds, the full pass (counts and records in the workspace)
+hipError_t launch_mfma_i8(const MfmaI8Layout& m, const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim,
+                          const float* d_Q, int n_queries, int n_candidates, char* ws, hipStream_t stream);
+// REPAIR: one launch re-scans the codes for every query whose flag is set (keys at repair_off), at once back when none is
+hipError_t launch_scan_i8_flagged(const MfmaI8Layout& m, const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim,
+                                  int n_queries, int n_candidates, char* ws, hipStream_t stream);
+
 // ---- mutate.hip (in-place removal / upsert of rows; the reference has no counterpart) --------
 // d_error: an int32 the kernels INCREMENT for every pair / slot outside the contract (the caller zeroes it).
 hipError_t launch_rows_move(void* d_E, int elem_type, uint16_t* d_shadow, float* d_dewi32, float* d_ent32, int32_t* d_aux,

@@ -385,6 +385,15 @@ class _RangeBudget:
                              f"({self.total} after {self.done} of {self.n_queries} queries): raise the threshold or max_results")
 
 
+#: When int8 batches take the matrix-core pass by default (``batch_pass=None``): corpora of at least this many rows, or —
+#: whatever the corpus — batches of at least ``I8_BATCH_AUTO_MIN_BATCH`` queries.  The C entry point itself takes 4096 rows and
+#: 2 queries.  Measured at 768 columns (profiles/r20/int8_batch/crossover_rows.txt): at 4096, 16 384 and 65 536
+#: rows the pass's seven launches lost to the row passes at 2 queries (0.08 against 0.06 ms) and tied at 4, and won every round
+#: from 8 queries on; at 262 144 rows and 1 M it won every round from 2 queries on.
+I8_BATCH_AUTO_MIN_ROWS = 262144
+I8_BATCH_AUTO_MIN_BATCH = 8
+
+
 class DeviceCorpus:
     """Embedding block + payload columns of one doc-id shard, resident on one GPU."""
 
@@ -551,17 +560,36 @@ class DeviceCorpus:
                 self.i8_codes = self.i8_scales = None
         return Int8Corpus(codes, scales, self.dewi32, self.ent32, self.id_offset)
 
-    def candidates_i8_device(self, q_dev, n_candidates: int, out=None, id_offset: Optional[int] = None):
+    def candidates_i8_device(self, q_dev, n_candidates: int, out=None, id_offset: Optional[int] = None,
+                             batch_pass: Optional[bool] = None):
         """The ``n_candidates`` best rows of every query BY THE INT8 SCORES as candidate records, int32 view
         [B, n_candidates, 4], in ``candidates_device``'s layout and order (``dewi_knn_candidates_i8``).  ``id_offset``:
-        default the corpus's."""
+        default the corpus's.  ``batch_pass``: ``None`` takes the matrix-core pass of 32 queries per read of the codes
+        (``dewi_knn_candidates_i8_batch``) where it takes the shape AND either the corpus has at least
+        ``I8_BATCH_AUTO_MIN_ROWS`` rows or the batch at least ``I8_BATCH_AUTO_MIN_BATCH`` queries (a few queries over a small
+        corpus: its seven launches cost more than the row passes they save) — the same records, bit for bit —,
+        ``False`` forces the row passes (four queries per read), ``True`` takes the pass wherever it takes the shape and
+        raises ``ValueError`` where it does not."""
         codes, scales = self._int8()
         b, c = int(q_dev.shape[0]), int(n_candidates)
+        n = int(codes.shape[0])
+        use_pass = False
+        if batch_pass is None or batch_pass:
+            use_pass = int(self._lib.dewi_knn_i8_batch_workspace_bytes(n, self.dim, b, c)) > 0
+            if batch_pass is None and n < I8_BATCH_AUTO_MIN_ROWS and b < I8_BATCH_AUTO_MIN_BATCH:
+                use_pass = False
+            if batch_pass and not use_pass:
+                raise ValueError(f"batch_pass=True: the int8 batch pass does not take {n} rows x {self.dim} columns, "
+                                 f"{b} queries, {c} candidates")
         if out is None:
             out = _torch().empty((b, c, 4), dtype=_torch().int32, device=self.device)
-        n = int(codes.shape[0])
-        ws = self._cached_workspace(("i8", b, c), self._lib.dewi_knn_i8_workspace_bytes, n, self.dim, b, c)
-        nat.check(self._lib.dewi_knn_candidates_i8(
+        if use_pass:
+            ws = self._cached_workspace(("i8batch", b, c), self._lib.dewi_knn_i8_batch_workspace_bytes, n, self.dim, b, c)
+            entry = self._lib.dewi_knn_candidates_i8_batch
+        else:
+            ws = self._cached_workspace(("i8", b, c), self._lib.dewi_knn_i8_workspace_bytes, n, self.dim, b, c)
+            entry = self._lib.dewi_knn_candidates_i8
+        nat.check(entry(
             nat.ptr(codes), nat.ptr(scales), n, self.dim, nat.ptr(q_dev), b, nat.ptr(self.dewi32), nat.ptr(self.ent32), c,
             self.id_offset if id_offset is None else int(id_offset), nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
         return out
@@ -584,23 +612,33 @@ class DeviceCorpus:
         then blended and cut to k exactly as every search (``dewi_knn_candidates_i8`` -> ``dewi_rescore_candidates_f32`` ->
         ``dewi_merge_rerank``).  With ``rescore`` the returned scores are fp32 similarities' blends; a document is missed
         only when the int8 scores drop it from the cut (recall: DESIGN.md 4.1q).  ``k`` above the cut and a cut above 1024
-        raise ``ValueError``.  NOT thread-safe on one instance (shared workspaces)."""
+        raise ``ValueError``.  Batches take the matrix-core pass over the codes where it takes the shape
+        (``candidates_i8_device``; the same bits either way — ``search_approx(batch_pass=False)`` is the way back to the row
+        passes).  NOT thread-safe on one instance (shared workspaces)."""
+        return self._search_approx_device(q_dev, k, eta, entropy_pref, candidates, rescore, out_ids, out_scores, None)
+
+    def _search_approx_device(self, q_dev, k, eta, entropy_pref, candidates, rescore, out_ids, out_scores, batch_pass):
+        """``search_approx_device`` with ``candidates_i8_device``'s ``batch_pass``."""
         b, k = check_search_args(q_dev.shape, self.dim, k, None, "ip")
         if k <= 0:
             return empty_result(b, self.device)
         c = approx_cut(k, candidates, self.n_rows)
-        recs = self.candidates_i8_device(q_dev, c, id_offset=0)
+        recs = self.candidates_i8_device(q_dev, c, id_offset=0, batch_pass=batch_pass)
         if rescore:
             self.rescore_candidates_device(q_dev, recs, id_offset=0)
         return merge_rerank_device(recs.view(1, b, c, 4), c, k, eta, entropy_pref, out_ids, out_scores)
 
     def search_approx(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
-                      candidates: Optional[int] = None, rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+                      candidates: Optional[int] = None, rescore: bool = True,
+                      batch_pass: Optional[bool] = None) -> Tuple[np.ndarray, np.ndarray]:
         """Blocking twin of ``search`` for ``search_approx_device``: (ids int64 [B, k] including id_offset, scores fp32
-        [B, k]) on the host.  Serialised by the per-corpus lock."""
+        [B, k]) on the host.  Serialised by the per-corpus lock.  ``batch_pass``: as ``candidates_i8_device`` — ``None``
+        takes the matrix-core pass where it takes the shape, ``False`` the row passes, ``True`` insists (``ValueError``)."""
         with self._lock, _torch().cuda.device(self.device):
             q = self.stage_queries(queries)
-            ids_d, sc_d = self.search_approx_device(q, k, eta, entropy_pref, candidates, rescore)
+            # (the private twin, NOT self.search_approx_device: the public method's parameter list is pinned and cannot carry
+            # batch_pass — a subclass that overrides search_approx_device must override this method too, as Int8Corpus does)
+            ids_d, sc_d = self._search_approx_device(q, k, eta, entropy_pref, candidates, rescore, None, None, batch_pass)
             ids_h, scores_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
         if self.id_offset:
             ids_h = ids_h + self.id_offset
@@ -2048,8 +2086,11 @@ class Int8Corpus(DeviceCorpus):
         return DeviceCorpus.search_approx_device(self, q_dev, k, eta, entropy_pref, candidates, False, out_ids, out_scores)
 
     def search_approx(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
-                      candidates: Optional[int] = None, rescore: bool = False) -> Tuple[np.ndarray, np.ndarray]:
-        return DeviceCorpus.search_approx(self, queries, k, eta, entropy_pref, candidates, rescore)
+                      candidates: Optional[int] = None, rescore: bool = False,
+                      batch_pass: Optional[bool] = None) -> Tuple[np.ndarray, np.ndarray]:
+        if rescore:
+            raise NotImplementedError("a stand-alone int8 corpus has no fp32 rows to re-score from: pass rescore=False")
+        return DeviceCorpus.search_approx(self, queries, k, eta, entropy_pref, candidates, False, batch_pass=batch_pass)
 
 
 class PipelinedSearcher:

@@ -67,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "dewi_rows_move", "dewi_rows_put_f32",
     "dewi_quantize_rows_i8", "dewi_prepare_queries_i8", "dewi_knn_i8_workspace_bytes", "dewi_knn_candidates_i8",
     "dewi_rescore_candidates_f32",
+    "dewi_knn_i8_batch_workspace_bytes", "dewi_knn_i8_batch_plan", "dewi_knn_candidates_i8_batch",
     "dewi_knn_i8_filtered_workspace_bytes", "dewi_knn_candidates_i8_filtered", "dewi_knn_candidates_i8_query_filtered",
     "dewi_collapse_workspace_bytes", "dewi_collapse_rerank", "dewi_knn_candidates_filtered",
     "dewi_robust_fit_fast_plan",
@@ -77,6 +78,9 @@ EXPORTED_SYMBOLS = (
 #: the words dewi_robust_fit_fast_plan fills, in order (include/dewi_hip.h)
 FIT_FAST_PLAN_WORDS = ("supported", "slices", "counters_offset", "counters_bytes", "small_n", "sample", "delta", "buckets",
                        "bucket_lds", "bucket_cap", "reg_keys")
+#: the words dewi_knn_i8_batch_plan fills, in order (include/dewi_hip.h DEWI_I8_BATCH_PLAN_WORDS)
+I8_BATCH_PLAN_WORDS = ("groups", "n_blocks", "n_seg", "seg_cap", "tile_stride", "n_sample_tiles", "sample_blocks", "flags_off",
+                       "cnt_off", "cand_off", "repair_off", "total")
 
 
 class NativeLibraryError(RuntimeError):
@@ -237,6 +241,12 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_knn_i8_workspace_bytes.argtypes = [i64, i32, i32, i32]
     lib.dewi_knn_candidates_i8.restype = i32
     lib.dewi_knn_candidates_i8.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i32, i64, vp, vp, sz, vp]
+    lib.dewi_knn_i8_batch_workspace_bytes.restype = sz
+    lib.dewi_knn_i8_batch_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_knn_i8_batch_plan.restype = i32
+    lib.dewi_knn_i8_batch_plan.argtypes = [i64, i32, i32, i32, c.POINTER(i64)]
+    lib.dewi_knn_candidates_i8_batch.restype = i32
+    lib.dewi_knn_candidates_i8_batch.argtypes = lib.dewi_knn_candidates_i8.argtypes
     lib.dewi_rescore_candidates_f32.restype = i32
     lib.dewi_rescore_candidates_f32.argtypes = [vp, i64, i32, vp, i32, vp, i32, i64, vp]
     lib.dewi_knn_i8_filtered_workspace_bytes.restype = sz
@@ -335,6 +345,13 @@ def fit_fast_plan(n: int, n_signals: int) -> dict:
     out = (ctypes.c_int64 * len(FIT_FAST_PLAN_WORDS))()
     check(load_library(require_gpu=False).dewi_robust_fit_fast_plan(n, n_signals, out, len(out)))
     return dict(zip(FIT_FAST_PLAN_WORDS, (int(v) for v in out)))
+
+
+def i8_batch_plan(n_rows: int, dim: int, n_queries: int, n_candidates: int) -> dict:
+    """``dewi_knn_i8_batch_plan`` as a dict keyed by ``I8_BATCH_PLAN_WORDS`` (host only: needs no GPU)."""
+    out = (ctypes.c_int64 * len(I8_BATCH_PLAN_WORDS))()
+    check(load_library(require_gpu=False).dewi_knn_i8_batch_plan(n_rows, dim, n_queries, n_candidates, out))
+    return dict(zip(I8_BATCH_PLAN_WORDS, (int(v) for v in out)))
 
 
 def is_device_tensor(x) -> bool:

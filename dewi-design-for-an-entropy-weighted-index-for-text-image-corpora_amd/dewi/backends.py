@@ -712,9 +712,10 @@ class ExactIndex(BaseIndex):
             return self.make_query_filters(filter)
         return self.make_filter(**filter_kwargs(filter))
 
-    #: largest batch ``approx=None`` sends through the int8 route: it scans the corpus once per FOUR queries (no matrix-core
-    #: pass), so it wins for one query and small batches and loses to the exact matrix-core batch beyond (1 M x 768, k = 10:
-    #: 4 queries 0.34 ms against 0.50 exact, 32 queries 2.58 ms against 0.55 — DESIGN.md 4.1q)
+    #: largest batch ``approx=None`` sends through the int8 route.  Set when the route scanned the corpus once per FOUR queries
+    #: and lost to the exact matrix-core batch beyond (1 M x 768, k = 10: 4 queries 0.34 ms against 0.50 exact, 32 queries
+    #: 2.58 ms against 0.55 — DESIGN.md 4.1q).  Larger batches now take the int8 matrix-core pass when they ARE
+    #: sent (``approx=True``); the default stays: raising it would change what existing calls return.
     APPROX_AUTO_MAX_BATCH = 4
 
     def _use_approx(self, approx: Optional[bool], similarity: str, filter, k: int, candidates: Optional[int],
@@ -781,8 +782,9 @@ class ExactIndex(BaseIndex):
         from the fp32 rows (``rescore=True``; ``False`` blends the int8 scores as they are) and finish as ever.  Approximate:
         a document is missed when the int8 scores drop it from the cut (measured recall: DESIGN.md 4.1q).  ``None`` (default)
         means "the index has an int8 shadow" — where the route serves the call (no filter, no similarity transform, a cut
-        of at most 1024, at most ``APPROX_AUTO_MAX_BATCH`` = 4 queries: the route scans the corpus once per four queries and
-        loses to the exact matrix-core batch beyond; ``approx=True`` takes it for any batch); ``True`` without a shadow, with ``filter=`` or with a transform raises ``ValueError``; ``False`` is
+        of at most 1024, at most ``APPROX_AUTO_MAX_BATCH`` = 4 queries; ``approx=True`` takes it for any batch — from 2
+        queries on through the int8 matrix-core pass, 32 queries per read of the codes, with the same results bit for bit:
+        DESIGN.md 4.1x); ``True`` without a shadow, with ``filter=`` or with a transform raises ``ValueError``; ``False`` is
         the exact path, bit for bit.  After ``remove`` / ``upsert*`` the next approximate search re-quantises the whole
         matrix (one pass over the fp32 rows), so a mutated index answers as a freshly built one."""
         use_approx = self._use_approx(approx, similarity, filter, k, candidates,      # (argument errors before any build)

@@ -808,6 +808,53 @@ int dewi_select_run_blocked_grouped(const void* d_E, int elem_type, int64_t n_ro
                                     int32_t* d_out_group_counts /* [n_groups], may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ * INT8 batch pass (additive to ABI 6): dewi_knn_candidates_i8 for query BATCHES on the matrix cores — the
+ * codes are read once per 32 queries instead of once per four.  The int8 score (see "INT8 copy" below) is defined in exact
+ * integers, so the pass (v_mfma_i32_32x32x32_i8, then the row kernels' own int32 -> fp32 step) gives the same D and the same
+ * sim in every bit: no error band, no tolerance, and the records equal dewi_knn_candidates_i8's record for record.
+ *
+ * dewi_knn_i8_batch_workspace_bytes: 0 for a shape the pass does not take — the "supported" predicate; needs no device.
+ *   Non-zero for dim % 16 == 0 with 64 <= dim <= 1536, 1 <= n_candidates <= 256, 2 <= n_queries <= 2^20 (kI8MfmaMinQueries, kI8MfmaMaxQueries),
+ *   4096 <= n_rows <= 2^32-1, as long as the records of one pass of 32 queries stay below 2^32.
+ * dewi_knn_i8_batch_plan: the plan behind that size, for tests that pin the path taken; needs no device.  out_words (HOST)
+ *   receives DEWI_I8_BATCH_PLAN_WORDS int64 words, in this order:
+ *     0 groups          passes of up to 32 queries (ceil(n_queries / 32))
+ *     1 n_blocks        workgroups of the full pass
+ *     2 n_seg           survivor segments per query (one per workgroup)
+ *     3 seg_cap         records a segment holds; a query's segments overflow only if it has more than n_seg * seg_cap survivors
+ *     4 tile_stride     the sample launch takes every tile_stride-th 32-row tile
+ *     5 n_sample_tiles
+ *     6 sample_blocks   workgroups of the sample launch
+ *     7 flags_off       byte offset in the workspace of the refusal flags, uint32 [n_queries]: after the call 1 = the pass
+ *                       refused the query and the repair answered it, 0 = the pass answered it
+ *     8 cnt_off         byte offset of the survivor counts, uint32 [groups][n_seg][32] (query q: group q / 32, column q % 32);
+ *                       a count above seg_cap is an overflowed segment.  Overwritten by the repair's keys when
+ *                       repair_off == cnt_off and a query was flagged.
+ *     9 cand_off        byte offset of the records, uint64 [groups][n_seg][32][seg_cap]
+ *    10 repair_off      byte offset of the repair's keys
+ *    11 total           = dewi_knn_i8_batch_workspace_bytes
+ *   Offsets ascend (repair_off aside) and are multiples of 256.  DEWI_ERR_UNSUPPORTED where the size function returns 0.
+ * dewi_knn_candidates_i8_batch: the arguments and the contract of dewi_knn_candidates_i8, word for word — d_out
+ *   [n_queries][n_candidates] sorted by (ord(sim) desc, id asc), NaN first, -0 written as +0, padding (id = -1, sim = -inf)
+ *   behind min(n_candidates, n_rows), the payload pair attached and id_offset added; nothing is read outside [d_codes,
+ *   d_codes + n_rows * dim) or outside d_scales [n_rows]; asynchronous on `stream`, nothing allocated, nothing synchronised.
+ *   Every argument error is reported before any device work, in the order and with the codes of dewi_knn_candidates_i8;
+ *   then a shape the pass does not take (the size function's 0): DEWI_ERR_UNSUPPORTED; a short workspace:
+ *   DEWI_ERR_WORKSPACE; a workspace that is not 16-byte aligned: DEWI_ERR_INVALID_ARG.  The workspace's contents on entry
+ *   are undefined.  IT ALWAYS ANSWERS: a query whose survivor segments overflow (every row ties: a zero or NaN query, a
+ *   corpus of copies) is scanned again inside the call, on the stream, with the row route's arithmetic — the same integers,
+ *   so its records are the same too; no id -1 reaches a caller for a query the corpus could answer.
+ * dewi_knn_candidates_i8 itself is unchanged.
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_I8_BATCH_PLAN_WORDS 12
+size_t dewi_knn_i8_batch_workspace_bytes(int64_t n_rows, int dim, int n_queries, int n_candidates);
+int dewi_knn_i8_batch_plan(int64_t n_rows, int dim, int n_queries, int n_candidates, int64_t* out_words /* HOST */);
+int dewi_knn_candidates_i8_batch(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const float* d_Q,
+                                 int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates,
+                                 int64_t id_offset, dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes,
+                                 void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Approximate search over an INT8 copy of the corpus (additive to ABI 6; the reference has no counterpart).  One byte per
  * element instead of four: a symmetric per-row scalar quantisation, integer inner products, and — optionally — the candidate
  * cut re-scored from the fp32 rows.  Unlike the bf16 shadow this route is NOT exact: no error band of a useful width is
