@@ -2146,6 +2146,95 @@ int dewi_rows_put_f32(float* d_E, void* d_E_bf16, float* d_dewi32, float* d_ent3
                   "rows_put launch");
 }
 
+// ---- metadata predicates (additive to ABI 6): include/dewi_hip.h has the contract, the error order included ----
+int dewi_predicate_masks(const void* const* d_columns, const int32_t* column_types, int n_columns, int64_t n_rows,
+                         const dewi_pred_instr* programs, const int32_t* program_lengths, int n_programs,
+                         const uint32_t* d_sets, int64_t n_set_words, const uint8_t* d_base, uint8_t* d_masks, void* stream) {
+  if (!programs || !program_lengths || !d_masks || (n_columns > 0 && (!d_columns || !column_types)) || (n_set_words > 0 && !d_sets))
+    return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (n_rows < 0 || n_columns < 0 || n_programs <= 0 || n_set_words < 0)
+    return fail(DEWI_ERR_INVALID_ARG, "bad counts: %lld rows, %d columns, %d programs, %lld set words", static_cast<long long>(n_rows),
+                n_columns, n_programs, static_cast<long long>(n_set_words));
+  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (n_columns > DEWI_PRED_MAX_COLUMNS)
+    return fail(DEWI_ERR_UNSUPPORTED, "%d columns exceed DEWI_PRED_MAX_COLUMNS = %d", n_columns, DEWI_PRED_MAX_COLUMNS);
+  if (n_programs > DEWI_PRED_MAX_PROGRAMS)
+    return fail(DEWI_ERR_UNSUPPORTED, "%d programs exceed DEWI_PRED_MAX_PROGRAMS = %d", n_programs, DEWI_PRED_MAX_PROGRAMS);
+  for (int c = 0; c < n_columns; ++c) {
+    if (!d_columns[c]) return fail(DEWI_ERR_INVALID_ARG, "null pointer for column %d", c);
+    if (column_types[c] != 0 && column_types[c] != 1)
+      return fail(DEWI_ERR_INVALID_ARG, "unknown type %d of column %d (0 int32, 1 fp32)", column_types[c], c);
+  }
+  int64_t at = 0;
+  for (int p = 0; p < n_programs; ++p) {
+    const int len = program_lengths[p];
+    if (len < 1 || len > DEWI_PRED_MAX_INSTR)
+      return fail(DEWI_ERR_INVALID_ARG, "program %d: %d instructions (1 .. %d)", p, len, DEWI_PRED_MAX_INSTR);
+    int depth = 0;
+    for (int i = 0; i < len; ++i) {
+      const dewi_pred_instr& in = programs[at + i];
+      if (in.op < DEWI_PRED_I_LT || in.op > DEWI_PRED_NOT) return fail(DEWI_ERR_INVALID_ARG, "program %d instruction %d: unknown op %d", p, i, in.op);
+      if (in.op < DEWI_PRED_TRUE) {
+        if (in.column < 0 || in.column >= n_columns)
+          return fail(DEWI_ERR_INVALID_ARG, "program %d instruction %d: column %d outside [0, %d)", p, i, in.column, n_columns);
+        const int want = in.op >= DEWI_PRED_F_LT ? 1 : 0;
+        if (column_types[in.column] != want)
+          return fail(DEWI_ERR_INVALID_ARG, "program %d instruction %d: op %d takes %s column, column %d is %s", p, i, in.op,
+                      want ? "an fp32" : "an int32", in.column, want ? "int32" : "fp32");
+        if (in.op == DEWI_PRED_I_IN_SET && static_cast<int64_t>(in.a) + (static_cast<int64_t>(in.b) + 31) / 32 > n_set_words)
+          return fail(DEWI_ERR_INVALID_ARG, "program %d instruction %d: a set of %u bits from word %u on lies outside the %lld set words",
+                      p, i, in.b, in.a, static_cast<long long>(n_set_words));
+      }
+      if (in.op == DEWI_PRED_AND || in.op == DEWI_PRED_OR) {
+        if (depth < 2) return fail(DEWI_ERR_INVALID_ARG, "program %d instruction %d: stack underflow", p, i);
+        --depth;
+      } else if (in.op == DEWI_PRED_NOT) {
+        if (depth < 1) return fail(DEWI_ERR_INVALID_ARG, "program %d instruction %d: stack underflow", p, i);
+      } else if (++depth > DEWI_PRED_MAX_DEPTH) {
+        return fail(DEWI_ERR_INVALID_ARG, "program %d instruction %d: stack deeper than %d", p, i, DEWI_PRED_MAX_DEPTH);
+      }
+    }
+    if (depth != 1) return fail(DEWI_ERR_INVALID_ARG, "program %d ends with %d values on the stack, not 1", p, depth);
+    at += len;
+  }
+  if (n_rows == 0) return DEWI_OK;
+  // consecutive programs per launch: as many as its kernel arguments hold
+  dewi::PredLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.sets = d_sets;
+  L.base = d_base;
+  L.n_rows = n_rows;
+  at = 0;
+  int p = 0;
+  while (p < n_programs) {
+    int n_instr = 0, np = 0;
+    int slot_of[DEWI_PRED_MAX_COLUMNS];   // column -> its slot in this launch, -1: not read
+    for (int c = 0; c < DEWI_PRED_MAX_COLUMNS; ++c) slot_of[c] = -1;
+    L.n_cols = 0;
+    while (p + np < n_programs && np < dewi::kPredLaunchPrograms && n_instr + program_lengths[p + np] <= dewi::kPredLaunchInstr) {
+      const int len = program_lengths[p + np];
+      for (int i = 0; i < len; ++i) {
+        const dewi_pred_instr& in = programs[at + i];
+        const bool leaf = in.op < DEWI_PRED_TRUE;
+        if (leaf && slot_of[in.column] < 0) {
+          slot_of[in.column] = L.n_cols;
+          L.cols[L.n_cols++] = static_cast<const uint32_t*>(d_columns[in.column]);
+        }
+        L.instr[n_instr + i] = dewi::PredInstr{static_cast<uint32_t>(in.op) | (leaf ? static_cast<uint32_t>(slot_of[in.column]) << 8 : 0u), in.a, in.b};
+      }
+      n_instr += len;
+      at += len;
+      L.prog_end[np++] = static_cast<uint32_t>(n_instr);
+    }
+    L.n_programs = np;
+    L.masks = d_masks + static_cast<size_t>(p) * static_cast<size_t>(n_rows);
+    hipError_t e = dewi::launch_predicate_masks(L, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "predicate_masks launch");
+    p += np;
+  }
+  return DEWI_OK;
+}
+
 int dewi_timing_enable(int every) {
   g_timing.every = every > 0 ? every : 0;
   g_timing.calls = 0;

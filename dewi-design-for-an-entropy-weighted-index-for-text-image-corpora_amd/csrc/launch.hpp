@@ -627,4 +627,28 @@ struct ScoreParams {
 hipError_t launch_score(const void* d_S, int is_f64, int64_t n, int64_t ld, const ScoreParams& sp, const float* d_med,
                         const float* d_mad, double* d_out, float* d_out32, hipStream_t stream);
 
+// ---- where.hip: metadata predicates (dewi_predicate_masks) -----------------------------------
+// What one launch carries in its kernel arguments: the pointers of the columns its programs name (n_cols of them, in order of
+// first use: a "slot" each), the instructions of up to kPredLaunchPrograms consecutive programs (packed to 12 bytes:
+// op | slot << 8, a, b) and where each program ends.  The whole struct stays well under the 4 KB a launch may pass.
+constexpr int kPredLaunchPrograms = 32;
+constexpr int kPredLaunchInstr = 272;
+struct PredInstr {
+  uint32_t op_col;
+  uint32_t a, b;
+};
+struct PredLaunch {
+  const uint32_t* cols[DEWI_PRED_MAX_COLUMNS];
+  const uint32_t* sets;
+  const uint8_t* base;
+  uint8_t* masks;                 // of the launch's first program
+  int64_t n_rows;
+  int32_t n_cols;                 // columns the launch's programs read: cols[0 .. n_cols)
+  int32_t n_programs;
+  uint32_t prog_end[kPredLaunchPrograms];   // program p: instructions [prog_end[p - 1], prog_end[p])
+  PredInstr instr[kPredLaunchInstr];
+};
+static_assert(sizeof(PredLaunch) <= 3584, "the predicate launch must fit the kernel arguments");
+hipError_t launch_predicate_masks(const PredLaunch& L, hipStream_t stream);
+
 }  // namespace dewi

@@ -1057,6 +1057,58 @@ class DeviceCorpus:
         return DeviceQueryFilters(buf, m8, np.frombuffer(counts, dtype=np.int64).copy(), n_union.value, self.corpus_id,
                                   self.n_rows)
 
+    # ------------------------------------------------------------------ predicates over attribute columns
+    def predicate_masks(self, columns, programs, sets, base=None):
+        """Evaluate postfix predicate programs (``dewi.where``; ``dewi_predicate_masks``) over attribute columns of this corpus:
+        ``columns`` device tensors [n_rows] of int32 or float32, ``programs`` P lists of ``(op, column, a, b)``, ``sets`` the
+        uint32 words of the ``isin`` bitsets (numpy or device), ``base`` ``None`` or device bytes / bools [n_rows] ANDed into
+        every result.  Returns a device uint8 tensor [P, n_rows] of 0 / 1.  Asynchronous on the current stream: no
+        synchronisation, no workspace."""
+        torch = _torch()
+        n = self.n_rows
+        cols = list(columns)
+        types = (ctypes.c_int32 * max(len(cols), 1))()
+        ptrs = (ctypes.c_void_p * max(len(cols), 1))()
+        for i, c in enumerate(cols):
+            if not (isinstance(c, torch.Tensor) and c.is_cuda and c.dim() == 1 and int(c.shape[0]) == n and c.is_contiguous()
+                    and c.dtype in (torch.int32, torch.float32)):
+                raise ValueError(f"attribute column {i} must be a contiguous CUDA int32 / float32 tensor of shape ({n},)")
+            types[i] = 1 if c.dtype == torch.float32 else 0
+            ptrs[i] = c.data_ptr()
+        progs = [list(p) for p in programs]
+        n_instr = sum(len(p) for p in progs)
+        instr = (nat.PredInstr * max(n_instr, 1))()
+        lengths = (ctypes.c_int32 * max(len(progs), 1))()
+        at = 0
+        for j, p in enumerate(progs):
+            lengths[j] = len(p)
+            for op, c, a, b in p:
+                instr[at] = nat.PredInstr(int(op), int(c), int(a) & 0xFFFFFFFF, int(b) & 0xFFFFFFFF)
+                at += 1
+        with torch.cuda.device(self.device):
+            if isinstance(sets, torch.Tensor):
+                s = sets.to(device=self.device).contiguous()
+                assert s.dtype == torch.int32
+            else:
+                s = torch.from_numpy(np.ascontiguousarray(sets, dtype=np.uint32).view(np.int32)).to(self.device)
+            b8 = None
+            if base is not None:
+                if tuple(base.shape) != (n,) or base.dtype not in (torch.uint8, torch.bool):
+                    raise ValueError(f"base mask must be bytes or bools of shape ({n},)")
+                b8 = base.to(device=self.device).view(torch.uint8).contiguous()
+            out = torch.empty((len(progs), n), dtype=torch.uint8, device=self.device)
+            nat.check(self._lib.dewi_predicate_masks(ptrs, types, len(cols), n, instr, lengths, len(progs),
+                                                     nat.ptr(s) if s.numel() else None, int(s.numel()), nat.ptr(b8),
+                                                     nat.ptr(out), nat.stream_ptr()))
+        return out
+
+    def make_filter_bytes(self, mask8) -> DeviceFilter:
+        """``make_filter`` of a device byte mask [n_rows] of 0 / 1 that this corpus made itself (``predicate_masks``): no copy,
+        and the filter's ``byte_mask()`` is seeded with the mask."""
+        f = self.make_filter(mask8.view(_torch().bool))
+        f._mask = mask8
+        return f
+
     def check_query_filters(self, qf: DeviceQueryFilters, n_queries: Optional[int] = None) -> None:
         if not isinstance(qf, DeviceQueryFilters):
             raise TypeError(f"expected DeviceQueryFilters (make_query_filters), got {type(qf).__name__}")

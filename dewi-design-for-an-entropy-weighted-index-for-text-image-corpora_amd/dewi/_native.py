@@ -45,6 +45,15 @@ I8_MAX_CANDIDATES = 1024
 I8_MAX_DIM = 4096
 #: which row of a group represents it (include/dewi_hip.h DEWI_GROUPS_KEEP_*): the lowest row / the highest key (the dewi column)
 KEEP_CODES = {"first": 0, "dewi": 1}
+#: limits of dewi_predicate_masks (include/dewi_hip.h DEWI_PRED_MAX_*)
+PRED_MAX_COLUMNS = 16
+PRED_MAX_INSTR = 64
+PRED_MAX_DEPTH = 32
+PRED_MAX_PROGRAMS = 256
+#: opcodes of a predicate program (include/dewi_hip.h DEWI_PRED_*), in the header's order
+PRED_OPS = ("I_LT", "I_LE", "I_EQ", "I_NE", "I_GE", "I_GT", "I_BETWEEN", "I_ANY_BITS", "I_ALL_BITS", "I_IN_SET",
+            "F_LT", "F_LE", "F_EQ", "F_NE", "F_GE", "F_GT", "F_BETWEEN", "F_IS_NAN", "TRUE", "AND", "OR", "NOT")
+PRED_OP_CODES = {name: code for code, name in enumerate(PRED_OPS)}
 
 #: every symbol include/dewi_hip.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -74,6 +83,7 @@ EXPORTED_SYMBOLS = (
     "dewi_select_workspace_bytes", "dewi_select_begin", "dewi_select_seed", "dewi_select_run",
     "dewi_select_block_max", "dewi_select_blocked_workspace_bytes", "dewi_select_seed_blocked", "dewi_select_run_blocked",
     "dewi_select_grouped_workspace_bytes", "dewi_select_groups_begin", "dewi_select_run_grouped", "dewi_select_run_blocked_grouped",
+    "dewi_predicate_masks",
 )
 #: the words dewi_robust_fit_fast_plan fills, in order (include/dewi_hip.h)
 FIT_FAST_PLAN_WORDS = ("supported", "slices", "counters_offset", "counters_bytes", "small_n", "sample", "delta", "buckets",
@@ -85,6 +95,11 @@ I8_BATCH_PLAN_WORDS = ("groups", "n_blocks", "n_seg", "seg_cap", "tile_stride", 
 
 class NativeLibraryError(RuntimeError):
     """The HIP extension is missing, stale, or no MI355X is visible."""
+
+
+class PredInstr(ctypes.Structure):
+    """``dewi_pred_instr``: one instruction of a predicate program (include/dewi_hip.h; ``dewi.where`` compiles them)."""
+    _fields_ = [("op", ctypes.c_int32), ("column", ctypes.c_int32), ("a", ctypes.c_uint32), ("b", ctypes.c_uint32)]
 
 
 class DewiCandidate(ctypes.Structure):
@@ -288,6 +303,9 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_knn_candidates_filtered.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, vp, vp, i32, i32, i64, vp, vp, sz, vp]
     lib.dewi_robust_fit_fast_plan.restype = i32
     lib.dewi_robust_fit_fast_plan.argtypes = [i64, i32, c.POINTER(i64), i32]
+    lib.dewi_predicate_masks.restype = i32
+    lib.dewi_predicate_masks.argtypes = [c.POINTER(vp), c.POINTER(c.c_int32), i32, i64, c.POINTER(PredInstr), c.POINTER(c.c_int32), i32,
+                                         vp, i64, vp, vp, vp]
 
 
 def load_library(require_gpu: bool = True) -> ctypes.CDLL:

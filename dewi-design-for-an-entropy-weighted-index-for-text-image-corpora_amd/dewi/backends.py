@@ -24,7 +24,9 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
+from .attributes import AttributesMixin
 from .types import PAYLOAD_FIELDS, Payload, PayloadStore, payload_columns
+from .where import Where, is_where_list
 
 logger = logging.getLogger(__name__)
 
@@ -155,7 +157,7 @@ class FAISSIndex(BaseIndex):
         raise ImportError("FAISS not available in the MI355X build: use ExactIndex (HIP brute force)")
 
 
-class ExactIndex(BaseIndex):
+class ExactIndex(AttributesMixin, BaseIndex):
     """Exact nearest-neighbour search with DEWI re-ranking, on the GPU.
 
     Drop-in for reference ``ExactIndex`` (backends.py:386-556): same constructor, same
@@ -169,7 +171,9 @@ class ExactIndex(BaseIndex):
       stored rows can differ from the reference's in the last fp32 bit;
     * the payload values the re-rank reads (``dewi``, ``ht_mean``, ``hi_mean``) are
       snapshotted into HBM columns at ``build``; call ``refresh_payloads()`` after mutating
-      ``Payload`` objects in place.
+      ``Payload`` objects in place;
+    * attribute columns and predicates over them (``set_attributes``, ``make_filter_where``, ``filter=`` a
+      ``dewi.where.Where``): ``dewi.attributes.AttributesMixin``.
     """
 
     def __init__(self, dim: int, space: str = "cosine", **kwargs: Any):
@@ -197,6 +201,7 @@ class ExactIndex(BaseIndex):
             from ._engine import check_int8_shape
             check_int8_shape(space, False, dim)
         self._id_rows: Optional[Dict[str, int]] = None  # doc_id -> row of remove / upsert: made once, then kept per call
+        self._attrs_init()                          # attribute columns (dewi.attributes)
 
     # ---------------------------------------------------------------- ingest (A1)
     def add(self, doc_id: str, embedding: np.ndarray, payload: Payload) -> None:
@@ -291,6 +296,7 @@ class ExactIndex(BaseIndex):
         (``DeviceCorpus.reserve``: a device-to-device copy, peak memory old plus new; the storage never shrinks)."""
         self._ensure_built()
         self._corpus.reserve(int(rows))
+        self._attr_columns()                        # (the attribute columns grow with the storage)
 
     def _row_map(self) -> Dict[str, int]:
         """doc_id -> row: built once in O(N), then maintained by every remove / upsert (``add`` drops it).  An index that
@@ -350,8 +356,10 @@ class ExactIndex(BaseIndex):
             return 0
         n_old = len(self._doc_ids)
         self._check_removal(n_old - len(ids))
+        self._attr_columns()                        # (a loaded index's attributes go to the device before its rows move)
         src, dst = self._corpus_remove(rows)
         n_keep = n_old - len(ids)
+        self._attrs_after_remove(src, dst, n_keep)
         m, all_ids = self._id_rows, self._doc_ids
         for d in ids:
             del m[d]
@@ -423,7 +431,9 @@ class ExactIndex(BaseIndex):
                 r = n + len(fresh)
                 fresh.append(d)
             rows[i] = r
+        self._attr_columns()
         self._corpus_put(rows, emb, triple)
+        self._attrs_after_put(rows, payloads, cols)
         self._doc_ids.extend(fresh)
         m.update(zip(fresh, range(n, n + len(fresh))))
         self._payloads.follow_put(rows, n, self._doc_ids, ids, objects=payloads, columns=cols)
@@ -549,11 +559,10 @@ class ExactIndex(BaseIndex):
         self._host_rows = None
         self._is_trained = True
 
-    def _payload_columns(self) -> Dict[str, np.ndarray]:
-        """float64 ``dewi`` / ``ht_mean`` / ``hi_mean`` of every row, in row order.  Column-ingested
+    def _payload_columns(self, fields: Tuple[str, ...] = ("dewi", "ht_mean", "hi_mean")) -> Dict[str, np.ndarray]:
+        """float64 ``dewi`` / ``ht_mean`` / ``hi_mean`` (or other ``Payload`` ``fields``) of every row, in row order.  Column-ingested
         blocks are copied as arrays (objects already handed out for some of their rows win, so in-place
         edits of a returned ``Payload`` are seen by ``refresh_payloads``); the rest is read from objects."""
-        fields = ("dewi", "ht_mean", "hi_mean")
         n = len(self._doc_ids)
         store = self._payloads
         out = {name: np.zeros(n, dtype=np.float64) for name in fields}
@@ -703,9 +712,14 @@ class ExactIndex(BaseIndex):
         return self._corpus.make_query_filters(self.query_filter_masks(masks, doc_ids=doc_ids, rows=rows))
 
     def _prepared(self, filter):
-        """A ``DeviceFilter`` / ``DeviceQueryFilters``, anything ``make_filter`` takes (bool mask, doc ids, integer rows)
-        or a bool [B, N] mask (``make_query_filters``), prepared on the fly."""
+        """A ``DeviceFilter`` / ``DeviceQueryFilters``, a ``Where`` predicate over the attribute columns (a list of B of them:
+        one per query), anything ``make_filter`` takes (bool mask, doc ids, integer rows) or a bool [B, N] mask
+        (``make_query_filters``), prepared on the fly."""
         from ._engine import DeviceFilter, DeviceQueryFilters
+        if isinstance(filter, Where):
+            return self.make_filter_where(filter)
+        if is_where_list(filter):
+            return self.make_query_filters_where(filter)
         if filter is None or isinstance(filter, (DeviceFilter, DeviceQueryFilters)):
             return filter
         if len(getattr(filter, "shape", ())) == 2:
@@ -935,7 +949,9 @@ class ExactIndex(BaseIndex):
         n = len(self._doc_ids)
         with corpus._lock, torch.cuda.device(corpus.device):
             mask = None
-            if isinstance(filter, DeviceQueryFilters):
+            if isinstance(filter, Where):
+                filter = self.make_filter_where(filter)
+            if isinstance(filter, DeviceQueryFilters) or is_where_list(filter):
                 raise ValueError("select_subset takes one allow-list, not per-query filters")
             if isinstance(filter, DeviceFilter):
                 corpus.check_filter(filter)
@@ -1058,7 +1074,7 @@ class ExactIndex(BaseIndex):
         from ._engine import DeviceQueryFilters
         if int(per_group) <= 0:
             raise ValueError(f"per_group must be positive, got {per_group}")
-        if isinstance(filter, DeviceQueryFilters) or (filter is not None and len(getattr(filter, "shape", ())) == 2):
+        if isinstance(filter, DeviceQueryFilters) or is_where_list(filter) or (filter is not None and len(getattr(filter, "shape", ())) == 2):
             raise NotImplementedError("a collapsed search takes one allow-list for the batch (per-query filters: not in this build)")
         self._ensure_built()
         q = np.asarray(queries, dtype=np.float32)
@@ -1113,7 +1129,7 @@ class ExactIndex(BaseIndex):
             raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
         b = int(q.shape[0])
         thr = check_thresholds(threshold, b)
-        if isinstance(filter, DeviceQueryFilters) or (filter is not None and len(getattr(filter, "shape", ())) == 2):
+        if isinstance(filter, DeviceQueryFilters) or is_where_list(filter) or (filter is not None and len(getattr(filter, "shape", ())) == 2):
             raise NotImplementedError("range search takes one allow-list for the batch (per-query filters: not in this build)")
         if not self._doc_ids or b == 0:         # an empty index has no rows to return (and nothing to build)
             return (np.zeros(b + 1, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32), np.zeros(0, np.float32))
@@ -1221,6 +1237,7 @@ class ExactIndex(BaseIndex):
                 fh.write(json.dumps({"doc_id": doc_id, "payload": self._payloads[doc_id].to_dict()}) + "\n")
         if len(matrix) > 0:
             np.save(str(root / "embeddings.npy"), matrix)
+        self._attrs_save(root)                      # attributes.npz / attributes.json, only when there are attributes
 
     @classmethod
     def load(cls, path: Union[str, Path], **kwargs: Any) -> "ExactIndex":
@@ -1242,4 +1259,5 @@ class ExactIndex(BaseIndex):
         elif inst._doc_ids:
             logger.warning("No embeddings found during load, index will need to be rebuilt")
         inst._is_trained = False  # the device copy is rebuilt lazily on the first search
+        inst._attrs_load(root)
         return inst

@@ -6,6 +6,8 @@ this build every backend choice resolves to the HIP ``ExactIndex`` (ANN graph li
 are out of scope), with the reference's own warning when an ANN backend was asked for.
 Additions: ``add_batch``, ``search_batch``, ``range_search``, ``range_search_batch``, ``near_duplicates``, ``duplicate_groups``,
 ``dedup_filter``, ``make_groups`` / ``search_collapsed`` / ``search_collapsed_batch`` and the in-place ``remove`` / ``upsert`` / ``upsert_batch`` / ``upsert_batch_columns`` / ``rows_of`` / ``reserve``.
+Attribute columns and predicates over them (``set_attributes``, ``attributes_from_payload``, ``update_attributes``,
+``attributes_of``, ``make_filter_where``, ``make_query_filters_where``, ``count_where``; ``filter=`` takes a ``dewi.where.Where``).
 """
 from __future__ import annotations
 
@@ -382,6 +384,47 @@ class DewiIndex(BaseIndex):
         out = self._backend.dedup_filter(threshold, keep=keep)
         self._built = True
         return out
+
+    # ------------------------------------------------------------------ attribute columns and predicates (additive)
+    def _built_backend(self):
+        if not self._built:
+            self.build()
+        return self._backend
+
+    def set_attributes(self, **columns) -> None:
+        """Set per-document attribute columns by name (``ExactIndex.set_attributes``): integers, floats or strings, one
+        value per document; ``filter=`` then takes ``dewi.where`` predicates over them."""
+        self._built_backend().set_attributes(**columns)
+
+    def attribute_names(self) -> List[str]:
+        return self._backend.attribute_names()
+
+    def attribute_schema(self):
+        return self._backend.attribute_schema()
+
+    def drop_attributes(self, *names: str) -> None:
+        self._built_backend().drop_attributes(*names)
+
+    def attributes_from_payload(self, *fields: str) -> None:
+        """Mirror ``Payload`` fields as fp32 attribute columns of the same name (``ExactIndex.attributes_from_payload``)."""
+        self._built_backend().attributes_from_payload(*fields)
+
+    def update_attributes(self, doc_ids: Sequence[str], **values) -> None:
+        self._built_backend().update_attributes(doc_ids, **values)
+
+    def attributes_of(self, doc_ids: Sequence[str]) -> Dict[str, Any]:
+        return self._built_backend().attributes_of(doc_ids)
+
+    def make_filter_where(self, where, base=None):
+        """Prepare the allow-list of a ``dewi.where`` predicate on the device (``ExactIndex.make_filter_where``)."""
+        return self._built_backend().make_filter_where(where, base=base)
+
+    def make_query_filters_where(self, wheres, base=None):
+        """One predicate per query (``ExactIndex.make_query_filters_where``)."""
+        return self._built_backend().make_query_filters_where(wheres, base=base)
+
+    def count_where(self, where) -> int:
+        return self._built_backend().count_where(where)
 
     # ------------------------------------------------------------------ accessors (index.py:95-119)
     def __len__(self) -> int:

@@ -1060,6 +1060,84 @@ int dewi_score_f64_dev(const void* d_S, int signals_are_f64, int64_t n, int64_t 
                        float* d_out32, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Metadata predicates (additive to ABI 6; the reference has no counterpart): boolean expressions over
+ * per-row ATTRIBUTE COLUMNS of 4-byte values, evaluated on the device into the byte masks that dewi_filter_prepare /
+ * dewi_query_filter_prepare take.  One call evaluates n_programs predicates over the same columns.
+ *
+ * A predicate is a POSTFIX PROGRAM of dewi_pred_instr over a stack of bits (one u32 of stack per row):
+ *   leaf ops push one bit.  int32 column x: I_LT .. I_GT signed compares of x against (int32) a; I_BETWEEN
+ *     (int32) a <= x <= (int32) b; I_ANY_BITS (x & a) != 0; I_ALL_BITS (x & a) == a; I_IN_SET: a bitset of b bits that
+ *     starts at word a of d_sets — true iff 0 <= x < b and bit x % 32 of word a + x / 32 is set (no word is read for
+ *     another x).  fp32 column x, a and b holding the BITS of fp32 constants: F_LT .. F_GT and F_BETWEEN (a <= x <= b)
+ *     compare as IEEE does (every compare with a NaN is false but F_NE, which is true; -0 equals +0); F_IS_NAN.  TRUE
+ *     pushes 1 (column ignored).
+ *   AND / OR pop two bits and push one; NOT flips the top (column, a, b ignored).
+ * A VALID program has 1 .. DEWI_PRED_MAX_INSTR instructions, never pops an empty stack, never holds more than
+ * DEWI_PRED_MAX_DEPTH bits and ends with exactly one; its leaf ops name a column in [0, n_columns) of the op's type; every
+ * I_IN_SET has a + ceil(b / 32) <= n_set_words.
+ *
+ * d_columns: a HOST array of n_columns device pointers, each to n_rows 4-byte elements; column_types (HOST): 0 int32,
+ * 1 fp32.  programs (HOST): the instructions of all programs, concatenated; program_lengths (HOST): n_programs lengths.
+ * d_sets: n_set_words u32 on the device (NULL with n_set_words == 0).  d_base: NULL, or n_rows bytes ANDed into every
+ * program's result (non-zero = allowed).  d_masks: [n_programs][n_rows] bytes, program p's mask from byte p * n_rows on (NOT
+ * 4-byte aligned for n_rows % 4 != 0 and p > 0); every byte is written, 0 or 1.
+ *
+ * Execution: asynchronous on `stream`; allocates nothing, synchronises nothing, needs no workspace and no copy: the column
+ * pointers and the programs travel as KERNEL ARGUMENTS (wave-uniform, read with scalar loads).  One launch takes as many
+ * consecutive programs as fit its arguments (at most 32 programs and 272 instructions: under 4 KB); a larger batch takes
+ * several launches.  A launch reads each column its programs name once per row for all of them (a lane takes four consecutive
+ * rows: one 16-byte load where the column is 16-byte aligned, 4-byte loads otherwise), and writes one byte per row and
+ * program (four at a time where the mask is 4-byte aligned there).  Nothing is read outside a column's n_rows elements, d_base[n_rows] or
+ * d_sets[n_set_words]; nothing is written outside d_masks.
+ *
+ * Errors, every one before any device work, in this order:
+ *   1. a NULL programs, program_lengths or d_masks; NULL d_columns or column_types with n_columns > 0; NULL d_sets with
+ *      n_set_words > 0: DEWI_ERR_INVALID_ARG "null pointer";
+ *   2. n_rows < 0, n_columns < 0, n_programs <= 0 or n_set_words < 0: DEWI_ERR_INVALID_ARG;
+ *   3. n_rows >= 2^32, n_columns > DEWI_PRED_MAX_COLUMNS, n_programs > DEWI_PRED_MAX_PROGRAMS: DEWI_ERR_UNSUPPORTED;
+ *   4. a NULL d_columns[c], a column type other than 0 / 1 (columns in order): DEWI_ERR_INVALID_ARG;
+ *   5. the programs in order, each: its length, then its instructions in order (unknown op; column out of range; column of
+ *      the other type; set outside d_sets; stack underflow; stack deeper than 32), then its final depth:
+ *      DEWI_ERR_INVALID_ARG.
+ * n_rows == 0 (after those checks): DEWI_OK, nothing launched.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct dewi_pred_instr {
+  int32_t op;      /* DEWI_PRED_* */
+  int32_t column;  /* leaf ops: index into d_columns */
+  uint32_t a;
+  uint32_t b;
+} dewi_pred_instr; /* 16 bytes */
+#define DEWI_PRED_MAX_COLUMNS 16
+#define DEWI_PRED_MAX_INSTR 64    /* per program */
+#define DEWI_PRED_MAX_DEPTH 32    /* the stack is one u32 of bits per row */
+#define DEWI_PRED_MAX_PROGRAMS 256
+#define DEWI_PRED_I_LT 0
+#define DEWI_PRED_I_LE 1
+#define DEWI_PRED_I_EQ 2
+#define DEWI_PRED_I_NE 3
+#define DEWI_PRED_I_GE 4
+#define DEWI_PRED_I_GT 5
+#define DEWI_PRED_I_BETWEEN 6
+#define DEWI_PRED_I_ANY_BITS 7
+#define DEWI_PRED_I_ALL_BITS 8
+#define DEWI_PRED_I_IN_SET 9
+#define DEWI_PRED_F_LT 10
+#define DEWI_PRED_F_LE 11
+#define DEWI_PRED_F_EQ 12
+#define DEWI_PRED_F_NE 13
+#define DEWI_PRED_F_GE 14
+#define DEWI_PRED_F_GT 15
+#define DEWI_PRED_F_BETWEEN 16
+#define DEWI_PRED_F_IS_NAN 17
+#define DEWI_PRED_TRUE 18
+#define DEWI_PRED_AND 19
+#define DEWI_PRED_OR 20
+#define DEWI_PRED_NOT 21
+int dewi_predicate_masks(const void* const* d_columns, const int32_t* column_types, int n_columns, int64_t n_rows,
+                         const dewi_pred_instr* programs, const int32_t* program_lengths, int n_programs,
+                         const uint32_t* d_sets, int64_t n_set_words, const uint8_t* d_base, uint8_t* d_masks, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): dewi_timing_enable(n) makes every n-th dewi_knn_* call bracket its
  * corpus-scan kernel with hipEvents on `stream` (n = 1: every call; 0: off — the two event records
  * cost ~5 us of stream time, so throughput runs sample); dewi_timing_read synchronises those
