@@ -951,6 +951,119 @@ int dewi_knn_candidates_filtered(const void* d_E, int elem_type, int64_t n_rows,
                               workspace_bytes, "select launch (filtered records)", n_candidates);
 }
 
+// ---- search by examples (additive to ABI 6) ---------------------------------------------------------------------------
+// Workspace: the keys of the last pass, then the two fp32 arrays [n_scan] through which chained passes hand on (p, n).
+// (Always laid out, also for a request of one pass: the size then depends on the shape alone, not on the pass split.)
+struct ExamplesLayout {
+  dewi::ScanPlan plan;
+  size_t keys_off, part_p_off, part_n_off, total;
+};
+static bool examples_layout(int64_t n_scan, int dim, int n_candidates, ExamplesLayout* out) {
+  if (n_scan <= 0 || n_scan > 0xFFFFFFFFll || n_candidates <= 0 || n_candidates > dewi::kMaxSortCandidates) return false;
+  ExamplesLayout L;
+  const int c = n_candidates < n_scan ? n_candidates : static_cast<int>(n_scan);
+  L.plan = dewi::plan_scan_examples(n_scan, dim, c);
+  if (L.plan.kind != dewi::kScanAnyLong) return false;
+  L.keys_off = 0;
+  L.part_p_off = align_up(static_cast<size_t>(L.plan.keys_per_query) * 8, 256);
+  L.part_n_off = L.part_p_off + align_up(static_cast<size_t>(n_scan) * 4, 256);
+  L.total = L.part_n_off + align_up(static_cast<size_t>(n_scan) * 4, 256);
+  *out = L;
+  return true;
+}
+
+static thread_local int g_examples_per_pass = 0;   // dewi_examples_tuning_set: 0 = the plan's nq_max
+
+size_t dewi_knn_examples_workspace_bytes(int64_t n_scan, int dim, int n_examples, int n_candidates) {
+  ExamplesLayout L;
+  if (n_examples < 1 || n_examples > dewi::kExamplesMax || !examples_layout(n_scan, dim, n_candidates, &L)) return 0;
+  return L.total;
+}
+
+int dewi_examples_tuning_set(int examples_per_pass) {
+  if (examples_per_pass < 0) return fail(DEWI_ERR_INVALID_ARG, "examples_per_pass must be >= 0 (got %d)", examples_per_pass);
+  g_examples_per_pass = examples_per_pass;
+  return DEWI_OK;
+}
+
+int dewi_knn_candidates_examples(const float* d_E, int64_t n_rows, int dim, const float* d_examples, int n_positive,
+                                 int n_negative, int match, int negative_rule, double negative_weight,
+                                 const int64_t* d_exclude, int n_exclude, const void* d_filter, int64_t n_allowed,
+                                 const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
+                                 dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!d_E || !d_examples) return fail(DEWI_ERR_INVALID_ARG, "null embedding or example pointer");
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
+  if (n_positive < 1) return fail(DEWI_ERR_INVALID_ARG, "a request needs at least one positive example (got %d)", n_positive);
+  if (n_negative < 0) return fail(DEWI_ERR_INVALID_ARG, "n_negative must be >= 0 (got %d)", n_negative);
+  if (static_cast<int64_t>(n_positive) + n_negative > dewi::kExamplesMax)
+    return fail(DEWI_ERR_UNSUPPORTED, "%lld examples exceed the %d one request takes",
+                static_cast<long long>(n_positive) + n_negative, dewi::kExamplesMax);
+  if (match != DEWI_EXAMPLES_MATCH_ANY && match != DEWI_EXAMPLES_MATCH_ALL) return fail(DEWI_ERR_INVALID_ARG, "unknown match %d", match);
+  if (negative_rule != DEWI_EXAMPLES_RULE_PENALTY && negative_rule != DEWI_EXAMPLES_RULE_BEST_SCORE)
+    return fail(DEWI_ERR_INVALID_ARG, "unknown negative_rule %d", negative_rule);
+  if (!std::isfinite(static_cast<float>(negative_weight))) return fail(DEWI_ERR_INVALID_ARG, "negative_weight must be finite in fp32");
+  if (n_exclude < 0 || n_exclude > dewi::kExamplesMax)
+    return fail(DEWI_ERR_INVALID_ARG, "n_exclude %d outside [0, %d]", n_exclude, dewi::kExamplesMax);
+  if (n_exclude > 0 && !d_exclude) return fail(DEWI_ERR_INVALID_ARG, "null exclude pointer");
+  if (d_filter && (n_allowed < 0 || n_allowed > n_rows))
+    return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+  if (n_candidates <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_candidates must be positive (got %d)", n_candidates);
+  if (n_candidates > dewi::kMaxSortCandidates)
+    return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds the %d candidate records take", n_candidates, dewi::kMaxSortCandidates);
+  if (dim % 4 != 0 || dim <= 128 || dim > 4096)
+    return fail(DEWI_ERR_UNSUPPORTED, "search by examples serves rows of 33 to 1024 whole 16-byte units (dim %% 4 == 0, 132 <= dim <= 4096; got %d)", dim);
+  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
+  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
+                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
+  if (d_filter && n_allowed == 0) return DEWI_OK;   // nothing launched, nothing written (dewi_knn_candidates_filtered's rule)
+  const int64_t n_scan = d_filter ? n_allowed : n_rows;
+  ExamplesLayout L;
+  if (!examples_layout(n_scan, dim, n_candidates, &L)) return fail(DEWI_ERR_UNSUPPORTED, "shape outside the search by examples");
+  if (int rc = check_workspace(d_workspace, workspace_bytes, L.total)) return rc;
+
+  char* ws = static_cast<char*>(d_workspace);
+  uint64_t* keys = reinterpret_cast<uint64_t*>(ws + L.keys_off);
+  float* part_p = reinterpret_cast<float*>(ws + L.part_p_off);
+  float* part_n = reinterpret_cast<float*>(ws + L.part_n_off);
+  const int c = n_candidates < n_scan ? n_candidates : static_cast<int>(n_scan);
+  const int n_examples = n_positive + n_negative;
+  int per_pass = L.plan.nq_max;
+  if (g_examples_per_pass > 0 && g_examples_per_pass < per_pass) per_pass = g_examples_per_pass;
+  {
+    ScanTimer timer(stream);
+    for (int e0 = 0; e0 < n_examples; e0 += per_pass) {
+      const int m = n_examples - e0 < per_pass ? n_examples - e0 : per_pass;
+      const int ne = m <= 1 ? 1 : (m <= 2 ? 2 : 4);   // the instantiated slot counts; spare slots repeat the pass's last example
+      dewi::ExamplesPass ps{};
+      for (int s = 0; s < dewi::kExamplesPassMax; ++s) {
+        const int j = e0 + (s < m ? s : m - 1);
+        ps.idx[s] = j;
+        if (j >= n_positive) ps.neg_mask |= 1u << s;
+      }
+      ps.first = e0 == 0;
+      ps.last = e0 + m == n_examples;
+      ps.has_neg = n_negative > 0;
+      ps.match_all = match == DEWI_EXAMPLES_MATCH_ALL;
+      ps.rule = negative_rule;
+      ps.weight = static_cast<float>(negative_weight);
+      ps.n_exclude = n_exclude;
+      const hipError_t e = d_filter ? dewi::launch_scan_examples_list(L.plan, d_E, d_examples, ps, ne, part_p, part_n, d_exclude,
+                                                                      static_cast<const uint32_t*>(d_filter), c, keys, stream)
+                                    : dewi::launch_scan_examples(L.plan, d_E, n_rows, d_examples, ps, ne, part_p, part_n, d_exclude,
+                                                                 c, keys, stream);
+      if (e != hipSuccess) return hip_fail(e, "scan launch (examples)");
+    }
+  }
+  // (records: n_candidates per query; lists shorter than that are not "n_candidates sorted keys each": the unsorted route, as
+  // scan_select_filtered)
+  const hipError_t e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, (L.plan.slots == 1 && n_candidates == c) ? L.plan.n_lists : 0,
+                                                  1, n_candidates, 0, make_rerank(0.0, 0.0), d_dewi32, d_ent32, id_offset, nullptr,
+                                                  nullptr, d_out, nullptr, dewi::SegmentLayout{}, stream);
+  return launched(e, "select launch (example records)");
+}
+
 // ---- per-query filters (additive to ABI 6) ----------------------------------------------------------------------------
 // Prepared query-filter buffer (u32 words): the prepared filter of the union U (dewi_filter_prepare's layout: header, then the
 // union list, capacity n_rows), the query-word planes [ceil(B / 32)][|U|] (capacity [ceil(B / 32)][n_rows]), |F_j| for every j,

@@ -578,6 +578,35 @@ hipError_t launch_mfma_i8(const MfmaI8Layout& m, const int8_t* d_codes, const fl
 hipError_t launch_scan_i8_flagged(const MfmaI8Layout& m, const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim,
                                   int n_queries, int n_candidates, char* ws, hipStream_t stream);
 
+// ---- knn_scan_examples.hip / knn_scan_examples_list.hip: search by examples (include/dewi_hip.h, "Search by examples") ----
+constexpr int kExamplesMax = DEWI_EXAMPLES_MAX;
+constexpr int kExamplesPassMax = 4;      // most examples of one pass (scan_any.hpp any_nq_max's largest answer)
+constexpr int kExamplesMaxBlocks = 256;  // workgroups of a pass: one per compute unit of an MI355X, whatever the device (the
+                                         // plan, and with it the workspace size, needs no device)
+// One pass of a request, by value in the kernel arguments (wave-uniform: scalar registers).
+struct ExamplesPass {
+  int32_t idx[kExamplesPassMax];   // the examples (rows of d_examples) of the pass's slots; slots behind the pass's last
+                                   // example repeat it (max / min of a value with itself: no change)
+  uint32_t neg_mask;               // bit s: slot s holds a negative
+  int32_t first, last;             // first: nothing to read from the partial arrays; last: score and offer instead of writing them
+  int32_t has_neg;                 // the REQUEST has negatives
+  int32_t match_all;               // p = min over the positives (DEWI_EXAMPLES_MATCH_ALL)
+  int32_t rule;                    // DEWI_EXAMPLES_RULE_*
+  float weight;                    // fp32(negative_weight)
+  int32_t n_exclude;
+};
+// fills blocks / waves, slots (1 / 4 / dense 0), n_lists, keys_per_query, units, u_pad, level, rows_per_iter and nq_max (the
+// examples one pass holds) by plan_scan's rules; kind == kScanGeneric: a shape the route does not take.  Needs no device.
+ScanPlan plan_scan_examples(int64_t n_scan, int dim, int n_candidates);
+// one pass: `ne` slots (1, 2 or 4, at most plan.nq_max); part_p / part_n [n_scan] fp32 (unused by a pass that is first and last)
+hipError_t launch_scan_examples(const ScanPlan& plan, const float* d_E, int64_t n_rows, const float* d_X, const ExamplesPass& ps,
+                                int ne, float* part_p, float* part_n, const int64_t* d_exclude, int c, uint64_t* keys,
+                                hipStream_t stream);
+// the same over the rows of a prepared filter (one bucket) — plan made on the list's length, partials and dense keys at list positions
+hipError_t launch_scan_examples_list(const ScanPlan& plan, const float* d_E, const float* d_X, const ExamplesPass& ps, int ne,
+                                     float* part_p, float* part_n, const int64_t* d_exclude, const uint32_t* d_filter, int c,
+                                     uint64_t* keys, hipStream_t stream);
+
 // ---- mutate.hip (in-place removal / upsert of rows; the reference has no counterpart) --------
 // d_error: an int32 the kernels INCREMENT for every pair / slot outside the contract (the caller zeroes it).
 hipError_t launch_rows_move(void* d_E, int elem_type, uint16_t* d_shadow, float* d_dewi32, float* d_ent32, int32_t* d_aux,

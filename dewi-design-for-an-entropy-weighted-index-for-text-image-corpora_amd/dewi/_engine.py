@@ -71,6 +71,40 @@ def check_int8_shape(space: str, is_bf16: bool, dim: int) -> None:
         raise ValueError(f"the int8 shadow takes dim % 16 == 0 from 16 to {nat.I8_MAX_DIM} columns, got dim = {dim}")
 
 
+#: largest candidate cut of a search by examples (what one workgroup of the select sorts: 2048 records)
+EXAMPLES_MAX_CANDIDATES = 2048
+
+
+def check_examples_shape(space: str, is_bf16: bool, dim: int) -> None:
+    """What a search by examples serves: cosine, an fp32 corpus, ``dim % 4 == 0`` from 132 to 4096 columns — anything else
+    is a ``ValueError``.  Host logic only."""
+    if space != "cosine":
+        raise ValueError(f"a search by examples serves cosine corpora, not space={space!r}")
+    if is_bf16:
+        raise ValueError("a search by examples serves fp32 corpora (this corpus is bf16)")
+    if int(dim) % 4 != 0 or not 132 <= int(dim) <= 4096:
+        raise ValueError(f"a search by examples takes dim % 4 == 0 from 132 to 4096 columns, got dim = {dim}")
+
+
+def check_examples_request(n_positive: int, n_negative: int, match: str, negative_rule: str, negative_weight) -> Tuple[int, int]:
+    """A request's counts and rules: at least one positive, at most ``EXAMPLES_MAX`` = 16 examples, ``match`` "any" / "all",
+    ``negative_rule`` "penalty" / "best_score", a weight that is finite in fp32 — ``ValueError`` otherwise.  Host logic only."""
+    if n_positive < 1:
+        raise ValueError("a search by examples needs at least one positive example")
+    if n_negative < 0:
+        raise ValueError(f"n_negative must be >= 0, got {n_negative}")
+    if n_positive + n_negative > nat.EXAMPLES_MAX:
+        raise ValueError(f"a search by examples takes at most {nat.EXAMPLES_MAX} examples, got {n_positive + n_negative}")
+    if match not in nat.EXAMPLES_MATCH_CODES:
+        raise ValueError(f"unknown match {match!r} (one of {sorted(nat.EXAMPLES_MATCH_CODES)})")
+    if negative_rule not in nat.EXAMPLES_RULE_CODES:
+        raise ValueError(f"unknown negative_rule {negative_rule!r} (one of {sorted(nat.EXAMPLES_RULE_CODES)})")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(np.float32(negative_weight)):
+            raise ValueError(f"negative_weight must be finite in fp32, got {negative_weight!r}")
+    return n_positive, n_negative
+
+
 def approx_cut(k: int, candidates: Optional[int], n: int) -> int:
     """The cut of an approximate search: the project's one rule (``cut_size``: ``min(2k, n)``, or ``candidates``), which the
     int8 route serves up to ``I8_MAX_CANDIDATES``; ``k`` must fit into it.  ``ValueError`` otherwise.  Host logic only."""
@@ -1966,6 +2000,90 @@ class DeviceCorpus:
             nat.ptr(self.dewi32), nat.ptr(self.ent32), c, nat.SPACE_CODES[self.space], self.id_offset, nat.ptr(out), nat.ptr(ws),
             ws.numel(), nat.stream_ptr()))
         return out
+
+    # ------------------------------------------------------------------ search by examples
+    def candidates_examples_device(self, x_dev, n_positive: int, n_candidates: int, *, match: str = "any",
+                                   negative_rule: str = "penalty", negative_weight: float = 1.0, exclude=None,
+                                   filter: Optional[DeviceFilter] = None, out=None):
+        """The candidate cut of ONE request by examples (``dewi_knn_candidates_examples``): ``x_dev`` fp32 [P + N, d] raw
+        example vectors on this device, the first ``n_positive`` of them positive.  Every row gets one combined score — the
+        max (``match="any"``) or min (``"all"``) of its similarities to the positives, less ``negative_weight`` times its
+        largest positive similarity to a negative (``negative_rule="penalty"``), or, with ``"best_score"``, minus that
+        similarity squared where a negative is at least as near as the positives — and the ``n_candidates`` best rows
+        come back as records, int32 view [1, n_candidates, 4], in ``candidates_device``'s layout and order; padding behind
+        the rows offered.  ``exclude``: up to 16 LOCAL rows (int64 tensor on this device) that are never offered.  ``filter``:
+        only the rows of one ``DeviceFilter`` are scanned; an empty one writes nothing: ``out`` is returned filled with
+        padding.  fp32 cosine corpora of 132 to 4096 columns, ``dim % 4 == 0`` (``check_examples_shape``).  No sync."""
+        torch = _torch()
+        check_examples_shape(self.space, self.is_bf16, self.dim)
+        n_pos, n_neg = check_examples_request(int(n_positive), int(x_dev.shape[0]) - int(n_positive), match, negative_rule,
+                                              negative_weight)
+        if int(x_dev.shape[1]) != self.dim:
+            raise ValueError(f"Expected examples of shape ({self.dim},), got {tuple(x_dev.shape[1:])}")
+        c = int(n_candidates)
+        if not 1 <= c <= EXAMPLES_MAX_CANDIDATES:
+            raise ValueError(f"a search by examples re-ranks 1 to {EXAMPLES_MAX_CANDIDATES} candidates, got {c}")
+        n_excl = 0 if exclude is None else int(exclude.shape[0])
+        if n_excl > nat.EXAMPLES_MAX:
+            raise ValueError(f"at most {nat.EXAMPLES_MAX} rows can be excluded, got {n_excl}")
+        if out is None:
+            out = torch.empty((1, c, 4), dtype=torch.int32, device=self.device)
+        n_scan = self.n_rows
+        if filter is not None:
+            self.check_filter(filter)
+            n_scan = filter.n_allowed
+            if n_scan == 0:
+                out.copy_(torch.tensor([-0x800000, 0, 0, -1], dtype=torch.int32, device=self.device).expand(1, c, 4))
+                return out
+        ws = self._cached_workspace(("examples", n_scan, min(c, n_scan)), self._lib.dewi_knn_examples_workspace_bytes, n_scan,
+                                    self.dim, n_pos + n_neg, c)
+        nat.check(self._lib.dewi_knn_candidates_examples(
+            nat.ptr(self.emb), self.n_rows, self.dim, nat.ptr(x_dev), n_pos, n_neg, nat.EXAMPLES_MATCH_CODES[match],
+            nat.EXAMPLES_RULE_CODES[negative_rule], float(negative_weight), nat.ptr(exclude) if n_excl else None, n_excl,
+            nat.ptr(filter.buf) if filter is not None else None, n_scan if filter is not None else 0, nat.ptr(self.dewi32),
+            nat.ptr(self.ent32), c, self.id_offset, nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+        return out
+
+    def search_examples_device(self, x_dev, n_positive: int, k: int, eta: float, entropy_pref: float, *, match: str = "any",
+                               negative_rule: str = "penalty", negative_weight: float = 1.0, candidates: Optional[int] = None,
+                               exclude=None, filter: Optional[DeviceFilter] = None, n_offered: Optional[int] = None,
+                               out_ids=None, out_scores=None):
+        """Enqueue one search by examples on the current stream: ``candidates_examples_device`` for the cut —
+        ``min(2k, rows offered)``, or ``candidates`` up to 2048 — then ``dewi_merge_rerank`` for the DEWI blend and the cut
+        to k.  Returns device tensors ``(ids [1, k] as the records carry them, adjusted scores [1, k])``; [1, 0] for
+        ``k <= 0`` or an empty filter; ``ValueError`` for k above the rows offered, as ``search`` raises it.
+        ``n_offered``: the rows the request can return (scanned rows less the excluded rows among them) where the caller
+        knows it; otherwise it is worked out here, which with both ``filter`` and ``exclude`` reads the filter's mask at the
+        excluded rows (one small copy to the host)."""
+        torch = _torch()
+        check_examples_shape(self.space, self.is_bf16, self.dim)
+        k = int(k)
+        if filter is not None:
+            self.check_filter(filter)
+        n_scan = self.n_rows if filter is None else filter.n_allowed
+        if k <= 0 or n_scan == 0:
+            return empty_result(1, self.device)
+        if n_offered is None:
+            n_offered = n_scan
+            if exclude is not None and int(exclude.shape[0]):
+                rows = torch.unique(exclude)
+                rows = rows[(rows >= 0) & (rows < self.n_rows)]
+                n_offered -= int(rows.numel()) if filter is None else int(filter.byte_mask()[rows].ne(0).sum().item())
+        n_offered = int(n_offered)
+        if k > n_offered:
+            raise ValueError(f"kth(={n_offered - k}) out of bounds ({n_offered})")
+        if candidates is not None and int(candidates) < k:
+            raise ValueError(f"n_candidates {int(candidates)} must be at least k = {k}")
+        if candidates is not None and int(candidates) > EXAMPLES_MAX_CANDIDATES:
+            raise ValueError(f"a search by examples re-ranks at most {EXAMPLES_MAX_CANDIDATES} candidates, got candidates = "
+                             f"{int(candidates)}")
+        c = cut_size(k, candidates, n_offered)
+        if c > EXAMPLES_MAX_CANDIDATES:
+            raise ValueError(f"a search by examples re-ranks at most {EXAMPLES_MAX_CANDIDATES} candidates, "
+                             f"{'k = %d' % k if candidates is None else 'candidates = %d' % int(candidates)} asks for {c}")
+        recs = self.candidates_examples_device(x_dev, n_positive, c, match=match, negative_rule=negative_rule,
+                                               negative_weight=negative_weight, exclude=exclude, filter=filter)
+        return merge_rerank_device(recs.unsqueeze(0), c, k, eta, entropy_pref, out_ids, out_scores)
 
     def collapse_rerank_device(self, recs, k: int, eta: float, entropy_pref: float, groups: DeviceGroups, per_group: int = 1,
                                out_ids=None, out_scores=None, out_hits=None, out_counts=None):

@@ -50,6 +50,10 @@ PRED_MAX_COLUMNS = 16
 PRED_MAX_INSTR = 64
 PRED_MAX_DEPTH = 32
 PRED_MAX_PROGRAMS = 256
+#: search by examples (include/dewi_hip.h DEWI_EXAMPLES_*): most examples of a request, how the positives combine, what the negatives do
+EXAMPLES_MAX = 16
+EXAMPLES_MATCH_CODES = {"any": 0, "all": 1}
+EXAMPLES_RULE_CODES = {"penalty": 0, "best_score": 1}
 #: opcodes of a predicate program (include/dewi_hip.h DEWI_PRED_*), in the header's order
 PRED_OPS = ("I_LT", "I_LE", "I_EQ", "I_NE", "I_GE", "I_GT", "I_BETWEEN", "I_ANY_BITS", "I_ALL_BITS", "I_IN_SET",
             "F_LT", "F_LE", "F_EQ", "F_NE", "F_GE", "F_GT", "F_BETWEEN", "F_IS_NAN", "TRUE", "AND", "OR", "NOT")
@@ -84,6 +88,7 @@ EXPORTED_SYMBOLS = (
     "dewi_select_block_max", "dewi_select_blocked_workspace_bytes", "dewi_select_seed_blocked", "dewi_select_run_blocked",
     "dewi_select_grouped_workspace_bytes", "dewi_select_groups_begin", "dewi_select_run_grouped", "dewi_select_run_blocked_grouped",
     "dewi_predicate_masks",
+    "dewi_knn_examples_workspace_bytes", "dewi_knn_candidates_examples", "dewi_examples_tuning_set",
 )
 #: the words dewi_robust_fit_fast_plan fills, in order (include/dewi_hip.h)
 FIT_FAST_PLAN_WORDS = ("supported", "slices", "counters_offset", "counters_bytes", "small_n", "sample", "delta", "buckets",
@@ -303,6 +308,13 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_knn_candidates_filtered.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, vp, vp, i32, i32, i64, vp, vp, sz, vp]
     lib.dewi_robust_fit_fast_plan.restype = i32
     lib.dewi_robust_fit_fast_plan.argtypes = [i64, i32, c.POINTER(i64), i32]
+    lib.dewi_knn_examples_workspace_bytes.restype = sz
+    lib.dewi_knn_examples_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_knn_candidates_examples.restype = i32
+    lib.dewi_knn_candidates_examples.argtypes = [vp, i64, i32, vp, i32, i32, i32, i32, f64, vp, i32, vp, i64, vp, vp, i32, i64, vp,
+                                                 vp, sz, vp]
+    lib.dewi_examples_tuning_set.restype = i32
+    lib.dewi_examples_tuning_set.argtypes = [i32]
     lib.dewi_predicate_masks.restype = i32
     lib.dewi_predicate_masks.argtypes = [c.POINTER(vp), c.POINTER(c.c_int32), i32, i64, c.POINTER(PredInstr), c.POINTER(c.c_int32), i32,
                                          vp, i64, vp, vp, vp]

@@ -1098,6 +1098,88 @@ class ExactIndex(AttributesMixin, BaseIndex):
             res += (pool,)
         return res
 
+    # ---------------------------------------------------------------- search by examples (additive)
+    def _example_parts(self, positive, negative):
+        """``positive`` / ``negative`` (sequences whose elements are doc ids — strings — or ``[dim]`` vectors, mixed freely) ->
+        ``(vectors fp32 [P + N, dim] with zeros where an id stands, rows int64 [P + N] with -1 where a vector stands, P)``.
+        Host logic only; an unknown id raises ``KeyError``."""
+        from ._engine import check_examples_request
+
+        def as_list(x):
+            if x is None:
+                return []
+            if isinstance(x, str):
+                return [x]                                   # one bare id
+            if hasattr(x, "is_cuda") and x.dim() == 1:
+                return [x]                                   # one bare vector (torch)
+            if isinstance(x, np.ndarray) and x.ndim == 1 and x.dtype.kind in "fiu":
+                return [x]                                   # one bare vector (numpy)
+            return list(x)
+        pos, neg = as_list(positive), as_list(negative)
+        check_examples_request(len(pos), len(neg), "any", "penalty", 1.0)
+        vec = np.zeros((len(pos) + len(neg), self.dim), dtype=np.float32)
+        rows = np.full(len(pos) + len(neg), -1, dtype=np.int64)
+        ids = [(j, e) for j, e in enumerate(pos + neg) if isinstance(e, str)]
+        if ids:
+            rows[[j for j, _ in ids]] = self.rows_of([e for _, e in ids])
+        for j, e in enumerate(pos + neg):
+            if isinstance(e, str):
+                continue
+            v = e.detach().cpu().numpy() if hasattr(e, "is_cuda") else np.asarray(e)
+            if v.shape != (self.dim,):
+                raise ValueError(f"an example is a doc id or a vector of shape ({self.dim},), got shape {v.shape}")
+            vec[j] = v
+        return vec, rows, len(pos)
+
+    def search_by_examples(self, positive, negative=None, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, *,
+                           match: str = "any", negative_rule: str = "penalty", negative_weight: float = 1.0,
+                           candidates: Optional[int] = None, filter=None, exclude_examples: bool = True) -> SearchResult:
+        """Search by EXAMPLES instead of one query vector (additive; the reference has no such method; vector databases call
+        it *recommend*): "more like these documents, and not like those", or "near this caption AND near this picture".
+        ``positive`` (at least one) and ``negative`` are sequences of doc ids and / or ``[dim]`` vectors, at most 16 together;
+        a doc id stands for its stored row, gathered on the device.
+
+        Every document gets ONE score from its cosine similarities to the examples, each exactly what ``search`` reports for
+        that pair: ``p`` = the largest (``match="any"``) or the smallest (``match="all"``: near EVERY positive) similarity to
+        a positive, ``n`` = the largest similarity to a negative, and then ``p - negative_weight * max(n, 0)``
+        (``negative_rule="penalty"``), or ``p`` where ``p > n`` and ``-n * n`` elsewhere (``"best_score"``: a document
+        nearer to a negative than to every positive ranks behind all others, the nearest to a negative last).  The
+        ``min(2k, rows offered)`` best documents by that score — ``candidates=`` up to 2048 — are blended with DEWI
+        and cut to k as in ``search``.  The whole request costs one pass over the corpus per 4 examples (2 beyond 2048
+        columns), not one per example.
+
+        ``exclude_examples``: documents given as examples are not returned.  ``filter``: what ``search(filter=)`` takes for
+        ONE allow-list (a mask, doc ids, rows, a ``Where``, ``dedup_filter(...)``, a prepared filter).  Returns
+        ``(doc_id, adjusted score, Payload)`` tuples; ``[]`` for ``k <= 0`` or an empty filter; ``ValueError`` for k above the
+        rows offered (as ``search``), for more than 16 examples, and for what the route does not serve: bf16 or l2
+        indexes, ``dim % 4 != 0``, fewer than 132 or more than 4096 columns."""
+        from ._engine import DeviceQueryFilters, check_examples_request, check_examples_shape
+        import torch
+        vec, rows, n_pos = self._example_parts(positive, negative)          # (argument errors before any build)
+        check_examples_request(n_pos, len(rows) - n_pos, match, negative_rule, negative_weight)
+        if isinstance(filter, DeviceQueryFilters) or is_where_list(filter) or (filter is not None and len(getattr(filter, "shape", ())) == 2):
+            raise NotImplementedError("a search by examples takes one allow-list (per-query filters: not in this build)")
+        self._ensure_built()
+        corpus = self._corpus
+        check_examples_shape(corpus.space, corpus.is_bf16, corpus.dim)
+        prepared = self._prepared(filter)
+        with corpus._lock, torch.cuda.device(corpus.device):
+            x = torch.from_numpy(vec).to(corpus.device)
+            given = np.flatnonzero(rows >= 0)
+            if given.size:
+                x[torch.from_numpy(given).to(corpus.device)] = corpus.emb.index_select(
+                    0, torch.from_numpy(rows[given]).to(corpus.device)).float()
+            exclude = None
+            if exclude_examples and given.size:
+                exclude = torch.from_numpy(np.unique(rows[given])).to(corpus.device)
+            ids_d, sc_d = corpus.search_examples_device(x, n_pos, int(k), float(eta), float(entropy_pref), match=match,
+                                                        negative_rule=negative_rule, negative_weight=float(negative_weight),
+                                                        candidates=candidates, exclude=exclude, filter=prepared)
+            ids_h, sc_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
+        if corpus.id_offset:
+            ids_h = ids_h - corpus.id_offset
+        return self.results_for(ids_h, sc_h)[0]
+
     # ---------------------------------------------------------------- range search (additive)
     def range_search(self, query: np.ndarray, threshold: float, eta: float = 0.5, entropy_pref: float = 0.0, filter=None,
                      max_results: Optional[int] = None) -> SearchResult:

@@ -5,7 +5,7 @@ the query, fills in the default ``eta`` / ``entropy_pref`` and delegates to a ba
 this build every backend choice resolves to the HIP ``ExactIndex`` (ANN graph libraries
 are out of scope), with the reference's own warning when an ANN backend was asked for.
 Additions: ``add_batch``, ``search_batch``, ``range_search``, ``range_search_batch``, ``near_duplicates``, ``duplicate_groups``,
-``dedup_filter``, ``make_groups`` / ``search_collapsed`` / ``search_collapsed_batch`` and the in-place ``remove`` / ``upsert`` / ``upsert_batch`` / ``upsert_batch_columns`` / ``rows_of`` / ``reserve``.
+``dedup_filter``, ``make_groups`` / ``search_collapsed`` / ``search_collapsed_batch``, ``search_by_examples`` and the in-place ``remove`` / ``upsert`` / ``upsert_batch`` / ``upsert_batch_columns`` / ``rows_of`` / ``reserve``.
 Attribute columns and predicates over them (``set_attributes``, ``attributes_from_payload``, ``update_attributes``,
 ``attributes_of``, ``make_filter_where``, ``make_query_filters_where``, ``count_where``; ``filter=`` takes a ``dewi.where.Where``).
 """
@@ -169,6 +169,20 @@ class DewiIndex(BaseIndex):
         else:
             rows, scores = self._backend.search_batch(q, k, eta, entropy_pref, **self._approx_kwargs(approx, rescore))
         return self._backend.results_for(rows, scores)
+
+    def search_by_examples(self, positive, negative=None, k: int = 10, eta: Optional[float] = None,
+                           entropy_pref: Optional[float] = None, *, match: str = "any", negative_rule: str = "penalty",
+                           negative_weight: float = 1.0, candidates: Optional[int] = None, filter=None,
+                           exclude_examples: bool = True) -> List[Tuple[str, float, Payload]]:
+        """Search by examples (additive; ``ExactIndex.search_by_examples``): ``positive`` / ``negative`` are doc ids and / or
+        ``[dim]`` vectors, at most 16 together; every document is scored by its nearest (``match="any"``) or farthest
+        (``"all"``) positive, less what ``negative_rule`` takes off for its nearest negative."""
+        if not self._built:
+            self.build()
+        eta, entropy_pref = self._defaults(eta, entropy_pref)
+        return self._backend.search_by_examples(positive, negative, k, eta, entropy_pref, match=match,
+                                                negative_rule=negative_rule, negative_weight=negative_weight,
+                                                candidates=candidates, filter=filter, exclude_examples=exclude_examples)
 
     def search_approx_filtered(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
                                entropy_pref: Optional[float] = None, candidates: Optional[int] = None, *, filter,

@@ -87,7 +87,8 @@ class IVFIndex(ExactIndex):
     exact cut over every row, not over the probed cells, and there is no ``nprobe`` argument.  A diverse search over an IVF
     probe is not part of this build.  ``search_collapsed`` / ``search_collapsed_batch`` are inherited in the same EXACT form
     (the pool is the exact cut over every row, or over every row of ``filter``; no ``nprobe``): a collapsed search over a
-    probe is not part of this build.
+    probe is not part of this build.  ``search_by_examples`` is inherited in its EXACT form as well (every row, or every row of
+    ``filter``, is scored against the examples; no ``nprobe``).
 
     ``remove`` / ``upsert`` / ``upsert_batch`` / ``upsert_batch_columns`` maintain the cells instead of retraining: the
     centroids stay as trained, a surviving document keeps its cell, a replaced or appended one goes to the centroid nearest to

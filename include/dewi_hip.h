@@ -1138,6 +1138,64 @@ int dewi_predicate_masks(const void* const* d_columns, const int32_t* column_typ
                          const uint32_t* d_sets, int64_t n_set_words, const uint8_t* d_base, uint8_t* d_masks, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Search by examples (additive to ABI 6): ONE request of P >= 1 positive and N >= 0 negative example vectors,
+ * P + N <= DEWI_EXAMPLES_MAX, answered in ceil((P + N) / E_pass) passes over the corpus — "more like these, not like those",
+ * or "near this caption AND near this picture".  max and min over similarities are not linear: no single query vector
+ * reproduces them, and a caller without this entry point pays one dense pass per example plus N-sized results on the host.
+ *
+ * Semantics (tests/examples_model.py restates them in NumPy):
+ *   1. every example is prepared exactly as a query of the one-query search: float64-summed norm, one rounding after the
+ *      square root, IEEE division, left alone when the norm is 0 or NaN;
+ *   2. s_j(r), the similarity of row r to example j, is BIT FOR BIT what dewi_knn_rerank_f32 and dewi_knn_range_count report
+ *      for that (query, row) on this corpus: the lanes and the summation order of the width's row kernel (lane l takes the
+ *      units l + 64 u, four fused multiply-adds per unit with u ascending, then the wave sum);
+ *   3. p = max_j s_j (match DEWI_EXAMPLES_MATCH_ANY) or min_j s_j (DEWI_EXAMPLES_MATCH_ALL) over the positives, n = max_j s_j
+ *      over the negatives; fp32, exact;
+ *   4. score = p                                        when N == 0;
+ *      score = fl(p - fl(w * m)), w = fp32(negative_weight), m = n > 0 ? n : +0      (DEWI_EXAMPLES_RULE_PENALTY);
+ *      score = p > n ? p : fl(-fl(n * n))                                            (DEWI_EXAMPLES_RULE_BEST_SCORE);
+ *      score = NaN when ANY similarity of the row is NaN (tested for explicitly), ordered as every search orders a NaN
+ *      (largest in the cut, step 3 of the search above);
+ *   5. up to DEWI_EXAMPLES_MAX rows d_exclude[0 .. n_exclude) (LOCAL rows, int64, on the device; a value that is no row of
+ *      the corpus excludes nothing) are never offered: the examples themselves when they were given as documents;
+ *   6. the cut is the c = n_candidates best rows by (ord(score) descending, row ascending), emitted as dewi_candidate records
+ *      in exactly dewi_knn_candidates' layout and order: sim = the combined score (a NaN leaves as 0x7FFFFFFF, -0 as +0:
+ *      the key's round trip, as everywhere), the payload pair attached, id = row + id_offset, padding (id -1, sim -inf) behind
+ *      min(c, rows offered).  dewi_merge_rerank on those records (n_lists = 1) then does the blend and the cut to k.
+ * d_filter != NULL: only the n_allowed rows of that prepared filter (dewi_filter_prepare) are scanned.
+ *
+ * Scope: fp32 corpus, cosine, dim % 4 == 0, 33 .. 1024 sixteen-byte units per row (dim 132 .. 4096); anything else
+ * (dim <= 128, dim % 4 != 0, dim > 4096) is DEWI_ERR_UNSUPPORTED.  1 <= n_candidates <= 2048.  One request per call.
+ *
+ * dewi_knn_examples_workspace_bytes: workspace for n_scan scanned rows (n_rows, or n_allowed with a filter); needs no device;
+ * 0 for a shape the route does not take (n_scan <= 0, an unsupported dim, n_examples outside [1, DEWI_EXAMPLES_MAX],
+ * n_candidates outside [1, 2048]).  It holds the keys and the two fp32 arrays [n_scan] through which chained passes hand
+ * on (p, n); its contents on entry are undefined.
+ * dewi_knn_candidates_examples: d_examples [P + N][dim] raw fp32, positives first.  Asynchronous on `stream`, allocates
+ * nothing, synchronises nothing.  Errors, every one before any device work: a NULL d_E / d_examples / d_dewi32 / d_ent32 /
+ * d_out, NULL d_exclude with n_exclude > 0, a bad shape, P < 1, N < 0, an unknown match or negative_rule, a non-finite
+ * negative_weight, n_exclude outside [0, DEWI_EXAMPLES_MAX], n_allowed outside [0, n_rows] (with a filter),
+ * n_candidates <= 0: DEWI_ERR_INVALID_ARG; P + N > DEWI_EXAMPLES_MAX, an unsupported dim, n_candidates > 2048, an id range
+ * that does not fit int32: DEWI_ERR_UNSUPPORTED; a short workspace: DEWI_ERR_WORKSPACE.  n_allowed == 0 with a filter:
+ * DEWI_OK, nothing launched, nothing written.
+ * dewi_examples_tuning_set (tests): examples per pass of the CALLING THREAD's requests, 0 = the planner's choice (4 up to 8
+ * units per lane, 2 beyond), otherwise min(value, that choice).  The workspace size does not depend on it, nor does any bit
+ * of a result.
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_EXAMPLES_MAX 16
+#define DEWI_EXAMPLES_MATCH_ANY 0
+#define DEWI_EXAMPLES_MATCH_ALL 1
+#define DEWI_EXAMPLES_RULE_PENALTY 0
+#define DEWI_EXAMPLES_RULE_BEST_SCORE 1
+size_t dewi_knn_examples_workspace_bytes(int64_t n_scan, int dim, int n_examples, int n_candidates);
+int dewi_knn_candidates_examples(const float* d_E, int64_t n_rows, int dim, const float* d_examples, int n_positive,
+                                 int n_negative, int match, int negative_rule, double negative_weight,
+                                 const int64_t* d_exclude, int n_exclude, const void* d_filter, int64_t n_allowed,
+                                 const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
+                                 dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, void* stream);
+int dewi_examples_tuning_set(int examples_per_pass);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): dewi_timing_enable(n) makes every n-th dewi_knn_* call bracket its
  * corpus-scan kernel with hipEvents on `stream` (n = 1: every call; 0: off — the two event records
  * cost ~5 us of stream time, so throughput runs sample); dewi_timing_read synchronises those
