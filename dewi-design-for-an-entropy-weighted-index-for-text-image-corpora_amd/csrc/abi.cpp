@@ -1919,6 +1919,101 @@ int dewi_knn_candidates_i8(const int8_t* d_codes, const float* d_scales, int64_t
                   "select launch");
 }
 
+// ---- approximate search over a 1-bit copy of the corpus (additive to ABI 6; knn_scan_b1.hip) -------------------
+// the shape checks the binary entry points share, in check_i8_shape's order: rows, 2^32, dim, whole 128-bit units
+static int check_b1_shape(int64_t n_rows, int dim) {
+  if (n_rows <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_rows must be positive (got %lld)", static_cast<long long>(n_rows));
+  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "dim must be positive (got %d)", dim);
+  if (dim % DEWI_B1_MIN_DIM != 0 || dim > DEWI_I8_MAX_DIM)
+    return fail(DEWI_ERR_UNSUPPORTED, "dim %d: the binary route takes dim %% %d == 0 up to %d columns", dim, DEWI_B1_MIN_DIM,
+                DEWI_I8_MAX_DIM);
+  return DEWI_OK;
+}
+static bool b1_shape_taken(int64_t n_rows, int dim, int n_queries, int n_candidates) {
+  return n_rows > 0 && n_rows <= 0xFFFFFFFFll && dim > 0 && dim % DEWI_B1_MIN_DIM == 0 && dim <= DEWI_I8_MAX_DIM && n_queries > 0 &&
+         n_candidates > 0 && n_candidates <= DEWI_I8_MAX_CANDIDATES;
+}
+
+static thread_local int g_b1_max_blocks = 0;   // dewi_b1_tuning_set: 0 = the plan's choice
+
+int dewi_b1_tuning_set(int max_blocks) {
+  if (max_blocks < 0) return fail(DEWI_ERR_INVALID_ARG, "max_blocks must be >= 0 (got %d)", max_blocks);
+  g_b1_max_blocks = max_blocks;
+  return DEWI_OK;
+}
+
+int dewi_binarize_rows_f32(const float* d_E, int64_t n_rows, int dim, uint32_t* d_bits, void* stream) {
+  if (n_rows == 0 && dim > 0) return DEWI_OK;
+  if (int rc = check_b1_shape(n_rows, dim)) return rc;
+  if (!d_E || !d_bits) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (int rc = check_aligned16(d_E, "the rows")) return rc;
+  if (int rc = check_aligned16(d_bits, "the bits")) return rc;
+  return launched(dewi::launch_binarize_f32(d_E, n_rows, dim, d_bits, static_cast<hipStream_t>(stream)), "binarize_rows_f32 launch");
+}
+
+int dewi_prepare_queries_b1(const float* d_Q, int n_queries, int dim, uint32_t* d_bits, void* stream) {
+  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
+  if (int rc = check_b1_shape(n_queries, dim)) return rc;
+  if (!d_Q || !d_bits) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
+  if (int rc = check_aligned16(d_bits, "the bits")) return rc;
+  return launched(dewi::launch_binarize_f32(d_Q, n_queries, dim, d_bits, static_cast<hipStream_t>(stream)), "prepare_queries_b1 launch");
+}
+
+size_t dewi_knn_b1_workspace_bytes(int64_t n_rows, int dim, int n_queries, int n_candidates) {
+  if (!b1_shape_taken(n_rows, dim, n_queries, n_candidates)) return 0;
+  const int c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
+  return i8_workspace(dewi::plan_scan_b1(n_rows, dim, c_local, g_b1_max_blocks), n_queries);
+}
+
+int dewi_knn_b1_plan(int64_t n_rows, int dim, int n_candidates, int64_t* out_words) {
+  if (!out_words) return fail(DEWI_ERR_INVALID_ARG, "null out_words");
+  if (!b1_shape_taken(n_rows, dim, 1, n_candidates))
+    return fail(DEWI_ERR_UNSUPPORTED, "the binary route does not take %lld rows x %d columns, %d candidates",
+                static_cast<long long>(n_rows), dim, n_candidates);
+  const int c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
+  const dewi::ScanPlan p = dewi::plan_scan_b1(n_rows, dim, c_local, g_b1_max_blocks);
+  const int64_t words[DEWI_B1_PLAN_WORDS] = {p.blocks, p.rows_per_iter, p.log2p, p.slots, p.n_lists, p.keys_per_query};
+  for (int i = 0; i < DEWI_B1_PLAN_WORDS; ++i) out_words[i] = words[i];
+  return DEWI_OK;
+}
+
+int dewi_knn_candidates_b1(const uint32_t* d_bits, int64_t n_rows, int dim, const float* d_Q, int n_queries, const float* d_dewi32,
+                           const float* d_ent32, int n_candidates, int64_t id_offset, dewi_candidate* d_out, void* d_workspace,
+                           size_t workspace_bytes, void* stream_) {
+  // the checks of dewi_knn_candidates_i8, in its order
+  if (!d_bits || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "null bits or query pointer");
+  if (int rc = check_b1_shape(n_rows, dim)) return rc;
+  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
+  if (int rc = check_i8_candidates(n_candidates)) return rc;
+  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
+  if (int rc = check_aligned16(d_bits, "the bits")) return rc;
+  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
+  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
+    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
+                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
+  const int c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
+  const dewi::ScanPlan plan = dewi::plan_scan_b1(n_rows, dim, c_local, g_b1_max_blocks);
+  if (int rc = check_workspace(d_workspace, workspace_bytes, i8_workspace(plan, n_queries))) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  uint64_t* keys = static_cast<uint64_t*>(d_workspace);
+  {
+    ScanTimer timer(stream);
+    for (int q = 0; q < n_queries;) {           // four queries per corpus pass, then one by one
+      const int nq = n_queries - q >= 4 ? 4 : 1;
+      const hipError_t e = dewi::launch_scan_b1(plan, d_bits, n_rows, dim, d_Q, q, nq, c_local, keys, stream);
+      if (e != hipSuccess) return hip_fail(e, "binary scan launch");
+      q += nq;
+    }
+  }
+  const int sorted = (plan.slots == 1 && c_local == n_candidates) ? plan.n_lists : 0;
+  return launched(dewi::launch_select_rerank(keys, plan.keys_per_query, sorted, n_queries, n_candidates, 0, make_rerank(0.0, 0.0),
+                                             d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out, nullptr, dewi::SegmentLayout{},
+                                             stream),
+                  "select launch");
+}
+
 // ---- query batches on the int8 codes: 32 queries per matrix-core pass (additive to ABI 6; knn_mfma_i8.hip) ------
 // the plan of a shape the pass takes; false otherwise (the size function's 0)
 static bool i8_batch_layout(int64_t n_rows, int dim, int n_queries, int n_candidates, dewi::MfmaI8Layout* out) {

@@ -537,6 +537,24 @@ hipError_t launch_scan_i8_list(const ScanPlan& plan, const int8_t* d_codes, cons
 hipError_t launch_rescore_candidates_f32(const float* d_E, int64_t n_rows, int dim, const float* d_Q, int n_queries,
                                          dewi_candidate* d_cand, int n_candidates, int64_t id_offset, hipStream_t stream);
 
+// ---- knn_scan_b1.hip: the approximate route over a 1-bit copy of the corpus (include/dewi_hip.h, "BINARY copy") ----
+constexpr int kB1MinDim = DEWI_B1_MIN_DIM;
+#ifndef DEWI_B1_LIST_BLOCKS
+#define DEWI_B1_LIST_BLOCKS 64
+#endif
+// most workgroups of a pass that keeps per-wave lists (65 .. 256 candidates).  1 M x 768, one query, whole search with 256 / 128 /
+// 64 / 32 / 16 workgroups: cut 128 0.630 / 0.503 / 0.471 / 0.534 / 0.677 ms, cut 256 1.327 / 0.848 / 0.729 / 0.782 / 0.961 ms
+// (profiles/r23/binary/): the select reads waves * cut keys per query and outweighs the slower scan down to 64
+constexpr int kB1ListBlocks = DEWI_B1_LIST_BLOCKS;
+// plan_scan_i8's fields for rows of dim / 128 units of 16 bytes (always kScanAnyShort); needs no device.  max_blocks > 0
+// caps the workgroups (dewi_b1_tuning_set)
+ScanPlan plan_scan_b1(int64_t n_rows, int dim, int n_candidates, int max_blocks = 0);
+// the sign bits of n_rows * dim floats (the stored rows, or raw queries)
+hipError_t launch_binarize_f32(const float* d_X, int64_t n_rows, int dim, uint32_t* d_bits, hipStream_t stream);
+// one corpus pass for queries [q0, q0 + nq), nq = 1 or 4 (raw queries; keys at d_keys + q * plan.keys_per_query)
+hipError_t launch_scan_b1(const ScanPlan& plan, const uint32_t* d_bits, int64_t n_rows, int dim, const float* d_q_raw, int q0, int nq,
+                          int n_candidates, uint64_t* d_keys, hipStream_t stream);
+
 // ---- knn_mfma_i8.hip: query batches on the int8 codes, 32 queries per matrix-core pass (include/dewi_hip.h, "INT8 batch pass") ----
 #ifndef DEWI_I8_MFMA_MIN_QUERIES
 #define DEWI_I8_MFMA_MIN_QUERIES 2

@@ -118,6 +118,35 @@ def approx_cut(k: int, candidates: Optional[int], n: int) -> int:
     return c
 
 
+def check_binary_shape(space: str, is_bf16: bool, dim: int) -> None:
+    """What the binary route serves: cosine, an fp32 main matrix, ``dim % 128 == 0`` from 128 to 4096 columns (rows of whole
+    128-bit units) — anything else is a ``ValueError``.  Host logic only."""
+    if space != "cosine":
+        raise ValueError(f"the binary shadow serves cosine corpora, not space={space!r}")
+    if is_bf16:
+        raise ValueError("the binary shadow is made from an fp32 main matrix (this corpus is bf16)")
+    if int(dim) % nat.B1_MIN_DIM != 0 or not nat.B1_MIN_DIM <= int(dim) <= nat.I8_MAX_DIM:
+        raise ValueError(f"the binary shadow takes dim % {nat.B1_MIN_DIM} == 0 from {nat.B1_MIN_DIM} to {nat.I8_MAX_DIM} columns, "
+                         f"got dim = {dim}")
+
+
+def binary_cut(k: int, candidates: Optional[int], n: int) -> int:
+    """The cut of a binary search: ``min(n, 1024, max(128, 16 k))`` by default — a Hamming score is far coarser than an int8
+    one, so the cut is wider than the project's ``2k`` (recall per cut: DESIGN.md 4.1aa) —, or ``candidates`` (at most
+    ``I8_MAX_CANDIDATES`` = 1024, the re-scoring kernel's limit; at most the ``n`` rows there are).  ``k`` must fit into it.
+    ``ValueError`` otherwise.  Host logic only."""
+    if candidates is None:
+        c = min(int(n), nat.I8_MAX_CANDIDATES, max(128, 16 * int(k)))
+    else:
+        if int(candidates) > nat.I8_MAX_CANDIDATES:
+            raise ValueError(f"the binary route re-ranks at most {nat.I8_MAX_CANDIDATES} candidates, got candidates = {int(candidates)}")
+        c = min(int(candidates), int(n))
+    c = max(c, 1)
+    if int(k) > c:
+        raise ValueError(f"k = {int(k)} exceeds the cut of {c} candidates")
+    return c
+
+
 def library_size(size_fn, *args) -> int:
     """``size_fn(*args)`` in bytes.  A size function of the library answers 0 for a shape it refuses: ``NativeLibraryError``
     with its last error."""
@@ -465,6 +494,8 @@ class DeviceCorpus:
         self.i8_codes = None          # int8 copy of an fp32 matrix (enable_int8_shadow): [N, dim] codes ...
         self.i8_scales = None         # ... and one fp32 scale per row
         self._i8_stale = False        # the rows changed since the copy was made: the next approximate search re-quantises
+        self.b1_bits = None           # 1-bit copy of an fp32 matrix (enable_binary_shadow): [N, dim / 32] dwords as int32
+        self._b1_stale = False        # the rows changed since the copy was made: the next binary search re-binarises
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -673,6 +704,87 @@ class DeviceCorpus:
             # (the private twin, NOT self.search_approx_device: the public method's parameter list is pinned and cannot carry
             # batch_pass — a subclass that overrides search_approx_device must override this method too, as Int8Corpus does)
             ids_d, sc_d = self._search_approx_device(q, k, eta, entropy_pref, candidates, rescore, None, None, batch_pass)
+            ids_h, scores_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
+        if self.id_offset:
+            ids_h = ids_h + self.id_offset
+        return ids_h, scores_h
+
+    # ------------------------------------------------------------------ binary shadow (approximate route)
+    def enable_binary_shadow(self) -> "DeviceCorpus":
+        """Keep a 1-BIT copy of this fp32 matrix next to it — the sign of every element, ``dim / 8`` bytes per row: +3 %
+        memory — for the APPROXIMATE route ``search_binary_device`` (``dewi_binarize_rows_f32``).  Cosine, an fp32 main
+        matrix, ``dim % 128 == 0`` from 128 to 4096 columns; anything else raises ``ValueError``.  Nothing else changes:
+        every other search of the corpus runs as before, and nothing routes here by itself.
+
+        ``remove_rows`` / ``put_rows`` mark the copy stale; the next binary search re-binarises the WHOLE matrix (one pass
+        over the fp32 rows) — so a mutated corpus and a freshly built one hold the same bits.  The int8 copy's rule."""
+        check_binary_shape(self.space, self.is_bf16, self.dim)
+        with self._lock, _torch().cuda.device(self.device):
+            if self.b1_bits is None or self._b1_stale:
+                self._binarize()
+        return self
+
+    @property
+    def has_binary_shadow(self) -> bool:
+        return self.b1_bits is not None
+
+    def _binarize(self) -> None:
+        torch = _torch()
+        n = self.n_rows
+        bits = torch.empty((n, self.dim // 32), dtype=torch.int32, device=self.device)
+        nat.check(self._lib.dewi_binarize_rows_f32(nat.ptr(self.emb), n, self.dim, nat.ptr(bits), nat.stream_ptr()))
+        self.b1_bits, self._b1_stale = bits, False
+
+    def _binary(self):
+        """The bits of the binary copy, made again first if the rows changed since."""
+        if self.b1_bits is None:
+            raise ValueError("this corpus has no binary shadow: call enable_binary_shadow() (ExactIndex(binary_shadow=True))")
+        if self._b1_stale:
+            self._binarize()
+        return self.b1_bits
+
+    def candidates_b1_device(self, q_dev, n_candidates: int, out=None, id_offset: Optional[int] = None):
+        """The ``n_candidates`` best rows of every RAW query by the HAMMING scores of the binary copy as candidate records,
+        int32 view [B, n_candidates, 4], in ``candidates_device``'s layout and order (``dewi_knn_candidates_b1``).
+        ``id_offset``: default the corpus's."""
+        bits = self._binary()
+        b, c = int(q_dev.shape[0]), int(n_candidates)
+        n = int(bits.shape[0])
+        if out is None:
+            out = _torch().empty((b, c, 4), dtype=_torch().int32, device=self.device)
+        ws = self._cached_workspace(("b1", b, c), self._lib.dewi_knn_b1_workspace_bytes, n, self.dim, b, c)
+        nat.check(self._lib.dewi_knn_candidates_b1(
+            nat.ptr(bits), n, self.dim, nat.ptr(q_dev), b, nat.ptr(self.dewi32), nat.ptr(self.ent32), c,
+            self.id_offset if id_offset is None else int(id_offset), nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+        return out
+
+    def search_binary_device(self, q_dev, k: int, eta: float, entropy_pref: float, candidates: Optional[int] = None,
+                             rescore: bool = True, out_ids=None, out_scores=None):
+        """Enqueue one APPROXIMATE search over the binary copy on the current stream; returns device tensors ``(ids, scores)``
+        [B, k] (local row ids, as ``search_device``), no sync.  The cut — ``binary_cut``: ``min(N, 1024, max(128, 16 k))``, or
+        ``candidates`` (up to 1024) — is taken by Hamming distance between sign bits (1 / 32 of the fp32 rows' bytes), then —
+        ``rescore=True`` — re-scored from the fp32 rows, then blended and cut to k exactly as every search
+        (``dewi_knn_candidates_b1`` -> ``dewi_rescore_candidates_f32`` -> ``dewi_merge_rerank``).  ``rescore=False`` blends
+        the Hamming similarity ``(dim - 2 h) / dim`` as it is.  A document is missed when the Hamming scores drop it from the
+        cut (recall: DESIGN.md 4.1aa).  ``k`` above the cut and a cut above 1024 raise ``ValueError``.  NOT thread-safe on
+        one instance (shared workspaces)."""
+        b, k = check_search_args(q_dev.shape, self.dim, k, None, "ip")
+        if k <= 0:
+            return empty_result(b, self.device)
+        self._binary()
+        c = binary_cut(k, candidates, self.n_rows)
+        recs = self.candidates_b1_device(q_dev, c, id_offset=0)
+        if rescore:
+            self.rescore_candidates_device(q_dev, recs, id_offset=0)
+        return merge_rerank_device(recs.view(1, b, c, 4), c, k, eta, entropy_pref, out_ids, out_scores)
+
+    def search_binary(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
+                      candidates: Optional[int] = None, rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """Blocking twin of ``search`` for ``search_binary_device``: (ids int64 [B, k] including id_offset, scores fp32
+        [B, k]) on the host.  Serialised by the per-corpus lock."""
+        with self._lock, _torch().cuda.device(self.device):
+            q = self.stage_queries(queries)
+            ids_d, sc_d = self.search_binary_device(q, k, eta, entropy_pref, candidates, rescore)
             ids_h, scores_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
         if self.id_offset:
             ids_h = ids_h + self.id_offset
@@ -887,6 +999,8 @@ class DeviceCorpus:
         self._last_call = None
         if self.i8_codes is not None:
             self._i8_stale = True              # re-quantised as a whole by the next approximate search (_int8)
+        if self.b1_bits is not None:
+            self._b1_stale = True              # re-binarised as a whole by the next binary search (_binary)
 
     def _read_error(self, err, what: str) -> None:
         bad = int(err.item())                  # the call's one synchronisation

@@ -43,6 +43,8 @@ COLLAPSE_MAX_CANDIDATES = 2048
 #: largest candidate cut and widest row of the int8 route (include/dewi_hip.h DEWI_I8_MAX_CANDIDATES / DEWI_I8_MAX_DIM)
 I8_MAX_CANDIDATES = 1024
 I8_MAX_DIM = 4096
+#: narrowest row of the binary route: one 128-bit unit (include/dewi_hip.h DEWI_B1_MIN_DIM); its widest row and largest cut are the int8 route's
+B1_MIN_DIM = 128
 #: which row of a group represents it (include/dewi_hip.h DEWI_GROUPS_KEEP_*): the lowest row / the highest key (the dewi column)
 KEEP_CODES = {"first": 0, "dewi": 1}
 #: limits of dewi_predicate_masks (include/dewi_hip.h DEWI_PRED_MAX_*)
@@ -89,6 +91,8 @@ EXPORTED_SYMBOLS = (
     "dewi_select_grouped_workspace_bytes", "dewi_select_groups_begin", "dewi_select_run_grouped", "dewi_select_run_blocked_grouped",
     "dewi_predicate_masks",
     "dewi_knn_examples_workspace_bytes", "dewi_knn_candidates_examples", "dewi_examples_tuning_set",
+    "dewi_binarize_rows_f32", "dewi_prepare_queries_b1", "dewi_knn_b1_workspace_bytes", "dewi_knn_b1_plan", "dewi_knn_candidates_b1",
+    "dewi_b1_tuning_set",
 )
 #: the words dewi_robust_fit_fast_plan fills, in order (include/dewi_hip.h)
 FIT_FAST_PLAN_WORDS = ("supported", "slices", "counters_offset", "counters_bytes", "small_n", "sample", "delta", "buckets",
@@ -96,6 +100,8 @@ FIT_FAST_PLAN_WORDS = ("supported", "slices", "counters_offset", "counters_bytes
 #: the words dewi_knn_i8_batch_plan fills, in order (include/dewi_hip.h DEWI_I8_BATCH_PLAN_WORDS)
 I8_BATCH_PLAN_WORDS = ("groups", "n_blocks", "n_seg", "seg_cap", "tile_stride", "n_sample_tiles", "sample_blocks", "flags_off",
                        "cnt_off", "cand_off", "repair_off", "total")
+#: the words dewi_knn_b1_plan fills, in order (include/dewi_hip.h DEWI_B1_PLAN_WORDS)
+B1_PLAN_WORDS = ("blocks", "rows_per_step", "log2p", "slots", "n_lists", "keys_per_query")
 
 
 class NativeLibraryError(RuntimeError):
@@ -315,6 +321,18 @@ def _declare(lib: ctypes.CDLL) -> None:
                                                  vp, sz, vp]
     lib.dewi_examples_tuning_set.restype = i32
     lib.dewi_examples_tuning_set.argtypes = [i32]
+    lib.dewi_binarize_rows_f32.restype = i32
+    lib.dewi_binarize_rows_f32.argtypes = [vp, i64, i32, vp, vp]
+    lib.dewi_prepare_queries_b1.restype = i32
+    lib.dewi_prepare_queries_b1.argtypes = [vp, i32, i32, vp, vp]
+    lib.dewi_knn_b1_workspace_bytes.restype = sz
+    lib.dewi_knn_b1_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dewi_knn_b1_plan.restype = i32
+    lib.dewi_knn_b1_plan.argtypes = [i64, i32, i32, c.POINTER(i64)]
+    lib.dewi_b1_tuning_set.restype = i32
+    lib.dewi_b1_tuning_set.argtypes = [i32]
+    lib.dewi_knn_candidates_b1.restype = i32
+    lib.dewi_knn_candidates_b1.argtypes = [vp, i64, i32, vp, i32, vp, vp, i32, i64, vp, vp, sz, vp]
     lib.dewi_predicate_masks.restype = i32
     lib.dewi_predicate_masks.argtypes = [c.POINTER(vp), c.POINTER(c.c_int32), i32, i64, c.POINTER(PredInstr), c.POINTER(c.c_int32), i32,
                                          vp, i64, vp, vp, vp]
@@ -382,6 +400,13 @@ def i8_batch_plan(n_rows: int, dim: int, n_queries: int, n_candidates: int) -> d
     out = (ctypes.c_int64 * len(I8_BATCH_PLAN_WORDS))()
     check(load_library(require_gpu=False).dewi_knn_i8_batch_plan(n_rows, dim, n_queries, n_candidates, out))
     return dict(zip(I8_BATCH_PLAN_WORDS, (int(v) for v in out)))
+
+
+def b1_plan(n_rows: int, dim: int, n_candidates: int) -> dict:
+    """``dewi_knn_b1_plan`` as a dict keyed by ``B1_PLAN_WORDS`` (host only: needs no GPU)."""
+    out = (ctypes.c_int64 * len(B1_PLAN_WORDS))()
+    check(load_library(require_gpu=False).dewi_knn_b1_plan(n_rows, dim, n_candidates, out))
+    return dict(zip(B1_PLAN_WORDS, (int(v) for v in out)))
 
 
 def is_device_tensor(x) -> bool:

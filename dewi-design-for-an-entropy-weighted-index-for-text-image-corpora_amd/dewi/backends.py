@@ -200,6 +200,13 @@ class ExactIndex(AttributesMixin, BaseIndex):
         if self._int8_shadow:
             from ._engine import check_int8_shape
             check_int8_shape(space, False, dim)
+        # additive: keep a 1-bit copy of the fp32 matrix (the signs, +3 % HBM) for search_binary: the candidate cut by Hamming
+        # distance over 1 / 32 of the bytes, re-scored from the fp32 rows (DeviceCorpus.enable_binary_shadow).  Nothing routes
+        # there by itself; remove / upsert* mark the copy stale exactly as they mark the int8 copy.
+        self._binary_shadow: bool = bool(kwargs.get("binary_shadow", False))
+        if self._binary_shadow:
+            from ._engine import check_binary_shape
+            check_binary_shape(space, False, dim)
         self._id_rows: Optional[Dict[str, int]] = None  # doc_id -> row of remove / upsert: made once, then kept per call
         self._attrs_init()                          # attribute columns (dewi.attributes)
 
@@ -516,6 +523,8 @@ class ExactIndex(AttributesMixin, BaseIndex):
             self._corpus.enable_bf16_shadow(single_query=self._shadow_single)
         if self._int8_shadow:
             self._corpus.enable_int8_shadow()
+        if self._binary_shadow:
+            self._corpus.enable_binary_shadow()
         self._pending = []
         self._pending_rows = 0
         self._loaded_rows = None
@@ -553,6 +562,8 @@ class ExactIndex(AttributesMixin, BaseIndex):
                         if self._batch_shadow and self.space == "cosine" else corpus)
         if self._int8_shadow:
             self._corpus.enable_int8_shadow()
+        if self._binary_shadow:
+            self._corpus.enable_binary_shadow()
         self._pending = []
         self._pending_rows = 0
         self._loaded_rows = None
@@ -815,6 +826,35 @@ class ExactIndex(AttributesMixin, BaseIndex):
                                        similarity=similarity, filter=self._prepared(filter))
         return self._corpus.search(q, int(k), float(eta), float(entropy_pref), candidates=candidates,
                                    similarity=similarity)
+
+    # ---------------------------------------------------------------- approximate search over the binary copy (additive)
+    def search_binary(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, *,
+                      candidates: Optional[int] = None, rescore: bool = True) -> SearchResult:
+        """``search`` over the 1-bit copy (an index built with ``binary_shadow=True``): see ``search_binary_batch``."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        rows, scores = self.search_binary_batch(q[:1], k, eta, entropy_pref, candidates=candidates, rescore=rescore)
+        return self.results_for(rows[:1], scores[:1])[0]
+
+    def search_binary_batch(self, queries: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, *,
+                            candidates: Optional[int] = None, rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """[B, dim] queries -> (row indices int64 [B, k], adjusted scores fp32 [B, k]) with the candidate cut taken by HAMMING
+        distance between the sign bits of the query and of the stored rows: one bit per element, 1 / 32 of the fp32 rows'
+        bytes.  The cut is ``min(N, 1024, max(128, 16 k))`` or ``candidates`` (up to 1024); ``rescore=True`` re-scores it from
+        the fp32 rows and blends as every search, ``False`` blends the Hamming similarity ``(dim - 2 h) / dim``.
+        Approximate: a document is missed when the Hamming scores drop it from the cut (measured recall: DESIGN.md 4.1aa).
+        Cosine, ``dim % 128 == 0`` from 128 to 4096; no filter, no similarity transform; nothing routes here by itself
+        (``search`` and its ``approx=`` mean what they meant).  ``ValueError``: no binary shadow, ``k`` above the cut, a cut
+        above 1024.  After ``remove`` / ``upsert*`` the next binary search re-binarises the whole matrix."""
+        if not self._binary_shadow:
+            raise ValueError("search_binary needs an index built with binary_shadow=True")
+        self._ensure_built()
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        return self._corpus.search_binary(q, int(k), float(eta), float(entropy_pref), candidates=candidates,
+                                          rescore=bool(rescore))
 
     # ---------------------------------------------------------------- approximate search over an allow-list (additive)
     def search_approx_filtered(self, query: np.ndarray, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,

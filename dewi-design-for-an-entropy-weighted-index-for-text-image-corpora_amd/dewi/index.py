@@ -46,7 +46,7 @@ class DewiIndex(BaseIndex):
             # index.py:58-60: requested ANN library missing -> warn, use the exact index
             logger.warning("ANN backend unavailable; falling back to ExactIndex.")
         # (additive switches of the exact backend; everything else in **kwargs is accepted and ignored as in the reference)
-        exact_kwargs = {k: v for k, v in kwargs.items() if k in ("device", "batch_shadow", "shadow_single_query", "int8_shadow")}
+        exact_kwargs = {k: v for k, v in kwargs.items() if k in ("device", "batch_shadow", "shadow_single_query", "int8_shadow", "binary_shadow")}
         self._backend: BaseIndex = ExactIndex(dim, space, **exact_kwargs)
 
     # ------------------------------------------------------------------ ingest / build
@@ -183,6 +183,30 @@ class DewiIndex(BaseIndex):
         return self._backend.search_by_examples(positive, negative, k, eta, entropy_pref, match=match,
                                                 negative_rule=negative_rule, negative_weight=negative_weight,
                                                 candidates=candidates, filter=filter, exclude_examples=exclude_examples)
+
+    def search_binary(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None, entropy_pref: Optional[float] = None,
+                      *, candidates: Optional[int] = None, rescore: bool = True) -> List[Tuple[str, float, Payload]]:
+        """``search`` with the candidate cut taken by Hamming distance over the 1-bit copy of the rows
+        (``ExactIndex.search_binary_batch``; an index made with ``binary_shadow=True``)."""
+        q = np.asarray(query, dtype=np.float32)
+        if q.shape != (self.dim,):
+            raise ValueError(f"Expected query shape ({self.dim},), got {q.shape}")
+        return self.search_binary_batch(q.reshape(1, -1), k, eta, entropy_pref, candidates=candidates, rescore=rescore)[0]
+
+    def search_binary_batch(self, queries: np.ndarray, k: int = 10, eta: Optional[float] = None,
+                            entropy_pref: Optional[float] = None, *, candidates: Optional[int] = None,
+                            rescore: bool = True) -> List[List[Tuple[str, float, Payload]]]:
+        """One call for B queries ([B, dim]); each result list equals ``search_binary`` of that row."""
+        eta, entropy_pref = self._defaults(eta, entropy_pref)
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        if not getattr(self._backend, "_binary_shadow", False):         # (argument errors before any build)
+            raise ValueError("search_binary needs an index built with binary_shadow=True")
+        if not self._built:
+            self.build()
+        rows, scores = self._backend.search_binary_batch(q, k, eta, entropy_pref, candidates=candidates, rescore=rescore)
+        return self._backend.results_for(rows, scores)
 
     def search_approx_filtered(self, query: np.ndarray, k: int = 10, eta: Optional[float] = None,
                                entropy_pref: Optional[float] = None, candidates: Optional[int] = None, *, filter,
@@ -475,9 +499,9 @@ class DewiIndex(BaseIndex):
 
     @classmethod
     def load(cls, path: Union[str, Path], **kwargs: Any) -> "DewiIndex":
-        """``kwargs`` (additive): the exact backend's switches, e.g. ``int8_shadow=True`` — nothing of the int8 shadow is on
-        disk; it is made again from the fp32 rows at the first build, and quantisation is deterministic, so a loaded index
-        answers bit-equally."""
+        """``kwargs`` (additive): the exact backend's switches, e.g. ``int8_shadow=True`` or ``binary_shadow=True`` — nothing of
+        either copy is on disk; it is made again from the fp32 rows at the first build, and both codes are deterministic, so a
+        loaded index answers bit-equally."""
         root = Path(path)
         with open(root / "config.json", "r", encoding="utf-8") as fh:
             cfg = json.load(fh)
@@ -487,7 +511,7 @@ class DewiIndex(BaseIndex):
         inst = cls(dim=cfg["dim"], space=cfg["space"], backend="exact", use_ann=cfg.get("use_ann", True),
                    ef_query=cfg.get("ef_query", 200), rerank_eta=cfg.get("rerank_eta", 0.25),
                    entropy_pref=cfg.get("entropy_pref", 0.0))
-        exact_kwargs = {k: v for k, v in kwargs.items() if k in ("device", "batch_shadow", "shadow_single_query", "int8_shadow")}
+        exact_kwargs = {k: v for k, v in kwargs.items() if k in ("device", "batch_shadow", "shadow_single_query", "int8_shadow", "binary_shadow")}
         inst._backend = backend_cls.load(root / "ann_index", **exact_kwargs)
         inst._built = False  # device copy is rebuilt on first use
         meta_path = root / "meta.json"

@@ -59,7 +59,7 @@ class IVFIndex(ExactIndex):
     ``APPROX_AUTO_MAX_BATCH``; ``approx=False`` is the fp32 probe, bit for bit.  The int8 probe is SLOWER than the fp32 probe
     wherever the probe is short (fixed cost: profiles/r14/int8_lists/).  ``remove`` / ``upsert*`` mark the copy stale (the
     next approximate search re-quantises); ``load(path, int8_codes=True)`` re-quantises, nothing changes on disk.
-    ``int8_shadow=True`` (``ExactIndex``'s unfiltered int8 route) is refused.
+    ``int8_shadow=True`` (``ExactIndex``'s unfiltered int8 route) and ``binary_shadow=True`` (its 1-bit route) are refused.
 
     ``nlist=None``: ``min(4096, max(1, round(sqrt(N))))`` at build; ``nprobe=None``: ``max(1, nlist // 64)``.  Training:
     ``train_iters`` rounds of k-means from ``nlist`` distinct rows drawn with ``np.random.RandomState(train_seed)``, at most
@@ -109,6 +109,8 @@ class IVFIndex(ExactIndex):
         if kwargs.get("int8_shadow"):
             raise ValueError("IVFIndex does not take int8_shadow (the unfiltered int8 route scans every row): "
                              "int8_codes=True keeps the int8 copy for the probes")
+        if kwargs.get("binary_shadow"):
+            raise ValueError("IVFIndex does not take binary_shadow (the binary route scans every row)")
         int8_codes = bool(kwargs.pop("int8_codes", False))
         if int8_codes:
             from ._engine import check_int8_shape

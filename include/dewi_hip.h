@@ -944,6 +944,62 @@ int dewi_knn_candidates_i8_query_filtered(const int8_t* d_codes, const float* d_
                                           size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Approximate search over a BINARY copy of the corpus (additive to ABI 6; the reference has no counterpart; DESIGN.md
+ * 4.1aa).  One BIT per element: the sign.  Rows are compared by Hamming distance and the candidate cut is re-scored from the
+ * fp32 rows with dewi_rescore_candidates_f32.  Like the int8 route it is NOT exact, it is opt-in, its arithmetic is defined
+ * below bit for bit (tests/binary_model.py restates it in NumPy) and its recall is measured.
+ *
+ * Shapes: cosine, an fp32 main matrix, dim % 128 == 0, 128 <= dim <= 4096 (DEWI_B1_MIN_DIM, DEWI_I8_MAX_DIM), n_rows <=
+ *   2^32-1.  A row is dim / 128 whole 16-byte units, 1 to 32.
+ * Codes: a row is dim / 32 dwords; bit i % 32 of dword i / 32 is 1 iff x_i > 0.  +0, -0, negative values and NaN give 0,
+ *   +inf gives 1.  There is no scale array.  A NaN or all-zero row gets the bits this rule gives it, like any other row.
+ * Query bits: the same rule on the RAW fp32 query — dividing by a positive norm changes no sign, so no norm is formed.
+ * Score: h = popcount(row XOR query) over the dim bits, s = dim - 2 h in exact int32 (-dim <= s <= dim, s = dim (mod 2)),
+ *   sim = float(s) / float(dim): both conversions exact, ONE IEEE division, round to nearest.  For dim <= 4096 distinct s
+ *   give distinct sim in the same order (two values of s differ by at least 2 / dim relative to |sim| <= 1, far above fp32
+ *   resolution), so sorting by ord(sim) sorts by s.  sim is never NaN.  s takes dim + 1 values: ties are the rule, and the
+ *   key order (ord(sim) desc, id asc) decides them.
+ *
+ * dewi_binarize_rows_f32: the codes of d_E [n_rows][dim] -> d_bits [n_rows][dim / 32] dwords, row-major.  One streaming
+ *   pass, HBM-bound on the fp32 read.  n_rows == 0: DEWI_OK, nothing launched.
+ * dewi_prepare_queries_b1: the query bits of d_Q [n_queries][dim] -> d_bits [n_queries][dim / 32].  This is what
+ *   dewi_knn_candidates_b1 makes in registers; exposed so that tests can check it on its own and feed the model the very same
+ *   bits.
+ * dewi_knn_b1_workspace_bytes: 0 for a shape the route does not take; needs no device.
+ * dewi_knn_b1_plan: the launch plan behind that size, for tests that pin the path taken; needs no device.  out_words (HOST)
+ *   receives DEWI_B1_PLAN_WORDS int64 words, in this order:
+ *     0 blocks          workgroups of one corpus pass
+ *     1 rows_per_step   rows a wavefront has in flight: (64 >> log2p) * loads in flight
+ *     2 log2p           log2 of the lanes that share a row
+ *     3 slots           key registers per lane and query: 1 (c <= 64), 4 (c <= 256), 0 (dense keys)
+ *     4 n_lists         candidate lists per query: workgroups (slots 1), wavefronts (slots 4), 0 (dense)
+ *     5 keys_per_query  uint64 keys the scan writes per query
+ *   n_candidates is the cut AFTER min(n_candidates, n_rows).  DEWI_ERR_UNSUPPORTED where the size function returns 0.
+ * dewi_knn_candidates_b1: steps 1-3 of the search on the scores above; d_Q is RAW fp32 [n_queries][dim]; d_out
+ *   [n_queries][n_candidates] in exactly dewi_knn_candidates' layout and order — sorted by (ord(sim) desc, id asc), -0
+ *   written as +0, padding (id = -1, sim = -inf) behind min(n_candidates, n_rows) — with the payload pair of each row and
+ *   id_offset added.  1 <= n_candidates <= DEWI_I8_MAX_CANDIDATES (the re-scoring kernel's limit); d_bits and d_Q 16-byte
+ *   aligned.  Nothing is read outside [d_bits, d_bits + n_rows * dim / 8).  A corpus pass takes four queries, then one by
+ *   one.  The workspace's contents on entry are undefined: every key the select reads is written earlier in the same call.
+ * dewi_b1_tuning_set (measurements, tests): at most max_blocks workgroups per corpus pass for the CALLING THREAD's calls, 0 =
+ *   the plan's choice.  The plan, and with it the workspace size, depends on it; no bit of a result does.
+ * The four compute entry points are asynchronous on `stream`, allocate nothing and synchronise nothing; argument errors are reported before any
+ * device work: null pointers and bad shapes DEWI_ERR_INVALID_ARG; dim % 128 != 0, dim > 4096, n_candidates above the limit,
+ * 2^32 rows or more: DEWI_ERR_UNSUPPORTED; a short workspace: DEWI_ERR_WORKSPACE.  n_candidates > n_rows is not an error
+ * (padding).  Re-scoring and blending are dewi_rescore_candidates_f32 and dewi_merge_rerank on the records.
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_B1_MIN_DIM 128
+#define DEWI_B1_PLAN_WORDS 6
+int dewi_binarize_rows_f32(const float* d_E, int64_t n_rows, int dim, uint32_t* d_bits, void* stream);
+int dewi_prepare_queries_b1(const float* d_Q, int n_queries, int dim, uint32_t* d_bits, void* stream);
+size_t dewi_knn_b1_workspace_bytes(int64_t n_rows, int dim, int n_queries, int n_candidates);
+int dewi_knn_b1_plan(int64_t n_rows, int dim, int n_candidates, int64_t* out_words /* HOST */);
+int dewi_b1_tuning_set(int max_blocks);
+int dewi_knn_candidates_b1(const uint32_t* d_bits, int64_t n_rows, int dim, const float* d_Q, int n_queries,
+                           const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
+                           dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-place mutation of a built corpus (ABI 6, additive; the reference has no counterpart: its indexes only append and
  * rebuild).  A removal does not shift rows: the tail fills the holes.  With n rows, m of them deleted and n_keep = n - m,
  * the holes are the deleted rows below n_keep (ascending), the movers the surviving rows at or above n_keep (ascending),
