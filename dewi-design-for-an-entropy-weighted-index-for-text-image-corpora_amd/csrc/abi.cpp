@@ -2443,6 +2443,116 @@ int dewi_predicate_masks(const void* const* d_columns, const int32_t* column_typ
   return DEWI_OK;
 }
 
+// ---- facets (additive to ABI 6): include/dewi_hip.h "FACETS" has the contract, the error order included ----
+static thread_local int g_facet_force_path = -1;   // dewi_facet_tuning_set: 1 = global counters everywhere
+static thread_local int g_facet_max_blocks = 0;    //   0 = the plan's choice
+
+int dewi_facet_tuning_set(int force_path, int max_blocks) {
+  g_facet_force_path = force_path;
+  g_facet_max_blocks = max_blocks > 0 ? max_blocks : 0;
+  return DEWI_OK;
+}
+
+// steps 1, 3 and 4 of dewi_facet_run's checks (step 2, the pointers, lies between 1 and 3: `pointers_ok`)
+static int facet_check(int key_kind, int64_t n_rows, int64_t n_bins, int sel_kind, int n_selections, int64_t n_listed, int value_type,
+                       bool pointers_ok) {
+  if (key_kind < DEWI_FACET_KEY_I32_RANGE || key_kind > DEWI_FACET_KEY_F32_EDGES)
+    return fail(DEWI_ERR_INVALID_ARG, "unknown key_kind %d", key_kind);
+  if (sel_kind < DEWI_FACET_SEL_ALL || sel_kind > DEWI_FACET_SEL_LISTS) return fail(DEWI_ERR_INVALID_ARG, "unknown sel_kind %d", sel_kind);
+  if (value_type < DEWI_FACET_VALUE_NONE || value_type > DEWI_FACET_VALUE_F32)
+    return fail(DEWI_ERR_INVALID_ARG, "unknown value_type %d", value_type);
+  if (!pointers_ok) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
+  const bool lists = sel_kind == DEWI_FACET_SEL_LISTS;
+  if (n_rows < 0 || n_bins < 1 || n_selections < 1 || (lists && n_listed < 0))
+    return fail(DEWI_ERR_INVALID_ARG, "bad counts: %lld rows, %lld bins, %d selections, %lld listed", static_cast<long long>(n_rows),
+                static_cast<long long>(n_bins), n_selections, static_cast<long long>(n_listed));
+  if (sel_kind == DEWI_FACET_SEL_ALL && n_selections != 1)
+    return fail(DEWI_ERR_INVALID_ARG, "DEWI_FACET_SEL_ALL is one selection, got %d", n_selections);
+  if (n_bins > DEWI_FACET_MAX_BINS) return fail(DEWI_ERR_UNSUPPORTED, "%lld bins exceed DEWI_FACET_MAX_BINS = %d", static_cast<long long>(n_bins), DEWI_FACET_MAX_BINS);
+  if (n_selections > DEWI_FACET_MAX_SELECTIONS)
+    return fail(DEWI_ERR_UNSUPPORTED, "%d selections exceed DEWI_FACET_MAX_SELECTIONS = %d", n_selections, DEWI_FACET_MAX_SELECTIONS);
+  if (static_cast<int64_t>(n_selections) * (n_bins + 2) > DEWI_FACET_MAX_SLOTS)
+    return fail(DEWI_ERR_UNSUPPORTED, "%d selections of %lld slots exceed DEWI_FACET_MAX_SLOTS = %d", n_selections,
+                static_cast<long long>(n_bins + 2), DEWI_FACET_MAX_SLOTS);
+  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+  if (lists && n_listed > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_listed %lld exceeds 2^32-1", static_cast<long long>(n_listed));
+  return DEWI_OK;
+}
+
+static size_t facet_workspace(int64_t n_bins, int n_selections, int value_type) {
+  const size_t keys = value_type != DEWI_FACET_VALUE_NONE ? 2 * sizeof(uint32_t) * static_cast<size_t>(n_selections) * static_cast<size_t>(n_bins + 2) : 0;
+  return keys ? (keys + 255) & ~static_cast<size_t>(255) : 256;   // never 0: that is the size function's refusal
+}
+
+size_t dewi_facet_workspace_bytes(int64_t n_bins, int n_selections, int value_type) {
+  if (facet_check(DEWI_FACET_KEY_I32_RANGE, 0, n_bins, DEWI_FACET_SEL_MASKS, n_selections, 0, value_type, true) != DEWI_OK) return 0;
+  return facet_workspace(n_bins, n_selections, value_type);
+}
+
+int dewi_facet_plan(int64_t n_work, int key_kind, int64_t n_bins, int sel_kind, int n_selections, int value_type, int64_t* out_words) {
+  const bool lists = sel_kind == DEWI_FACET_SEL_LISTS;
+  const int rc = facet_check(key_kind, lists ? 0 : n_work, n_bins, sel_kind, n_selections, lists ? n_work : 0, value_type, out_words != nullptr);
+  if (rc != DEWI_OK) return rc;
+  const dewi::FacetPlan plan = dewi::facet_plan(n_work, key_kind, n_bins, sel_kind, n_selections, value_type, g_facet_force_path, g_facet_max_blocks);
+  out_words[0] = plan.path;
+  out_words[1] = plan.blocks;
+  out_words[2] = plan.per_launch;
+  out_words[3] = plan.lds_bytes;
+  out_words[4] = plan.launches;
+  return DEWI_OK;
+}
+
+int dewi_facet_run(const void* d_keys, int key_kind, int64_t n_rows, int32_t key_lo, const void* d_edges, int64_t n_bins,
+                   int sel_kind, int n_selections, const uint8_t* d_masks, const int64_t* d_rows, const int64_t* d_lims,
+                   int64_t n_listed, const void* d_values, int value_type, int64_t* d_counts, int64_t* d_vcount,
+                   void* d_vmin, void* d_vmax, void* d_vsum, void* d_workspace, size_t workspace_bytes, void* stream) {
+  const bool lists = sel_kind == DEWI_FACET_SEL_LISTS;
+  const bool with_value = value_type != DEWI_FACET_VALUE_NONE;
+  const bool pointers_ok = d_keys && d_counts && (key_kind == DEWI_FACET_KEY_I32_RANGE || d_edges) &&
+                           (sel_kind != DEWI_FACET_SEL_MASKS || d_masks) && (!lists || (d_rows && d_lims)) &&
+                           (!with_value || (d_values && d_vcount && d_vmin && d_vmax && d_vsum));
+  int rc = facet_check(key_kind, n_rows, n_bins, sel_kind, n_selections, n_listed, value_type, pointers_ok);
+  if (rc != DEWI_OK) return rc;
+  rc = check_workspace(d_workspace, workspace_bytes, facet_workspace(n_bins, n_selections, value_type));
+  if (rc != DEWI_OK) return rc;
+  const int64_t n_work = lists ? n_listed : n_rows;
+  const dewi::FacetPlan plan = dewi::facet_plan(n_work, key_kind, n_bins, sel_kind, n_selections, value_type, g_facet_force_path, g_facet_max_blocks);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dewi::FacetLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.keys = static_cast<const uint32_t*>(d_keys);
+  L.edges = key_kind == DEWI_FACET_KEY_I32_RANGE ? nullptr : static_cast<const uint32_t*>(d_edges);
+  L.masks = d_masks;
+  L.rows = d_rows;
+  L.lims = d_lims;
+  L.values = with_value ? static_cast<const uint32_t*>(d_values) : nullptr;
+  L.counts = reinterpret_cast<unsigned long long*>(d_counts);
+  L.vcount = with_value ? reinterpret_cast<unsigned long long*>(d_vcount) : nullptr;
+  L.kmin = with_value ? static_cast<uint32_t*>(d_workspace) : nullptr;
+  L.kmax = with_value ? L.kmin + static_cast<size_t>(n_selections) * static_cast<size_t>(n_bins + 2) : nullptr;
+  L.vsum = with_value ? d_vsum : nullptr;
+  L.n_rows = n_rows;
+  L.n_listed = lists ? n_listed : 0;
+  L.key_lo = key_lo;
+  L.n_bins = static_cast<int32_t>(n_bins);
+  L.key_kind = key_kind;
+  L.sel_kind = sel_kind;
+  L.n_selections = n_selections;
+  L.lds_edges = plan.lds_edges;
+  hipError_t e = dewi::launch_facet_init(L, value_type, s);
+  if (e != hipSuccess) return hip_fail(e, "facet init launch");
+  if (n_rows > 0 && n_work > 0) {
+    for (int p0 = 0; p0 < n_selections; p0 += plan.per_launch) {
+      L.p0 = p0;
+      L.np = n_selections - p0 < plan.per_launch ? n_selections - p0 : plan.per_launch;
+      e = dewi::launch_facet(L, plan, value_type, s);
+      if (e != hipSuccess) return hip_fail(e, "facet launch");
+    }
+  }
+  if (!with_value) return DEWI_OK;
+  return launched(dewi::launch_facet_finish(L, value_type, d_vmin, d_vmax, s), "facet finish launch");
+}
+
 int dewi_timing_enable(int every) {
   g_timing.every = every > 0 ? every : 0;
   g_timing.calls = 0;

@@ -698,4 +698,50 @@ struct PredLaunch {
 static_assert(sizeof(PredLaunch) <= 3584, "the predicate launch must fit the kernel arguments");
 hipError_t launch_predicate_masks(const PredLaunch& L, hipStream_t stream);
 
+// ---- facets.hip: histograms and per-bin statistics (dewi_facet_run) ---------------------------
+constexpr int kFacetThreads = 256;
+constexpr int kFacetRows = 4;                            // consecutive rows per lane (ALL, MASKS); LISTS: one element per lane
+constexpr int kFacetMaxBlocks = 512;                     // two workgroups per CU; grid-stride beyond
+constexpr int kFacetMinRowsPerBlock = 4096;              // a workgroup flushes its counters once: give it four trips first
+constexpr int kFacetLdsEdgeBytes = 16384;                // edges up to this size are staged in LDS
+constexpr int kFacetSlotBytes = 4;                      // LDS per slot on path 0: a u32 count ...
+constexpr int kFacetValueSlotBytes = 24;                 // ... and with a value column a 64-bit sum, u32 vcount, kmin, kmax
+constexpr int kFacetPeel = 8;                            // distinct slots a wavefront folds before its lanes add on their own
+struct FacetPlan {
+  int path;             // 0: workgroup-private counters in LDS, 1: global counters
+  int blocks;           // workgroups per launch
+  int per_launch;       // selections per launch
+  int lds_bytes;        // dynamic LDS of a workgroup
+  int launches;
+  int lds_edges;        // edge VALUES staged in LDS (0: searched in global memory, or no edges)
+};
+struct FacetLaunch {
+  const uint32_t* keys;
+  const uint32_t* edges;
+  const uint8_t* masks;
+  const int64_t* rows;
+  const int64_t* lims;
+  const uint32_t* values;
+  unsigned long long* counts;
+  unsigned long long* vcount;
+  uint32_t* kmin;       // ordered keys of the minimum / maximum, in the workspace
+  uint32_t* kmax;
+  void* vsum;
+  int64_t n_rows;
+  int64_t n_listed;
+  int64_t key_lo;
+  int32_t n_bins;
+  int32_t key_kind;
+  int32_t sel_kind;
+  int32_t n_selections; // all of the call
+  int32_t p0;           // this launch: selections [p0, p0 + np)
+  int32_t np;
+  int32_t lds_edges;
+};
+FacetPlan facet_plan(int64_t n_work, int key_kind, int64_t n_bins, int sel_kind, int n_selections, int value_type, int force_path,
+                     int max_blocks);
+hipError_t launch_facet_init(const FacetLaunch& L, int value_type, hipStream_t stream);
+hipError_t launch_facet(const FacetLaunch& L, const FacetPlan& plan, int value_type, hipStream_t stream);
+hipError_t launch_facet_finish(const FacetLaunch& L, int value_type, void* d_vmin, void* d_vmax, hipStream_t stream);
+
 }  // namespace dewi

@@ -1250,6 +1250,69 @@ class DeviceCorpus:
                                                      nat.ptr(out), nat.stream_ptr()))
         return out
 
+    # ------------------------------------------------------------------ facets over attribute columns
+    def facet_device(self, keys, key_kind: int, n_bins: int, key_lo: int = 0, edges=None, masks=None, lists=None, values=None):
+        """``dewi_facet_run`` over a key column of this corpus: ``keys`` a contiguous CUDA int32 / float32 tensor [n_rows];
+        ``edges`` ``None`` (an integer range from ``key_lo``) or ``n_bins + 1`` edges of the keys' dtype (numpy or device);
+        the selections — neither ``masks`` nor ``lists``: all rows; ``masks``: device bytes / bools [P, n_rows]; ``lists``:
+        ``(lims int64 [P + 1], rows int64 [T])`` on the device, LOCAL rows —; ``values``: ``None`` or a CUDA int32 / float32
+        column [n_rows].  Returns device tensors ``(counts int64 [P, n_bins + 2], stats)``, ``stats`` ``None`` or a dict
+        ``vcount`` / ``vmin`` / ``vmax`` / ``vsum``.  Asynchronous on the current stream: no synchronisation."""
+        torch = _torch()
+        n = self.n_rows
+
+        def column(t, what):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 1 and int(t.shape[0]) == n and t.is_contiguous()
+                    and t.dtype in (torch.int32, torch.float32)):
+                raise ValueError(f"{what} must be a contiguous CUDA int32 / float32 tensor of shape ({n},)")
+            return t
+
+        keys = column(keys, "the key column")
+        if (keys.dtype == torch.float32) != (key_kind == nat.FACET_KEY_CODES["f32_edges"]):
+            raise ValueError(f"key kind {key_kind} does not take a {keys.dtype} column")
+        if masks is not None and lists is not None:
+            raise ValueError("pass masks or lists, not both")
+        vt = nat.FACET_VALUE_CODES[None]
+        if values is not None:
+            values = column(values, "the value column")
+            vt = nat.FACET_VALUE_CODES["float" if values.dtype == torch.float32 else "int"]
+        with torch.cuda.device(self.device):
+            e = None
+            if edges is not None:
+                e = edges if isinstance(edges, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edges))
+                e = e.to(device=self.device, dtype=keys.dtype).contiguous()
+                if tuple(e.shape) != (int(n_bins) + 1,):
+                    raise ValueError(f"{n_bins} bins take {int(n_bins) + 1} edges, got {tuple(e.shape)}")
+            sel, p, m8, lims, rows, t = nat.FACET_SEL_CODES["all"], 1, None, None, None, 0
+            if masks is not None:
+                if masks.dim() != 2 or int(masks.shape[1]) != n or masks.dtype not in (torch.uint8, torch.bool):
+                    raise ValueError(f"selection masks must be bytes or bools of shape (P, {n})")
+                m8 = masks.to(device=self.device).view(torch.uint8).contiguous()
+                sel, p = nat.FACET_SEL_CODES["masks"], int(m8.shape[0])
+            elif lists is not None:
+                lims = lists[0].to(device=self.device, dtype=torch.int64).contiguous()
+                rows = lists[1].to(device=self.device, dtype=torch.int64).contiguous()
+                sel, p, t = nat.FACET_SEL_CODES["lists"], int(lims.shape[0]) - 1, int(rows.shape[0])
+                if t == 0:                      # (an empty tensor has no address; the call reads none of it)
+                    rows = torch.zeros(1, dtype=torch.int64, device=self.device)
+            slots = int(n_bins) + 2
+            ws = self._cached_workspace(("facet", int(n_bins), p, vt), self._lib.dewi_facet_workspace_bytes, int(n_bins), p, vt)
+            counts = torch.empty((p, slots), dtype=torch.int64, device=self.device)
+            stats = None
+            if vt:
+                stats = {"vcount": torch.empty((p, slots), dtype=torch.int64, device=self.device),
+                         "vmin": torch.empty((p, slots), dtype=values.dtype, device=self.device),
+                         "vmax": torch.empty((p, slots), dtype=values.dtype, device=self.device),
+                         "vsum": torch.empty((p, slots), dtype=torch.float64 if vt == 2 else torch.int64, device=self.device)}
+            nat.check(self._lib.dewi_facet_run(
+                nat.ptr(keys), int(key_kind), n, int(key_lo), nat.ptr(e) if e is not None else None, int(n_bins), sel, p,
+                nat.ptr(m8) if m8 is not None else None, nat.ptr(rows) if rows is not None else None,
+                nat.ptr(lims) if lims is not None else None, t, nat.ptr(values) if vt else None, vt, nat.ptr(counts),
+                nat.ptr(stats["vcount"]) if vt else None, nat.ptr(stats["vmin"]) if vt else None,
+                nat.ptr(stats["vmax"]) if vt else None, nat.ptr(stats["vsum"]) if vt else None, nat.ptr(ws), ws.numel(),
+                nat.stream_ptr()))
+        return counts, stats
+
     def make_filter_bytes(self, mask8) -> DeviceFilter:
         """``make_filter`` of a device byte mask [n_rows] of 0 / 1 that this corpus made itself (``predicate_masks``): no copy,
         and the filter's ``byte_mask()`` is seeded with the mask."""

@@ -56,6 +56,13 @@ PRED_MAX_PROGRAMS = 256
 EXAMPLES_MAX = 16
 EXAMPLES_MATCH_CODES = {"any": 0, "all": 1}
 EXAMPLES_RULE_CODES = {"penalty": 0, "best_score": 1}
+#: facets (include/dewi_hip.h DEWI_FACET_*): the key kinds, the selection forms, the value types, the limits
+FACET_KEY_CODES = {"i32_range": 0, "i32_edges": 1, "f32_edges": 2}
+FACET_SEL_CODES = {"all": 0, "masks": 1, "lists": 2}
+FACET_VALUE_CODES = {None: 0, "int": 1, "float": 2}
+FACET_MAX_BINS = 1 << 20
+FACET_MAX_SELECTIONS = 4096
+FACET_MAX_SLOTS = 1 << 27
 #: opcodes of a predicate program (include/dewi_hip.h DEWI_PRED_*), in the header's order
 PRED_OPS = ("I_LT", "I_LE", "I_EQ", "I_NE", "I_GE", "I_GT", "I_BETWEEN", "I_ANY_BITS", "I_ALL_BITS", "I_IN_SET",
             "F_LT", "F_LE", "F_EQ", "F_NE", "F_GE", "F_GT", "F_BETWEEN", "F_IS_NAN", "TRUE", "AND", "OR", "NOT")
@@ -93,6 +100,7 @@ EXPORTED_SYMBOLS = (
     "dewi_knn_examples_workspace_bytes", "dewi_knn_candidates_examples", "dewi_examples_tuning_set",
     "dewi_binarize_rows_f32", "dewi_prepare_queries_b1", "dewi_knn_b1_workspace_bytes", "dewi_knn_b1_plan", "dewi_knn_candidates_b1",
     "dewi_b1_tuning_set",
+    "dewi_facet_workspace_bytes", "dewi_facet_plan", "dewi_facet_tuning_set", "dewi_facet_run",
 )
 #: the words dewi_robust_fit_fast_plan fills, in order (include/dewi_hip.h)
 FIT_FAST_PLAN_WORDS = ("supported", "slices", "counters_offset", "counters_bytes", "small_n", "sample", "delta", "buckets",
@@ -102,6 +110,8 @@ I8_BATCH_PLAN_WORDS = ("groups", "n_blocks", "n_seg", "seg_cap", "tile_stride", 
                        "cnt_off", "cand_off", "repair_off", "total")
 #: the words dewi_knn_b1_plan fills, in order (include/dewi_hip.h DEWI_B1_PLAN_WORDS)
 B1_PLAN_WORDS = ("blocks", "rows_per_step", "log2p", "slots", "n_lists", "keys_per_query")
+#: the words dewi_facet_plan fills, in order (include/dewi_hip.h DEWI_FACET_PLAN_WORDS)
+FACET_PLAN_WORDS = ("path", "blocks", "per_launch", "lds_bytes", "launches")
 
 
 class NativeLibraryError(RuntimeError):
@@ -333,6 +343,14 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.dewi_b1_tuning_set.argtypes = [i32]
     lib.dewi_knn_candidates_b1.restype = i32
     lib.dewi_knn_candidates_b1.argtypes = [vp, i64, i32, vp, i32, vp, vp, i32, i64, vp, vp, sz, vp]
+    lib.dewi_facet_workspace_bytes.restype = sz
+    lib.dewi_facet_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.dewi_facet_plan.restype = i32
+    lib.dewi_facet_plan.argtypes = [i64, i32, i64, i32, i32, i32, c.POINTER(i64)]
+    lib.dewi_facet_tuning_set.restype = i32
+    lib.dewi_facet_tuning_set.argtypes = [i32, i32]
+    lib.dewi_facet_run.restype = i32
+    lib.dewi_facet_run.argtypes = [vp, i32, i64, c.c_int32, vp, i64, i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.dewi_predicate_masks.restype = i32
     lib.dewi_predicate_masks.argtypes = [c.POINTER(vp), c.POINTER(c.c_int32), i32, i64, c.POINTER(PredInstr), c.POINTER(c.c_int32), i32,
                                          vp, i64, vp, vp, vp]
@@ -407,6 +425,13 @@ def b1_plan(n_rows: int, dim: int, n_candidates: int) -> dict:
     out = (ctypes.c_int64 * len(B1_PLAN_WORDS))()
     check(load_library(require_gpu=False).dewi_knn_b1_plan(n_rows, dim, n_candidates, out))
     return dict(zip(B1_PLAN_WORDS, (int(v) for v in out)))
+
+
+def facet_plan(n_work: int, key_kind: int, n_bins: int, sel_kind: int, n_selections: int, value_type: int) -> dict:
+    """``dewi_facet_plan`` as a dict keyed by ``FACET_PLAN_WORDS`` (host only: needs no GPU)."""
+    out = (ctypes.c_int64 * len(FACET_PLAN_WORDS))()
+    check(load_library(require_gpu=False).dewi_facet_plan(n_work, key_kind, n_bins, sel_kind, n_selections, value_type, out))
+    return dict(zip(FACET_PLAN_WORDS, (int(v) for v in out)))
 
 
 def is_device_tensor(x) -> bool:

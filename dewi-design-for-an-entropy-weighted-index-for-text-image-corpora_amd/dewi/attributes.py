@@ -17,6 +17,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._native import PRED_MAX_COLUMNS
+from .facets import Facet, check_lists, facets_from_outputs, resolve_bins
 from .types import PAYLOAD_FIELDS
 from .where import Where, compile_programs, is_where_list
 
@@ -387,6 +388,161 @@ class AttributesMixin:
             raise TypeError(f"expected a Where (dewi.where.col), got {type(where).__name__}")
         import torch
         return int(self._where_masks([where])[0].sum(dtype=torch.int64).item())
+
+    # ---------------------------------------------------------------- facets
+    def _facet_column(self, column):
+        """``(name, kind, vocabulary, device tensor [N])`` of an attribute name or of prepared group labels."""
+        from ._engine import DeviceGroups
+        if isinstance(column, DeviceGroups):
+            self._corpus.check_groups(column)
+            return "groups", "int", None, column.labels
+        have = self._attr_columns()
+        if not isinstance(column, str) or column not in have:
+            raise ValueError(f"unknown attribute column {column!r} (the index has {list(have)})")
+        c = have[column]
+        return column, c.kind, c.vocab, c.view()
+
+    def _facet_selection(self, filter, rows):
+        """``(masks, lists, many)``: device bytes [P, N] or ``None``; device ``(lims, rows)`` of LOCAL rows or ``None``;
+        whether the caller gets a list of results."""
+        from ._engine import DeviceFilter, DeviceQueryFilters
+        from .backends import filter_kwargs
+        import torch
+        corpus = self._corpus
+        n = corpus.n_rows
+        if rows is not None:
+            if filter is not None:
+                raise ValueError("pass filter or rows, not both")
+            if not isinstance(rows, (tuple, list)) or len(rows) != 2:
+                raise ValueError("rows=(lims, rows)")
+            lims, ids = rows
+            if hasattr(lims, "is_cuda") and hasattr(ids, "is_cuda"):
+                lims, ids = lims.to(corpus.device, torch.int64), ids.to(corpus.device, torch.int64)
+                if lims.dim() != 1 or int(lims.shape[0]) < 2 or ids.dim() != 1:
+                    raise ValueError("rows=(lims, rows): lims [P + 1] with P >= 1 and rows [T], both 1-D")
+                if ids.numel() and (int(ids.min().item()) < 0 or int(ids.max().item()) >= n):
+                    raise ValueError(f"listed rows must lie in [0, {n})")
+            else:
+                li, ro = check_lists(lims.cpu().numpy() if hasattr(lims, "is_cuda") else lims,
+                                     ids.cpu().numpy() if hasattr(ids, "is_cuda") else ids, n)
+                lims, ids = torch.from_numpy(li).to(corpus.device), torch.from_numpy(ro).to(corpus.device)
+            return None, (lims, ids), True
+        if filter is None:
+            return None, None, False
+        if isinstance(filter, Where):
+            return self._where_masks([filter]), None, False
+        if is_where_list(filter):
+            return self._where_masks(list(filter)), None, True
+        if isinstance(filter, DeviceFilter):
+            corpus.check_filter(filter)
+            return filter.byte_mask().view(1, n), None, False
+        if isinstance(filter, DeviceQueryFilters):
+            corpus.check_query_filters(filter)
+            return filter.masks, None, True
+        if len(getattr(filter, "shape", ())) == 2:
+            m = self.query_filter_masks(filter)
+            m = m if hasattr(m, "is_cuda") else torch.from_numpy(np.ascontiguousarray(m))
+            return m.to(corpus.device).view(torch.uint8), None, True
+        m = self.filter_mask(**filter_kwargs(filter))
+        m = m if hasattr(m, "is_cuda") else torch.from_numpy(np.ascontiguousarray(m))
+        return m.to(corpus.device).view(torch.uint8).view(1, n), None, False
+
+    def _facet_run(self, columns, bins, value, masks, lists, many):
+        """One ``dewi_facet_run`` per column over prepared selections -> per column a ``Facet`` or a list of them."""
+        import torch
+        corpus = self._corpus
+        vals = None
+        if value is not None:
+            vname, vkind, _, vals = self._facet_column(value)
+            if vkind == "cat":
+                raise ValueError(f"value column {vname!r} is categorical: statistics need numbers")
+        out = []
+        with corpus._lock, torch.cuda.device(corpus.device):
+            for column, b in zip(columns, bins):
+                name, kind, vocab, keys = self._facet_column(column)
+
+                def min_max(keys=keys, groups=name == "groups"):
+                    lo, hi = (int(v.item()) for v in torch.aminmax(keys))   # the one synchronisation
+                    return (0, max(hi, 0)) if groups else (lo, hi)           # negative labels: ungrouped, counted as other
+
+                fb = resolve_bins(kind, vocab, b, name, min_max)
+                counts, stats = corpus.facet_device(keys, fb.key_kind, fb.n_bins, fb.key_lo, fb.edges, masks=masks, lists=lists,
+                                                    values=vals)
+                got = facets_from_outputs(name, fb, counts.cpu().numpy(),
+                                          None if stats is None else {k: v.cpu().numpy() for k, v in stats.items()})
+                out.append(got if many else got[0])
+        return out
+
+    def facet(self, column, *, filter=None, rows=None, bins=None, value=None):
+        """How the selected documents are distributed over a column (additive; ``dewi_facet_run``): a ``dewi.facets.Facet``
+        with one count per bin, ``other``, ``nan`` and ``total``, counted on the device in one pass over the column.
+
+        ``column``: an attribute name, or a ``make_groups(...)`` result (the labels are the keys, negative labels go to
+        ``other``).  ``bins``: see ``dewi.facets.resolve_bins`` — ``None`` (a categorical column: its vocabulary; an int
+        column: ``min .. max``, one synchronisation), a tuple ``(lo, hi)`` of integers (an inclusive range) or a sequence of
+        ascending edges.  ``value``: a numeric attribute whose count / min / max / sum / mean per bin become ``stats``.
+        ``filter``: whatever ``search(filter=)`` takes for one allow-list — a mask, doc ids, rows, a prepared filter, a
+        ``Where`` —; a list of ``Where`` or a 2-D mask gives a LIST of results, one per predicate, from one pass.
+        ``rows=(lims, rows)``: host arrays or CUDA tensors, one selection per segment ``rows[lims[p]:lims[p + 1]]``, a row
+        counted once per appearance; a list of results; an id outside the index raises ``ValueError``.  ``rows`` and
+        ``filter`` together raise ``ValueError``.  After ``remove`` / ``upsert*`` the columns are counted as they stand; a
+        stale prepared filter raises, as everywhere."""
+        self._ensure_built()
+        masks, lists, many = self._facet_selection(filter, rows)
+        return self._facet_run([column], [bins], value, masks, lists, many)[0]
+
+    def facets(self, columns: Sequence, *, filter=None, rows=None, bins=None, value=None) -> Dict[str, Any]:
+        """``facet`` for several columns over the same selections: the predicate masks are evaluated once.  ``bins``: ``None``
+        or ``{column name: bins}``.  Returns ``{column name: Facet or list}`` in the order given."""
+        columns = list(columns)
+        self._ensure_built()
+        names = [self._facet_column(c)[0] for c in columns]
+        unknown = [k for k in (bins or {}) if k not in names]
+        if unknown:
+            raise ValueError(f"bins given for columns {unknown} that are not counted")
+        masks, lists, many = self._facet_selection(filter, rows)
+        got = self._facet_run(columns, [(bins or {}).get(x) for x in names], value, masks, lists, many)
+        return dict(zip(names, got))
+
+    def facet_range(self, queries, thresholds, column, *, filter=None, value=None, bins=None):
+        """One ``Facet`` per query over the documents at least ``thresholds`` similar to it (``range_search_batch``'s rows):
+        the range search leaves its ``lims`` and ``rows`` on the device and ``dewi_facet_run`` counts them there — nothing of
+        the size of the result crosses to the host.  ``filter``: one allow-list for the batch, as ``range_search_batch``."""
+        from ._engine import DeviceQueryFilters, check_thresholds
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"Expected queries of shape (B, {self.dim}), got {q.shape}")
+        thr = check_thresholds(thresholds, int(q.shape[0]))
+        if isinstance(filter, DeviceQueryFilters) or is_where_list(filter) or (filter is not None and len(getattr(filter, "shape", ())) == 2):
+            raise NotImplementedError("range search takes one allow-list for the batch (per-query filters: not in this build)")
+        if q.shape[0] == 0:
+            return []
+        self._ensure_built()
+        import torch
+        corpus = self._corpus
+        with corpus._lock, torch.cuda.device(corpus.device):
+            lims, rows, _, _ = corpus.range_search_device(corpus.stage_queries(q), thr, 0.0, 0.0, filter=self._prepared(filter), sort=False)
+            if corpus.id_offset:
+                rows = rows - corpus.id_offset
+            return self._facet_run([column], [bins], value, None, (lims, rows), True)[0]
+
+    def stratify_by_dewi(self, bins, *, filter=None, rows=None) -> Dict[Tuple[float, float], float]:
+        """The reference's ``metrics.stratify_by_dewi`` over the index: ``{(lo, hi): proportion}`` of the selected documents
+        whose ``dewi`` lies in each bin — ``lo <= dewi < hi``, the last bin closed at both ends —, the denominator being every
+        selected document, inside a bin or not.  ``rows=(lims, rows)`` pools every segment, as the reference pools the
+        rankings of all queries.  Needs the ``dewi`` attribute: call ``attributes_from_payload("dewi")`` first."""
+        if bins is None or len(bins) < 2:
+            raise ValueError("At least two bin boundaries required")
+        if "dewi" not in self.attribute_schema():
+            raise ValueError('stratify_by_dewi reads the "dewi" attribute column: call attributes_from_payload("dewi") first')
+        got = self.facet("dewi", filter=filter, rows=rows, bins=list(bins))
+        if isinstance(got, list):
+            pooled = Facet("dewi", got[0].keys, sum(f.counts for f in got), sum(f.other for f in got), sum(f.nan for f in got))
+        else:
+            pooled = got
+        return pooled.proportions()
 
     # ---------------------------------------------------------------- persistence
     def _attrs_save(self, root: Path) -> None:

@@ -464,6 +464,23 @@ class DewiIndex(BaseIndex):
     def count_where(self, where) -> int:
         return self._built_backend().count_where(where)
 
+    # ------------------------------------------------------------------ facets (additive)
+    def facet(self, column, *, filter=None, rows=None, bins=None, value=None):
+        """How the selected documents are distributed over an attribute column (``ExactIndex.facet``)."""
+        return self._built_backend().facet(column, filter=filter, rows=rows, bins=bins, value=value)
+
+    def facets(self, columns, *, filter=None, rows=None, bins=None, value=None):
+        """``facet`` for several columns over the same selections (``ExactIndex.facets``)."""
+        return self._built_backend().facets(columns, filter=filter, rows=rows, bins=bins, value=value)
+
+    def facet_range(self, queries, thresholds, column, *, filter=None, value=None, bins=None):
+        """One ``Facet`` per query over its range-search results (``ExactIndex.facet_range``)."""
+        return self._built_backend().facet_range(queries, thresholds, column, filter=filter, value=value, bins=bins)
+
+    def stratify_by_dewi(self, bins, *, filter=None, rows=None):
+        """``{(lo, hi): proportion}`` of the ``dewi`` attribute over the selected documents (``ExactIndex.stratify_by_dewi``)."""
+        return self._built_backend().stratify_by_dewi(bins, filter=filter, rows=rows)
+
     # ------------------------------------------------------------------ accessors (index.py:95-119)
     def __len__(self) -> int:
         return len(self._backend._doc_ids)

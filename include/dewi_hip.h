@@ -1252,6 +1252,98 @@ int dewi_knn_candidates_examples(const float* d_E, int64_t n_rows, int dim, cons
 int dewi_examples_tuning_set(int examples_per_pass);
 
 /* ------------------------------------------------------------------------------------------
+ * FACETS (additive to ABI 6; tests/facet_model.py restates this section in NumPy): for each of P SELECTIONS
+ * of rows, a histogram of a KEY column and, optionally, per-bin statistics of a VALUE column — what a search front end shows
+ * next to a filter ("1 200 from site A, 400 from B"), and the reference's metrics.stratify_by_dewi (metrics.py:152-161).
+ *
+ * Key column: n_rows 4-byte elements, 4-byte aligned only.  A row falls into one SLOT of n_bins + 2: a bin, `other`
+ * (slot n_bins) or `nan` (slot n_bins + 1).
+ *   DEWI_FACET_KEY_I32_RANGE: b = (int64) x - key_lo; bin b iff 0 <= b < n_bins, else `other`.  The subtraction is done in
+ *     64 bits: x = INT32_MIN with key_lo = INT32_MAX is `other`.  d_edges is ignored.
+ *   DEWI_FACET_KEY_I32_EDGES / DEWI_FACET_KEY_F32_EDGES: d_edges holds n_bins + 1 values of the column's type on the device,
+ *     strictly ascending (fp32: no NaN, +-inf allowed).  Bin i < n_bins - 1 holds e_i <= x < e_{i+1}; the LAST bin holds
+ *     e_{n-1} <= x <= e_n, closed at both ends.  fp32 compares as IEEE does (-0 equals +0).  A NaN key goes to `nan`,
+ *     everything else outside the edges to `other`.  Ascending order is the caller's duty: the edges are not read on the
+ *     host.  key_lo is ignored.
+ *
+ * Selections:
+ *   DEWI_FACET_SEL_ALL: n_selections == 1, every row.
+ *   DEWI_FACET_SEL_MASKS: d_masks [P][n_rows] bytes, non-zero = selected — what dewi_predicate_masks writes.  Selection p
+ *     starts at byte p * n_rows (unaligned for p > 0 and n_rows % 4 != 0).
+ *   DEWI_FACET_SEL_LISTS: d_rows int64 [n_listed], d_lims int64 [P + 1] on the device, non-decreasing: selection p is
+ *     d_rows[d_lims[p] .. d_lims[p + 1]) — what the range search returns.  A row counts once per appearance.  An id outside
+ *     [0, n_rows) is skipped and never dereferenced; so is an element at or beyond d_lims[P] or below d_lims[0].
+ *
+ * Outputs, per selection p and slot s, at [p * (n_bins + 2) + s]:
+ *   d_counts int64: the selected rows of the slot (`nan` is always 0 for int keys).
+ *   With a value column (value_type DEWI_FACET_VALUE_I32 / _F32, d_values n_rows elements; DEWI_FACET_VALUE_NONE: the four
+ *   pointers below are ignored):
+ *     d_vcount int64: the values that are not NaN (int values: == d_counts).
+ *     d_vmin / d_vmax, of the value's type: an empty slot holds INT32_MAX / INT32_MIN or +inf / -inf.  fp32 values are ordered
+ *       by the total order of their bits, so -0 sits below +0; NaN values are left out.
+ *     d_vsum: an exact (wrapping) int64 for int values; fp64 for fp32 values.  The fp64 sum is the one output that is not
+ *       bit-reproducible, the order of additions being free: |d_vsum - exact| <= vcount * 2^-52 * sum|x| per slot (the
+ *       fp32 -> fp64 widening is exact, fewer than vcount additions, each off by at most 2^-53 of a partial sum <= sum|x|).
+ *   Everything else is exact.  The library clears its outputs inside the call, on the stream: their contents on entry are
+ *   undefined, and so are the workspace's.
+ *
+ * Limits: 1 <= n_bins <= DEWI_FACET_MAX_BINS; 1 <= P <= DEWI_FACET_MAX_SELECTIONS; P * (n_bins + 2) <=
+ * DEWI_FACET_MAX_SLOTS; n_rows < 2^32; n_listed < 2^32.
+ *
+ * Execution.  Path 0: the counters of a launch fit DEWI_FACET_LDS_COUNTER_BYTES of LDS (4 bytes per slot, 24 with a value
+ * column; edges of up to 16 KB are staged next to them, so a workgroup asks for at most 64 KB and two fit a CU): every
+ * workgroup keeps private u32 counters and value slots there and flushes the non-zero ones once with 64-bit global atomics.
+ * A launch takes as many consecutive selections as fit; more take more launches, each reading the key column once for all
+ * of its selections.  Path 1: the counters do not fit; one launch adds to the global counters directly.  On both paths a
+ * wavefront folds equal slots before it touches a counter: the rows of a wavefront that share the first row's slot become
+ * ONE add of their number (and one min / max / sum of their values when that is the whole wavefront), repeated for up to
+ * eight distinct slots, before the remaining lanes add on their own — a corpus sorted by source costs one add per wavefront
+ * and slot, not 64 to one address.  A lane takes four consecutive rows (a 16-byte load where the column is 16-byte aligned,
+ * 4-byte loads otherwise).  Edges are searched branch-free, from LDS when they fit 16 KB.
+ *
+ * dewi_facet_workspace_bytes: needs no device; 0 for arguments dewi_facet_run refuses.  The workspace holds the min / max
+ *   keys of the value column while the call runs.
+ * dewi_facet_plan: the plan, for tests that pin the path taken; needs no device.  out_words (HOST) receives
+ *   DEWI_FACET_PLAN_WORDS int64 words: 0 path, 1 workgroups per launch, 2 selections per launch, 3 LDS bytes per workgroup,
+ *   4 launches.  n_work is n_rows (ALL, MASKS) or n_listed (LISTS).  The same argument errors as dewi_facet_run's steps 1, 3, 4.
+ * dewi_facet_tuning_set (measurements, tests): force_path 1 = path 1 everywhere, anything else = the plan's choice;
+ *   max_blocks > 0 = at most that many workgroups per launch.  For the CALLING THREAD's calls; no bit of a result depends
+ *   on it (the fp64 sum within its bound).
+ * dewi_facet_run: asynchronous on `stream`, allocates nothing, synchronises nothing.  Errors, every one before any device
+ *   work, in this order:
+ *   1. an unknown key_kind, sel_kind or value_type: DEWI_ERR_INVALID_ARG;
+ *   2. a NULL d_keys or d_counts; NULL d_edges with an EDGES kind; NULL d_masks with MASKS; NULL d_rows or d_lims with LISTS;
+ *      with a value column a NULL d_values, d_vcount, d_vmin, d_vmax or d_vsum: DEWI_ERR_INVALID_ARG "null pointer";
+ *   3. n_rows < 0, n_bins < 1, n_selections < 1, n_listed < 0 (LISTS), n_selections != 1 with ALL: DEWI_ERR_INVALID_ARG;
+ *   4. n_bins > DEWI_FACET_MAX_BINS, n_selections > DEWI_FACET_MAX_SELECTIONS, more than DEWI_FACET_MAX_SLOTS slots,
+ *      n_rows >= 2^32, n_listed >= 2^32: DEWI_ERR_UNSUPPORTED;
+ *   5. a workspace below dewi_facet_workspace_bytes: DEWI_ERR_WORKSPACE.
+ *   n_rows == 0 or (LISTS) n_listed == 0: DEWI_OK with cleared outputs (zeros, and the empty min / max).
+ * ------------------------------------------------------------------------------------------ */
+#define DEWI_FACET_MAX_BINS (1 << 20)
+#define DEWI_FACET_MAX_SELECTIONS 4096
+#define DEWI_FACET_MAX_SLOTS (1 << 27)
+#define DEWI_FACET_LDS_COUNTER_BYTES 49152
+#define DEWI_FACET_KEY_I32_RANGE 0
+#define DEWI_FACET_KEY_I32_EDGES 1
+#define DEWI_FACET_KEY_F32_EDGES 2
+#define DEWI_FACET_SEL_ALL 0
+#define DEWI_FACET_SEL_MASKS 1
+#define DEWI_FACET_SEL_LISTS 2
+#define DEWI_FACET_VALUE_NONE 0
+#define DEWI_FACET_VALUE_I32 1
+#define DEWI_FACET_VALUE_F32 2
+#define DEWI_FACET_PLAN_WORDS 5
+size_t dewi_facet_workspace_bytes(int64_t n_bins, int n_selections, int value_type);
+int dewi_facet_plan(int64_t n_work, int key_kind, int64_t n_bins, int sel_kind, int n_selections, int value_type,
+                    int64_t* out_words /* HOST */);
+int dewi_facet_tuning_set(int force_path, int max_blocks);
+int dewi_facet_run(const void* d_keys, int key_kind, int64_t n_rows, int32_t key_lo, const void* d_edges, int64_t n_bins,
+                   int sel_kind, int n_selections, const uint8_t* d_masks, const int64_t* d_rows, const int64_t* d_lims,
+                   int64_t n_listed, const void* d_values, int value_type, int64_t* d_counts, int64_t* d_vcount,
+                   void* d_vmin, void* d_vmax, void* d_vsum, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): dewi_timing_enable(n) makes every n-th dewi_knn_* call bracket its
  * corpus-scan kernel with hipEvents on `stream` (n = 1: every call; 0: off — the two event records
  * cost ~5 us of stream time, so throughput runs sample); dewi_timing_read synchronises those
