@@ -51,6 +51,78 @@ int check_workspace(const void* d_ws, size_t ws_bytes, size_t need) {
   if (!d_ws || ws_bytes < need) return fail(DEWI_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
   return DEWI_OK;
 }
+int check_aligned16(const void* p, const char* what) {
+  if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return fail(DEWI_ERR_INVALID_ARG, "%s must be 16-byte aligned", what);
+  return DEWI_OK;
+}
+// candidate records carry GLOBAL row ids as int32: the rows [id_offset, id_offset + n_rows) must fit
+bool ids_fit_int32(int64_t id_offset, int64_t n_rows) { return id_offset >= 0 && id_offset + n_rows <= 0x7FFFFFFFll; }
+int check_id_range(int64_t id_offset, int64_t n_rows) {
+  if (ids_fit_int32(id_offset, n_rows)) return DEWI_OK;
+  return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)", static_cast<long long>(id_offset),
+              static_cast<long long>(n_rows));
+}
+// the length of a prepared filter's list, as its caller states it
+int check_n_allowed(int64_t n_allowed, int64_t n_rows) {
+  if (n_allowed >= 0 && n_allowed <= n_rows) return DEWI_OK;
+  return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+}
+// candidates a shard (or a list) of n rows can contribute; a route that owes more records per query pads the tail
+int shard_cut(int n_candidates, int64_t n) { return n_candidates < n ? n_candidates : static_cast<int>(n); }
+
+// ---- the routes over a compact copy of the corpus (int8 codes, sign bits) and the re-scoring of their records ----
+// which condition of the shape fails first: the entry points' message (check_codes_shape), the size functions' 0
+enum class ShapeFault { None, Rows, Rows2_32, Dim, Unit };
+ShapeFault codes_shape_fault(int64_t n_rows, int dim, int unit) {
+  if (n_rows <= 0) return ShapeFault::Rows;
+  if (n_rows > 0xFFFFFFFFll) return ShapeFault::Rows2_32;
+  if (dim <= 0) return ShapeFault::Dim;
+  if (dim % unit != 0 || dim > DEWI_I8_MAX_DIM) return ShapeFault::Unit;
+  return ShapeFault::None;
+}
+// `route`: "int8" (units of 16 codes; the re-scoring: 4 floats) / "binary" (units of DEWI_B1_MIN_DIM bits)
+int check_codes_shape(int64_t n_rows, int dim, int unit, const char* route) {
+  switch (codes_shape_fault(n_rows, dim, unit)) {
+    case ShapeFault::Rows: return fail(DEWI_ERR_INVALID_ARG, "n_rows must be positive (got %lld)", static_cast<long long>(n_rows));
+    case ShapeFault::Rows2_32: return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
+    case ShapeFault::Dim: return fail(DEWI_ERR_INVALID_ARG, "dim must be positive (got %d)", dim);
+    case ShapeFault::Unit:
+      return fail(DEWI_ERR_UNSUPPORTED, "dim %d: the %s route takes dim %% %d == 0 up to %d columns", dim, route, unit, DEWI_I8_MAX_DIM);
+    default: return DEWI_OK;
+  }
+}
+int check_i8_shape(int64_t n_rows, int dim, int unit) { return check_codes_shape(n_rows, dim, unit, "int8"); }
+int check_b1_shape(int64_t n_rows, int dim) { return check_codes_shape(n_rows, dim, DEWI_B1_MIN_DIM, "binary"); }
+int check_i8_candidates(int n_candidates) {
+  if (n_candidates <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_candidates must be positive (got %d)", n_candidates);
+  if (n_candidates > DEWI_I8_MAX_CANDIDATES)
+    return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds the %d the int8 route takes", n_candidates, DEWI_I8_MAX_CANDIDATES);
+  return DEWI_OK;
+}
+bool records_shape_taken(int64_t n_rows, int dim, int unit, int n_queries, int n_candidates) {
+  return codes_shape_fault(n_rows, dim, unit) == ShapeFault::None && n_queries > 0 && n_candidates > 0 &&
+         n_candidates <= DEWI_I8_MAX_CANDIDATES;
+}
+
+// The argument block of the entry points that leave candidate records from a compact copy, in its one order.  A route says its
+// shape check (name, unit) and the words of its messages; d_scales and d_filter are checked where the route has them.
+struct RecordsRoute { const char* name; int unit; bool scales, filtered; const char* null_inputs; const char* copy; };
+constexpr RecordsRoute kI8Route{"int8", 16, true, false, "null codes, scales or query pointer", "the codes"};
+constexpr RecordsRoute kI8ListRoute{"int8", 16, true, true, "null codes, scales or query pointer", "the codes"};
+constexpr RecordsRoute kB1Route{"binary", DEWI_B1_MIN_DIM, false, false, "null bits or query pointer", "the bits"};
+int check_records_call(const RecordsRoute& R, const void* d_copy, const float* d_scales, int64_t n_rows, int dim, const float* d_Q,
+                       int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
+                       const dewi_candidate* d_out, const void* d_filter = nullptr) {
+  if (!d_copy || (R.scales && !d_scales) || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "%s", R.null_inputs);
+  if (int rc = check_codes_shape(n_rows, dim, R.unit, R.name)) return rc;
+  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
+  if (int rc = check_i8_candidates(n_candidates)) return rc;
+  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
+  if (R.filtered && !d_filter) return fail(DEWI_ERR_INVALID_ARG, "null filter pointer");
+  if (int rc = check_aligned16(d_copy, R.copy)) return rc;
+  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
+  return check_id_range(id_offset, n_rows);
+}
 
 struct DeviceInfo {
   bool ready = false;
@@ -261,6 +333,34 @@ int resolve_cut(int k, int64_t n, int n_override, int* c) {
   return DEWI_OK;
 }
 
+// The corpus passes of a row route that takes four queries per pass and the rest one by one, under one timing bracket:
+// launch(q, nq) enqueues the pass of the queries [q, q + nq) (passes of four start at multiples of 4: inside one query word)
+// and returns its status; `what` names a failed launch.
+template <class Launch>
+int for_passes_of_four(int n_queries, hipStream_t stream, const char* what, Launch launch) {
+  ScanTimer timer(stream);
+  for (int q = 0; q < n_queries;) {
+    const int nq = n_queries - q >= 4 ? 4 : 1;
+    const hipError_t e = launch(q, nq);
+    if (e != hipSuccess) return hip_fail(e, what);
+    q += nq;
+  }
+  return DEWI_OK;
+}
+
+// The select step of a route that leaves candidate RECORDS: n_candidates per query (id_offset added, padding behind c_local)
+// from the keys of a row scan planned for c_local = shard_cut(n_candidates, rows scanned).  Lists shorter than n_candidates
+// are not "n_candidates sorted keys each": the unsorted route, as batch_select.  `what` names the launch in the error message.
+int select_records(const dewi::ScanPlan& plan, const uint64_t* keys, int n_queries, int n_candidates, int c_local,
+                   const float* d_dewi32, const float* d_ent32, int64_t id_offset, dewi_candidate* d_out, hipStream_t stream,
+                   const char* what) {
+  const int sorted = (plan.slots == 1 && c_local == n_candidates) ? plan.n_lists : 0;
+  return launched(dewi::launch_select_rerank(keys, plan.keys_per_query, sorted, n_queries, n_candidates, 0, make_rerank(0.0, 0.0),
+                                             d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out, nullptr, dewi::SegmentLayout{},
+                                             stream),
+                  what);
+}
+
 // ---- one query batch = a SCAN step (steps 1-3 of ExactIndex.search for every query, into the workspace) and a
 // SELECT step (the exact top-c cut, then either the re-rank or the shard's candidate records).  Three scan paths,
 // chosen from the shapes alone so that dewi_knn_scan and dewi_knn_finish (two calls, two streams) agree:
@@ -301,7 +401,7 @@ bool plan_repair(BatchPlan& P, size_t path_total, int64_t n_rows, int dim, int c
 BatchPlan plan_batch(int elem_type, int64_t n_rows, int dim, int n_queries, int n_candidates, int space, int cus) {
   BatchPlan P{};
   const int elem_bytes = elem_type ? 2 : 4;
-  P.c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
+  P.c_local = shard_cut(n_candidates, n_rows);
   // the matrix-core paths select exactly n_candidates rows: a shard with fewer rows stays on the row kernels (padding)
   // space l2 on the matrix cores is scored 2<e,q> - ||e||^2 - ||q||^2: absolute error ~ulp(||e||^2 + ||q||^2), where the
   // reference's -sum((e - q)^2) (backends.py:434-436) has a small RELATIVE error of the distance — a near-duplicate of the
@@ -611,8 +711,7 @@ int dewi_knn_scan_kernel(int elem_type, int64_t n_rows, int dim, int n_queries, 
   DeviceInfo dev;
   int rc = ensure_device(dev);
   if (rc) return rc;
-  const BatchPlan P = plan_batch(elem_type, n_rows, dim, n_queries, n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows),
-                                 space, dev.cus);
+  const BatchPlan P = plan_batch(elem_type, n_rows, dim, n_queries, shard_cut(n_candidates, n_rows), space, dev.cus);
   const char* e = elem_type ? "bf16" : "f32";
   if (P.path == BatchPath::Depth) {
     snprintf(out, out_bytes, "mfma_scan_f32<%s", elem_type ? "true" : "false");
@@ -760,8 +859,8 @@ int dewi_knn_finish(void* d_workspace, size_t workspace_bytes, const void* d_E, 
     if (k <= 0) return DEWI_OK;
     if (k > n_candidates) return fail(DEWI_ERR_K_OUT_OF_BOUNDS, "kth(=%d) out of bounds (%d)", n_candidates - k, n_candidates);
     if (!d_out_ids || !d_out_scores) return fail(DEWI_ERR_INVALID_ARG, "null output pointer");
-  } else if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll) {
-    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32");
+  } else if (!ids_fit_int32(id_offset, n_rows)) {
+    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32");   // (check_id_range's rule; this entry's own, shorter text)
   }
   DeviceInfo dev;
   int rc = ensure_device(dev);
@@ -791,9 +890,8 @@ int dewi_knn_candidates(const void* d_E, int elem_type, int64_t n_rows, int dim,
   if (n_candidates <= 0) return DEWI_OK;
   if (n_candidates > (1 << 30)) return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds 2^30", n_candidates);
   if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
-  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
-    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
-                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
+  rc = check_id_range(id_offset, n_rows);
+  if (rc) return rc;
   DeviceInfo dev;
   rc = ensure_device(dev);
   if (rc) return rc;
@@ -849,8 +947,7 @@ size_t dewi_knn_filtered_workspace_bytes(int64_t n_allowed, int dim, int n_queri
   DeviceInfo dev;
   if (ensure_device(dev)) return 0;
   if (n_allowed <= 0 || dim <= 0 || n_queries <= 0 || n_candidates <= 0) return 0;
-  const int c = n_candidates < n_allowed ? n_candidates : static_cast<int>(n_allowed);
-  return layout_knn(n_allowed, dim, 4, n_queries, c, dev.cus).total;
+  return layout_knn(n_allowed, dim, 4, n_queries, shard_cut(n_candidates, n_allowed), dev.cus).total;
 }
 
 // the re-rank rule of the two filtered entry points: a similarity transform only together with a candidate count
@@ -880,6 +977,8 @@ static int scan_select_filtered(const Batch& B, const SelectOut& O, int64_t n_sc
   rc = run_scan(L, B, c, ws, d_filter, d_qwords, n_scan);
   if (rc) return rc;
   const uint64_t* keys = reinterpret_cast<const uint64_t*>(ws + L.keys_off);
+  if (O.d_out_cand)
+    return select_records(L.plan, keys, B.n_queries, n_out, c, O.d_dewi32, O.d_ent32, O.id_offset, O.d_out_cand, B.stream, what);
   hipError_t e;
   if (c > dewi::kMaxSortCandidates) {
     uint64_t* g1 = reinterpret_cast<uint64_t*>(ws + L.big_off);
@@ -887,11 +986,9 @@ static int scan_select_filtered(const Batch& B, const SelectOut& O, int64_t n_sc
                                          g1 + static_cast<size_t>(B.n_queries) * L.p2, O.d_out_ids, O.d_out_scores, nullptr, c,
                                          B.stream);
   } else {
-    // (records: n_out per query; lists shorter than that are not "n_out sorted keys each": the unsorted route, as batch_select)
-    const int n_select = O.d_out_cand ? n_out : c;
-    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, (L.plan.slots == 1 && n_select == c) ? L.plan.n_lists : 0,
-                                   B.n_queries, n_select, O.k, O.rp, O.d_dewi32, O.d_ent32, O.id_offset, O.d_out_ids, O.d_out_scores,
-                                   O.d_out_cand, nullptr, dewi::SegmentLayout{}, B.stream);
+    e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, L.plan.slots == 1 ? L.plan.n_lists : 0, B.n_queries, c, O.k, O.rp,
+                                   O.d_dewi32, O.d_ent32, O.id_offset, O.d_out_ids, O.d_out_scores, nullptr, nullptr,
+                                   dewi::SegmentLayout{}, B.stream);
   }
   return launched(e, what);
 }
@@ -906,8 +1003,8 @@ int dewi_knn_rerank_filtered(const void* d_E, int elem_type, int64_t n_rows, int
   rc = check_fp32_only(elem_type, "filtered search");
   if (rc) return rc;
   if (!d_filter) return fail(DEWI_ERR_INVALID_ARG, "null filter pointer");
-  if (n_allowed < 0 || n_allowed > n_rows)
-    return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+  rc = check_n_allowed(n_allowed, n_rows);
+  if (rc) return rc;
   rc = check_rerank_rule(sim_transform, n_candidates);
   if (rc) return rc;
   // the reference's rule on a score vector of length |A| (backends.py:439-441, 468): no candidates -> nothing; k > |A| -> error
@@ -934,21 +1031,19 @@ int dewi_knn_candidates_filtered(const void* d_E, int elem_type, int64_t n_rows,
   rc = check_fp32_only(elem_type, "filtered search");
   if (rc) return rc;
   if (!d_filter) return fail(DEWI_ERR_INVALID_ARG, "null filter pointer");
-  if (n_allowed < 0 || n_allowed > n_rows)
-    return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+  rc = check_n_allowed(n_allowed, n_rows);
+  if (rc) return rc;
   if (n_candidates <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_candidates must be positive (got %d)", n_candidates);
   if (n_candidates > dewi::kMaxSortCandidates)   // (the select of larger cuts writes final results only)
     return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds the %d filtered candidate records take", n_candidates,
                 dewi::kMaxSortCandidates);
   if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
-  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
-    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
-                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
+  rc = check_id_range(id_offset, n_rows);
+  if (rc) return rc;
   if (n_allowed == 0) return DEWI_OK;            // nothing launched, nothing written (dewi_knn_rerank_filtered's rule)
-  const int c_local = n_candidates < n_allowed ? n_candidates : static_cast<int>(n_allowed);
   const SelectOut O{0, make_rerank(0.0, 0.0), d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out};
-  return scan_select_filtered(B, O, n_allowed, c_local, static_cast<const uint32_t*>(d_filter), nullptr, d_workspace,
-                              workspace_bytes, "select launch (filtered records)", n_candidates);
+  return scan_select_filtered(B, O, n_allowed, shard_cut(n_candidates, n_allowed), static_cast<const uint32_t*>(d_filter), nullptr,
+                              d_workspace, workspace_bytes, "select launch (filtered records)", n_candidates);
 }
 
 // ---- search by examples (additive to ABI 6) ---------------------------------------------------------------------------
@@ -961,8 +1056,7 @@ struct ExamplesLayout {
 static bool examples_layout(int64_t n_scan, int dim, int n_candidates, ExamplesLayout* out) {
   if (n_scan <= 0 || n_scan > 0xFFFFFFFFll || n_candidates <= 0 || n_candidates > dewi::kMaxSortCandidates) return false;
   ExamplesLayout L;
-  const int c = n_candidates < n_scan ? n_candidates : static_cast<int>(n_scan);
-  L.plan = dewi::plan_scan_examples(n_scan, dim, c);
+  L.plan = dewi::plan_scan_examples(n_scan, dim, shard_cut(n_candidates, n_scan));
   if (L.plan.kind != dewi::kScanAnyLong) return false;
   L.keys_off = 0;
   L.part_p_off = align_up(static_cast<size_t>(L.plan.keys_per_query) * 8, 256);
@@ -1006,18 +1100,16 @@ int dewi_knn_candidates_examples(const float* d_E, int64_t n_rows, int dim, cons
   if (n_exclude < 0 || n_exclude > dewi::kExamplesMax)
     return fail(DEWI_ERR_INVALID_ARG, "n_exclude %d outside [0, %d]", n_exclude, dewi::kExamplesMax);
   if (n_exclude > 0 && !d_exclude) return fail(DEWI_ERR_INVALID_ARG, "null exclude pointer");
-  if (d_filter && (n_allowed < 0 || n_allowed > n_rows))
-    return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+  if (d_filter)
+    if (int rc = check_n_allowed(n_allowed, n_rows)) return rc;
   if (n_candidates <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_candidates must be positive (got %d)", n_candidates);
   if (n_candidates > dewi::kMaxSortCandidates)
     return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds the %d candidate records take", n_candidates, dewi::kMaxSortCandidates);
   if (dim % 4 != 0 || dim <= 128 || dim > 4096)
     return fail(DEWI_ERR_UNSUPPORTED, "search by examples serves rows of 33 to 1024 whole 16-byte units (dim %% 4 == 0, 132 <= dim <= 4096; got %d)", dim);
   if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
-  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
-    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
-                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
-  if (d_filter && n_allowed == 0) return DEWI_OK;   // nothing launched, nothing written (dewi_knn_candidates_filtered's rule)
+  if (int rc = check_id_range(id_offset, n_rows)) return rc;
+  if (d_filter && n_allowed == 0) return DEWI_OK;  // nothing launched, nothing written (dewi_knn_candidates_filtered's rule)
   const int64_t n_scan = d_filter ? n_allowed : n_rows;
   ExamplesLayout L;
   if (!examples_layout(n_scan, dim, n_candidates, &L)) return fail(DEWI_ERR_UNSUPPORTED, "shape outside the search by examples");
@@ -1027,7 +1119,7 @@ int dewi_knn_candidates_examples(const float* d_E, int64_t n_rows, int dim, cons
   uint64_t* keys = reinterpret_cast<uint64_t*>(ws + L.keys_off);
   float* part_p = reinterpret_cast<float*>(ws + L.part_p_off);
   float* part_n = reinterpret_cast<float*>(ws + L.part_n_off);
-  const int c = n_candidates < n_scan ? n_candidates : static_cast<int>(n_scan);
+  const int c = shard_cut(n_candidates, n_scan);
   const int n_examples = n_positive + n_negative;
   int per_pass = L.plan.nq_max;
   if (g_examples_per_pass > 0 && g_examples_per_pass < per_pass) per_pass = g_examples_per_pass;
@@ -1056,12 +1148,7 @@ int dewi_knn_candidates_examples(const float* d_E, int64_t n_rows, int dim, cons
       if (e != hipSuccess) return hip_fail(e, "scan launch (examples)");
     }
   }
-  // (records: n_candidates per query; lists shorter than that are not "n_candidates sorted keys each": the unsorted route, as
-  // scan_select_filtered)
-  const hipError_t e = dewi::launch_select_rerank(keys, L.plan.keys_per_query, (L.plan.slots == 1 && n_candidates == c) ? L.plan.n_lists : 0,
-                                                  1, n_candidates, 0, make_rerank(0.0, 0.0), d_dewi32, d_ent32, id_offset, nullptr,
-                                                  nullptr, d_out, nullptr, dewi::SegmentLayout{}, stream);
-  return launched(e, "select launch (example records)");
+  return select_records(L.plan, keys, 1, n_candidates, c, d_dewi32, d_ent32, id_offset, d_out, stream, "select launch (example records)");
 }
 
 // ---- per-query filters (additive to ABI 6) ----------------------------------------------------------------------------
@@ -1165,6 +1252,22 @@ static bool ivf_shape_ok(int64_t n_rows, int dim, int elem_type) {
   return n_rows > 0 && n_rows <= 0xFFFFFFFFll && dim > 0 && (elem_type == 0 || elem_type == 1);
 }
 
+// what the IVF entry points check after their pointers, in one order: fp32, the shape, the cells
+static int check_ivf_corpus(int elem_type, int64_t n_rows, int dim, int n_cells) {
+  if (int rc = check_fp32_only(elem_type, "IVF")) return rc;
+  if (int rc = check_rows_dim(n_rows, dim)) return rc;
+  if (n_cells <= 0 || n_cells > dewi::kIvfMaxCells || n_cells > n_rows)
+    return fail(DEWI_ERR_INVALID_ARG, "n_cells %d outside [1, min(%d, n_rows)]", n_cells, dewi::kIvfMaxCells);
+  return DEWI_OK;
+}
+// ... and the two probe preparations behind it: the batch, nprobe, the group
+static int check_ivf_probe(int n_cells, int n_queries, int nprobe, int group) {
+  if (n_queries <= 0 || n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
+  if (nprobe <= 0 || nprobe > n_cells) return fail(DEWI_ERR_INVALID_ARG, "nprobe %d outside [1, n_cells = %d]", nprobe, n_cells);
+  if (group <= 0 || group > 32) return fail(DEWI_ERR_INVALID_ARG, "group %d outside [1, 32]", group);
+  return DEWI_OK;
+}
+
 int dewi_ivf_buckets(int dim, int elem_type) {
   if (dim <= 0 || (elem_type != 0 && elem_type != 1)) return 0;
   return filter_buckets(dim, elem_type);
@@ -1179,10 +1282,7 @@ int dewi_ivf_lists_build(int elem_type, int64_t n_rows, int dim, int n_cells, co
                          size_t lists_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!d_assign || !d_lists) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  if (int rc = check_fp32_only(elem_type, "IVF")) return rc;
-  if (int rc = check_rows_dim(n_rows, dim)) return rc;
-  if (n_cells <= 0 || n_cells > dewi::kIvfMaxCells || n_cells > n_rows)
-    return fail(DEWI_ERR_INVALID_ARG, "n_cells %d outside [1, min(%d, n_rows)]", n_cells, dewi::kIvfMaxCells);
+  if (int rc = check_ivf_corpus(elem_type, n_rows, dim, n_cells)) return rc;
   const size_t need = dewi_ivf_lists_bytes(n_rows, dim, elem_type, n_cells);
   if (lists_bytes < need) return fail(DEWI_ERR_WORKSPACE, "cell-list buffer %zu B < required %zu B", lists_bytes, need);
   return launched(dewi::launch_ivf_lists_build(d_assign, n_rows, n_cells, filter_buckets(dim, elem_type), static_cast<uint32_t*>(d_lists),
@@ -1225,13 +1325,8 @@ int dewi_ivf_probe_prepare(int elem_type, int64_t n_rows, int dim, const void* d
                            int64_t* out_n_allowed, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!d_lists || !d_probe_ids || !d_out || !out_n_union || !out_n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  if (int rc = check_fp32_only(elem_type, "IVF")) return rc;
-  if (int rc = check_rows_dim(n_rows, dim)) return rc;
-  if (n_cells <= 0 || n_cells > dewi::kIvfMaxCells || n_cells > n_rows)
-    return fail(DEWI_ERR_INVALID_ARG, "n_cells %d outside [1, min(%d, n_rows)]", n_cells, dewi::kIvfMaxCells);
-  if (n_queries <= 0 || n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
-  if (nprobe <= 0 || nprobe > n_cells) return fail(DEWI_ERR_INVALID_ARG, "nprobe %d outside [1, n_cells = %d]", nprobe, n_cells);
-  if (group <= 0 || group > 32) return fail(DEWI_ERR_INVALID_ARG, "group %d outside [1, 32]", group);
+  if (int rc = check_ivf_corpus(elem_type, n_rows, dim, n_cells)) return rc;
+  if (int rc = check_ivf_probe(n_cells, n_queries, nprobe, group)) return rc;
   const size_t need = dewi_ivf_probe_bytes(n_rows, dim, elem_type, n_queries, group);
   if (out_bytes < need) return fail(DEWI_ERR_WORKSPACE, "probe buffer %zu B < required %zu B", out_bytes, need);
   const int g = filter_buckets(dim, elem_type);
@@ -1279,13 +1374,8 @@ int dewi_ivf_probe_prepare_filtered(int elem_type, int64_t n_rows, int dim, cons
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!d_lists || !d_probe_ids || !d_allow || !d_out || !out_n_union || !out_n_allowed)
     return fail(DEWI_ERR_INVALID_ARG, "null pointer");
-  if (int rc = check_fp32_only(elem_type, "IVF")) return rc;
-  if (int rc = check_rows_dim(n_rows, dim)) return rc;
-  if (n_cells <= 0 || n_cells > dewi::kIvfMaxCells || n_cells > n_rows)
-    return fail(DEWI_ERR_INVALID_ARG, "n_cells %d outside [1, min(%d, n_rows)]", n_cells, dewi::kIvfMaxCells);
-  if (n_queries <= 0 || n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);
-  if (nprobe <= 0 || nprobe > n_cells) return fail(DEWI_ERR_INVALID_ARG, "nprobe %d outside [1, n_cells = %d]", nprobe, n_cells);
-  if (group <= 0 || group > 32) return fail(DEWI_ERR_INVALID_ARG, "group %d outside [1, 32]", group);
+  if (int rc = check_ivf_corpus(elem_type, n_rows, dim, n_cells)) return rc;
+  if (int rc = check_ivf_probe(n_cells, n_queries, nprobe, group)) return rc;
   if (allow_per_query != 0 && allow_per_query != 1)
     return fail(DEWI_ERR_INVALID_ARG, "allow_per_query %d is neither 0 nor 1", allow_per_query);
   const size_t need = dewi_ivf_probe_filtered_bytes(n_rows, dim, elem_type, n_queries, group);
@@ -1344,8 +1434,7 @@ int dewi_knn_range_count(const void* d_E, int elem_type, int64_t n_rows, int dim
     return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, %d]: split the batch", n_queries, DEWI_RANGE_MAX_QUERIES);
   if (!d_thresholds || !d_counts) return fail(DEWI_ERR_INVALID_ARG, "null threshold or count pointer");
   if (d_filter && (rc = check_fp32_only(elem_type, "filtered search"))) return rc;
-  if (d_filter && (n_allowed < 0 || n_allowed > n_rows))
-    return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+  if (d_filter && (rc = check_n_allowed(n_allowed, n_rows))) return rc;
   const int64_t n_scan = d_filter ? n_allowed : n_rows;
   if (n_scan == 0) {   // an empty allow-list: every query's answer is empty
     const hipError_t e = hipMemsetAsync(d_counts, 0, sizeof(int64_t) * static_cast<size_t>(n_queries), stream);
@@ -1828,26 +1917,6 @@ int dewi_select_run_blocked_grouped(const void* d_E, int elem_type, int64_t n_ro
 }
 
 // ---- approximate search over an int8 copy of the corpus (additive to ABI 6; knn_scan_i8.hip) ---------------------------------
-// the shape checks the int8 entry points share, in one order: rows, 2^32, dim, the unit (16 codes; the re-scoring: 4 floats)
-static int check_i8_shape(int64_t n_rows, int dim, int unit) {
-  if (n_rows <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_rows must be positive (got %lld)", static_cast<long long>(n_rows));
-  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
-  if (dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "dim must be positive (got %d)", dim);
-  if (dim % unit != 0 || dim > DEWI_I8_MAX_DIM)
-    return fail(DEWI_ERR_UNSUPPORTED, "dim %d: the int8 route takes dim %% %d == 0 up to %d columns", dim, unit, DEWI_I8_MAX_DIM);
-  return DEWI_OK;
-}
-static int check_i8_candidates(int n_candidates) {
-  if (n_candidates <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_candidates must be positive (got %d)", n_candidates);
-  if (n_candidates > DEWI_I8_MAX_CANDIDATES)
-    return fail(DEWI_ERR_UNSUPPORTED, "n_candidates %d exceeds the %d the int8 route takes", n_candidates, DEWI_I8_MAX_CANDIDATES);
-  return DEWI_OK;
-}
-static int check_aligned16(const void* p, const char* what) {
-  if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return fail(DEWI_ERR_INVALID_ARG, "%s must be 16-byte aligned", what);
-  return DEWI_OK;
-}
-
 int dewi_quantize_rows_i8(const float* d_E, int64_t n_rows, int dim, int8_t* d_codes, float* d_scales, void* stream) {
   if (n_rows == 0 && dim > 0) return DEWI_OK;
   if (int rc = check_i8_shape(n_rows, dim, 16)) return rc;
@@ -1877,64 +1946,29 @@ static size_t i8_workspace(const dewi::ScanPlan& plan, int n_queries) {
 }
 
 size_t dewi_knn_i8_workspace_bytes(int64_t n_rows, int dim, int n_queries, int n_candidates) {
-  if (n_rows <= 0 || n_rows > 0xFFFFFFFFll || dim <= 0 || dim % 16 != 0 || dim > DEWI_I8_MAX_DIM || n_queries <= 0 ||
-      n_candidates <= 0 || n_candidates > DEWI_I8_MAX_CANDIDATES)
-    return 0;
-  const int c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
-  return i8_workspace(dewi::plan_scan_i8(n_rows, dim, c_local), n_queries);
+  if (!records_shape_taken(n_rows, dim, 16, n_queries, n_candidates)) return 0;
+  return i8_workspace(dewi::plan_scan_i8(n_rows, dim, shard_cut(n_candidates, n_rows)), n_queries);
 }
 
 int dewi_knn_candidates_i8(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const float* d_Q,
                            int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
                            dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, void* stream_) {
-  if (!d_codes || !d_scales || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "null codes, scales or query pointer");
-  if (int rc = check_i8_shape(n_rows, dim, 16)) return rc;
-  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
-  if (int rc = check_i8_candidates(n_candidates)) return rc;
-  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
-  if (int rc = check_aligned16(d_codes, "the codes")) return rc;
-  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
-  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
-    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
-                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
-  // a shard with fewer rows than n_candidates selects every row and pads the tail (id = -1, sim = -inf), as dewi_knn_candidates
-  const int c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
+  if (int rc = check_records_call(kI8Route, d_codes, d_scales, n_rows, dim, d_Q, n_queries, d_dewi32, d_ent32, n_candidates,
+                                  id_offset, d_out))
+    return rc;
+  const int c_local = shard_cut(n_candidates, n_rows);
   const dewi::ScanPlan plan = dewi::plan_scan_i8(n_rows, dim, c_local);
   if (int rc = check_workspace(d_workspace, workspace_bytes, i8_workspace(plan, n_queries))) return rc;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   uint64_t* keys = static_cast<uint64_t*>(d_workspace);
-  {
-    ScanTimer timer(stream);
-    for (int q = 0; q < n_queries;) {           // four queries per corpus pass, then one by one
-      const int nq = n_queries - q >= 4 ? 4 : 1;
-      const hipError_t e = dewi::launch_scan_i8(plan, d_codes, d_scales, n_rows, dim, d_Q, q, nq, c_local, keys, stream);
-      if (e != hipSuccess) return hip_fail(e, "int8 scan launch");
-      q += nq;
-    }
-  }
-  const int sorted = (plan.slots == 1 && c_local == n_candidates) ? plan.n_lists : 0;
-  return launched(dewi::launch_select_rerank(keys, plan.keys_per_query, sorted, n_queries, n_candidates, 0, make_rerank(0.0, 0.0),
-                                             d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out, nullptr, dewi::SegmentLayout{},
-                                             stream),
-                  "select launch");
+  if (int rc = for_passes_of_four(n_queries, stream, "int8 scan launch", [&](int q, int nq) {
+        return dewi::launch_scan_i8(plan, d_codes, d_scales, n_rows, dim, d_Q, q, nq, c_local, keys, stream);
+      }))
+    return rc;
+  return select_records(plan, keys, n_queries, n_candidates, c_local, d_dewi32, d_ent32, id_offset, d_out, stream, "select launch");
 }
 
 // ---- approximate search over a 1-bit copy of the corpus (additive to ABI 6; knn_scan_b1.hip) -------------------
-// the shape checks the binary entry points share, in check_i8_shape's order: rows, 2^32, dim, whole 128-bit units
-static int check_b1_shape(int64_t n_rows, int dim) {
-  if (n_rows <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_rows must be positive (got %lld)", static_cast<long long>(n_rows));
-  if (n_rows > 0xFFFFFFFFll) return fail(DEWI_ERR_UNSUPPORTED, "n_rows %lld exceeds 2^32-1 rows per device", static_cast<long long>(n_rows));
-  if (dim <= 0) return fail(DEWI_ERR_INVALID_ARG, "dim must be positive (got %d)", dim);
-  if (dim % DEWI_B1_MIN_DIM != 0 || dim > DEWI_I8_MAX_DIM)
-    return fail(DEWI_ERR_UNSUPPORTED, "dim %d: the binary route takes dim %% %d == 0 up to %d columns", dim, DEWI_B1_MIN_DIM,
-                DEWI_I8_MAX_DIM);
-  return DEWI_OK;
-}
-static bool b1_shape_taken(int64_t n_rows, int dim, int n_queries, int n_candidates) {
-  return n_rows > 0 && n_rows <= 0xFFFFFFFFll && dim > 0 && dim % DEWI_B1_MIN_DIM == 0 && dim <= DEWI_I8_MAX_DIM && n_queries > 0 &&
-         n_candidates > 0 && n_candidates <= DEWI_I8_MAX_CANDIDATES;
-}
-
 static thread_local int g_b1_max_blocks = 0;   // dewi_b1_tuning_set: 0 = the plan's choice
 
 int dewi_b1_tuning_set(int max_blocks) {
@@ -1962,18 +1996,16 @@ int dewi_prepare_queries_b1(const float* d_Q, int n_queries, int dim, uint32_t* 
 }
 
 size_t dewi_knn_b1_workspace_bytes(int64_t n_rows, int dim, int n_queries, int n_candidates) {
-  if (!b1_shape_taken(n_rows, dim, n_queries, n_candidates)) return 0;
-  const int c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
-  return i8_workspace(dewi::plan_scan_b1(n_rows, dim, c_local, g_b1_max_blocks), n_queries);
+  if (!records_shape_taken(n_rows, dim, DEWI_B1_MIN_DIM, n_queries, n_candidates)) return 0;
+  return i8_workspace(dewi::plan_scan_b1(n_rows, dim, shard_cut(n_candidates, n_rows), g_b1_max_blocks), n_queries);
 }
 
 int dewi_knn_b1_plan(int64_t n_rows, int dim, int n_candidates, int64_t* out_words) {
   if (!out_words) return fail(DEWI_ERR_INVALID_ARG, "null out_words");
-  if (!b1_shape_taken(n_rows, dim, 1, n_candidates))
+  if (!records_shape_taken(n_rows, dim, DEWI_B1_MIN_DIM, 1, n_candidates))
     return fail(DEWI_ERR_UNSUPPORTED, "the binary route does not take %lld rows x %d columns, %d candidates",
                 static_cast<long long>(n_rows), dim, n_candidates);
-  const int c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
-  const dewi::ScanPlan p = dewi::plan_scan_b1(n_rows, dim, c_local, g_b1_max_blocks);
+  const dewi::ScanPlan p = dewi::plan_scan_b1(n_rows, dim, shard_cut(n_candidates, n_rows), g_b1_max_blocks);
   const int64_t words[DEWI_B1_PLAN_WORDS] = {p.blocks, p.rows_per_iter, p.log2p, p.slots, p.n_lists, p.keys_per_query};
   for (int i = 0; i < DEWI_B1_PLAN_WORDS; ++i) out_words[i] = words[i];
   return DEWI_OK;
@@ -1982,36 +2014,19 @@ int dewi_knn_b1_plan(int64_t n_rows, int dim, int n_candidates, int64_t* out_wor
 int dewi_knn_candidates_b1(const uint32_t* d_bits, int64_t n_rows, int dim, const float* d_Q, int n_queries, const float* d_dewi32,
                            const float* d_ent32, int n_candidates, int64_t id_offset, dewi_candidate* d_out, void* d_workspace,
                            size_t workspace_bytes, void* stream_) {
-  // the checks of dewi_knn_candidates_i8, in its order
-  if (!d_bits || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "null bits or query pointer");
-  if (int rc = check_b1_shape(n_rows, dim)) return rc;
-  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
-  if (int rc = check_i8_candidates(n_candidates)) return rc;
-  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
-  if (int rc = check_aligned16(d_bits, "the bits")) return rc;
-  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
-  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
-    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
-                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
-  const int c_local = n_candidates < n_rows ? n_candidates : static_cast<int>(n_rows);
+  if (int rc = check_records_call(kB1Route, d_bits, nullptr, n_rows, dim, d_Q, n_queries, d_dewi32, d_ent32, n_candidates,
+                                  id_offset, d_out))
+    return rc;
+  const int c_local = shard_cut(n_candidates, n_rows);
   const dewi::ScanPlan plan = dewi::plan_scan_b1(n_rows, dim, c_local, g_b1_max_blocks);
   if (int rc = check_workspace(d_workspace, workspace_bytes, i8_workspace(plan, n_queries))) return rc;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   uint64_t* keys = static_cast<uint64_t*>(d_workspace);
-  {
-    ScanTimer timer(stream);
-    for (int q = 0; q < n_queries;) {           // four queries per corpus pass, then one by one
-      const int nq = n_queries - q >= 4 ? 4 : 1;
-      const hipError_t e = dewi::launch_scan_b1(plan, d_bits, n_rows, dim, d_Q, q, nq, c_local, keys, stream);
-      if (e != hipSuccess) return hip_fail(e, "binary scan launch");
-      q += nq;
-    }
-  }
-  const int sorted = (plan.slots == 1 && c_local == n_candidates) ? plan.n_lists : 0;
-  return launched(dewi::launch_select_rerank(keys, plan.keys_per_query, sorted, n_queries, n_candidates, 0, make_rerank(0.0, 0.0),
-                                             d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out, nullptr, dewi::SegmentLayout{},
-                                             stream),
-                  "select launch");
+  if (int rc = for_passes_of_four(n_queries, stream, "binary scan launch", [&](int q, int nq) {
+        return dewi::launch_scan_b1(plan, d_bits, n_rows, dim, d_Q, q, nq, c_local, keys, stream);
+      }))
+    return rc;
+  return select_records(plan, keys, n_queries, n_candidates, c_local, d_dewi32, d_ent32, id_offset, d_out, stream, "select launch");
 }
 
 // ---- query batches on the int8 codes: 32 queries per matrix-core pass (additive to ABI 6; knn_mfma_i8.hip) ------
@@ -2046,18 +2061,10 @@ int dewi_knn_i8_batch_plan(int64_t n_rows, int dim, int n_queries, int n_candida
 int dewi_knn_candidates_i8_batch(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const float* d_Q,
                                  int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
                                  dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, void* stream_) {
-  // the checks of dewi_knn_candidates_i8, in its order; then what the pass itself does not take
-  if (!d_codes || !d_scales || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "null codes, scales or query pointer");
-  if (int rc = check_i8_shape(n_rows, dim, 16)) return rc;
-  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
-  if (int rc = check_i8_candidates(n_candidates)) return rc;
-  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
-  if (int rc = check_aligned16(d_codes, "the codes")) return rc;
-  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
-  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
-    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
-                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
-  dewi::MfmaI8Layout m;
+  if (int rc = check_records_call(kI8Route, d_codes, d_scales, n_rows, dim, d_Q, n_queries, d_dewi32, d_ent32, n_candidates,
+                                  id_offset, d_out))
+    return rc;
+  dewi::MfmaI8Layout m;   // then what the pass itself does not take
   if (!i8_batch_layout(n_rows, dim, n_queries, n_candidates, &m))
     return fail(DEWI_ERR_UNSUPPORTED, "the int8 batch pass does not take %lld rows x %d columns, %d queries, %d candidates "
                 "(dewi_knn_i8_batch_workspace_bytes is 0: use dewi_knn_candidates_i8)",
@@ -2096,72 +2103,40 @@ int dewi_knn_candidates_i8_batch(const int8_t* d_codes, const float* d_scales, i
 // ---- the int8 scan over the rows of a prepared filter / of per-query lists (additive to ABI 6) -----------------
 size_t dewi_knn_i8_filtered_workspace_bytes(int64_t n_scan, int dim, int n_queries, int n_candidates) {
   // today what the unfiltered call needs on n_scan rows (keys of every query: lists, or one dense key per list position)
-  if (n_scan <= 0 || n_scan > 0xFFFFFFFFll || dim <= 0 || dim % 16 != 0 || dim > DEWI_I8_MAX_DIM || n_queries <= 0 ||
-      n_candidates <= 0 || n_candidates > DEWI_I8_MAX_CANDIDATES)
-    return 0;
-  const int c_local = n_candidates < n_scan ? n_candidates : static_cast<int>(n_scan);
-  return i8_workspace(dewi::plan_scan_i8(n_scan, dim, c_local), n_queries);
+  return dewi_knn_i8_workspace_bytes(n_scan, dim, n_queries, n_candidates);
 }
 
-// the argument checks the two filtered int8 entry points share, in the order of dewi_knn_candidates_i8 (the filter pointer
-// after the payload pointers)
-static int check_i8_filtered(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const void* d_filter,
-                             const float* d_Q, int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates,
-                             int64_t id_offset, const dewi_candidate* d_out) {
-  if (!d_codes || !d_scales || !d_Q) return fail(DEWI_ERR_INVALID_ARG, "null codes, scales or query pointer");
-  if (int rc = check_i8_shape(n_rows, dim, 16)) return rc;
-  if (n_queries <= 0) return fail(DEWI_ERR_INVALID_ARG, "n_queries must be positive (got %d)", n_queries);
-  if (int rc = check_i8_candidates(n_candidates)) return rc;
-  if (!d_dewi32 || !d_ent32 || !d_out) return fail(DEWI_ERR_INVALID_ARG, "null payload or output pointer");
-  if (!d_filter) return fail(DEWI_ERR_INVALID_ARG, "null filter pointer");
-  if (int rc = check_aligned16(d_codes, "the codes")) return rc;
-  if (int rc = check_aligned16(d_Q, "the queries")) return rc;
-  if (id_offset < 0 || id_offset + n_rows > 0x7FFFFFFFll)
-    return fail(DEWI_ERR_UNSUPPORTED, "global row ids must fit int32 (offset %lld + %lld rows)",
-                static_cast<long long>(id_offset), static_cast<long long>(n_rows));
-  return DEWI_OK;
-}
-
-// Both entry points from the device on: the LIST (d_qwords: QMASK) kernels planned on the n_scan listed rows, four queries
-// per pass and then one by one, then the select of dewi_knn_candidates_i8 over the keys they left.
+// Both entry points from the device on: the LIST (d_qwords: QMASK) kernels planned on the n_scan listed rows, then the
+// select of dewi_knn_candidates_i8 over the keys they left.
 static int scan_select_i8_filtered(const int8_t* d_codes, const float* d_scales, int dim, const uint32_t* d_filter,
                                    const uint32_t* d_qwords, int64_t n_scan, const float* d_Q, int n_queries,
                                    const float* d_dewi32, const float* d_ent32, int n_candidates, int64_t id_offset,
                                    dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes, hipStream_t stream) {
-  const int c_local = n_candidates < n_scan ? n_candidates : static_cast<int>(n_scan);
+  const int c_local = shard_cut(n_candidates, n_scan);
   const dewi::ScanPlan plan = dewi::plan_scan_i8(n_scan, dim, c_local);
   if (int rc = check_workspace(d_workspace, workspace_bytes, i8_workspace(plan, n_queries))) return rc;
   uint64_t* keys = static_cast<uint64_t*>(d_workspace);
-  {
-    ScanTimer timer(stream);
-    for (int q = 0; q < n_queries;) {           // passes of four start at multiples of 4: inside one query word
-      const int nq = n_queries - q >= 4 ? 4 : 1;
-      dewi::QWords qw;
-      if (d_qwords) {
-        qw.words = d_qwords + static_cast<int64_t>(q / 32) * n_scan;
-        qw.shift = q % 32;
-      }
-      const hipError_t e = dewi::launch_scan_i8_list(plan, d_codes, d_scales, dim, d_Q, q, nq, c_local, keys, d_filter, stream, qw);
-      if (e != hipSuccess) return hip_fail(e, "int8 filtered scan launch");
-      q += nq;
-    }
-  }
-  const int sorted = (plan.slots == 1 && c_local == n_candidates) ? plan.n_lists : 0;
-  return launched(dewi::launch_select_rerank(keys, plan.keys_per_query, sorted, n_queries, n_candidates, 0, make_rerank(0.0, 0.0),
-                                             d_dewi32, d_ent32, id_offset, nullptr, nullptr, d_out, nullptr, dewi::SegmentLayout{},
-                                             stream),
-                  "select launch (int8 filtered)");
+  if (int rc = for_passes_of_four(n_queries, stream, "int8 filtered scan launch", [&](int q, int nq) {
+        dewi::QWords qw;
+        if (d_qwords) {
+          qw.words = d_qwords + static_cast<int64_t>(q / 32) * n_scan;
+          qw.shift = q % 32;
+        }
+        return dewi::launch_scan_i8_list(plan, d_codes, d_scales, dim, d_Q, q, nq, c_local, keys, d_filter, stream, qw);
+      }))
+    return rc;
+  return select_records(plan, keys, n_queries, n_candidates, c_local, d_dewi32, d_ent32, id_offset, d_out, stream,
+                        "select launch (int8 filtered)");
 }
 
 int dewi_knn_candidates_i8_filtered(const int8_t* d_codes, const float* d_scales, int64_t n_rows, int dim, const void* d_filter,
                                     int64_t n_allowed, const float* d_Q, int n_queries, const float* d_dewi32,
                                     const float* d_ent32, int n_candidates, int64_t id_offset, dewi_candidate* d_out,
                                     void* d_workspace, size_t workspace_bytes, void* stream_) {
-  if (int rc = check_i8_filtered(d_codes, d_scales, n_rows, dim, d_filter, d_Q, n_queries, d_dewi32, d_ent32, n_candidates,
-                                 id_offset, d_out))
+  if (int rc = check_records_call(kI8ListRoute, d_codes, d_scales, n_rows, dim, d_Q, n_queries, d_dewi32, d_ent32,
+                                  n_candidates, id_offset, d_out, d_filter))
     return rc;
-  if (n_allowed < 0 || n_allowed > n_rows)
-    return fail(DEWI_ERR_INVALID_ARG, "n_allowed %lld outside [0, %lld]", static_cast<long long>(n_allowed), static_cast<long long>(n_rows));
+  if (int rc = check_n_allowed(n_allowed, n_rows)) return rc;
   if (n_allowed == 0) return DEWI_OK;           // nothing launched, nothing written (dewi_knn_rerank_filtered's rule)
   return scan_select_i8_filtered(d_codes, d_scales, dim, static_cast<const uint32_t*>(d_filter), nullptr, n_allowed, d_Q, n_queries,
                                  d_dewi32, d_ent32, n_candidates, id_offset, d_out, d_workspace, workspace_bytes,
@@ -2173,8 +2148,8 @@ int dewi_knn_candidates_i8_query_filtered(const int8_t* d_codes, const float* d_
                                           int n_queries, const float* d_dewi32, const float* d_ent32, int n_candidates,
                                           int64_t id_offset, dewi_candidate* d_out, void* d_workspace, size_t workspace_bytes,
                                           void* stream_) {
-  if (int rc = check_i8_filtered(d_codes, d_scales, n_rows, dim, d_filter, d_Q, n_queries, d_dewi32, d_ent32, n_candidates,
-                                 id_offset, d_out))
+  if (int rc = check_records_call(kI8ListRoute, d_codes, d_scales, n_rows, dim, d_Q, n_queries, d_dewi32, d_ent32,
+                                  n_candidates, id_offset, d_out, d_filter))
     return rc;
   if (!n_allowed) return fail(DEWI_ERR_INVALID_ARG, "null count pointer");
   if (n_queries > 65535) return fail(DEWI_ERR_INVALID_ARG, "n_queries %d outside [1, 65535]", n_queries);

@@ -646,8 +646,7 @@ class DeviceCorpus:
             if batch_pass and not use_pass:
                 raise ValueError(f"batch_pass=True: the int8 batch pass does not take {n} rows x {self.dim} columns, "
                                  f"{b} queries, {c} candidates")
-        if out is None:
-            out = _torch().empty((b, c, 4), dtype=_torch().int32, device=self.device)
+        out = self._records_out(b, c, out)
         if use_pass:
             ws = self._cached_workspace(("i8batch", b, c), self._lib.dewi_knn_i8_batch_workspace_bytes, n, self.dim, b, c)
             entry = self._lib.dewi_knn_candidates_i8_batch
@@ -656,8 +655,44 @@ class DeviceCorpus:
             entry = self._lib.dewi_knn_candidates_i8
         nat.check(entry(
             nat.ptr(codes), nat.ptr(scales), n, self.dim, nat.ptr(q_dev), b, nat.ptr(self.dewi32), nat.ptr(self.ent32), c,
-            self.id_offset if id_offset is None else int(id_offset), nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+            self._record_id_offset(id_offset), nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
         return out
+
+    # ---- what every ``candidates_*_device`` and every search over candidate records shares
+    def _records_out(self, b: int, c: int, out, padded: bool = False):
+        """The int32 view [b, c, 4] a ``candidates_*_device`` writes into: the caller's ``out`` or a fresh tensor.  ``padded``
+        (the call is going to write nothing): filled with the padding record (sim -inf, dewi 0, ent 0, id -1)."""
+        torch = _torch()
+        if out is None:
+            out = torch.empty((b, c, 4), dtype=torch.int32, device=self.device)
+        if padded:
+            out.copy_(torch.tensor([-0x800000, 0, 0, -1], dtype=torch.int32, device=self.device).expand(b, c, 4))
+        return out
+
+    def _record_id_offset(self, id_offset: Optional[int]) -> int:
+        return self.id_offset if id_offset is None else int(id_offset)
+
+    def _rerank_records(self, q_dev, recs, rescore: bool, k: int, eta: float, entropy_pref: float, out_ids, out_scores):
+        """The tail of a search over candidate records with LOCAL ids ([B, c, 4] int32 view): re-scored from the fp32 rows
+        where ``rescore`` says so, then blended and cut to k (``dewi_merge_rerank``) -> (ids, scores) [B, k]."""
+        b, c = int(recs.shape[0]), int(recs.shape[1])
+        if rescore:
+            self.rescore_candidates_device(q_dev, recs, id_offset=0)
+        return merge_rerank_device(recs.view(1, b, c, 4), c, k, eta, entropy_pref, out_ids, out_scores)
+
+    def _blocking(self, search_device, queries: ArrayLike, *args, ids: str = "offset") -> Tuple[np.ndarray, np.ndarray]:
+        """The blocking twin of a ``*_device`` search: the queries staged and ``search_device(q, *args)`` run under the
+        per-corpus lock, (ids int64, scores fp32) brought to the host.  ``ids``: how they become global — ``"offset"`` adds
+        ``id_offset``, ``"offset_valid"`` adds it where the id is not the padding's (-1 stays -1), ``"global"`` leaves them
+        (the candidate records already carried global ids)."""
+        with self._lock, _torch().cuda.device(self.device):
+            ids_d, sc_d = search_device(self.stage_queries(queries), *args)
+            ids_h, scores_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
+        if self.id_offset and ids == "offset":
+            ids_h = ids_h + self.id_offset
+        elif self.id_offset and ids == "offset_valid":
+            ids_h = np.where(ids_h >= 0, ids_h + self.id_offset, ids_h)
+        return ids_h, scores_h
 
     def rescore_candidates_device(self, q_dev, recs, id_offset: Optional[int] = None):
         """In place: the similarity of every record of ``recs`` ([B, c, 4] int32 view) becomes the fp32 inner product of its
@@ -666,7 +701,7 @@ class DeviceCorpus:
             raise NotImplementedError("candidates are re-scored from fp32 rows (this corpus is bf16)")
         nat.check(self._lib.dewi_rescore_candidates_f32(
             nat.ptr(self.emb), self.n_rows, self.dim, nat.ptr(q_dev), int(recs.shape[0]), nat.ptr(recs), int(recs.shape[1]),
-            self.id_offset if id_offset is None else int(id_offset), nat.stream_ptr()))
+            self._record_id_offset(id_offset), nat.stream_ptr()))
         return recs
 
     def search_approx_device(self, q_dev, k: int, eta: float, entropy_pref: float, candidates: Optional[int] = None,
@@ -689,9 +724,7 @@ class DeviceCorpus:
             return empty_result(b, self.device)
         c = approx_cut(k, candidates, self.n_rows)
         recs = self.candidates_i8_device(q_dev, c, id_offset=0, batch_pass=batch_pass)
-        if rescore:
-            self.rescore_candidates_device(q_dev, recs, id_offset=0)
-        return merge_rerank_device(recs.view(1, b, c, 4), c, k, eta, entropy_pref, out_ids, out_scores)
+        return self._rerank_records(q_dev, recs, rescore, k, eta, entropy_pref, out_ids, out_scores)
 
     def search_approx(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
                       candidates: Optional[int] = None, rescore: bool = True,
@@ -699,15 +732,9 @@ class DeviceCorpus:
         """Blocking twin of ``search`` for ``search_approx_device``: (ids int64 [B, k] including id_offset, scores fp32
         [B, k]) on the host.  Serialised by the per-corpus lock.  ``batch_pass``: as ``candidates_i8_device`` — ``None``
         takes the matrix-core pass where it takes the shape, ``False`` the row passes, ``True`` insists (``ValueError``)."""
-        with self._lock, _torch().cuda.device(self.device):
-            q = self.stage_queries(queries)
-            # (the private twin, NOT self.search_approx_device: the public method's parameter list is pinned and cannot carry
-            # batch_pass — a subclass that overrides search_approx_device must override this method too, as Int8Corpus does)
-            ids_d, sc_d = self._search_approx_device(q, k, eta, entropy_pref, candidates, rescore, None, None, batch_pass)
-            ids_h, scores_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
-        if self.id_offset:
-            ids_h = ids_h + self.id_offset
-        return ids_h, scores_h
+        # (the private twin, NOT self.search_approx_device: the public method's parameter list is pinned and cannot carry
+        # batch_pass — a subclass that overrides search_approx_device must override this method too, as Int8Corpus does)
+        return self._blocking(self._search_approx_device, queries, k, eta, entropy_pref, candidates, rescore, None, None, batch_pass)
 
     # ------------------------------------------------------------------ binary shadow (approximate route, DESIGN.md 4.1aa)
     def enable_binary_shadow(self) -> "DeviceCorpus":
@@ -750,12 +777,11 @@ class DeviceCorpus:
         bits = self._binary()
         b, c = int(q_dev.shape[0]), int(n_candidates)
         n = int(bits.shape[0])
-        if out is None:
-            out = _torch().empty((b, c, 4), dtype=_torch().int32, device=self.device)
+        out = self._records_out(b, c, out)
         ws = self._cached_workspace(("b1", b, c), self._lib.dewi_knn_b1_workspace_bytes, n, self.dim, b, c)
         nat.check(self._lib.dewi_knn_candidates_b1(
             nat.ptr(bits), n, self.dim, nat.ptr(q_dev), b, nat.ptr(self.dewi32), nat.ptr(self.ent32), c,
-            self.id_offset if id_offset is None else int(id_offset), nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+            self._record_id_offset(id_offset), nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
         return out
 
     def search_binary_device(self, q_dev, k: int, eta: float, entropy_pref: float, candidates: Optional[int] = None,
@@ -774,21 +800,13 @@ class DeviceCorpus:
         self._binary()
         c = binary_cut(k, candidates, self.n_rows)
         recs = self.candidates_b1_device(q_dev, c, id_offset=0)
-        if rescore:
-            self.rescore_candidates_device(q_dev, recs, id_offset=0)
-        return merge_rerank_device(recs.view(1, b, c, 4), c, k, eta, entropy_pref, out_ids, out_scores)
+        return self._rerank_records(q_dev, recs, rescore, k, eta, entropy_pref, out_ids, out_scores)
 
     def search_binary(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
                       candidates: Optional[int] = None, rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """Blocking twin of ``search`` for ``search_binary_device``: (ids int64 [B, k] including id_offset, scores fp32
         [B, k]) on the host.  Serialised by the per-corpus lock."""
-        with self._lock, _torch().cuda.device(self.device):
-            q = self.stage_queries(queries)
-            ids_d, sc_d = self.search_binary_device(q, k, eta, entropy_pref, candidates, rescore)
-            ids_h, scores_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
-        if self.id_offset:
-            ids_h = ids_h + self.id_offset
-        return ids_h, scores_h
+        return self._blocking(self.search_binary_device, queries, k, eta, entropy_pref, candidates, rescore)
 
     # ------------------------------------------------------------------ approximate route over allow-lists (DESIGN.md 4.1r)
     def candidates_i8_filtered_device(self, q_dev, n_candidates: int, filter, out=None, id_offset: Optional[int] = None):
@@ -796,15 +814,13 @@ class DeviceCorpus:
         query: ``dewi_knn_candidates_i8_filtered``) or a ``DeviceQueryFilters`` of B lists, every one of them at least
         ``n_candidates`` long (``dewi_knn_candidates_i8_query_filtered``; shorter lists are the caller's split).  Ids are rows
         of the whole corpus.  An empty ``DeviceFilter`` writes nothing: ``out`` is returned filled with padding."""
-        torch = _torch()
         codes, scales = self._int8()
         b, c = int(q_dev.shape[0]), int(n_candidates)
         n = int(codes.shape[0])
-        off = self.id_offset if id_offset is None else int(id_offset)
+        off = self._record_id_offset(id_offset)
         if isinstance(filter, DeviceQueryFilters):
             self.check_query_filters(filter, b)
-            if out is None:
-                out = torch.empty((b, c, 4), dtype=torch.int32, device=self.device)
+            out = self._records_out(b, c, out)
             ws = self._cached_workspace(("i8qf", b, filter.n_union, c), self._lib.dewi_knn_i8_filtered_workspace_bytes,
                                         filter.n_union, self.dim, b, c)
             n_a = (ctypes.c_int64 * b)(*[int(x) for x in filter.n_allowed])
@@ -813,11 +829,8 @@ class DeviceCorpus:
                 nat.ptr(self.dewi32), nat.ptr(self.ent32), c, off, nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
             return out
         self.check_filter(filter)
-        if out is None:
-            out = torch.empty((b, c, 4), dtype=torch.int32, device=self.device)
+        out = self._records_out(b, c, out, padded=filter.n_allowed == 0)
         if filter.n_allowed == 0:
-            # the padding record (sim -inf, dewi 0, ent 0, id -1) as int32 words
-            out.copy_(torch.tensor([-0x800000, 0, 0, -1], dtype=torch.int32, device=self.device).expand(b, c, 4))
             return out
         ws = self._cached_workspace(("i8f", b, filter.n_allowed, c), self._lib.dewi_knn_i8_filtered_workspace_bytes,
                                     filter.n_allowed, self.dim, b, c)
@@ -828,12 +841,8 @@ class DeviceCorpus:
 
     def _approx_one_list(self, q_dev, k: int, eta: float, entropy_pref: float, candidates: Optional[int], rescore: bool,
                          f: DeviceFilter, out_ids, out_scores):
-        c = approx_cut(k, candidates, f.n_allowed)
-        b = int(q_dev.shape[0])
-        recs = self.candidates_i8_filtered_device(q_dev, c, f, id_offset=0)
-        if rescore:
-            self.rescore_candidates_device(q_dev, recs, id_offset=0)
-        return merge_rerank_device(recs.view(1, b, c, 4), c, k, eta, entropy_pref, out_ids, out_scores)
+        recs = self.candidates_i8_filtered_device(q_dev, approx_cut(k, candidates, f.n_allowed), f, id_offset=0)
+        return self._rerank_records(q_dev, recs, rescore, k, eta, entropy_pref, out_ids, out_scores)
 
     def search_approx_filtered_device(self, q_dev, k: int, eta: float, entropy_pref: float, filter,
                                       candidates: Optional[int] = None, rescore: bool = True, out_ids=None, out_scores=None):
@@ -844,7 +853,6 @@ class DeviceCorpus:
         empty ``DeviceFilter`` gives [B, 0].  ``DeviceQueryFilters``: the host split of ``search_device``: lists at least as
         long as the cut share one pass over the union, a shorter list runs on a filter of its own (its cut is ``|F_j|``), an
         empty list leaves id -1 / score NaN in its row."""
-        torch = _torch()
         if isinstance(filter, DeviceQueryFilters):
             qf = filter
             self.check_query_filters(qf, int(q_dev.shape[0]))
@@ -866,51 +874,22 @@ class DeviceCorpus:
                 raise ValueError(f"query {j}: k = {k} exceeds the {int(counts[j])} rows its filter allows")
         c = approx_cut(k, candidates, self.n_rows)
         out_ids, out_scores = default_outputs(b, k, self.device, out_ids, out_scores)
-        shared = [j for j in range(b) if counts[j] >= c]
-        if len(shared) < b:
-            out_ids.fill_(-1)
-            out_scores.fill_(float("nan"))
-        if shared:
-            if len(shared) == b:
-                sub, q_sub, o_ids, o_sc = qf, q_dev, out_ids, out_scores
-            else:
-                key = tuple(shared)
-                sub = qf._subsets.get(key)
-                if sub is None:
-                    if len(qf._subsets) > 8:
-                        qf._subsets.clear()
-                    sub = qf._subsets[key] = self.make_query_filters(qf.masks[list(shared)].view(torch.bool))
-                q_sub = q_dev[shared].contiguous()
-                o_ids, o_sc = default_outputs(len(shared), k, self.device)
-            nb = len(shared)
+
+        def run_shared(sub, q_sub, o_ids, o_sc):
             recs = self.candidates_i8_filtered_device(q_sub, c, sub, id_offset=0)
-            if rescore:
-                self.rescore_candidates_device(q_sub, recs, id_offset=0)
-            merge_rerank_device(recs.view(1, nb, c, 4), c, k, eta, entropy_pref, o_ids, o_sc)
-            if o_ids is not out_ids:
-                idx = torch.tensor(shared, dtype=torch.int64, device=self.device)
-                out_ids.index_copy_(0, idx, o_ids)
-                out_scores.index_copy_(0, idx, o_sc)
-        for j in range(b):
-            if 0 < counts[j] < c:          # a short list: on a filter of its own (cut |F_j|)
-                f = qf._singles.get(j)
-                if f is None:
-                    f = qf._singles[j] = self.make_filter(qf.masks[j].view(torch.bool))
-                self._approx_one_list(q_dev[j:j + 1], k, eta, entropy_pref, candidates, rescore, f, out_ids[j:j + 1],
-                                      out_scores[j:j + 1])
-        return out_ids, out_scores
+            self._rerank_records(q_sub, recs, rescore, k, eta, entropy_pref, o_ids, o_sc)
+
+        def run_single(f, q_1, o_ids, o_sc):
+            self._approx_one_list(q_1, k, eta, entropy_pref, candidates, rescore, f, o_ids, o_sc)
+
+        return self._split_query_lists(qf, q_dev, k, c, out_ids, out_scores, run_shared, run_single)
 
     def search_approx_filtered(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, *, filter,
                                candidates: Optional[int] = None, rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """Blocking twin of ``search_approx_filtered_device``: (ids int64 [B, k] including id_offset — -1 stays -1 —, scores
         fp32 [B, k]) on the host.  Serialised by the per-corpus lock."""
-        with self._lock, _torch().cuda.device(self.device):
-            q = self.stage_queries(queries)
-            ids_d, sc_d = self.search_approx_filtered_device(q, k, eta, entropy_pref, filter, candidates, rescore)
-            ids_h, scores_h = ids_d.cpu().numpy(), sc_d.cpu().numpy()
-        if self.id_offset:
-            ids_h = np.where(ids_h >= 0, ids_h + self.id_offset, ids_h)
-        return ids_h, scores_h
+        return self._blocking(self.search_approx_filtered_device, queries, k, eta, entropy_pref, filter, candidates, rescore,
+                              ids="offset_valid")
 
     # ------------------------------------------------------------------ properties
     @property
@@ -1335,7 +1314,6 @@ class DeviceCorpus:
         ``candidates``) share one pass of the QMASK row kernels over the union (``dewi_knn_rerank_query_filtered``); a
         query with 0 < |F_j| < c runs the one-list search on a filter of its own list (its cut is |F_j|); an empty list
         gives id -1 / score NaN in that query's row.  Every query's result is bit-equal to its one-list search."""
-        torch = _torch()
         self.check_query_filters(qf, int(q_dev.shape[0]))
         b, k = check_search_args(q_dev.shape, self.dim, k, candidates, similarity)
         if self.is_bf16:
@@ -1349,44 +1327,59 @@ class DeviceCorpus:
                                  f"the {int(counts[j])} rows its filter allows")
         out_ids, out_scores = default_outputs(b, k, self.device, out_ids, out_scores)
         c = cut_size(k, candidates)
-        shared = [j for j in range(b) if counts[j] >= c]
-        if len(shared) < b:
-            out_ids.fill_(-1)
-            out_scores.fill_(float("nan"))
-        if shared:
-            if len(shared) == b:
-                sub, q_sub, o_ids, o_sc = qf, q_dev, out_ids, out_scores
-            else:
-                key = tuple(shared)
-                sub = qf._subsets.get(key)
-                if sub is None:
-                    if len(qf._subsets) > 8:
-                        qf._subsets.clear()
-                    sub = qf._subsets[key] = self.make_query_filters(qf.masks[list(shared)].view(torch.bool))
-                q_sub = q_dev[shared].contiguous()
-                o_ids, o_sc = default_outputs(len(shared), k, self.device)
-            nb = len(shared)
+
+        def run_shared(sub, q_sub, o_ids, o_sc):
+            nb = int(q_sub.shape[0])
             ws = self._cached_workspace(("qfiltered", nb, sub.n_union, c), self._lib.dewi_knn_query_filtered_workspace_bytes,
                                         sub.n_union, self.dim, nb, c)
             self._last_call = (nb, k, c, False, ws)
             n_a = (ctypes.c_int64 * nb)(*[int(x) for x in sub.n_allowed])
-            rc = self._lib.dewi_knn_rerank_query_filtered(
+            nat.check(self._lib.dewi_knn_rerank_query_filtered(
                 nat.ptr(self.emb), 0, self.n_rows, self.dim, nat.ptr(sub.buf), sub.n_union, n_a, nat.ptr(q_sub), nb,
                 nat.ptr(self.dewi32), nat.ptr(self.ent32), k, 0 if candidates is None else int(candidates),
                 nat.SIM_CODES[similarity], float(eta), float(entropy_pref), nat.SPACE_CODES[self.space], nat.ptr(o_ids),
-                nat.ptr(o_sc), nat.ptr(ws), ws.numel(), nat.stream_ptr())
-            nat.check(rc)
-            if o_ids is not out_ids:
-                idx = torch.tensor(shared, dtype=torch.int64, device=self.device)
-                out_ids.index_copy_(0, idx, o_ids)
-                out_scores.index_copy_(0, idx, o_sc)
+                nat.ptr(o_sc), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+
+        def run_single(f, q_1, o_ids, o_sc):
+            self._search_filtered(q_1, k, eta, entropy_pref, o_ids, o_sc, candidates, similarity, f)
+
+        return self._split_query_lists(qf, q_dev, k, c, out_ids, out_scores, run_shared, run_single)
+
+    def _split_query_lists(self, qf: DeviceQueryFilters, q_dev, k: int, c: int, out_ids, out_scores, run_shared, run_single):
+        """The host split of a batch whose every query has a list of its own, into ``out_ids`` / ``out_scores`` [B, k].  The
+        lists at least as long as the cut ``c`` share one pass: ``run_shared(filters, queries, ids, scores)``, on ``qf`` itself
+        when every list is that long, else on the sub-filter of those lists (kept in ``qf._subsets``: cleared when it holds
+        more than 8) with outputs of its own that are copied back.  A shorter list runs alone: ``run_single(filter, query
+        [1, d], ids [1, k], scores [1, k])`` on the filter of that list (kept in ``qf._singles``).  An empty list leaves the
+        padding, id -1 / score NaN, in its row."""
+        torch = _torch()
+        counts = qf.n_allowed
+        b = int(q_dev.shape[0])
+        shared = [j for j in range(b) if counts[j] >= c]
+        if len(shared) < b:
+            out_ids.fill_(-1)
+            out_scores.fill_(float("nan"))
+        if shared and len(shared) == b:
+            run_shared(qf, q_dev, out_ids, out_scores)
+        elif shared:
+            key = tuple(shared)
+            sub = qf._subsets.get(key)
+            if sub is None:
+                if len(qf._subsets) > 8:
+                    qf._subsets.clear()
+                sub = qf._subsets[key] = self.make_query_filters(qf.masks[list(shared)].view(torch.bool))
+            q_sub = q_dev[shared].contiguous()
+            o_ids, o_sc = default_outputs(len(shared), k, self.device)
+            run_shared(sub, q_sub, o_ids, o_sc)
+            idx = torch.tensor(shared, dtype=torch.int64, device=self.device)
+            out_ids.index_copy_(0, idx, o_ids)
+            out_scores.index_copy_(0, idx, o_sc)
         for j in range(b):
-            if 0 < counts[j] < c:          # a short list: the one-list search on its own filter (cut |F_j|)
+            if 0 < counts[j] < c:          # a short list: on a filter of its own (its cut is |F_j|)
                 f = qf._singles.get(j)
                 if f is None:
                     f = qf._singles[j] = self.make_filter(qf.masks[j].view(torch.bool))
-                self._search_filtered(q_dev[j:j + 1], k, eta, entropy_pref, out_ids[j:j + 1], out_scores[j:j + 1],
-                                      candidates, similarity, f)
+                run_single(f, q_dev[j:j + 1], out_ids[j:j + 1], out_scores[j:j + 1])
         return out_ids, out_scores
 
     def _search_filtered(self, q_dev, k: int, eta: float, entropy_pref: float, out_ids, out_scores,
@@ -1880,10 +1873,8 @@ class DeviceCorpus:
 
     def candidates_device(self, q_dev, n_candidates: int, out=None):
         """Per-shard top-``n_candidates`` records, int32 view [B, n_candidates, 4] (16 B each)."""
-        torch = _torch()
         b = int(q_dev.shape[0])
-        if out is None:
-            out = torch.empty((b, n_candidates, 4), dtype=torch.int32, device=self.device)
+        out = self._records_out(b, n_candidates, out)
         c_local = max(1, min(n_candidates, self.n_rows))
         ws = self._workspace(b, c_local)
         self._last_call = (b, max(1, c_local // 2), c_local, False, ws)
@@ -1968,21 +1959,14 @@ class DeviceCorpus:
         """Blocking twin of ``search`` for ``search_diverse_device``: (ids int64 [B, k] — global, as the candidate records
         carry them —, scores fp32 [B, k]) on the host, in pick order; the tail of a short row holds id -1 / score NaN.  Safe to
         call from several threads on one instance (serialised by the per-corpus lock)."""
-        torch = _torch()
-        with self._lock, torch.cuda.device(self.device):
-            q = self.stage_queries(queries)
-            ids_d, sc_d = self.search_diverse_device(q, k, eta, entropy_pref, mmr_lambda, candidates, max_sim)
-            return ids_d.cpu().numpy(), sc_d.cpu().numpy()
+        return self._blocking(self.search_diverse_device, queries, k, eta, entropy_pref, mmr_lambda, candidates, max_sim, ids="global")
 
     def search_diverse_approx(self, queries: ArrayLike, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0,
                               mmr_lambda: float = 0.5, candidates: Optional[int] = None, max_sim: Optional[float] = None,
                               rescore: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """Blocking twin of ``search_diverse`` for ``search_diverse_approx_device``."""
-        torch = _torch()
-        with self._lock, torch.cuda.device(self.device):
-            q = self.stage_queries(queries)
-            ids_d, sc_d = self.search_diverse_approx_device(q, k, eta, entropy_pref, mmr_lambda, candidates, max_sim, rescore)
-            return ids_d.cpu().numpy(), sc_d.cpu().numpy()
+        return self._blocking(self.search_diverse_approx_device, queries, k, eta, entropy_pref, mmr_lambda, candidates, max_sim,
+                              rescore, ids="global")
 
     # ------------------------------------------------------------------ subset selection (greedy coverage of the whole corpus)
     def select_subset_device(self, budget: int, mmr_lambda: float = 0.5, max_sim: Optional[float] = None, relevance=None,
@@ -2160,15 +2144,11 @@ class DeviceCorpus:
         """``candidates_device`` over the rows of ``filter`` only (``dewi_knn_candidates_filtered``; fp32 corpora, at most
         2048 records per query): int32 view [B, n_candidates, 4], ids rows of the whole corpus plus ``id_offset``, padding
         behind ``min(n_candidates, |A|)``.  An empty filter writes nothing: ``out`` is returned filled with padding."""
-        torch = _torch()
         self.check_filter(filter)
         b, c = int(q_dev.shape[0]), int(n_candidates)
-        if out is None:
-            out = torch.empty((b, c, 4), dtype=torch.int32, device=self.device)
         n_a = filter.n_allowed
+        out = self._records_out(b, c, out, padded=n_a == 0)
         if n_a == 0:
-            # the padding record (sim -inf, dewi 0, ent 0, id -1) as int32 words
-            out.copy_(torch.tensor([-0x800000, 0, 0, -1], dtype=torch.int32, device=self.device).expand(b, c, 4))
             return out
         ws = self._cached_workspace(("filtered", b, n_a, min(c, n_a)), self._lib.dewi_knn_filtered_workspace_bytes, n_a, self.dim,
                                     b, c)
@@ -2191,7 +2171,6 @@ class DeviceCorpus:
         the rows offered.  ``exclude``: up to 16 LOCAL rows (int64 tensor on this device) that are never offered.  ``filter``:
         only the rows of one ``DeviceFilter`` are scanned; an empty one writes nothing: ``out`` is returned filled with
         padding.  fp32 cosine corpora of 132 to 4096 columns, ``dim % 4 == 0`` (``check_examples_shape``).  No sync."""
-        torch = _torch()
         check_examples_shape(self.space, self.is_bf16, self.dim)
         n_pos, n_neg = check_examples_request(int(n_positive), int(x_dev.shape[0]) - int(n_positive), match, negative_rule,
                                               negative_weight)
@@ -2203,15 +2182,14 @@ class DeviceCorpus:
         n_excl = 0 if exclude is None else int(exclude.shape[0])
         if n_excl > nat.EXAMPLES_MAX:
             raise ValueError(f"at most {nat.EXAMPLES_MAX} rows can be excluded, got {n_excl}")
-        if out is None:
-            out = torch.empty((1, c, 4), dtype=torch.int32, device=self.device)
         n_scan = self.n_rows
         if filter is not None:
             self.check_filter(filter)
             n_scan = filter.n_allowed
-            if n_scan == 0:
-                out.copy_(torch.tensor([-0x800000, 0, 0, -1], dtype=torch.int32, device=self.device).expand(1, c, 4))
-                return out
+        empty = filter is not None and n_scan == 0
+        out = self._records_out(1, c, out, padded=empty)
+        if empty:
+            return out
         ws = self._cached_workspace(("examples", n_scan, min(c, n_scan)), self._lib.dewi_knn_examples_workspace_bytes, n_scan,
                                     self.dim, n_pos + n_neg, c)
         nat.check(self._lib.dewi_knn_candidates_examples(

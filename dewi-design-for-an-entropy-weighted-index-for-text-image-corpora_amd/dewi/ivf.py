@@ -400,7 +400,7 @@ class IVFIndex(ExactIndex):
         fp32 rows unless ``rescore`` is off, then ``dewi_merge_rerank``.  Every query holds at least c rows."""
         import torch
         from . import _native as nat
-        from ._engine import library_size, merge_rerank_device
+        from ._engine import library_size
         corpus, lib = self._corpus, self._corpus._lib
         codes, scales = corpus._int8()
         b = int(q_dev.shape[0])
@@ -423,9 +423,7 @@ class IVFIndex(ExactIndex):
                     nat.ptr(codes), nat.ptr(scales), corpus.n_rows, self.dim, nat.ptr(buf), n_union[g], counts, nat.ptr(q_g), nq,
                     nat.ptr(corpus.dewi32), nat.ptr(corpus.ent32), c, 0, nat.ptr(recs), nat.ptr(ws), ws.numel(), nat.stream_ptr())
             nat.check(rc)
-            if rescore:
-                corpus.rescore_candidates_device(q_g, recs, id_offset=0)
-            merge_rerank_device(recs.view(1, nq, c, 4), c, k, eta, pref, out_ids[q0:q0 + nq], out_scores[q0:q0 + nq])
+            corpus._rerank_records(q_g, recs, rescore, k, eta, pref, out_ids[q0:q0 + nq], out_scores[q0:q0 + nq])
 
     def search_device(self, q_dev, k: int = 10, eta: float = 0.5, entropy_pref: float = 0.0, candidates: Optional[int] = None,
                       similarity: str = "ip", nprobe: Optional[int] = None, approx: Optional[bool] = None, rescore: bool = True):
@@ -454,36 +452,18 @@ class IVFIndex(ExactIndex):
         out_ids, out_scores = default_outputs(b, k, corpus.device)
         probe_ids, _ = st.coarse.search_device(q_dev, npb, 0.0, 0.0, candidates=npb)
         n_union, n_allowed, stride = self._prepare_probe(probe_ids, b, npb)
-        short = [j for j in range(b) if n_allowed[j] < c]
-        if use_i8:
-            if short:
-                out_ids.fill_(-1)
-                out_scores.fill_(float("nan"))
-                shared = [j for j in range(b) if n_allowed[j] >= c]
-                if shared:
-                    idx = torch.tensor(shared, dtype=torch.int64, device=corpus.device)
-                    pid_s, q_s = probe_ids[idx].contiguous(), q_dev[idx].contiguous()
-                    o_ids, o_sc = default_outputs(len(shared), k, corpus.device)
-                    u_s, a_s, stride = self._prepare_probe(pid_s, len(shared), npb)
-                    self._search_groups_i8(q_s, u_s, a_s, stride, k, c, rescore, eta, pref, o_ids, o_sc)
-                    out_ids.index_copy_(0, idx, o_ids)
-                    out_scores.index_copy_(0, idx, o_sc)
-                for j in short:                      # one list each, cut and k limited to |F_j|
-                    if n_allowed[j] == 0:
-                        continue
-                    kk, cj = min(k, n_allowed[j]), min(c, n_allowed[j])
-                    u_1, a_1, stride = self._prepare_probe(probe_ids[j:j + 1], 1, npb)
-                    o_ids, o_sc = default_outputs(1, kk, corpus.device)
-                    self._search_groups_i8(q_dev[j:j + 1], u_1, a_1, stride, kk, cj, rescore, eta, pref, o_ids, o_sc)
-                    out_ids[j, :kk] = o_ids[0]
-                    out_scores[j, :kk] = o_sc[0]
+
+        def groups(q, n_union, n_allowed, stride, kk, cc, o_ids, o_sc):
+            if use_i8:
+                self._search_groups_i8(q, n_union, n_allowed, stride, kk, cc, rescore, eta, pref, o_ids, o_sc)
             else:
-                self._search_groups_i8(q_dev, n_union, n_allowed, stride, k, c, rescore, eta, pref, out_ids, out_scores)
-            return out_ids, out_scores
+                self._search_groups(q, n_union, n_allowed, stride, kk, cc, candidates, sim, eta, pref, o_ids, o_sc)
+
+        short = [j for j in range(b) if n_allowed[j] < c]
         if not short:
-            self._search_groups(q_dev, n_union, n_allowed, stride, k, c, candidates, sim, eta, pref, out_ids, out_scores)
+            groups(q_dev, n_union, n_allowed, stride, k, c, out_ids, out_scores)
             return out_ids, out_scores
-        # queries whose cells hold fewer rows than the cut leave the shared passes: one list each, cut |F_j|, at most |F_j| results
+        # queries whose cells hold fewer rows than the cut leave the shared passes: one list each, at most |F_j| results
         out_ids.fill_(-1)
         out_scores.fill_(float("nan"))
         shared = [j for j in range(b) if n_allowed[j] >= c]
@@ -492,7 +472,7 @@ class IVFIndex(ExactIndex):
             pid_s, q_s = probe_ids[idx].contiguous(), q_dev[idx].contiguous()
             o_ids, o_sc = default_outputs(len(shared), k, corpus.device)
             u_s, a_s, stride = self._prepare_probe(pid_s, len(shared), npb)
-            self._search_groups(q_s, u_s, a_s, stride, k, c, candidates, sim, eta, pref, o_ids, o_sc)
+            groups(q_s, u_s, a_s, stride, k, c, o_ids, o_sc)
             out_ids.index_copy_(0, idx, o_ids)
             out_scores.index_copy_(0, idx, o_sc)
         for j in short:
@@ -501,7 +481,9 @@ class IVFIndex(ExactIndex):
             kk = min(k, n_allowed[j])
             u_1, a_1, stride = self._prepare_probe(probe_ids[j:j + 1], 1, npb)
             o_ids, o_sc = default_outputs(1, kk, corpus.device)
-            self._search_groups(q_dev[j:j + 1], u_1, a_1, stride, kk, c, candidates, sim, eta, pref, o_ids, o_sc)
+            # (the cut of a short list: |F_j| on the int8 codes, whose entry point takes no cut above the list; the fp32
+            # entry point caps the batch's cut at the list itself)
+            groups(q_dev[j:j + 1], u_1, a_1, stride, kk, min(c, n_allowed[j]) if use_i8 else c, o_ids, o_sc)
             out_ids[j, :kk] = o_ids[0]
             out_scores[j, :kk] = o_sc[0]
         return out_ids, out_scores

@@ -23,6 +23,7 @@ _buf = ctypes.create_string_buffer(4096 + 32)
 P = (ctypes.addressof(_buf) + 15) // 16 * 16          # a 16-byte aligned dummy "device" pointer
 N1 = ctypes.c_int64(0)
 CNT = (ctypes.c_int64 * 4)()
+CNT6 = (ctypes.c_int64 * 6)()
 F7 = (ctypes.c_double * 7)()
 SZ = ctypes.c_size_t(0)
 NAME = ctypes.create_string_buffer(128)
@@ -85,6 +86,11 @@ def ivf_probe(elem=0, n=100, d=64, lists=P, cells=4, b=2, nprobe=1, group=8, nby
     return lambda lib: lib.dewi_ivf_probe_prepare(elem, n, d, lists, cells, P, b, nprobe, group, P, nbytes, CNT, CNT, None)
 
 
+def ivf_probe_f(elem=0, n=100, d=64, lists=P, cells=4, b=2, nprobe=1, group=8, allow=P, per_query=0, nbytes=1 << 20):
+    return lambda lib: lib.dewi_ivf_probe_prepare_filtered(elem, n, d, lists, cells, P, b, nprobe, group, allow, per_query, P, nbytes,
+                                                           CNT, CNT, None)
+
+
 def rcount(E=P, elem=0, n=10, filt=None, n_a=0, b=1, thr=P, ws=P, nbytes=1 << 20):
     return lambda lib: lib.dewi_knn_range_count(E, elem, n, 8, filt, n_a, P, b, thr, 0, P, ws, nbytes, None)
 
@@ -121,6 +127,38 @@ def score(S=P, n=10, ld=10, med=F7, w=F7, mode=0, out=P):
 def score_dev(S=P, n=10, ld=10, med=P, mode=0):
     return lambda lib: lib.dewi_score_f64_dev(S, 1, n, ld, med, P, F7, 3.0, mode, P, None, None)
 
+
+def i8cand(codes=P, n=10, d=16, Q=P, b=1, dewi=P, c=4, id_offset=0, out=P, ws=P, nbytes=1 << 20):
+    return lambda lib: lib.dewi_knn_candidates_i8(codes, P, n, d, Q, b, dewi, P, c, id_offset, out, ws, nbytes, None)
+
+
+def i8batch(codes=P, n=4096, d=768, Q=P, b=8, dewi=P, c=20, id_offset=0, out=P):
+    return lambda lib: lib.dewi_knn_candidates_i8_batch(codes, P, n, d, Q, b, dewi, P, c, id_offset, out, P, 1 << 20, None)
+
+
+def i8filtered(codes=P, n=10, d=16, filt=P, n_a=10, Q=P, dewi=P, c=4, id_offset=0):
+    return lambda lib: lib.dewi_knn_candidates_i8_filtered(codes, P, n, d, filt, n_a, Q, 1, dewi, P, c, id_offset, P, P, 1 << 20, None)
+
+
+def b1cand(bits=P, n=10, d=128, Q=P, b=1, dewi=P, c=5, id_offset=0, out=P, ws=P, nbytes=1 << 20):
+    return lambda lib: lib.dewi_knn_candidates_b1(bits, n, d, Q, b, dewi, P, c, id_offset, out, ws, nbytes, None)
+
+
+def examples(E=P, n=100, d=256, x=P, pos=1, neg=0, match=0, rule=0, weight=1.0, excl=None, n_excl=0, filt=None, n_a=0, dewi=P, c=10,
+             id_offset=0, out=P, ws=P, nbytes=1 << 20):
+    return lambda lib: lib.dewi_knn_candidates_examples(E, n, d, x, pos, neg, match, rule, weight, excl, n_excl, filt, n_a, dewi, P, c,
+                                                        id_offset, out, ws, nbytes, None)
+
+
+def frecords(n=10, filt=P, n_a=10, dewi=P, c=4, id_offset=0):
+    """dewi_knn_candidates_filtered"""
+    return lambda lib: lib.dewi_knn_candidates_filtered(P, 0, n, 8, filt, n_a, P, 1, dewi, P, c, 0, id_offset, P, P, 1 << 20, None)
+
+
+I8_DIM = "the int8 route takes dim % 16 == 0 up to 4096 columns"
+B1_DIM = "the binary route takes dim % 128 == 0 up to 4096 columns"
+I8_CUT = "exceeds the 1024 the int8 route takes"
+EX_DIM = "search by examples serves rows of 33 to 1024 whole 16-byte units (dim % 4 == 0, 132 <= dim <= 4096; got {})"
 
 CASES = [
     # ---- check_common, through dewi_knn_rerank_f32 (every search entry point starts with it)
@@ -264,6 +302,33 @@ CASES = [
     ("ivf probe group", ivf_probe(group=33), INVALID, "group 33 outside [1, 32]"),
     ("ivf probe buffer", ivf_probe(nbytes=8), WORKSPACE, "probe buffer 8 B < required 2084 B"),
     ("ivf probe order: nprobe before group", ivf_probe(nprobe=0, group=33), INVALID, "nprobe 0 outside [1, n_cells = 4]"),
+    ("ivf build order: shape before cells", ivf_build(d=0, cells=0), INVALID, "bad shape 100 x 0"),
+    ("ivf probe order: shape before cells", ivf_probe(n=0, cells=0), INVALID, "bad shape 0 x 64"),
+    ("ivf probe order: cells before n_queries", ivf_probe(cells=101, b=0), INVALID, "n_cells 101 outside [1, min(65536, n_rows)]"),
+    ("ivf probe order: n_queries before nprobe", ivf_probe(b=65536, nprobe=5), INVALID, "n_queries 65536 outside [1, 65535]"),
+    # ---- dewi_ivf_probe_prepare_filtered: the same block, then allow_per_query
+    ("ivf filtered probe null lists", ivf_probe_f(lists=None), INVALID, "null pointer"),
+    ("ivf filtered probe null allow", ivf_probe_f(allow=None), INVALID, "null pointer"),
+    ("ivf filtered probe bf16", ivf_probe_f(elem=1), UNSUPPORTED, BF16_IVF),
+    ("ivf filtered probe elem", ivf_probe_f(elem=2), INVALID, "unknown elem_type 2"),
+    ("ivf filtered probe shape", ivf_probe_f(d=-2), INVALID, "bad shape 100 x -2"),
+    ("ivf filtered probe rows", ivf_probe_f(n=BIG), UNSUPPORTED, ROWS_2_32),
+    ("ivf filtered probe cells", ivf_probe_f(cells=0), INVALID, "n_cells 0 outside [1, min(65536, n_rows)]"),
+    ("ivf filtered probe cells above rows", ivf_probe_f(cells=101), INVALID, "n_cells 101 outside [1, min(65536, n_rows)]"),
+    ("ivf filtered probe n_queries", ivf_probe_f(b=0), INVALID, "n_queries 0 outside [1, 65535]"),
+    ("ivf filtered probe nprobe", ivf_probe_f(nprobe=5), INVALID, "nprobe 5 outside [1, n_cells = 4]"),
+    ("ivf filtered probe group", ivf_probe_f(group=33), INVALID, "group 33 outside [1, 32]"),
+    ("ivf filtered probe allow_per_query", ivf_probe_f(per_query=2), INVALID, "allow_per_query 2 is neither 0 nor 1"),
+    ("ivf filtered probe buffer", ivf_probe_f(nbytes=8), WORKSPACE, "probe buffer 8 B < required 2968 B"),
+    ("ivf filtered probe order: null before bf16", ivf_probe_f(allow=None, elem=1), INVALID, "null pointer"),
+    ("ivf filtered probe order: bf16 before shape", ivf_probe_f(elem=1, n=0), UNSUPPORTED, BF16_IVF),
+    ("ivf filtered probe order: shape before cells", ivf_probe_f(d=0, cells=0), INVALID, "bad shape 100 x 0"),
+    ("ivf filtered probe order: cells before n_queries", ivf_probe_f(cells=0, b=0), INVALID, "n_cells 0 outside [1, min(65536, n_rows)]"),
+    ("ivf filtered probe order: n_queries before nprobe", ivf_probe_f(b=0, nprobe=0), INVALID, "n_queries 0 outside [1, 65535]"),
+    ("ivf filtered probe order: nprobe before group", ivf_probe_f(nprobe=0, group=33), INVALID, "nprobe 0 outside [1, n_cells = 4]"),
+    ("ivf filtered probe order: group before allow_per_query", ivf_probe_f(group=0, per_query=2), INVALID, "group 0 outside [1, 32]"),
+    ("ivf filtered probe order: allow_per_query before the buffer", ivf_probe_f(per_query=-1, nbytes=8), INVALID,
+     "allow_per_query -1 is neither 0 nor 1"),
     # ---- range search
     ("range count common", rcount(E=None), INVALID, "null embedding or query pointer"),
     ("range count elem", rcount(elem=2), INVALID, "unknown elem_type 2"),
@@ -352,6 +417,128 @@ CASES = [
     ("score order: shape before mode", score(ld=9, mode=5), INVALID, "bad shape n=10 ld=9"),
     ("score dev null stats", score_dev(med=None), INVALID, "null pointer"),
     ("score dev mode", score_dev(mode=-1), INVALID, "unknown mode -1"),
+    # ---- candidate records over the int8 codes: what tests/test_int8_host.py, test_int8_batch_host.py and
+    # test_int8_list_host.py leave open of the argument block the four record entry points share
+    ("i8 records null scales", lambda lib: lib.dewi_knn_candidates_i8(P, None, 10, 16, P, 1, P, P, 4, 0, P, P, 1 << 20, None), INVALID,
+     "null codes, scales or query pointer"),
+    ("i8 records dim 0", i8cand(d=0), INVALID, "dim must be positive (got 0)"),
+    ("i8 records null ent", lambda lib: lib.dewi_knn_candidates_i8(P, P, 10, 16, P, 1, P, None, 4, 0, P, P, 1 << 20, None), INVALID,
+     "null payload or output pointer"),
+    ("i8 records queries alignment", i8cand(Q=P + 8), INVALID, "the queries must be 16-byte aligned"),
+    ("i8 records id_offset int32", i8cand(id_offset=(1 << 31) - 10), UNSUPPORTED,
+     "global row ids must fit int32 (offset 2147483638 + 10 rows)"),
+    ("i8 records id_offset at the limit", i8cand(id_offset=(1 << 31) - 11, nbytes=16), WORKSPACE, "workspace 16 B < required 256 B"),
+    ("i8 records order: null before the shape", i8cand(codes=None, n=0), INVALID, "null codes, scales or query pointer"),
+    ("i8 records order: rows before dim", i8cand(n=BIG, d=0), UNSUPPORTED, ROWS_2_32),
+    ("i8 records order: the shape before n_queries", i8cand(d=24, b=0), UNSUPPORTED, f"dim 24: {I8_DIM}"),
+    ("i8 records order: n_queries before the cut", i8cand(b=-1, c=2000), INVALID, "n_queries must be positive (got -1)"),
+    ("i8 records order: the null payload before the alignment", i8cand(out=None, codes=P + 4), INVALID, "null payload or output pointer"),
+    ("i8 records order: the codes before the queries", i8cand(codes=P + 4, Q=P + 8), INVALID, "the codes must be 16-byte aligned"),
+    ("i8 records order: the alignment before the id range", i8cand(Q=P + 8, id_offset=-1), INVALID, "the queries must be 16-byte aligned"),
+    ("i8 records order: the id range before the workspace", i8cand(id_offset=-1, nbytes=16), UNSUPPORTED,
+     "global row ids must fit int32 (offset -1 + 10 rows)"),
+    ("i8 batch null ent", lambda lib: lib.dewi_knn_candidates_i8_batch(P, P, 4096, 768, P, 8, P, None, 20, 0, P, P, 1 << 20, None),
+     INVALID, "null payload or output pointer"),
+    ("i8 batch order: rows before dim", i8batch(n=BIG, d=0), UNSUPPORTED, ROWS_2_32),
+    ("i8 batch order: the codes before the queries", i8batch(codes=P + 4, Q=P + 8), INVALID, "the codes must be 16-byte aligned"),
+    ("i8 batch order: the queries before the id range", i8batch(Q=P + 8, id_offset=-1), INVALID, "the queries must be 16-byte aligned"),
+    ("i8 filtered order: rows before dim", i8filtered(n=BIG, d=0), UNSUPPORTED, ROWS_2_32),
+    ("i8 filtered order: the cut before the null payload", i8filtered(c=2000, dewi=None), UNSUPPORTED, f"n_candidates 2000 {I8_CUT}"),
+    ("i8 filtered order: the codes before the queries", i8filtered(codes=P + 4, Q=P + 8), INVALID, "the codes must be 16-byte aligned"),
+    ("i8 filtered order: the alignment before the id range", i8filtered(Q=P + 8, id_offset=-1), INVALID,
+     "the queries must be 16-byte aligned"),
+    ("i8 filtered empty list", i8filtered(n_a=0), OK, None),
+    ("i8 filtered order: every check before the empty list", i8filtered(n_a=0, id_offset=-1), UNSUPPORTED,
+     "global row ids must fit int32 (offset -1 + 10 rows)"),
+    # ---- candidate records over the 1-bit codes (tests/test_binary_model_host.py matches fragments; here the whole text)
+    ("b1 records null bits", b1cand(bits=None), INVALID, "null bits or query pointer"),
+    ("b1 records null Q", b1cand(Q=None), INVALID, "null bits or query pointer"),
+    ("b1 records n_rows", b1cand(n=0), INVALID, "n_rows must be positive (got 0)"),
+    ("b1 records rows", b1cand(n=BIG), UNSUPPORTED, ROWS_2_32),
+    ("b1 records dim 0", b1cand(d=0), INVALID, "dim must be positive (got 0)"),
+    ("b1 records dim % 128", b1cand(d=64), UNSUPPORTED, f"dim 64: {B1_DIM}"),
+    ("b1 records dim > 4096", b1cand(d=4224), UNSUPPORTED, f"dim 4224: {B1_DIM}"),
+    ("b1 records n_queries", b1cand(b=0), INVALID, "n_queries must be positive (got 0)"),
+    ("b1 records c <= 0", b1cand(c=0), INVALID, "n_candidates must be positive (got 0)"),
+    ("b1 records c > 1024", b1cand(c=1025), UNSUPPORTED, f"n_candidates 1025 {I8_CUT}"),
+    ("b1 records null payload", b1cand(dewi=None), INVALID, "null payload or output pointer"),
+    ("b1 records null out", b1cand(out=None), INVALID, "null payload or output pointer"),
+    ("b1 records bits alignment", b1cand(bits=P + 8), INVALID, "the bits must be 16-byte aligned"),
+    ("b1 records queries alignment", b1cand(Q=P + 4), INVALID, "the queries must be 16-byte aligned"),
+    ("b1 records id_offset", b1cand(id_offset=-1), UNSUPPORTED, "global row ids must fit int32 (offset -1 + 10 rows)"),
+    ("b1 records id_offset int32", b1cand(id_offset=(1 << 31) - 5), UNSUPPORTED,
+     "global row ids must fit int32 (offset 2147483643 + 10 rows)"),
+    ("b1 records workspace", b1cand(nbytes=16), WORKSPACE, "workspace 16 B < required 256 B"),
+    ("b1 records null workspace", b1cand(ws=None), WORKSPACE, "workspace 1048576 B < required 256 B"),
+    ("b1 records c > n_rows is padding, not an error", b1cand(n=3, c=8, nbytes=16), WORKSPACE, "workspace 16 B < required 256 B"),
+    ("b1 records order: null before the shape", b1cand(bits=None, n=0), INVALID, "null bits or query pointer"),
+    ("b1 records order: the shape before n_queries", b1cand(d=64, b=0), UNSUPPORTED, f"dim 64: {B1_DIM}"),
+    ("b1 records order: n_queries before the cut", b1cand(b=0, c=2000), INVALID, "n_queries must be positive (got 0)"),
+    ("b1 records order: the cut before the null payload", b1cand(c=2000, dewi=None), UNSUPPORTED, f"n_candidates 2000 {I8_CUT}"),
+    ("b1 records order: the null payload before the alignment", b1cand(out=None, bits=P + 8), INVALID, "null payload or output pointer"),
+    ("b1 records order: the bits before the queries", b1cand(bits=P + 8, Q=P + 4), INVALID, "the bits must be 16-byte aligned"),
+    ("b1 records order: the alignment before the id range", b1cand(Q=P + 4, id_offset=-1), INVALID,
+     "the queries must be 16-byte aligned"),
+    ("b1 records order: the id range before the workspace", b1cand(id_offset=-1, nbytes=16), UNSUPPORTED,
+     "global row ids must fit int32 (offset -1 + 10 rows)"),
+    ("b1 binarize dim", lambda lib: lib.dewi_binarize_rows_f32(P, 10, 64, P, None), UNSUPPORTED, f"dim 64: {B1_DIM}"),
+    ("b1 binarize empty", lambda lib: lib.dewi_binarize_rows_f32(None, 0, 128, None, None), OK, None),
+    ("b1 binarize order: the shape before null", lambda lib: lib.dewi_binarize_rows_f32(None, 10, 64, P, None), UNSUPPORTED,
+     f"dim 64: {B1_DIM}"),
+    ("b1 prepare order: n_queries before dim", lambda lib: lib.dewi_prepare_queries_b1(P, 0, 64, P, None), INVALID,
+     "n_queries must be positive (got 0)"),
+    ("b1 plan not taken", lambda lib: lib.dewi_knn_b1_plan(10, 128, 5000, CNT6), UNSUPPORTED,
+     "the binary route does not take 10 rows x 128 columns, 5000 candidates"),
+    ("b1 plan dim", lambda lib: lib.dewi_knn_b1_plan(10, 64, 5, CNT6), UNSUPPORTED,
+     "the binary route does not take 10 rows x 64 columns, 5 candidates"),
+    ("b1 plan order: null before the shape", lambda lib: lib.dewi_knn_b1_plan(10, 64, 5, None), INVALID, "null out_words"),
+    # ---- search by examples
+    ("examples null E", examples(E=None), INVALID, "null embedding or example pointer"),
+    ("examples null examples", examples(x=None), INVALID, "null embedding or example pointer"),
+    ("examples shape", examples(n=0), INVALID, "bad shape 0 x 256"),
+    ("examples rows", examples(n=BIG), UNSUPPORTED, ROWS_2_32),
+    ("examples no positive", examples(pos=0), INVALID, "a request needs at least one positive example (got 0)"),
+    ("examples negative count", examples(neg=-1), INVALID, "n_negative must be >= 0 (got -1)"),
+    ("examples too many", examples(pos=9, neg=8), UNSUPPORTED, "17 examples exceed the 16 one request takes"),
+    ("examples match", examples(match=2), INVALID, "unknown match 2"),
+    ("examples rule", examples(rule=2), INVALID, "unknown negative_rule 2"),
+    ("examples weight", examples(weight=float("inf")), INVALID, "negative_weight must be finite in fp32"),
+    ("examples n_exclude", examples(n_excl=17), INVALID, "n_exclude 17 outside [0, 16]"),
+    ("examples null exclude", examples(n_excl=2), INVALID, "null exclude pointer"),
+    ("examples n_allowed", examples(filt=P, n_a=101), INVALID, "n_allowed 101 outside [0, 100]"),
+    ("examples n_allowed without a filter is not read", examples(n_a=101, nbytes=16), WORKSPACE, None),
+    ("examples c <= 0", examples(c=0), INVALID, "n_candidates must be positive (got 0)"),
+    ("examples c > 2048", examples(c=2049), UNSUPPORTED, "n_candidates 2049 exceeds the 2048 candidate records take"),
+    ("examples dim % 4", examples(d=258), UNSUPPORTED, EX_DIM.format(258)),
+    ("examples dim 128", examples(d=128), UNSUPPORTED, EX_DIM.format(128)),
+    ("examples dim > 4096", examples(d=4100), UNSUPPORTED, EX_DIM.format(4100)),
+    ("examples null payload", examples(dewi=None), INVALID, "null payload or output pointer"),
+    ("examples null out", examples(out=None), INVALID, "null payload or output pointer"),
+    ("examples id_offset", examples(id_offset=-1), UNSUPPORTED, "global row ids must fit int32 (offset -1 + 100 rows)"),
+    ("examples id_offset int32", examples(id_offset=(1 << 31) - 100), UNSUPPORTED,
+     "global row ids must fit int32 (offset 2147483548 + 100 rows)"),
+    ("examples empty list", examples(filt=P, n_a=0), OK, None),
+    ("examples null workspace", examples(ws=None), WORKSPACE, None),
+    ("examples order: null before the shape", examples(E=None, n=0), INVALID, "null embedding or example pointer"),
+    ("examples order: the shape before the examples", examples(d=0, pos=0), INVALID, "bad shape 100 x 0"),
+    ("examples order: the cut before dim", examples(c=0, d=128), INVALID, "n_candidates must be positive (got 0)"),
+    ("examples order: dim before the null payload", examples(d=128, dewi=None), UNSUPPORTED, EX_DIM.format(128)),
+    ("examples order: the null payload before the id range", examples(out=None, id_offset=-1), INVALID, "null payload or output pointer"),
+    ("examples order: the id range before the empty list", examples(filt=P, n_a=0, id_offset=-1), UNSUPPORTED,
+     "global row ids must fit int32 (offset -1 + 100 rows)"),
+    ("examples order: the id range before the workspace", examples(id_offset=-1, nbytes=16), UNSUPPORTED,
+     "global row ids must fit int32 (offset -1 + 100 rows)"),
+    # ---- dewi_knn_candidates_filtered (tests/test_collapse_host.py has its single faults): the id range and the empty list
+    ("filtered records id_offset int32", frecords(id_offset=(1 << 31) - 10), UNSUPPORTED,
+     "global row ids must fit int32 (offset 2147483638 + 10 rows)"),
+    ("filtered records order: the null payload before the id range", frecords(dewi=None, id_offset=-1), INVALID,
+     "null payload or output pointer"),
+    ("filtered records order: the id range before the empty list", frecords(n_a=0, id_offset=-1), UNSUPPORTED,
+     "global row ids must fit int32 (offset -1 + 10 rows)"),
+    ("filtered records empty list", frecords(n_a=0), OK, None),
+    # ---- the id range of dewi_knn_finish: its own, shorter text
+    ("finish records id_offset int32", finish(recs=P, id_offset=(1 << 31) - 10), UNSUPPORTED, "global row ids must fit int32"),
+    ("finish records order: the payload before the id range", finish(recs=P, dewi=None, id_offset=-1), INVALID, "null payload pointer"),
 ]
 
 

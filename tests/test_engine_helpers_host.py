@@ -91,6 +91,140 @@ def test_empty_result_and_default_outputs():
     assert ids3 is mine and sc3 is sc
 
 
+# ---------------------------------------------------------------------------------------------------------- the host split
+class _SplitCorpus:
+    """What ``_split_query_lists`` touches of a corpus: the device and the two filter factories, which record their masks."""
+
+    def __init__(self):
+        import torch
+        self.device = torch.device("cpu")
+        self.made_subsets, self.made_singles = [], []
+
+    def make_query_filters(self, masks):
+        self.made_subsets.append(masks.clone())
+        return ("subset", len(self.made_subsets))
+
+    def make_filter(self, mask):
+        self.made_singles.append(mask.clone())
+        return ("single", len(self.made_singles))
+
+
+def _split(counts, c, k=2, corpus=None, qf=None):
+    """Run the split over lists of the given lengths with callables that record their arguments and write a mark per row:
+    shared passes write 100 + (row within the pass), single lists 200."""
+    import torch
+    eng = _eng()
+    b = len(counts)
+    corpus = corpus or _SplitCorpus()
+    masks = (torch.arange(b * 6).reshape(b, 6) % 3 == 0).to(torch.uint8)
+    qf = qf or types.SimpleNamespace(n_allowed=list(counts), masks=masks, _subsets={}, _singles={})
+    qf.n_allowed = list(counts)
+    q = torch.arange(b * 4, dtype=torch.float32).reshape(b, 4)
+    ids = torch.full((b, k), 7, dtype=torch.int64)
+    sc = torch.zeros((b, k))
+    calls = []
+
+    def run_shared(sub, q_sub, o_ids, o_sc):
+        calls.append(("shared", sub, q_sub.clone(), o_ids is ids, tuple(o_ids.shape)))
+        assert q_sub.is_contiguous()
+        o_ids.copy_(100 + torch.arange(o_ids.shape[0]).reshape(-1, 1).expand_as(o_ids))
+        o_sc.fill_(1.0)
+
+    def run_single(f, q_1, o_ids, o_sc):
+        calls.append(("single", f, q_1.clone(), tuple(o_ids.shape)))
+        o_ids.fill_(200)
+        o_sc.fill_(2.0)
+
+    got = eng.DeviceCorpus._split_query_lists(corpus, qf, q, k, c, ids, sc, run_shared, run_single)
+    assert got[0] is ids and got[1] is sc
+    return corpus, qf, q, ids, sc, calls
+
+
+def test_split_all_lists_long():
+    corpus, qf, q, ids, sc, calls = _split([9, 5, 5], c=5)
+    assert len(calls) == 1 and calls[0][0] == "shared" and calls[0][1] is qf           # the filters themselves, the caller's outputs
+    assert calls[0][3] is True and (calls[0][2] == q).all()
+    assert corpus.made_subsets == [] and corpus.made_singles == [] and qf._subsets == {} and qf._singles == {}
+    assert ids.tolist() == [[100, 100], [101, 101], [102, 102]] and (sc == 1.0).all()
+
+
+def test_split_some_short_some_empty():
+    import torch
+    corpus, qf, q, ids, sc, calls = _split([9, 3, 0, 5, 1], c=5)
+    kinds = [c[0] for c in calls]
+    assert kinds == ["shared", "single", "single"]                                      # the shared pass first, then in query order
+    shared = calls[0]
+    assert shared[1] == ("subset", 1) and shared[3] is False and shared[4] == (2, 2)    # outputs of its own, copied back
+    assert (shared[2] == q[[0, 3]]).all()
+    assert list(qf._subsets) == [(0, 3)] and (corpus.made_subsets[0] == qf.masks[[0, 3]].view(torch.bool)).all()
+    assert corpus.made_subsets[0].dtype == torch.bool
+    assert [c[1] for c in calls[1:]] == [("single", 1), ("single", 2)] and sorted(qf._singles) == [1, 4]
+    assert (calls[1][2] == q[1:2]).all() and (calls[2][2] == q[4:5]).all() and calls[1][3] == (1, 2)
+    assert (corpus.made_singles[0] == qf.masks[1].view(torch.bool)).all()
+    assert ids.tolist() == [[100, 100], [200, 200], [-1, -1], [101, 101], [200, 200]]
+    assert sc[[0, 3]].eq(1.0).all() and sc[[1, 4]].eq(2.0).all() and torch.isnan(sc[2]).all()
+    # the same batch again: both caches hit, nothing is prepared twice
+    _split([9, 3, 0, 5, 1], c=5, corpus=corpus, qf=qf)
+    assert len(corpus.made_subsets) == 1 and len(corpus.made_singles) == 2
+
+
+def test_split_all_short_or_empty():
+    import torch
+    corpus, qf, q, ids, sc, calls = _split([2, 0, 4], c=5)
+    assert [c[0] for c in calls] == ["single", "single"] and corpus.made_subsets == [] and sorted(qf._singles) == [0, 2]
+    assert ids.tolist() == [[200, 200], [-1, -1], [200, 200]] and torch.isnan(sc[1]).all()
+    corpus, qf, q, ids, sc, calls = _split([0, 0], c=5)
+    assert calls == [] and ids.tolist() == [[-1, -1], [-1, -1]] and torch.isnan(sc).all()
+
+
+def test_split_subset_cache_is_cleared_beyond_eight_entries():
+    corpus = _SplitCorpus()
+    qf = None
+    for i in range(9):                               # nine distinct subsets of a batch of ten: {i, 9}
+        counts = [0] * 10
+        counts[i] = counts[9] = 5
+        corpus, qf, *_ = _split(counts, c=5, corpus=corpus, qf=qf)
+    assert len(qf._subsets) == 9                     # the rule as it is: cleared before a preparation that finds MORE than 8
+    counts = [5, 5] + [0] * 8
+    _split(counts, c=5, corpus=corpus, qf=qf)
+    assert list(qf._subsets) == [(0, 1)] and len(corpus.made_subsets) == 10
+    assert qf._singles == {}
+
+
+# ---------------------------------------------------------------------------------------------------------- the blocking twins
+def test_blocking_id_rules(monkeypatch):
+    import contextlib
+    import numpy as np
+    import torch
+    eng = _eng()
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
+    staged = []
+
+    def corpus(id_offset):
+        def stage(queries):
+            staged.append(queries)
+            return torch.as_tensor(queries)
+        return types.SimpleNamespace(_lock=threading.RLock(), device=torch.device("cpu"), id_offset=id_offset, stage_queries=stage)
+
+    def search(q, k, tag):
+        assert tag == "tag" and k == 3 and q.shape == (2, 4)
+        return torch.tensor([[4, -1, 0], [2, 1, -1]]), torch.tensor([[0.5, float("nan"), 0.25], [1.0, 0.5, float("nan")]])
+
+    q = np.zeros((2, 4), np.float32)
+    blocking = eng.DeviceCorpus._blocking
+    ids, sc = blocking(corpus(1000), search, q, 3, "tag")
+    assert ids.tolist() == [[1004, 999, 1000], [1002, 1001, 999]] and ids.dtype == np.int64      # "offset": every id
+    assert sc.dtype == np.float32 and sc[0, 0] == 0.5 and np.isnan(sc[0, 1])
+    ids, _ = blocking(corpus(1000), search, q, 3, "tag", ids="offset_valid")
+    assert ids.tolist() == [[1004, -1, 1000], [1002, 1001, -1]]                                  # -1 stays -1
+    ids, _ = blocking(corpus(1000), search, q, 3, "tag", ids="global")
+    assert ids.tolist() == [[4, -1, 0], [2, 1, -1]]                                              # as the records carried them
+    for rule in ("offset", "offset_valid", "global"):
+        ids, _ = blocking(corpus(0), search, q, 3, "tag", ids=rule)
+        assert ids.tolist() == [[4, -1, 0], [2, 1, -1]]
+    assert len(staged) == 6 and all(s is q for s in staged)
+
+
 # ---------------------------------------------------------------------------------------------------------- the workspace cache
 class _Sizes:
     """A fake size function: counts its calls, answers what it is told to."""
